@@ -20,6 +20,12 @@ initial state, observable sum Z, KRYLOV_SE discrete map, seed 0):
     c1: 4-qubit square, Blackman(200 ns, area pi), 200 steps, forward only (the reference's own CPU-runnable case).
 A bench "step" = one pass of the hot path over this rank's batch (fwd+grad for c3/c4, forward for c1/c2/c5);
 value = time-steps/sec = steps * T * (#trajectories of the whole job) / wall time (max over ranks).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds the secondary figures, each of which takes
+runs of its own: forward-only rate and roofline blocks of the dominant kernels (child rocprofv3 PMC passes for the traffic),
+the single-GPU c4 figure, the CPU baseline and the state-sharded c5 leg (--workload c5: its per-pass roofline / link).
+--dump-outputs DIR writes what the last timed step computed (expectation values, gradients; c5: a seeded sample of the final
+state) as DIR/<name>.npy in float64, at most 64 MiB in all, so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -62,6 +68,10 @@ def parse_args():
     ap.add_argument("--no-c5-leg", action="store_true", help="default run: skip the secondary state-sharded (c5) figure")
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--variant", type=int, default=0, help="kernel variant (RydProblem.kernel_variant); 0 = automatic")
+    ap.add_argument("--full", action="store_true", help="also the secondary figures (per-kernel rates and rooflines, c4 on one "
+                    "GPU, CPU baseline, state-sharded c5 leg); the --no-* options above switch single ones off again")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MiB in all)")
     return ap.parse_args()
 
 
@@ -149,6 +159,28 @@ def standin_evolve(amp, det, u_pairs, tsave, psi0, spec, obs):
     return torch.empty(0), e + 0.0 * u_pairs.sum()
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+C5_DUMP_SAMPLE = 1 << 20  # amplitudes of the c5 final state: 16 MiB as (re, im) float64
+
+
+def write_outputs(dirname: str, arrays: dict) -> None:
+    """--dump-outputs: every array as DIR/<name>.npy in float64.  When all of them together exceed DUMP_BUDGET_BYTES, arrays of
+    more than one row keep a fixed, seeded sample of their rows (the row numbers go to DIR/<name>_rows.npy)."""
+    import numpy as np
+
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    host = {k: v.detach().to("cpu", torch.float64).numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_BUDGET_BYTES and a.ndim and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * 0.5 * DUMP_BUDGET_BYTES / total))  # half the budget: room for the row numbers
+            rows = torch.randperm(a.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values.numpy()
+            a = a[rows]
+            np.save(d / f"{name}_rows.npy", rows.astype(np.float64))
+        np.save(d / f"{name}.npy", np.ascontiguousarray(a))
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # one rank
 # ---------------------------------------------------------------------------------------------------------------------
@@ -198,7 +230,8 @@ def run_rank(args) -> None:
     # and freed their GPUs; rank 0 hands its cached HBM back first): a transport problem on a node this code has never run on can
     # then cost at most the field — the children are killed as a group after C5_LEG_TIMEOUT_S, the error goes into the field, the
     # headline line is printed and rank 0 ends normally.  A power-of-two rank count is needed.
-    if rank == 0 and workload != "c5" and args.workload == "auto" and not STANDIN and not args.no_c5_leg and world & (world - 1) == 0:
+    if (rank == 0 and args.full and workload != "c5" and args.workload == "auto" and not STANDIN and not args.no_c5_leg
+            and world & (world - 1) == 0):
         import gc
 
         gc.collect()
@@ -217,7 +250,7 @@ def c5_leg_in_child_group(args, world: int) -> dict:
     import signal
 
     cmd = [sys.executable, str(Path(__file__).resolve()), "--gpus", str(world), "--workload", "c5", "--steps", "1", "--warmup", "1",
-           "--time-steps", "20", "--no-cpu-baseline", "--variant", str(args.variant)]
+           "--time-steps", "20", "--no-cpu-baseline", "--variant", str(args.variant), "--full"]
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "GROUP_RANK", "ROLE_RANK", "LOCAL_WORLD_SIZE",
                         "ROLE_WORLD_SIZE", "GROUP_WORLD_SIZE") and not k.startswith("TORCHELASTIC_")}
@@ -318,8 +351,9 @@ def run_trajectories(args, workload: str, rank: int, world: int, device, barrier
         p[:, -1] = 1.0
         return p
 
-    def one_pass(grad: bool = with_grad, sp=None):
-        """The hot path over this rank's batch, `chunk` trajectories per solver call."""
+    def one_pass(grad: bool = with_grad, sp=None, keep=None):
+        """The hot path over this rank's batch, `chunk` trajectories per solver call.  `keep` (a list): collects a copy of
+        each call's expectation values (n_t, b) for --dump-outputs."""
         sp = sp or spec
         loss_sum = torch.zeros((), dtype=torch.float64, device=device)
         if grad:
@@ -338,15 +372,18 @@ def run_trajectories(args, workload: str, rank: int, world: int, device, barrier
             if grad:
                 loss.backward()
             loss_sum += loss.detach()
+            if keep is not None:
+                keep.append(expect[0].detach().clone())  # a copy: no reference into the run's workspace survives the pass
             del states, expect, loss, amp, det  # releases this chunk's tape workspace before the next chunk plans its own
         return loss_sum
 
     for _ in range(args.warmup):
         one_pass()
     barrier()
+    last_expect = [] if args.dump_outputs else None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = one_pass()
+    for i in range(args.steps):
+        loss = one_pass(keep=last_expect if i == args.steps - 1 else None)
     barrier()
     elapsed = time.perf_counter() - t0
     gathered_sets = total
@@ -362,6 +399,20 @@ def run_trajectories(args, workload: str, rank: int, world: int, device, barrier
         lsum = loss.reshape(1).clone()
         dist.all_reduce(lsum)
         loss = lsum[0]
+    if args.dump_outputs:
+        # what a caller of the timed path received in the last step, for every parameter set of the job: <sum Z>(t_k) and,
+        # with gradients, dL/dOmega_k and dL/ddelta_k
+        none = torch.zeros(0, T + 1, dtype=torch.float64, device=device)
+        arrays = {"expect_sum_z": torch.cat(last_expect, dim=1).T if last_expect else none}
+        if with_grad:
+            for name, p in (("grad_omega", omega), ("grad_delta", delta)):
+                arrays[name] = p.grad if p.grad is not None else torch.zeros(mine, segs, dtype=torch.float64, device=device)
+        if world > 1:
+            from pulser_diff_amd.distributed import gather_trajectories
+
+            arrays = {k: gather_trajectories(v.contiguous(), total) for k, v in arrays.items()}
+        if rank == 0:
+            write_outputs(args.dump_outputs, arrays)
     stats = dict(spec.options.get("_last_stats", {}))
     value = args.steps * T * total / elapsed
     out = {
@@ -387,7 +438,7 @@ def run_trajectories(args, workload: str, rank: int, world: int, device, barrier
                    "tape": stats.get("tape")},
         "loss": float(loss),
     }
-    if STANDIN:
+    if STANDIN or not args.full:
         return out
 
     # ---- per-kernel figures on rank 0's device: forward-only rate, launch durations (HIP events on the launch stream)
@@ -553,6 +604,7 @@ def c4_reference(args) -> dict:
     the multi-GPU c4 lines have their single-GPU point next to the c3 headline."""
     sub = argparse.Namespace(**vars(args))
     sub.workload, sub.steps, sub.warmup, sub.batch, sub.no_cpu_baseline, sub.no_c4_reference = "c4", 1, 0, 0, True, True
+    sub.dump_outputs = None  # the outputs of the run are those of the headline workload
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
 
     def barrier():
@@ -613,13 +665,15 @@ def run_c5(args, rank: int, world: int, device, barrier) -> dict:
         run = lambda ts: S.run_distributed_native(prob, psi0, ts)  # noqa: E731
     for _ in range(max(args.warmup, 1)):
         run(tsave[:3])
-    # per-call set-up (plan, interaction tables of every slab, first-touch of the workspace) is paid once per trajectory whatever
-    # its length: a two-step call is timed so that the per-pass figure of the roofline block can leave it out
-    barrier()
-    t0 = time.perf_counter()
-    run(tsave[:3])
-    barrier()
-    t_short = time.perf_counter() - t0
+    t_short = None
+    if args.full:
+        # per-call set-up (plan, interaction tables of every slab, first-touch of the workspace) is paid once per trajectory
+        # whatever its length: a two-step call is timed so that the per-pass figure of the roofline block can leave it out
+        barrier()
+        t0 = time.perf_counter()
+        run(tsave[:3])
+        barrier()
+        t_short = time.perf_counter() - t0
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -634,19 +688,32 @@ def run_c5(args, rank: int, world: int, device, barrier) -> dict:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
         dist.all_reduce(nrm)
-    if world > 1:
+    if world > 1 and t_short is not None:
         tshort = torch.tensor([t_short], dtype=torch.float64, device=device)
         dist.all_reduce(tshort, op=dist.ReduceOp.MAX)
         t_short = float(tshort.item())
+    if args.dump_outputs:
+        # the final state has 2^24 amplitudes (256 MiB): a fixed, seeded sample of them, gathered from the slabs of all ranks
+        k = min(1 << n, C5_DUMP_SAMPLE)
+        idx = torch.randperm(1 << n, generator=torch.Generator().manual_seed(0))[:k].sort().values
+        flat = final.reshape(-1)
+        if virtual_bits:
+            amps = flat[idx.to(device)]
+        else:
+            mine = (idx // dloc) == rank  # rank r holds the contiguous slab r * dloc ... (r + 1) * dloc - 1
+            amps = torch.zeros(k, dtype=torch.complex128, device=device)
+            amps[mine.to(device)] = flat[(idx[mine] - rank * dloc).to(device)]
+            if world > 1:
+                ri = torch.view_as_real(amps).contiguous()
+                dist.all_reduce(ri)
+                amps = torch.view_as_complex(ri)
+        if rank == 0:
+            write_outputs(args.dump_outputs, {"final_state_sample": torch.view_as_real(amps),
+                                              "final_state_sample_index": idx.to(torch.float64),
+                                              "final_norm": nrm.to(torch.float64)})
     plan = S.ShardedPlan(prob, tsave, S._design_native)
     T = run_T
-    if run_T > 2:  # marginal cost of a factor pass: (whole run - two-step run) / the passes in between
-        us_pass = max(elapsed / args.steps - t_short, 0.0) / ((run_T - 2) * plan.degree) * 1e6
-    else:
-        us_pass = elapsed / (args.steps * run_T * plan.degree) * 1e6
-    sent = prob.n_gpu_bits * dloc * 16  # bytes every rank sends (and receives) per factor pass: one slab per GPU qubit
-    link = dloc * 16 / (us_pass * 1e-6) / 1e9  # each partner slab travels on its own link
-    return {
+    out = {
         "metric": "time-steps/sec (fwd)", "value": args.steps * T / elapsed, "unit": "time-steps/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
         "scaling": "strong", "vs_baseline": None, "dtype": "c128", "data": "synthetic",
@@ -655,6 +722,17 @@ def run_c5(args, rank: int, world: int, device, barrier) -> dict:
                    "n_qubits": n, "time_steps": T, "ranks": world, "virtual_ranks": (1 << virtual_bits) if virtual_bits else 0,
                    "matvecs_per_step_fwd": plan.degree, "parallelism": f"state-sharded x{world}: top {prob.n_gpu_bits} qubit(s) select the rank"},
         "final_norm": float(nrm.item()),
+    }
+    if not args.full:
+        return out
+    if run_T > 2:  # marginal cost of a factor pass: (whole run - two-step run) / the passes in between
+        us_pass = max(elapsed / args.steps - t_short, 0.0) / ((run_T - 2) * plan.degree) * 1e6
+    else:
+        us_pass = elapsed / (args.steps * run_T * plan.degree) * 1e6
+    sent = prob.n_gpu_bits * dloc * 16  # bytes every rank sends (and receives) per factor pass: one slab per GPU qubit
+    link = dloc * 16 / (us_pass * 1e-6) / 1e9  # each partner slab travels on its own link
+    return {
+        **out,
         "roofline": {"bound": "hbm", "applies": world == 1, "kernel": f"{run_stats.get('kernel_fwd') or 'k_chain'} (local factor pass of every slab, partner slabs added by the completing launch; whole run in one native call)",
                      "achieved": 32.0 * (1 << n) / (us_pass * 1e-6) / 1e9, "peak": HBM_PEAK_GBS * max(world, 1), "unit": "GB/s",
                      "frac": 32.0 * (1 << n) / (us_pass * 1e-6) / 1e9 / (HBM_PEAK_GBS * max(world, 1)), "traffic": None,
@@ -764,6 +842,8 @@ def main() -> int:
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return spawn_ranks(args)
     run_rank(args)

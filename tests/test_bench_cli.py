@@ -40,6 +40,44 @@ def test_single_rank_default_is_the_headline_workload():
     assert out["n_gpus"] == 1 and out["config"]["workload"].startswith("c3") and out["scaling"] == "weak"
 
 
+def _line(r):
+    assert r.returncode == 0, r.stderr
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+def test_dump_outputs_repeat_run_to_run_and_with_full(tmp_path):
+    """--dump-outputs: the last timed step's outputs as float64 .npy files (at most 64 MiB in all); the inputs are seeded, so
+    the same arguments — with or without --full, which only adds secondary figures — write the same arrays."""
+    import numpy as np
+
+    runs = {"a": (), "b": (), "full": ("--full",)}
+    for name, extra in runs.items():
+        out = _line(_run("--steps", "2", "--warmup", "1", "--time-steps", "8", "--dump-outputs", str(tmp_path / name), *extra))
+        assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["dtype"] == "c128" and out["higher_is_better"] is True
+    names = sorted(p.name for p in (tmp_path / "a").glob("*.npy"))
+    assert names == ["expect_sum_z.npy", "grad_delta.npy", "grad_omega.npy"]
+    assert np.load(tmp_path / "a" / "expect_sum_z.npy").shape == (1, 9)
+    assert np.load(tmp_path / "a" / "grad_omega.npy").shape == (1, 4)
+    for name in runs:
+        assert sum(p.stat().st_size for p in (tmp_path / name).glob("*.npy")) <= 64 << 20
+        for f in names:
+            a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / name / f)
+            assert a.dtype == np.float64 and np.array_equal(a, b)
+
+
+def test_dump_outputs_gather_every_parameter_set_over_the_ranks(tmp_path):
+    import numpy as np
+
+    out = _line(_run("--gpus", "2", "--steps", "1", "--warmup", "0", "--batch", "10", "--chunk", "3", "--time-steps", "8",
+                     "--dump-outputs", str(tmp_path)))
+    assert out["n_gpus"] == 2
+    ex = np.load(tmp_path / "expect_sum_z.npy")
+    assert ex.shape == (10, 9) and len(np.unique(ex[:, 0])) == 10  # one row per parameter set, rank 1's sets included
+    assert np.load(tmp_path / "grad_delta.npy").shape == (10, 4)
+
+
 def test_rank_count_must_match_the_flag():
     r = _run("--gpus", "4", env_extra={"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and "must match" in (r.stderr + r.stdout)
@@ -54,12 +92,14 @@ def _load_bench():
     return mod
 
 
-def test_state_sharded_leg_failure_only_costs_its_field():
-    """The secondary c5 leg of the default line runs in a child process group.  Without a GPU the child ends
-    with an error: the function must hand back an `error` field (rc and stderr tail) and nothing else."""
+def test_state_sharded_leg_failure_only_costs_its_field(tmp_path, monkeypatch):
+    """The secondary c5 leg of the --full line runs in a child process group.  Here the child ends with an
+    error on any machine (no GPU, or RYDIFF_LIB names a library that does not exist): the function must hand back an `error`
+    field (rc and stderr tail) and nothing else."""
     import argparse
 
     bench = _load_bench()
+    monkeypatch.setenv("RYDIFF_LIB", str(tmp_path / "missing" / "librydiff.so"))
     env_backup = os.environ.pop("RYDIFF_BENCH_STANDIN", None)
     try:
         out = bench.c5_leg_in_child_group(argparse.Namespace(variant=0), 1)

@@ -19,5 +19,5 @@ for n in 23 24; do
 done
 for lib in librydiff.so librydiff_lt13.so; do
   echo "== C5 virtual $lib" | tee -a $out/lt13.txt
-  RYDIFF_LIB=$PWD/pulser-diff_amd/csrc/$lib timeout -k 10 400 python bench.py --workload c5 --steps 2 --warmup 1 2>&1 | tail -n 1 | cut -c1-1500 | tee -a $out/lt13.txt
+  RYDIFF_LIB=$PWD/pulser-diff_amd/csrc/$lib timeout -k 10 400 python bench.py --full --workload c5 --steps 2 --warmup 1 2>&1 | tail -n 1 | cut -c1-1500 | tee -a $out/lt13.txt
 done

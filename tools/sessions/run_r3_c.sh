@@ -4,6 +4,6 @@ set -o pipefail
 out=gpurun_out/r3_c; mkdir -p $out
 python -m pytest tests/test_gpu_optimal_control.py tests/test_gpu_sharded.py -m gpu -x -q > $out/tests.log 2>&1; echo "tests rc $?" | tee -a $out/tests.log
 tail -n 15 $out/tests.log
-timeout -k 10 600 python bench.py --steps 3 --warmup 1 > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc $?"
+timeout -k 10 600 python bench.py --full --steps 3 --warmup 1 > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc $?"
 cut -c1-3000 $out/bench_default.json
 tail -n 5 $out/bench_default.err

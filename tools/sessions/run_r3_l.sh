@@ -4,7 +4,7 @@
 set -o pipefail
 out=gpurun_out/r3_l; mkdir -p $out
 for n in 2 4; do
-  RYDIFF_BENCH_ONE_GPU=1 timeout -k 10 500 python bench.py --gpus $n --steps 1 --warmup 1 --batch 16 --time-steps 100 > $out/bench_${n}ranks.json 2> $out/bench_${n}ranks.err; echo "ranks $n rc $?"
+  RYDIFF_BENCH_ONE_GPU=1 timeout -k 10 500 python bench.py --full --gpus $n --steps 1 --warmup 1 --batch 16 --time-steps 100 > $out/bench_${n}ranks.json 2> $out/bench_${n}ranks.err; echo "ranks $n rc $?"
   python - $n <<'PY'
 import json, sys
 n=sys.argv[1]

@@ -10,6 +10,6 @@ for n in 23 24; do
 done
 echo "== N=21 B=8 (C5 slab shape as a plain batch) 2^12" >> $out; timeout -k 10 200 python tools/time_forward.py 21 10 8 >> $out 2>&1
 echo "== N=21 B=8 2^13 wide" >> $out; RYDIFF_LIB=$L13 timeout -k 10 200 python tools/time_forward.py 21 10 8 >> $out 2>&1
-echo "== C5 bench 2^12" >> $out; timeout -k 10 300 python bench.py --workload c5 --time-steps 20 >> $out 2>&1
-echo "== C5 bench 2^13 wide" >> $out; RYDIFF_LIB=$L13 timeout -k 10 300 python bench.py --workload c5 --time-steps 20 >> $out 2>&1
+echo "== C5 bench 2^12" >> $out; timeout -k 10 300 python bench.py --full --workload c5 --time-steps 20 >> $out 2>&1
+echo "== C5 bench 2^13 wide" >> $out; RYDIFF_LIB=$L13 timeout -k 10 300 python bench.py --full --workload c5 --time-steps 20 >> $out 2>&1
 grep -v amdgpu.ids $out

@@ -17,5 +17,5 @@ for n in 20 21 22 23 24 25; do
     fi
   done
 done
-echo "== C5 bench (automatic)" >> $out; timeout -k 10 300 python bench.py --workload c5 --time-steps 20 >> $out 2>&1
+echo "== C5 bench (automatic)" >> $out; timeout -k 10 300 python bench.py --full --workload c5 --time-steps 20 >> $out 2>&1
 grep -v amdgpu.ids $out

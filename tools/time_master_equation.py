@@ -1,7 +1,8 @@
 """End-to-end time of a master-equation emulator run (DP5_ME on the doubled register) with a cProfile of the host side:
 python tools/time_master_equation.py [atoms] [noise types, comma separated]"""
 import cProfile, gc, pstats, sys, time
-sys.path.insert(0, "/root/repo")
+from pathlib import Path
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch
 import pulser_diff_amd as P
 from pulser_diff_amd import pulses as pl
