@@ -66,7 +66,7 @@ struct Plan {
 
     // workspace offsets (bytes)
     size_t off_meta_idx = 0, off_coef = 0, off_stats = 0, off_udiag = 0, off_buf0 = 0, off_buf1 = 0;
-    size_t off_tape = 0, off_chain = 0, off_ge = 0, off_wtot = 0, off_members = 0, off_meta2 = 0, off_pp0 = 0, off_pp1 = 0, off_split = 0, off_ptable = 0, ptable_bytes = 0;
+    size_t off_tape = 0, off_chain = 0, off_ge = 0, off_wtot = 0, off_members = 0, off_meta2 = 0, off_pp0 = 0, off_pp1 = 0, off_pp2 = 0, off_pp3 = 0, off_split = 0, off_ptable = 0, ptable_bytes = 0;
     size_t split_off_doubles[4] = {0, 0, 0, 0};  // where the split-diagonal table set of tile size 2^(10 + i) starts inside off_split
     size_t off_pm_begin = 0, off_pm_first = 0, off_pm_tau = 0, off_pm_nsub = 0;  // inputs of the on-device factor table build
     size_t state_bytes = 0;  // B * dim * 16
@@ -387,6 +387,10 @@ inline size_t carve(Plan& pl, int tape_mode, bool need_backward, int chain_slots
     pl.off_buf1 = take(pl.state_bytes);
     pl.off_pp0 = take(pl.state_bytes);  // partial vectors of the chained passes
     pl.off_pp1 = take(pl.state_bytes);
+    if (!pl.shard_bits && pl.N > 12 && pl.N <= 20) {  // the w / t pair of the block-of-two passes (pair_kernels.hpp): pp0..pp3
+        pl.off_pp2 = take(pl.state_bytes);
+        pl.off_pp3 = take(pl.state_bytes);
+    }
     // split interaction diagonal for the tile layouts: utt[3][2^LT] + vr[3][tiles][16] per tile size; one set per tile size
     // (LT = 10 .. 13: the forward and the adjoint chains pick their tile size independently)
     {   // (sharded runs index the table by the GLOBAL tile: 2^(N-LT) rows)

@@ -897,6 +897,7 @@ __global__ void k_scatter_grads(ScatterArgs a) {
 }
 
 #include "chain_kernels.hpp"
+#include "pair_kernels.hpp"
 #include "persist_kernels.hpp"
 #include "lane_kernels.hpp"
 static_assert(sizeof(PersistFactor) == 48, "plan.hpp sizes the factor table with 48 bytes per entry");
@@ -1036,6 +1037,7 @@ struct Runtime {
     int tile_mode = 0;            // 0 automatic | 12: variant 13, 2^12-amplitude tiles everywhere | 13: variant 14, wide tiles from 14 qubits
                                   // 11 / 10: variants 15 / 16, tiles of 2^11 / 2^10 amplitudes where two layouts are legal
     bool force_xcd = false;       // variant 10: trajectory-per-XCD placement of the chained tiles forced
+    int pair_mode = 0;            // block-of-two forward passes (k_chain2): 0 automatic | 1 variant 17, wherever legal | -1 variant 18, never
     int chain_lgt = 9;            // log2(threads per tile workgroup) of explicitly chosen chained variants
     // state-sharded run: where the partner slabs arrive and who moves them (RydProblem.shard_recv / shard_exchange)
     void* const* shard_recv = nullptr;
@@ -1048,7 +1050,9 @@ struct Runtime {
 // RydProblem.kernel_variant -> Runtime (include/rydiff.h lists the values)
 int decode_variant(const RydProblem* p, Runtime& rt) {
     int v = p->kernel_variant;
-    if (v < 0 || v > 16 || v == 5 || v == 6) return fail(RYDIFF_EINVAL, "kernel_variant must be 0..4 or 7..16");
+    if (v < 0 || v > 18 || v == 5 || v == 6) return fail(RYDIFF_EINVAL, "kernel_variant must be 0..4 or 7..18");
+    rt.pair_mode = v == 17 ? 1 : (v == 18 ? -1 : 0);
+    if (v == 17 || v == 18) v = 0;
     rt.generic_direct = v == 9;
     if (v == 9) v = 1;
     rt.force_three = v == 7 ? 1 : (v == 11 ? 2 : 0);
@@ -1250,7 +1254,7 @@ void fill_info(const Runtime& rt, double lo, double hi, size_t ws, RydPlanInfo* 
 // gradients from 7 * 2^16 amplitudes and 14 qubits on (below, the direct adjoint stays ahead).  Automatic choice only.
 bool small_tiles_win(const Runtime& rt, bool with_gradients) {
     const Plan& pl = rt.pl;
-    if (rt.variant != 0 || rt.force_three || rt.force_xcd || rt.tile_mode != 0 || pl.shard_bits || pl.n_pair || pl.ga.flagged) return false;
+    if (rt.pair_mode == 1 || rt.variant != 0 || rt.force_three || rt.force_xcd || rt.tile_mode != 0 || pl.shard_bits || pl.n_pair || pl.ga.flagged) return false;
     if (pl.N < 13 || pl.N > 19) return false;
     const size_t amps = size_t(pl.B) << pl.N;
     if (amps > (size_t(1) << 19)) return false;
@@ -1260,7 +1264,7 @@ bool small_tiles_win(const Runtime& rt, bool with_gradients) {
 bool few_tiles(const Runtime& rt, bool with_gradients) {
     const Plan& pl = rt.pl;
     if (rt.small_tiles) return false;
-    if (rt.variant != 0 || rt.force_three || rt.force_xcd || (rt.tile_mode != 0 && rt.tile_mode != kTileBits) || pl.shard_bits) return false;
+    if (rt.pair_mode == 1 || rt.variant != 0 || rt.force_three || rt.force_xcd || (rt.tile_mode != 0 && rt.tile_mode != kTileBits) || pl.shard_bits) return false;
     // forward only: crossover at 2^18 amplitudes in flight (N = 19: 12.5 us direct vs 10.8 us chained per pass).  With gradients the
     // direct ADJOINT pass (own tape element only, partner reads of the cotangent served by L2) stays ahead of the chained one up to
     // 2^19 (11.6-12.8 vs 14.0-14.7 us) and the pair of passes wins by 1-7 % there (profiles/r02_crossover_direct_vs_chained.txt);
@@ -1821,6 +1825,139 @@ int run_chain(const Runtime& rt, char* ws, const std::vector<ChainItem>& items, 
     return RYDIFF_OK;
 }
 
+// ---- block-of-two forward passes (k_chain2, pair_kernels.hpp) ------------------------------------------------------
+// Legal for one phase-free global drive and at most one detuning group on 13..20 qubits with the two-layout 2^12 tiles, un-sharded.
+bool pair_legal(const Runtime& rt) {
+    const Plan& pl = rt.pl;
+    const uint32_t all = uint32_t(pl.dim) - 1u;
+    const ChainGeom g = chain_geom(rt, false);
+    return rt.pair_mode >= 0 && rt.variant == 0 && !rt.force_three && !rt.force_xcd && chain_enabled(rt) && !pl.shard_bits &&
+           pl.N > kTileBits && pl.N <= 20 && g.lt == kTileBits && g.layouts == 2 && pl.ga.n == 1 && pl.gd.n <= 1 && !pl.ga.flagged &&
+           (pl.ga.amp_index_mask[0] & all) == all && !(rt.flags & 1) && pl.off_pp2 && pl.off_pp3;
+}
+
+// Automatic only where it measured faster: the 20-qubit single trajectory (C3).  Variant 17: wherever legal.
+bool pair_enabled(const Runtime& rt) {
+    if (!pair_legal(rt)) return false;
+    return rt.pair_mode == 1 || (rt.pl.N == 20 && rt.pl.B == 1);
+}
+
+template <int LGT>
+int launch_chain2_t(const Chain2Args& ca, unsigned tiles, hipStream_t stream) {
+    constexpr int LT = kTileBits;
+    const size_t lds = 2 * (size_t(1) << LT) * sizeof(double2) + 256;  // two tile buffers + one double per wave
+    static std::atomic<bool> attr_set{false};
+    if (!attr_set.load(std::memory_order_acquire)) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_chain2<LT, LGT>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+        attr_set.store(true, std::memory_order_release);
+    }
+    hipLaunchKernelGGL((k_chain2<LT, LGT>), dim3(tiles, unsigned(ca.b_count)), dim3(1 << LGT), lds, stream, ca);
+    LAUNCH_CHECK();
+    return RYDIFF_OK;
+}
+
+// Forward chain in blocks of two factors of one exponential (an exponential of odd degree ends in a one-factor block).  Same
+// contract as run_chain (no skip_last_finish); keep_mid: the output of a block's first factor is stored too (dst of that factor).
+template <class DstFn, class DoneFn, class ExpFn>
+int run_chain2(const Runtime& rt, char* ws, const std::vector<ChainItem>& items, const double2* start, DstFn dst, bool keep_mid,
+               DoneFn on_done, ExpFn exp_slot, const BatchSlice& bs, hipStream_t stream) {
+    const Plan& pl = rt.pl;
+    const int F = int(items.size());
+    if (F <= 0) return RYDIFF_OK;
+    double2* wt[2][2] = {{reinterpret_cast<double2*>(ws + pl.off_pp0), reinterpret_cast<double2*>(ws + pl.off_pp1)},
+                         {reinterpret_cast<double2*>(ws + pl.off_pp2), reinterpret_cast<double2*>(ws + pl.off_pp3)}};
+    std::vector<std::pair<int, int>> blk;  // (first factor, second factor or -1)
+    for (int i = 0; i < F;) {
+        if (i + 1 < F && items[i + 1].stage == items[i].stage) {
+            blk.push_back({i, i + 1});
+            i += 2;
+        } else {
+            blk.push_back({i, -1});
+            ++i;
+        }
+    }
+    const ChainGeom geom{kTileBits, 2};
+    const double* coef = reinterpret_cast<const double*>(ws + pl.off_coef);
+    const size_t tile_amps = size_t(1) << kTileBits;
+    const size_t per_layout = tile_amps + size_t((size_t(1) << pl.N) >> kTileBits) * 16;
+    const double* split = split_tables(pl, ws, kTileBits);
+    const unsigned tiles = unsigned(pl.dim >> kTileBits);
+    const int nb = int(blk.size());
+    const double2* cur = start;
+    for (int j = 0; j <= nb; ++j) {
+        const int L = j & 1;
+        const LayoutDesc Y = chain_layout(pl.NL, L, geom), X = chain_layout(pl.NL, L ^ 1, geom);
+        Chain2Args ca{};
+        ca.v = cur;
+        ca.w = j ? wt[(j - 1) & 1][0] : cur;  // (always loadable: the kernel requests v, w and t outside of control flow)
+        ca.t = j ? wt[(j - 1) & 1][1] : cur;
+        ca.utt = split + size_t(L) * per_layout;
+        ca.vr = ca.utt + tile_amps;
+        ca.coef_bstride = pl.Bc > 1 ? long(pl.stages.size()) * pl.NC : 0;
+        ca.coef_fin = coef + size_t(j ? items[blk[j - 1].first].stage : 0) * pl.NC;
+        ca.coef_sta = coef + size_t(j < nb ? items[blk[j].first].stage : 0) * pl.NC;
+        ca.lo = Y.lo;
+        ca.hs = Y.hs;
+        ca.hb = Y.hb;
+        ca.dim = uint32_t(pl.dim);
+        ca.has_p = j > 0;
+        ca.has_q = j < nb;
+        ca.gd = pl.gd.n;
+        for (int g = 0; g < pl.gd.n; ++g) {
+            ca.dmask[g] = pl.gd.amp_index_mask[g];
+            ca.dcnt[g] = pl.gd.count[g];
+        }
+        ca.b_first = bs.first;
+        ca.b_count = bs.count;
+        int f0 = -1, last = -1;
+        if (ca.has_p) {
+            f0 = blk[j - 1].first;
+            const int f1 = blk[j - 1].second;
+            last = f1 >= 0 ? f1 : f0;
+            const FactorScalars& s1 = items[f0].s;
+            const FactorScalars s2 = f1 >= 0 ? items[f1].s : FactorScalars{1.0, 0.0, 0.0, 0.0};
+            const std::complex<double> g1(s1.gr, s1.gi), b1(s1.br, s1.bi), g2(s2.gr, s2.gi), b2(s2.br, s2.bi);
+            const std::complex<double> qa = g1 * g2, qb = g1 * b2 + b1 * g2, qk = b1 * b2;
+            ca.a_r = qa.real();
+            ca.a_i = qa.imag();
+            ca.b_r = qb.real();
+            ca.b_i = qb.imag();
+            ca.k_r = qk.real();
+            ca.k_i = qk.imag();
+            ca.g1_r = s1.gr;
+            ca.g1_i = s1.gi;
+            ca.b1_r = s1.br;
+            ca.b1_i = s1.bi;
+            ca.vmid_out = (f1 >= 0 && keep_mid) ? dst(f0) : nullptr;
+            ca.y_out = dst(last);
+            if (!ca.y_out) return fail(RYDIFF_EINVAL, "internal: chain destination missing");
+            ca.fin_mask = to_tile_mask(Y, kTileBits, uint32_t(pl.dim - 1) & ~X.bits);
+            ChainStep cs{};
+            exp_slot(last, cs);
+            ca.obs = cs.obs;
+            ca.expect_slot = cs.expect_slot;
+            ca.n_obs = cs.n_obs;
+            ca.exp_ostride = cs.exp_ostride;
+        }
+        if (ca.has_q) {
+            ca.w_out = wt[j & 1][0];
+            ca.t_out = wt[j & 1][1];
+        }
+        int rc = launch_chain2_t<10>(ca, tiles, stream);
+        if (rc) return rc;
+        if (ca.has_p) {
+            if (ca.vmid_out) {
+                rc = on_done(f0, ca.vmid_out);
+                if (rc) return rc;
+            }
+            rc = on_done(last, ca.y_out);
+            if (rc) return rc;
+            cur = ca.y_out;
+        }
+    }
+    return RYDIFF_OK;
+}
+
 // Adjoint sweep of consecutive tsave intervals as ONE chain.  `items` are the forward factors (in forward order), xs[i] the
 // input of factor i, `lam_in` the cotangent w.r.t. the output of the last one; the cotangent w.r.t. the first one's input ends
 // up in lam_bufs[cl].  save_k[i] >= 0: the input of factor i is the state at save point save_k[i] — the launch that completes
@@ -2130,12 +2267,15 @@ void describe_kernels(const Runtime& rt, const RydProblem* p, bool backward, Ryd
     auto b = [](bool v) { return v ? "true" : "false"; };
     info->kernel_fwd[0] = info->kernel_bwd[0] = 0;
     if (info->kernel_family == 3) {
+        const bool pairs = pl.tape_mode != 3 && xcd_group_size(rt, false) == 0 && pair_enabled(rt);
         const bool fast = pl.ga.n == 1 && (pl.ga.amp_index_mask[0] & ((1u << pl.NL) - 1u)) == (1u << pl.NL) - 1u && !pl.ga.flagged;
         for (int bwd = 0; bwd <= (backward ? 1 : 0); ++bwd) {
             const bool cplx = (rt.flags & 1) != 0 || (bwd && !p->real_amp_grad);
             const int lgt = rt.variant == 0 ? ((bwd && cplx) ? 9 : 10) : rt.chain_lgt;
             const bool res = xcd_group_size(rt, bwd != 0) > 0;
-            if (chain_geom(rt, bwd != 0).lt == kWideTileBits)
+            if (!bwd && pairs)
+                std::snprintf(info->kernel_fwd, sizeof(info->kernel_fwd), "k_chain2<%d,10>", kTileBits);
+            else if (chain_geom(rt, bwd != 0).lt == kWideTileBits)
                 std::snprintf(bwd ? info->kernel_bwd : info->kernel_fwd, sizeof(info->kernel_fwd), "k_chain_wide<%d,%s,%s,%s>", kWideTileBits,
                               b(cplx), b(bwd != 0), b(fast));
             else
@@ -2343,7 +2483,8 @@ int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi
                     cs.expect_slot = expect_out + size_t(step_of_end[i]) * pl.B;
                 }
             };
-            rc = run_chain(rt, ws, all, cur, dst, done, exp_slot, false, bs, stream);
+            if (!partial_tape && !bs.xcd && pair_enabled(rt)) rc = run_chain2(rt, ws, all, cur, dst, full_tape, done, exp_slot, bs, stream);
+            else rc = run_chain(rt, ws, all, cur, dst, done, exp_slot, false, bs, stream);
             if (rc) return rc;
         }
         return RYDIFF_OK;
