@@ -123,9 +123,11 @@ typedef struct RydProblem {
      *  14 chained passes with wide tiles wherever they are legal (14 <= N <= 30; three layouts from 25)
      *  15 / 16 chained passes with tiles of 2^11 / 2^10 amplitudes where two layouts of them are legal (12 <= N <= 20 / 11 <= N <= 18;
      *     automatic takes the 2^11 tiles around 2^19 amplitudes in flight: 256 tiles, one per CU)
-     *  17 forward chains in blocks of two factors per launch (k_chain2) wherever they are legal: one phase-free
-     *     global drive, at most one detuning group, 13 <= N <= 20, un-sharded, no tape or the full tape (automatic: one 20-qubit trajectory)
-     *  18 automatic, but one factor per forward launch (k_chain) everywhere
+     *  17 chains in blocks of two factors per launch (k_chain2 forward, k_chain2_bwd adjoint) wherever they are
+     *     legal: one phase-free global drive, at most one detuning group, 13 <= N <= 20, un-sharded; forward with no tape or the full
+     *     tape, adjoint with real_amp_grad (automatic: one 20-qubit trajectory)
+     *  18 automatic, but one factor per launch (k_chain) everywhere
+     *  19 automatic, but one factor per adjoint launch (forward blocks as automatic)
      * "automatic" takes the one-launch sweeps up to 12 qubits, the direct kernels while few tiles are in flight
      * (B * 2^N <= 2^18, with gradients 2^19) and the chained passes beyond.  Results do not depend on the variant beyond rounding. */
     int32_t kernel_variant;

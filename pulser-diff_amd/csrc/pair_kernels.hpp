@@ -176,3 +176,284 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2(Chain2Args a) {
 #pragma unroll
     for (int r = 0; r < R; ++r) stream_store(a.t_out + boff + xg[r], t2[r]);
 }
+
+// ---- adjoint of a block (k_chain2_bwd) -------------------------------------------------------------------------------------
+// The cotangent runs through the same quadratic with conjugated scalars (H real symmetric).  A block holds the factors b then a of
+// one exponential (forward order; a one-factor block: b alone, a = identity), so the adjoint meets a first.  The launch that
+// STARTS a block in X writes, next to the complete cotangent mu at a's output, w = P_X mu and t = P_X (D mu + c w) (k_chain2's start
+// stage).  The launch that FINISHES it in Y reads mu, w, t and the tape vectors x_a, x_b (the inputs of a and b): 5R.  Round A gives
+//     s = P_Y' mu,  h1 = H mu = D mu + c (w + s),  e = h1 + c w,   P mu = w + s;
+// round B (skipped when k = 0) gives pe = P_Y' e, and P H mu = t + pe (as in k_chain2), so with tp = t + pe
+//     mu_mid = ga~ mu + ba~ h1                  (cotangent between the two factors; never written)
+//     P mu_mid = ga~ (w + s) + ba~ tp
+//     mu_out = q~(H) mu = (gb~ + bb~ H) mu_mid = (gb~ + bb~ D) mu_mid + bb~ c (ga~ (w + s) + ba~ tp)
+// (~: conjugate).  Both factors' gradients are exact contractions, with no further partner sums:
+//     dL/dc  += Re(beta_a <P mu, x_a>) + Re(beta_b <P mu_mid, x_b>)
+//     weight of d(x) (detuning group, U_ij accumulator) += Re(beta_a conj(mu) x_a) + Re(beta_b conj(mu_mid) x_b)
+// Both factors belong to one exponential, so both go to the same gradient record: one wtot atomic per amplitude, one parked
+// partial per quantity.  Registers (1024 threads: at most 128): mu, w, x_a are requested first, and x_a waits out round A in
+// this thread's own slots of the idle LDS buffer, where e replaces it.  After round A only mu_mid, P mu and factor a's weights
+// are kept; x_b and t are requested then.  x_b is consumed (factor b's weights, the wtot atomics, the (w + s) part of
+// <P mu_mid, x_b>, mu_out but its tp part) before round B, and t lands during it: t is only needed as tp.  Cotangent injection
+// at a save point (the state there is x_b) as in k_chain; then the next block starts on mu_out: 5R + 3W per two factors.
+struct Chain2BwdArgs {
+    const double2* mu;  // complete cotangent at the output of the block being finished (the start vector for the first launch)
+    const double2* w;   // P_X mu                              (unused when !has_p)
+    const double2* t;   // P_X (D mu + c w)                    (unused when !has_p)
+    const double2* xa;  // input of factor a (one-factor block: = xb)
+    const double2* xb;  // input of factor b
+    double2* mu_out;    // cotangent at the block's input (written when has_p)
+    double2* w_out;     // the next block's w, t (written when has_q)
+    double2* t_out;
+    const double* utt;  // split interaction diagonal of this layout (as ChainArgs)
+    const double* vr;
+    const double* coef_fin;  // coefficient record of the finished block's exponential (trajectory 0)
+    const double* coef_sta;  // ... of the started block's exponential
+    long coef_bstride;
+    double gb_r, gb_i, bb_r, bb_i;        // conj gamma_b, conj beta_b
+    double k_r, k_i;                      // conj beta_a beta_b: the H^2 coefficient of the block (0: one factor)
+    double ga_r, ga_i, ba_r, ba_i;        // conj gamma_a, conj beta_a (mu_mid)
+    double cba_r, cba_i, cbb_r, cbb_i;    // beta_a, beta_b un-conjugated (contraction weights; one-factor block: beta_a = 0)
+    int lo, hs, hb;                       // layout of this launch (as ChainArgs)
+    uint32_t dim;
+    int has_p, has_q;
+    int gd;                               // 0 or 1 detuning group
+    uint32_t fin_mask;                    // TILE-bit mask of the Y' bits
+    uint32_t dmask;
+    int dcnt;
+    int b_first, b_count;
+    double* ge_fin;  // gradient record of the finished block's exponential (trajectory 0, replica 0): [0] dL/dc, [det_slot] dL/ddelta
+    long ge_bstride, ge_rstride;
+    int det_slot;    // 2 * (number of amplitude groups)
+    double* wtot;    // optional U_ij-gradient accumulator [dim]
+    const double2* inj_gstate;  // fused cotangent injection at a save point (as ChainArgs)
+    const double* inj_gexp;
+    const double* inj_obs;      // [n_obs][dim]
+    int inj_n_obs;
+    long inj_ostride;
+};
+
+template <int LT, int LGT>
+__global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
+    constexpr int NT = 1 << LGT, R = 1 << (LT - LGT), NW = NT / 64;
+    extern __shared__ __attribute__((aligned(16))) double2 tiles[];
+    double* red = reinterpret_cast<double*>(tiles + 2 * (size_t(1) << LT));  // [2][NW] parked gradient partials: dL/dc, dL/ddelta
+    const unsigned tid = threadIdx.x;
+    const unsigned t = blockIdx.x;
+    const unsigned bl = blockIdx.y;
+    if (bl >= unsigned(a.b_count)) return;
+    const unsigned bt = unsigned(a.b_first) + bl;
+    const size_t boff = size_t(bt) * a.dim;
+    const unsigned lomask = (1u << a.lo) - 1u;
+    const int midlow = a.hs - a.lo;
+    const unsigned xbase = ((t & ((1u << midlow) - 1u)) << a.lo) | ((t >> midlow) << (a.hs + a.hb));
+    if (tid < 2 * NW) red[tid] = 0.0;  // published by the barrier of the first round
+    double2 uu[R], ww[R], xa[R], xb[R], tp[R];
+    unsigned xg[R];
+    // the amplitude indices (and the 64-bit offsets derived from them) are taken afresh for each stage's stores, from a copy of
+    // tid the compiler cannot see through: otherwise they stay live from the first loads to the last stores and spill
+    auto reindex = [&]() {
+        unsigned tid_o = tid;
+        asm volatile("" : "+v"(tid_o));
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const unsigned i = unsigned(r) * NT + tid_o;
+            xg[r] = xbase | (i & lomask) | ((i >> a.lo) << a.hs);
+        }
+    };
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const unsigned i = unsigned(r) * NT + tid;
+        xg[r] = xbase | (i & lomask) | ((i >> a.lo) << a.hs);
+        uu[r] = stream_load(a.mu + boff + xg[r]);
+    }
+    // w and x_a requested with mu, outside of control flow (the host passes valid pointers for the first launch too)
+#pragma unroll
+    for (int r = 0; r < R; ++r) ww[r] = stream_load(a.w + boff + xg[r]);
+#pragma unroll
+    for (int r = 0; r < R; ++r) xa[r] = stream_load(a.xa + boff + xg[r]);
+    // interaction diagonal (as k_chain), evaluated once per stage (table reads: L2 hits) so that it is not live across the rounds
+    auto interaction_diagonal = [&](double (&du)[R]) {
+        unsigned tid_o = tid;  // (table addresses taken afresh per stage, as in reindex)
+        asm volatile("" : "+v"(tid_o));
+        const double* __restrict__ vrow = a.vr + size_t(t) * 16;
+        double vloc[LT];
+#pragma unroll
+        for (int b2 = 0; b2 < LT; ++b2) vloc[b2] = vrow[b2];
+        double dlane = vrow[LT];
+#pragma unroll
+        for (int b2 = 0; b2 < LGT; ++b2)
+            if (!(tid >> b2 & 1u)) dlane += vloc[b2];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            double d = a.utt[unsigned(r) * NT + tid_o] + dlane;
+#pragma unroll
+            for (int b2 = LGT; b2 < LT; ++b2)
+                if (!(r >> (b2 - LGT) & 1)) d += vloc[b2];
+            du[r] = d;
+        }
+    };
+    double du[R];  // (the finish stage's copy: taken while the loads are in flight)
+    interaction_diagonal(du);
+    auto cnt = [&](int r) -> double { return a.gd ? double(a.dcnt - popc_i(xg[r] & a.dmask)) : 0.0; };
+    int buf = 0;  // LDS buffer the next round writes
+    auto put = [&](const double2 (&val)[R]) -> const double2* {
+        double2* tile = tiles + (size_t(buf) << LT);
+#pragma unroll
+        for (int r = 0; r < R; ++r) tile[unsigned(r) * NT + tid] = val[r];
+        __syncthreads();
+        buf ^= 1;
+        return tile;
+    };
+    auto cmul = [](double xr, double xi, const double2& z) { return make_double2(xr * z.x - xi * z.y, xr * z.y + xi * z.x); };
+    auto cdot = [](const double2& p, const double2& x) { return make_double2(p.x * x.x + p.y * x.y, p.x * x.y - p.y * x.x); };  // conj(p) x
+
+    double2 y[R];
+    if (a.has_p) {
+        const double* __restrict__ cf = a.coef_fin + bt * a.coef_bstride;
+        const double c = cf[0], cdet = a.gd ? cf[2] : 0.0;
+        double2 pm[R], mid[R];  // P mu, mu_mid: kept until x_b arrives (mu_out is formed from them, not from mu and H mu)
+        double wx[R];           // Re(beta_a conj(mu) x_a): factor a's weight of d(x) (factor b's, Re(beta_b conj(mu_mid) x_b), joins it)
+        double zc = 0.0;  // Re(beta_a <P mu, x_a>) + Re(beta_b <P mu_mid, x_b>): dL/dc
+        const bool two = a.k_r != 0.0 || a.k_i != 0.0;  // (uniform) a second finishing round: P_Y' e
+        {
+            // x_a waits out round A in this thread's own slots of the other LDS buffer (not in registers); e replaces it there
+            double2* etile = tiles + (size_t(buf ^ 1) << LT);
+#pragma unroll
+            for (int r = 0; r < R; ++r) etile[unsigned(r) * NT + tid] = xa[r];
+            double2 s[R], ds[R];
+            partner_sums<LT, LGT, false>(put(uu), uu, a.fin_mask, tid, s, ds);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double2 xav = etile[unsigned(r) * NT + tid];
+                const double d = du[r] + cdet * cnt(r);
+                pm[r] = make_double2(ww[r].x + s[r].x, ww[r].y + s[r].y);
+                const double2 h1 = make_double2(d * uu[r].x + c * pm[r].x, d * uu[r].y + c * pm[r].y);  // H mu
+                if (two) etile[unsigned(r) * NT + tid] = make_double2(h1.x + c * ww[r].x, h1.y + c * ww[r].y);  // e = h1 + c w
+                const double2 q1 = cdot(pm[r], xav);
+                zc += a.cba_r * q1.x - a.cba_i * q1.y;
+                const double2 wa = cdot(uu[r], xav);
+                wx[r] = a.cba_r * wa.x - a.cba_i * wa.y;
+                const double2 mm = cmul(a.ga_r, a.ga_i, uu[r]), mh = cmul(a.ba_r, a.ba_i, h1);
+                mid[r] = make_double2(mm.x + mh.x, mm.y + mh.y);
+            }
+        }
+        park1<NW>(zc, red, 0);  // factor a's drive contraction is complete: parked now, not kept through round B
+        zc = 0.0;
+        // the second tape vector and t (needed as tp = t + P_Y' e only) are requested once round A is done
+#pragma unroll
+        for (int r = 0; r < R; ++r) xb[r] = stream_load(a.xb + boff + xg[r]);
+#pragma unroll
+        for (int r = 0; r < R; ++r) tp[r] = stream_load(a.t + boff + xg[r]);
+        reindex();  // (the indices of round A are not kept through the second load)
+        double sgd = 0.0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const double2 wb = cdot(mid[r], xb[r]);
+            const double wr = wx[r] + (a.cbb_r * wb.x - a.cbb_i * wb.y);
+            if (a.wtot) unsafeAtomicAdd(a.wtot + xg[r], wr);  // both factors: one atomic
+            sgd += wr * cnt(r);
+            const double2 gpm = cmul(a.ga_r, a.ga_i, pm[r]);
+            const double2 q = cdot(gpm, xb[r]);
+            zc += a.cbb_r * q.x - a.cbb_i * q.y;
+            // mu_out = (gb~ + bb~ H) mu_mid, H mu_mid = d mu_mid + c (ga~ P mu + ba~ tp): all but the tp part now
+            const double d = du[r] + cdet * cnt(r);
+            const double2 y1 = cmul(a.gb_r + a.bb_r * d, a.gb_i + a.bb_i * d, mid[r]), y2 = cmul(a.bb_r * c, a.bb_i * c, gpm);
+            y[r] = make_double2(y1.x + y2.x, y1.y + y2.y);
+        }
+        // x_b is consumed before round B starts: its partner reads must not be scheduled while P mu and mu_mid are still live
+        __builtin_amdgcn_sched_barrier(0);
+        if (two) {
+            __syncthreads();  // e published
+            buf ^= 1;
+        }
+        if (two) {  // second finishing round, partners from LDS only: tp += P_Y' e
+            const double2* tile = tiles + (size_t(buf ^ 1) << LT);
+#pragma unroll
+            for (int b = 0; b < LT; ++b) {
+                if (a.fin_mask >> b & 1u) {  // wave-uniform
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        const double2 q = tile[(unsigned(r) * NT + tid) ^ (1u << b)];
+                        tp[r].x += q.x;
+                        tp[r].y += q.y;
+                    }
+                }
+            }
+        }
+        const double kc_r = a.k_r * c, kc_i = a.k_i * c;  // bb~ c ba~
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const double2 kt = cmul(kc_r, kc_i, tp[r]);
+            y[r].x += kt.x;
+            y[r].y += kt.y;
+            const double2 q = cdot(cmul(a.ba_r, a.ba_i, tp[r]), xb[r]);  // (one-factor block: ba~ = 0)
+            zc += a.cbb_r * q.x - a.cbb_i * q.y;
+        }
+        park2<NW>(zc, sgd, red, 0, 1);
+        reindex();
+        if (a.inj_gexp || a.inj_gstate) {  // wave-uniform: the completed cotangent sits at a save point whose state is x_b
+            if (a.inj_gexp) {
+                bool any = false;
+                for (int o = 0; o < a.inj_n_obs; ++o) any |= a.inj_gexp[o * a.inj_ostride + bt] != 0.0;
+                if (any) {
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        double wsum = 0.0;
+                        for (int o = 0; o < a.inj_n_obs; ++o) wsum += a.inj_gexp[o * a.inj_ostride + bt] * a.inj_obs[size_t(o) * a.dim + xg[r]];
+                        y[r].x += 2.0 * wsum * xb[r].x;
+                        y[r].y += 2.0 * wsum * xb[r].y;
+                    }
+                }
+            }
+            if (a.inj_gstate) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const double2 gs = stream_load(a.inj_gstate + boff + xg[r]);
+                    y[r].x += gs.x;
+                    y[r].y += gs.y;
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) stream_store(a.mu_out + boff + xg[r], y[r]);
+    } else {
+#pragma unroll
+        for (int r = 0; r < R; ++r) y[r] = uu[r];
+    }
+    auto flush = [&]() {  // after the barrier that follows the parks: one atomic per quantity and workgroup
+        if (a.has_p && tid < 2) {
+            double sum = 0.0;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) sum += red[tid * NW + w];
+            double* ge = a.ge_fin + bt * a.ge_bstride + (blockIdx.x % kGradReplicas) * a.ge_rstride;
+            if (sum != 0.0) unsafeAtomicAdd(ge + (tid ? a.det_slot : 0), sum);
+        }
+    };
+    if (!a.has_q) {
+        __syncthreads();
+        flush();
+        return;
+    }
+
+    // start the next block in this layout: w' = P_Y mu_out, t' = P_Y (D' mu_out + c' w')
+    const double* __restrict__ cf = a.coef_sta + bt * a.coef_bstride;
+    const double c = cf[0], cdet = a.gd ? cf[2] : 0.0;
+    reindex();
+    interaction_diagonal(du);
+    double2 w2[R], ds[R];
+    partner_sums<LT, LGT, false, true>(put(y), y, ~0u, tid, w2, ds);
+#pragma unroll
+    for (int r = 0; r < R; ++r) stream_store(a.w_out + boff + xg[r], w2[r]);
+    double2 z[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const double d = du[r] + cdet * cnt(r);
+        z[r] = make_double2(d * y[r].x + c * w2[r].x, d * y[r].y + c * w2[r].y);
+    }
+    double2 t2[R];
+    partner_sums<LT, LGT, false, true>(put(z), z, ~0u, tid, t2, ds);
+#pragma unroll
+    for (int r = 0; r < R; ++r) stream_store(a.t_out + boff + xg[r], t2[r]);
+    flush();  // (the barriers of the start rounds published the parked partials)
+}

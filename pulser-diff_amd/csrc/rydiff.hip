@@ -1037,7 +1037,8 @@ struct Runtime {
     int tile_mode = 0;            // 0 automatic | 12: variant 13, 2^12-amplitude tiles everywhere | 13: variant 14, wide tiles from 14 qubits
                                   // 11 / 10: variants 15 / 16, tiles of 2^11 / 2^10 amplitudes where two layouts are legal
     bool force_xcd = false;       // variant 10: trajectory-per-XCD placement of the chained tiles forced
-    int pair_mode = 0;            // block-of-two forward passes (k_chain2): 0 automatic | 1 variant 17, wherever legal | -1 variant 18, never
+    int pair_mode = 0;            // block-of-two passes (k_chain2, k_chain2_bwd): 0 automatic | 1 variant 17, wherever legal | -1 variant 18, never
+    bool pair_bwd_off = false;    // variant 19: automatic, but one factor per adjoint launch (k_chain)
     int chain_lgt = 9;            // log2(threads per tile workgroup) of explicitly chosen chained variants
     // state-sharded run: where the partner slabs arrive and who moves them (RydProblem.shard_recv / shard_exchange)
     void* const* shard_recv = nullptr;
@@ -1050,9 +1051,10 @@ struct Runtime {
 // RydProblem.kernel_variant -> Runtime (include/rydiff.h lists the values)
 int decode_variant(const RydProblem* p, Runtime& rt) {
     int v = p->kernel_variant;
-    if (v < 0 || v > 18 || v == 5 || v == 6) return fail(RYDIFF_EINVAL, "kernel_variant must be 0..4 or 7..18");
+    if (v < 0 || v > 19 || v == 5 || v == 6) return fail(RYDIFF_EINVAL, "kernel_variant must be 0..4 or 7..19");
     rt.pair_mode = v == 17 ? 1 : (v == 18 ? -1 : 0);
-    if (v == 17 || v == 18) v = 0;
+    rt.pair_bwd_off = v == 19;
+    if (v == 17 || v == 18 || v == 19) v = 0;
     rt.generic_direct = v == 9;
     if (v == 9) v = 1;
     rt.force_three = v == 7 ? 1 : (v == 11 ? 2 : 0);
@@ -2043,6 +2045,150 @@ int run_chain_bwd(const Runtime& rt, char* ws, const std::vector<ChainItem>& ite
     return RYDIFF_OK;
 }
 
+// ---- adjoint in blocks of two factors (k_chain2_bwd, pair_kernels.hpp) -------------------------------------------------
+// Where the forward blocks are, for the real-drive adjoint (RydProblem.real_amp_grad: no signed sums) on the 2^12 two-layout
+// tiles; variant 19 keeps the one-factor adjoint (k_chain) next to automatic forward blocks.
+bool pair_bwd_enabled(const Runtime& rt) {
+    const ChainGeom g = chain_geom(rt, true);
+    return !rt.pair_bwd_off && rt.real_amp_grad && pair_enabled(rt) && g.lt == kTileBits && g.layouts == 2;
+}
+
+template <int LGT>
+int launch_chain2_bwd_t(const Chain2BwdArgs& ca, unsigned tiles, hipStream_t stream) {
+    constexpr int LT = kTileBits;
+    const size_t lds = 2 * (size_t(1) << LT) * sizeof(double2) + 2 * ((size_t(1) << LGT) / 64) * sizeof(double);  // two tile buffers + [2][waves]
+    static std::atomic<bool> attr_set{false};
+    if (!attr_set.load(std::memory_order_acquire)) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_chain2_bwd<LT, LGT>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+        attr_set.store(true, std::memory_order_release);
+    }
+    hipLaunchKernelGGL((k_chain2_bwd<LT, LGT>), dim3(tiles, unsigned(ca.b_count)), dim3(1 << LGT), lds, stream, ca);
+    LAUNCH_CHECK();
+    return RYDIFF_OK;
+}
+
+// Same contract as run_chain_bwd (un-sharded, no trajectory-per-XCD placement), in blocks of two factors of one exponential.
+// Factors are paired from the end of each exponential backwards (an exponential of odd degree starts with a one-factor block),
+// so a block never spans two exponentials and only its first factor's input can be a save point.  Launch j finishes the adjoint
+// of block j-1 and starts block j, in layout j & 1 (w / t of a started block: pp0 / pp1 and pp2 / pp3, alternately).
+template <class StageEndFn>
+int run_chain2_bwd(const Runtime& rt, char* ws, const std::vector<ChainItem>& items, const std::vector<const double2*>& xs,
+                   const std::vector<int>& save_k, const double2* lam_in, double2* lam_bufs[2], int& cl, double* wtot,
+                   StageEndFn on_stage_end, const BatchSlice& bs, const InjectSource& inj, hipStream_t stream) {
+    const Plan& pl = rt.pl;
+    const int M = int(items.size());
+    if (M <= 0) return RYDIFF_OK;
+    double2* wt[2][2] = {{reinterpret_cast<double2*>(ws + pl.off_pp0), reinterpret_cast<double2*>(ws + pl.off_pp1)},
+                         {reinterpret_cast<double2*>(ws + pl.off_pp2), reinterpret_cast<double2*>(ws + pl.off_pp3)}};
+    std::vector<std::pair<int, int>> blk;  // adjoint order: (first forward factor b, second forward factor a or -1)
+    for (int f = M - 1; f >= 0;) {
+        if (f >= 1 && items[f - 1].stage == items[f].stage) {
+            blk.push_back({f - 1, f});
+            f -= 2;
+        } else {
+            blk.push_back({f, -1});
+            --f;
+        }
+    }
+    const ChainGeom geom{kTileBits, 2};
+    const double* coef = reinterpret_cast<const double*>(ws + pl.off_coef);
+    double* ge = reinterpret_cast<double*>(ws + pl.off_ge);
+    const long ge_rec = long(kGradReplicas) * (pl.NC + 1);
+    const size_t tile_amps = size_t(1) << kTileBits;
+    const size_t per_layout = tile_amps + size_t((size_t(1) << pl.N) >> kTileBits) * 16;
+    const double* split = split_tables(pl, ws, kTileBits);
+    const unsigned tiles = unsigned(pl.dim >> kTileBits);
+    const int nb = int(blk.size());
+    const double2* cur = lam_in;
+    int rc = on_stage_end(items[M - 1].stage, cur, xs[M]);  // the cotangent at the chain's output: exponential boundary for dL/dtau
+    if (rc) return rc;
+    for (int j = 0; j <= nb; ++j) {
+        const int L = j & 1;
+        const LayoutDesc Y = chain_layout(pl.NL, L, geom), X = chain_layout(pl.NL, L ^ 1, geom);
+        Chain2BwdArgs ca{};
+        ca.mu = cur;
+        ca.w = j ? wt[(j - 1) & 1][0] : cur;  // (always loadable: the kernel requests mu, w and the tape outside of control flow)
+        ca.t = j ? wt[(j - 1) & 1][1] : cur;
+        ca.xa = ca.xb = cur;
+        ca.utt = split + size_t(L) * per_layout;
+        ca.vr = ca.utt + tile_amps;
+        ca.coef_bstride = pl.Bc > 1 ? long(pl.stages.size()) * pl.NC : 0;
+        ca.coef_fin = coef + size_t(j ? items[blk[j - 1].first].stage : 0) * pl.NC;
+        ca.coef_sta = coef + size_t(j < nb ? items[blk[j].first].stage : 0) * pl.NC;
+        ca.lo = Y.lo;
+        ca.hs = Y.hs;
+        ca.hb = Y.hb;
+        ca.dim = uint32_t(pl.dim);
+        ca.has_p = j > 0;
+        ca.has_q = j < nb;
+        ca.gd = pl.gd.n;
+        if (pl.gd.n) {
+            ca.dmask = pl.gd.amp_index_mask[0];
+            ca.dcnt = pl.gd.count[0];
+        }
+        ca.b_first = bs.first;
+        ca.b_count = bs.count;
+        ca.ge_fin = ge;
+        ca.ge_bstride = pl.Bc > 1 ? long(pl.stages.size()) * ge_rec : 0;
+        ca.ge_rstride = pl.NC + 1;
+        ca.det_slot = 2 * pl.ga.n;
+        ca.wtot = wtot;
+        int fb = -1;
+        if (ca.has_p) {
+            fb = blk[j - 1].first;
+            const int fa = blk[j - 1].second;
+            const FactorScalars& sb = items[fb].s;
+            const FactorScalars sa = fa >= 0 ? items[fa].s : FactorScalars{1.0, 0.0, 0.0, 0.0};
+            const std::complex<double> gb(sb.gr, -sb.gi), bb(sb.br, -sb.bi), ga(sa.gr, -sa.gi), ba(sa.br, -sa.bi);  // conjugated
+            const std::complex<double> qk = ba * bb;
+            ca.gb_r = gb.real();
+            ca.gb_i = gb.imag();
+            ca.bb_r = bb.real();
+            ca.bb_i = bb.imag();
+            ca.k_r = qk.real();
+            ca.k_i = qk.imag();
+            ca.ga_r = ga.real();
+            ca.ga_i = ga.imag();
+            ca.ba_r = ba.real();
+            ca.ba_i = ba.imag();
+            ca.cba_r = sa.br;
+            ca.cba_i = sa.bi;
+            ca.cbb_r = sb.br;
+            ca.cbb_i = sb.bi;
+            ca.xb = xs[fb];
+            ca.xa = fa >= 0 ? xs[fa] : xs[fb];
+            ca.ge_fin = ge + size_t(items[fb].stage) * ge_rec;
+            ca.fin_mask = to_tile_mask(Y, kTileBits, uint32_t(pl.dim - 1) & ~X.bits);
+            cl ^= 1;
+            ca.mu_out = lam_bufs[cl];
+            if (ca.mu_out == cur) return fail(RYDIFF_EINVAL, "internal: cotangent ping-pong clash");
+            const int k = save_k[fb];
+            if (k >= 0 && inj.any()) {
+                const size_t sv = size_t(pl.B) * pl.dim;
+                ca.inj_gstate = inj.gstate ? inj.gstate + size_t(k) * sv : nullptr;
+                ca.inj_gexp = inj.gexp ? inj.gexp + size_t(k) * pl.B : nullptr;
+                ca.inj_obs = inj.obs;
+                ca.inj_n_obs = inj.n_obs;
+                ca.inj_ostride = long(pl.T + 1) * pl.B;
+            }
+        }
+        if (ca.has_q) {
+            ca.w_out = wt[j & 1][0];
+            ca.t_out = wt[j & 1][1];
+        }
+        rc = launch_chain2_bwd_t<10>(ca, tiles, stream);
+        if (rc) return rc;
+        if (ca.has_p) {
+            cur = ca.mu_out;  // complete cotangent at the input of forward factor fb
+            if (fb >= 1 && items[fb].stage != items[fb - 1].stage) {
+                rc = on_stage_end(items[fb - 1].stage, cur, xs[fb]);
+                if (rc) return rc;
+            }
+        }
+    }
+    return RYDIFF_OK;
+}
+
 // ---- persistent small-N forward (k_persist) ------------------------------------------------------------------------
 bool persist_enabled(const Runtime& rt) { return rt.variant != 1 && rt.pl.N <= kTileBits && !rt.pl.shard_bits; }
 
@@ -2268,6 +2414,7 @@ void describe_kernels(const Runtime& rt, const RydProblem* p, bool backward, Ryd
     info->kernel_fwd[0] = info->kernel_bwd[0] = 0;
     if (info->kernel_family == 3) {
         const bool pairs = pl.tape_mode != 3 && xcd_group_size(rt, false) == 0 && pair_enabled(rt);
+        const bool pairs_bwd = xcd_group_size(rt, true) == 0 && pair_bwd_enabled(rt);
         const bool fast = pl.ga.n == 1 && (pl.ga.amp_index_mask[0] & ((1u << pl.NL) - 1u)) == (1u << pl.NL) - 1u && !pl.ga.flagged;
         for (int bwd = 0; bwd <= (backward ? 1 : 0); ++bwd) {
             const bool cplx = (rt.flags & 1) != 0 || (bwd && !p->real_amp_grad);
@@ -2275,6 +2422,8 @@ void describe_kernels(const Runtime& rt, const RydProblem* p, bool backward, Ryd
             const bool res = xcd_group_size(rt, bwd != 0) > 0;
             if (!bwd && pairs)
                 std::snprintf(info->kernel_fwd, sizeof(info->kernel_fwd), "k_chain2<%d,10>", kTileBits);
+            else if (bwd && pairs_bwd)
+                std::snprintf(info->kernel_bwd, sizeof(info->kernel_bwd), "k_chain2_bwd<%d,10>", kTileBits);
             else if (chain_geom(rt, bwd != 0).lt == kWideTileBits)
                 std::snprintf(bwd ? info->kernel_bwd : info->kernel_fwd, sizeof(info->kernel_fwd), "k_chain_wide<%d,%s,%s,%s>", kWideTileBits,
                               b(cplx), b(bwd != 0), b(fast));
@@ -2339,6 +2488,7 @@ int rydiff_plan(const RydProblem* p, int need_tape, int need_backward, void* scr
     std::string err;
     int rc = decode_variant(p, rt);
     if (rc) return rc;
+    rt.real_amp_grad = p->real_amp_grad != 0;  // (describe_kernels: the adjoint blocks need it)
     if (!build_plan(p, rt.pl, err)) return fail(err.find("not implemented") != std::string::npos ? RYDIFF_ENOTIMPL : RYDIFF_EINVAL, err);
     double lo, hi;
     rc = run_stats(p, rt.pl, scratch, stream, lo, hi, rt.flags);
@@ -2722,7 +2872,8 @@ int rydiff_backward(const RydProblem* p, const RydPlanInfo* info, const void* st
             }
             xs[M] = state_at(k_hi + 1);
             if (chained) {
-                int rc2 = run_chain_bwd(rt, ws, chain, xs, save_k, lam[cl], lam, cl, wtot, dot_h, bs, inj, stream);
+                int rc2 = (!bs.xcd && pair_bwd_enabled(rt)) ? run_chain2_bwd(rt, ws, chain, xs, save_k, lam[cl], lam, cl, wtot, dot_h, bs, inj, stream)
+                                                            : run_chain_bwd(rt, ws, chain, xs, save_k, lam[cl], lam, cl, wtot, dot_h, bs, inj, stream);
                 if (rc2) return rc2;
                 continue;
             }
