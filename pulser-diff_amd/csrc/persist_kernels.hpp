@@ -717,3 +717,58 @@ __global__ __launch_bounds__((1 << LGT) < 64 ? 64 : (1 << LGT)) void k_persist_b
         }
     }
 }
+
+// ------------------------------------------------------------------------------------------------
+// Factor table of the one-launch sweeps (k_persist / k_lanes), built ON THE DEVICE from the per-exponential durations:
+// the scalars of factor f of a sub-exponential of duration tau are
+//   beta = -tau / (rho_d z_f),  gamma = 1 + tau sigma / (rho_d z_f),  both times exp(-i tau sigma) p(0) for the last factor
+// (factor_scalars on the host).  One thread per tsave interval walks its exponentials, sub-steps and factors.
+// ------------------------------------------------------------------------------------------------
+constexpr int kMaxDegreeDev = 96;
+struct PTableArgs {
+    PersistFactor* out;
+    const double* tau_sub;      // [E]
+    const int32_t* nsub;        // [E]
+    const int32_t* step_begin;  // [T+1]
+    const int32_t* step_first;  // [T]: index of the interval's first factor
+    int T, degree;
+    double sigma, rho_design, p0r, p0i;
+    double roots[2 * kMaxDegreeDev];
+};
+
+__global__ __launch_bounds__(64) void k_build_ptable(PTableArgs a) {
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= a.T) return;
+    int idx = a.step_first[k];
+    const int first = idx;
+    const int e_end = a.step_begin[k + 1];
+    for (int e = a.step_begin[k]; e < e_end; ++e) {
+        const double tau = a.tau_sub[e];
+        const int ns = a.nsub[e];
+        double sn, cs;
+        sincos(-tau * a.sigma, &sn, &cs);
+        const double kr = cs * a.p0r - sn * a.p0i, ki = cs * a.p0i + sn * a.p0r;  // kappa = exp(-i tau sigma) p(0)
+        for (int sub = 0; sub < ns; ++sub)
+            for (int f = 0; f < a.degree; ++f, ++idx) {
+                // 1 / (rho_d z)
+                const double zr = a.rho_design * a.roots[2 * f], zi = a.rho_design * a.roots[2 * f + 1];
+                const double inv = 1.0 / (zr * zr + zi * zi);
+                const double ir = zr * inv, ii = -zi * inv;
+                double br = -tau * ir, bi = -tau * ii;
+                double gr = 1.0 + tau * a.sigma * ir, gi = tau * a.sigma * ii;
+                if (f == a.degree - 1) {
+                    const double nbr = br * kr - bi * ki, nbi = br * ki + bi * kr;
+                    const double ngr = gr * kr - gi * ki, ngi = gr * ki + gi * kr;
+                    br = nbr; bi = nbi; gr = ngr; gi = ngi;
+                }
+                const bool last = (e == e_end - 1) && (sub == ns - 1) && (f == a.degree - 1);
+                PersistFactor pf;
+                pf.gr = gr; pf.gi = gi; pf.br = br; pf.bi = bi;
+                pf.stage = e;
+                pf.save_index = last ? k + 1 : 0;
+                pf.step_first = first;
+                pf.pad = 0;
+                a.out[idx] = pf;
+            }
+    }
+}
