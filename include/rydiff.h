@@ -145,15 +145,19 @@ typedef struct RydProblem {
      *     whenever a pass needs it, and shard_exchange says when: it is called (on the calling thread) with phase 0 right
      *     after the launch that produced the slab `src` (nbytes) which the partners need next — post the sends of `src` and
      *     the receives into shard_recv[] there, ordered after the work enqueued on `stream` so far — and with phase 1 before
-     *     the first launch that reads shard_recv[] — make `stream` wait for those receives there.  The library runs the whole
+     *     the first launch that reads shard_recv[] — make `stream` wait for those receives there.  Every phase 0 is followed by
+     *     exactly ONE phase 1 before the next phase 0; more than one launch may read shard_recv[] after it (with g_tsave the
+     *     dL/dtau pass at an exponential's output and the completing adjoint launch read the same received slabs).  The library runs the whole
      *     trajectory (every step, every factor) in ONE call and never touches the transport itself (torch.distributed /
      *     RCCL stay with the caller).  A non-zero return aborts the run with RYDIFF_EHIP.
      * GRADIENTS (round 3): rydiff_forward with need_tape (the slabs' trajectory in the workspace tape) followed by rydiff_backward runs
      * the whole reverse sweep natively as well.  The cotangent slabs take the SAME exchange (shard_exchange is called for them exactly as
      * for the state slabs, phase 0 / phase 1), the drive gradients of the rank qubits are contracted with the partner slabs inside the
      * completing launch, grad_expect is [n_obs][n_tsave][batch] (the cotangent of every slab's partial sum: normally the same number for
-     * all slabs) and g_amp / g_det / g_u receive this call's PARTIAL sums (the caller adds them over the ranks: one all-reduce of the
-     * tiny arrays); g_psi0 is [batch][2^(N-g)].  g_tsave is not available (RYDIFF_ENOTIMPL).
+     * all slabs) and g_amp / g_det / g_u / g_tsave receive this call's PARTIAL sums (the caller adds them over the ranks: one
+     * all-reduce of the tiny arrays); g_psi0 is [batch][2^(N-g)].  g_tsave costs one pass per exponential and NO slab exchange:
+     * Im<mu, H x_out> is taken as Im<H mu, x_out> (H is Hermitian: no pair terms here), and the partners' copies of the cotangent
+     * mu are the ones the next adjoint launch needs anyway.
      * No pair terms, 1 <= N-g, N <= RYDIFF_MAX_QUBITS. */
     int32_t shard_bits;
     int32_t shard_rank_first;
@@ -259,7 +263,8 @@ int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi
  *   g_amp        DEVICE complex128 [coeff_batch][n_amp_terms][n_samples] or NULL   (overwritten)
  *   g_det        DEVICE float64    [coeff_batch][n_det_terms][n_samples] or NULL   (overwritten)
  *   g_u          DEVICE float64 [N(N-1)/2] or NULL  (dist_grad, backend.py:456-460 / hamiltonian.py:341-344)
- *   g_tsave      DEVICE float64 [n_tsave] or NULL   (time_grad, backend.py:453-455)
+ *   g_tsave      DEVICE float64 [n_tsave] or NULL   (time_grad, backend.py:453-455; state-sharded runs: this call's partial
+ *                sum, to be added over the ranks like g_amp / g_det / g_u)
  *   g_psi0       DEVICE complex128 [B][2^N] or NULL */
 int rydiff_backward(const RydProblem* p, const RydPlanInfo* info, const void* states, const void* grad_states,
                     const double* grad_expect, void* g_amp, double* g_det, double* g_u, double* g_tsave, void* g_psi0,

@@ -261,11 +261,14 @@ int run_chain(const Runtime& rt, char* ws, const std::vector<ChainItem>& items, 
 // input of factor i, `lam_in` the cotangent w.r.t. the output of the last one; the cotangent w.r.t. the first one's input ends
 // up in lam_bufs[cl].  save_k[i] >= 0: the input of factor i is the state at save point save_k[i] — the launch that completes
 // the cotangent there also adds the cotangent injected at that save point (fused).  on_stage_end(stage, lam, x_out) is called
-// with the complete cotangent at every exponential's output.
+// with the complete cotangent at every exponential's output.  stage_end_reads_partners (matters in sharded runs only): on_stage_end
+// reads the partner ranks' copies of that cotangent too — the wait for them (shard_signal phase 1) then comes before the call instead
+// of before the completing launch that follows it; still one wait per posted exchange.
 template <class StageEndFn>
 int run_chain_bwd(const Runtime& rt, char* ws, const std::vector<ChainItem>& items, const std::vector<const double2*>& xs,
                   const std::vector<int>& save_k, const double2* lam_in, double2* lam_bufs[2], int& cl, double* wtot,
-                  StageEndFn on_stage_end, const BatchSlice& bs, const InjectSource& inj, hipStream_t stream) {
+                  StageEndFn on_stage_end, bool stage_end_reads_partners, const BatchSlice& bs, const InjectSource& inj,
+                  hipStream_t stream) {
     const Plan& pl = rt.pl;
     const int M = int(items.size());
     std::vector<KernelStep> ks;
@@ -273,6 +276,15 @@ int run_chain_bwd(const Runtime& rt, char* ws, const std::vector<ChainItem>& ite
     const double2* cur = lam_in;
     int rcx = shard_signal(rt, 0, cur);  // sharded: the partners need the incoming cotangent for the first completing launch
     if (rcx) return rcx;
+    bool posted = true;  // the exchange of `cur` is posted and nobody has waited for it yet
+    auto stage_end = [&](int stage, const double2* lam, const double2* x_out) -> int {
+        if (stage_end_reads_partners && posted) {
+            const int rc = shard_signal(rt, 1, nullptr);
+            if (rc) return rc;
+            posted = false;
+        }
+        return on_stage_end(stage, lam, x_out);
+    };
     // adjoint factor index a = 0..M-1 corresponds to forward factor f = M-1-a
     for (size_t k = 0; k < ks.size(); ++k) {
         const KernelStep& st = ks[k];
@@ -304,12 +316,14 @@ int run_chain_bwd(const Runtime& rt, char* ws, const std::vector<ChainItem>& ite
             cs.x_sta = xs[f];
             // the cotangent `cur` at the output of the chain's last factor: exponential boundary for dL/dtau
             if (st.sta == 0) {
-                int rc = on_stage_end(it.stage, cur, xs[M]);
+                int rc = stage_end(it.stage, cur, xs[M]);
                 if (rc) return rc;
             }
         }
-        int rc = (cs.has_p && st.completes) ? shard_signal(rt, 1, nullptr) : RYDIFF_OK;  // this launch reads the partners' copies of `cur`
+        // this launch reads the partners' copies of `cur` (a stage-end call in between may have waited for them already)
+        int rc = (cs.has_p && st.completes && posted) ? shard_signal(rt, 1, nullptr) : RYDIFF_OK;
         if (rc) return rc;
+        if (cs.has_p && st.completes) posted = false;
         rc = launch_chain(rt, ws, cs, bs, inj, stream);
         if (rc) return rc;
         if (cs.has_p && st.completes) {
@@ -317,10 +331,11 @@ int run_chain_bwd(const Runtime& rt, char* ws, const std::vector<ChainItem>& ite
             if (k + 1 < ks.size()) {  // the next completing launch needs the partners' copies of this cotangent
                 rc = shard_signal(rt, 0, cur);
                 if (rc) return rc;
+                posted = true;
             }
             const int f = M - 1 - st.fin;
             if (f >= 1 && items[f].stage != items[f - 1].stage) {
-                rc = on_stage_end(items[f - 1].stage, cur, xs[f]);
+                rc = stage_end(items[f - 1].stage, cur, xs[f]);
                 if (rc) return rc;
             }
         }

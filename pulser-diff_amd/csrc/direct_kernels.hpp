@@ -495,6 +495,8 @@ __global__ __launch_bounds__(256) void k_factor_bwd_direct_global(FactorBwdArgs 
 }
 
 // dL/dtau of one exponential:  Re< g, -i H x >  = Im( sum_x conj(g[x]) (H x)[x] )
+// State-sharded runs take the same number as Im( sum_x conj((H g)[x]) x[x] ): H goes onto the cotangent, whose partner slabs the next
+// adjoint launch needs anyway, so the state slabs at the exponential's output never travel.
 struct DotHArgs {
     const double2* g;
     const double2* x;
@@ -508,6 +510,10 @@ struct DotHArgs {
     int b_first;  // the grid's y dimension covers trajectories b_first, b_first + 1, ...
     GroupArgs gr;
     PairArgs pair;
+    // state-sharded run (ChainArgs documents the fields): slabs as trajectories, sh_rem = the partner ranks' COTANGENT slabs
+    int sh_bits = 0, sh_nl = 0, sh_rank_first = 0, sh_self = 0;
+    const double2* sh_rem[kShardMaxBits] = {};
+    int sh_grp[kShardMaxBits] = {};
 };
 
 __global__ __launch_bounds__(256) void k_dot_hx(DotHArgs a) {
@@ -517,11 +523,24 @@ __global__ __launch_bounds__(256) void k_dot_hx(DotHArgs a) {
     const uint32_t xs = live ? x : 0u;
     const int bt = a.b_first + int(blockIdx.y);
     const size_t boff = size_t(bt) * a.dim;
-    const double2* __restrict__ xin = a.x + boff;
+    // the vector H acts on and the one it is contracted with: (x, g), sharded (g, x)
+    const double2* __restrict__ xin = (a.sh_bits ? a.g : a.x) + boff;
+    const double2* __restrict__ oth = (a.sh_bits ? a.x : a.g) + boff;
     const double* __restrict__ cf = a.coef + bt * a.coef_bstride;
-    const double d = diag_value(a.udiag, cf, a.gr, xs);
+    const unsigned rank = unsigned(a.sh_rank_first + bt);
+    const uint32_t xglob = a.sh_bits ? (xs | (rank << a.sh_nl)) : xs;  // sharded: the diagonal lives at the global index
+    const double d = diag_value(a.udiag + (a.sh_bits ? boff : 0), cf, a.gr, xs, xglob);
     const double2 v = xin[xs];
     double hr = d * v.x, hi = d * v.y;
+    // Sharded: H on the cotangent instead of the state is legal because H is Hermitian here — sharded runs take neither pair terms
+    // nor conditioned flips (plan.hpp refuses both); whoever lifts the first refusal has to move H back onto x for those terms.
+    for (int k = 0; k < a.sh_bits; ++k) {  // flips of the rank qubits: the partner ranks' cotangent slabs at the same local index
+        if (a.sh_grp[k] < 0) continue;
+        const double cr = cf[a.sh_grp[k]], ci = (rank >> k & 1u) ? cf[a.gr.ga + a.sh_grp[k]] : -cf[a.gr.ga + a.sh_grp[k]];
+        const double2 p = a.sh_self ? a.g[size_t(unsigned(bt) ^ (1u << k)) * a.dim + xs] : a.sh_rem[k][boff + xs];
+        hr += cr * p.x - ci * p.y;
+        hi += cr * p.y + ci * p.x;
+    }
     for (int q = 0; q < a.gr.ga; ++q) {
         double s1r = 0.0, s1i = 0.0, s0r = 0.0, s0i = 0.0;
         uint32_t m = a.gr.amask[q];
@@ -541,9 +560,10 @@ __global__ __launch_bounds__(256) void k_dot_hx(DotHArgs a) {
         hr += pv.x;
         hi += pv.y;
     }
-    const double2 g = (a.g + boff)[xs];
-    // Im(conj(g) * h) = g.x*hi - g.y*hr
-    const double val = live ? (g.x * hi - g.y * hr) : 0.0;
+    const double2 g = oth[xs];
+    // Im(conj(g) * h) = g.x*hi - g.y*hr;  sharded: Im(conj(h) * x) = -(x.x*hi - x.y*hr)
+    double val = live ? (g.x * hi - g.y * hr) : 0.0;
+    if (a.sh_bits) val = -val;
     block_atomic_add(val, a.out + bt * a.out_bstride + (blockIdx.x % kGradReplicas) * a.out_rstride, lds);
 }
 

@@ -88,7 +88,8 @@ int launch_factor_bwd(const Runtime& rt, char* ws, const double2* gin, const dou
     return RYDIFF_OK;
 }
 
-// dL/dtau of exponential `stage`, taken at its output xout with the cotangent g there (k_dot_hx), for the trajectories of `bs`
+// dL/dtau of exponential `stage`, taken at its output xout with the cotangent g there (k_dot_hx), for the trajectories of `bs`.
+// State-sharded runs apply H to g instead (DotHArgs); with ranks elsewhere shard_recv[] must hold the partners' copies of g by now.
 int launch_dot_h(const Runtime& rt, char* ws, int stage, const double2* g, const double2* xout, const BatchSlice& bs, hipStream_t stream) {
     const Plan& pl = rt.pl;
     DotHArgs da{};
@@ -104,6 +105,9 @@ int launch_dot_h(const Runtime& rt, char* ws, int stage, const double2* g, const
     da.b_first = bs.first;
     da.gr = rt.garg;
     da.pair = rt.parg;
+    fill_shard(da, rt);  // (the partner ranks' cotangent slabs: the caller has waited for them, shard_signal phase 1)
+    if (pl.shard_bits)   // in-slab flips only; the rank bits are the partner slabs
+        for (int q = 0; q < da.gr.ga; ++q) da.gr.amask[q] &= uint32_t(pl.dim - 1);
     hipLaunchKernelGGL(k_dot_hx, dim3(unsigned((pl.dim + 255) / 256), unsigned(bs.count)), dim3(256), 0, stream, da);
     LAUNCH_CHECK();
     return RYDIFF_OK;

@@ -243,8 +243,9 @@ int adjoint_chained(const BackwardCtx& c, const BatchSlice& bs, const std::vecto
     auto dot_h = [&](int stage, const double2* g, const double2* xout) -> int {
         return c.want_tau ? launch_dot_h(rt, c.ws, stage, g, xout, bs, c.stream) : RYDIFF_OK;
     };
+    // sharded: dot_h reads the partners' copies of the cotangent it is handed, like the completing launch that follows it
     return (!bs.xcd && pair_bwd_enabled(rt)) ? run_chain2_bwd(rt, c.ws, chain, xs, save_k, lam[cl], lam, cl, c.wtot, dot_h, bs, c.inj, c.stream)
-                                             : run_chain_bwd(rt, c.ws, chain, xs, save_k, lam[cl], lam, cl, c.wtot, dot_h, bs, c.inj, c.stream);
+                                             : run_chain_bwd(rt, c.ws, chain, xs, save_k, lam[cl], lam, cl, c.wtot, dot_h, c.want_tau, bs, c.inj, c.stream);
 }
 
 int adjoint_direct(const BackwardCtx& c, const BatchSlice& bs, const std::vector<ChainItem>& chain, const std::vector<const double2*>& xs,
@@ -253,14 +254,14 @@ int adjoint_direct(const BackwardCtx& c, const BatchSlice& bs, const std::vector
     const int M = int(chain.size());
     for (int i = M; i >= 1; --i) {
         const ChainItem& it = chain[i - 1];
-        // dL/dtau of an exponential is taken at its output (end of its last factor)
+        int rc = shard_signal(rt, 0, c.lam[cl]);  // sharded: the partners need this rank's cotangent ...
+        if (!rc) rc = shard_signal(rt, 1, nullptr);  // ... and the launches below read theirs
+        if (rc) return rc;
+        // dL/dtau of an exponential is taken at its output (end of its last factor); sharded: with the partners' cotangent slabs
         if (c.want_tau && (i == M || chain[i].stage != it.stage)) {
-            const int rc = launch_dot_h(rt, c.ws, it.stage, c.lam[cl], xs[i], bs, c.stream);
+            rc = launch_dot_h(rt, c.ws, it.stage, c.lam[cl], xs[i], bs, c.stream);
             if (rc) return rc;
         }
-        int rc = shard_signal(rt, 0, c.lam[cl]);  // sharded: the partners need this rank's cotangent ...
-        if (!rc) rc = shard_signal(rt, 1, nullptr);  // ... and this launch reads theirs
-        if (rc) return rc;
         rc = launch_factor_bwd(rt, c.ws, c.lam[cl], xs[i - 1], c.lam[cl ^ 1], it.stage, it.s, c.wtot, c.inj, save_k[i - 1], c.stream);
         if (rc) return rc;
         cl ^= 1;
@@ -466,8 +467,6 @@ int rydiff_backward(const RydProblem* p, const RydPlanInfo* info, const void* st
     if (rc) return rc;
     const Plan& pl = rt.pl;
     if (!states && !pl.tape_mode) return fail(RYDIFF_EINVAL, "backward needs the trajectory: pass states or use the workspace tape");
-    if (pl.shard_bits && g_tsave)
-        return fail(RYDIFF_ENOTIMPL, "state-sharded runs: no gradient w.r.t. the evaluation times (pass g_tsave = NULL)");
     BackwardCtx c{{rt, p, static_cast<char*>(workspace), stream, size_t(pl.B) * pl.dim}};
     // the full workspace tape (written by a forward call with need_tape = 2) is preferred over `states`
     c.tape = (pl.tape_mode >= 2 || !states) ? reinterpret_cast<const double2*>(c.ws + pl.off_tape) : static_cast<const double2*>(states);

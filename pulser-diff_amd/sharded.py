@@ -179,7 +179,9 @@ class ShardedPlan:
             beta, gamma = beta * kappa, gamma * kappa
         return complex(gamma), complex(beta)
 
-    def calls_for_step(self, k: int, rank: int) -> list[FactorCall]:
+    def _step_terms(self, k: int, rank: int):
+        """Coefficients of interval k (tables interpolated at its END time) as rank `rank` sees them: local flip and diagonal
+        coefficients, E_rank, the flip coefficient c_q^(+-) of every GPU qubit and the partner behind it."""
         prob = self.prob
         g = prob.n_gpu_bits
         amp_now, det_now = prob.interp(float(self.tsave[k + 1]))
@@ -190,14 +192,23 @@ class ShardedPlan:
         c_q = [sum(amp_now[i] for i, m in enumerate(prob.amp_masks) if m >> q & 1) for q in range(g)]
         bits = [(rank >> (g - 1 - q)) & 1 for q in range(g)]
         partners = [rank ^ (1 << (g - 1 - q)) for q in range(g)]
+        return c_amp, c_det, e_rank, [c_q[q] if bits[q] else np.conj(c_q[q]) for q in range(g)], partners
+
+    def calls_for_step(self, k: int, rank: int) -> list[FactorCall]:
+        c_amp, c_det, e_rank, c_rem, partners = self._step_terms(k, rank)
         tau_sub = float(self.tsave[k + 1] - self.tsave[k]) / self.nsub[k]
         calls = []
         for _ in range(self.nsub[k]):
             for f in range(self.degree):
                 gamma, beta = self.factor_scalars(tau_sub, f)
-                rc = [beta * (c_q[q] if bits[q] else np.conj(c_q[q])) for q in range(g)]
-                calls.append(FactorCall(c_amp, c_det, gamma + beta * e_rank, beta, rc, partners))
+                calls.append(FactorCall(c_amp, c_det, gamma + beta * e_rank, beta, [beta * c for c in c_rem], partners))
         return calls
+
+    def hamiltonian_call(self, k: int, rank: int) -> FactorCall:
+        """y = H x of interval k on rank `rank` in the form of a factor pass (gamma = E_rank, beta = 1): what the gradient w.r.t.
+        the evaluation times contracts at the output of every sub-exponential."""
+        c_amp, c_det, e_rank, c_rem, partners = self._step_terms(k, rank)
+        return FactorCall(c_amp, c_det, complex(e_rank), 1.0 + 0.0j, [complex(c) for c in c_rem], partners)
 
 
 class NativeOps:
@@ -324,9 +335,23 @@ def run_distributed(prob: ShardedProblem, psi0_local: Tensor, tsave, group=None,
 # natively driven forward run: ONE call of rydiff_forward runs every step and every factor pass of the sharded trajectory
 # (include/rydiff.h, RydProblem.shard_bits); Python only posts the slab exchanges when the library asks for them.
 # ---------------------------------------------------------------------------------------------------------------------
+def _solver_code(solver) -> int:
+    """RydProblem.solver from None (KRYLOV_SE), a solver.SolverType or the native code itself."""
+    from . import _native
+
+    if solver is None:
+        return _native.SOLVER_KRYLOV_SE
+    if isinstance(solver, int):
+        return solver
+    from .solver import _SOLVER_CODE
+
+    return _SOLVER_CODE[solver]
+
+
 def _native_problem(prob: ShardedProblem, psi_slabs: Tensor, tsave, rank_first: int, obs_slabs: Optional[Tensor],
-                    recv: Optional[list], exchange: Optional[Callable]):
-    """The RydProblem of a state-sharded call (slabs of this call = its "trajectories") and the objects that must outlive it."""
+                    recv: Optional[list], exchange: Optional[Callable], solver=None):
+    """The RydProblem of a state-sharded call (slabs of this call = its "trajectories") and the objects that must outlive it.
+    solver: a solver.SolverType (or its native code), default KRYLOV_SE."""
     from . import _native
 
     dev = psi_slabs.device
@@ -351,7 +376,7 @@ def _native_problem(prob: ShardedProblem, psi_slabs: Tensor, tsave, rank_first: 
     p.det_tables = det.data_ptr() if len(det_masks) else None
     p.u_pairs = u.data_ptr() if u.numel() else None
     p.n_tsave, p.tsave = len(ts), ts.ctypes.data
-    p.solver, p.tol = _native.SOLVER_KRYLOV_SE, prob.tol
+    p.solver, p.tol = _solver_code(solver), prob.tol
     obs = None
     if obs_slabs is not None:
         obs = obs_slabs.to(torch.float64).contiguous().reshape(1, ranks_here, dloc)
@@ -371,13 +396,14 @@ def _native_problem(prob: ShardedProblem, psi_slabs: Tensor, tsave, rank_first: 
 
 
 def _native_forward(prob: ShardedProblem, psi_slabs: Tensor, tsave, rank_first: int, obs_slabs: Optional[Tensor],
-                    recv: Optional[list], exchange: Optional[Callable], lookup: Optional[list] = None) -> tuple[Tensor, Optional[Tensor], dict]:
+                    recv: Optional[list], exchange: Optional[Callable], lookup: Optional[list] = None,
+                    solver=None) -> tuple[Tensor, Optional[Tensor], dict]:
     """psi_slabs: (ranks_here, 2^(N-g)) on the GPU; obs_slabs: (ranks_here, 2^(N-g)) or None.  Returns the final slabs, the
     PARTIAL <O>(t_k) summed over the slabs of this call (n_tsave,) and the plan statistics."""
     from . import _native
 
     L = _native.lib()
-    p, psi, ts, _amp, _det, _u, obs, keep = _native_problem(prob, psi_slabs, tsave, rank_first, obs_slabs, recv, exchange)
+    p, psi, ts, _amp, _det, _u, obs, keep = _native_problem(prob, psi_slabs, tsave, rank_first, obs_slabs, recv, exchange, solver)
     p.final_state_only = 1
     dev = psi.device
     ranks_here = psi.shape[0]
@@ -401,16 +427,18 @@ def _native_forward(prob: ShardedProblem, psi_slabs: Tensor, tsave, rank_first: 
 
 
 def _native_value_and_grad(prob: ShardedProblem, psi_slabs: Tensor, tsave, rank_first: int, obs_slabs: Tensor, grad_expect,
-                           recv: Optional[list], exchange: Optional[Callable], lookup: Optional[list] = None, tape: int = 1) -> dict:
+                           recv: Optional[list], exchange: Optional[Callable], lookup: Optional[list] = None, tape: int = 1,
+                           time_grad: bool = False, solver=None) -> dict:
     """Forward + adjoint sweep of a state-sharded run in TWO native calls (rydiff_forward with the trajectory kept in the workspace
     tape, rydiff_backward): the library walks every factor of the reverse sweep itself — the cotangent slabs take the same
     hypercube exchange as the state slabs (same callback), the drive gradients of the rank qubits are contracted with the partner
     slabs inside the completing launch.  Returns this call's PARTIAL sums: expect (n_tsave,), g_amp, g_det, g_u (to be summed over
-    the ranks by the caller) and the cotangent slabs w.r.t. psi0."""
+    the ranks by the caller) and the cotangent slabs w.r.t. psi0.  time_grad: also "g_tsave" (n_tsave,), the gradient w.r.t. the
+    evaluation times — a PARTIAL sum like the others (one more streaming pass per exponential, no additional slab exchange)."""
     from . import _native
 
     L = _native.lib()
-    p, psi, ts, amp, det, u, obs, keep = _native_problem(prob, psi_slabs, tsave, rank_first, obs_slabs, recv, exchange)
+    p, psi, ts, amp, det, u, obs, keep = _native_problem(prob, psi_slabs, tsave, rank_first, obs_slabs, recv, exchange, solver)
     dev = psi.device
     ranks_here = psi.shape[0]
     n_t = len(ts)
@@ -427,6 +455,7 @@ def _native_value_and_grad(prob: ShardedProblem, psi_slabs: Tensor, tsave, rank_
         g_det = torch.zeros_like(det)
         g_u = torch.zeros_like(u)
         g_psi0 = torch.zeros_like(psi)
+        g_tsave = torch.zeros(n_t, dtype=torch.float64, device=dev) if time_grad else None
         keep.append(workspace)
         if lookup is not None:
             lookup[:] = [psi, workspace]
@@ -436,20 +465,24 @@ def _native_value_and_grad(prob: ShardedProblem, psi_slabs: Tensor, tsave, rank_
         _native.check(L.rydiff_backward(ctypes.byref(p), ctypes.byref(info), None, None, ctypes.c_void_p(gexp.data_ptr()),
                                         ctypes.c_void_p(g_amp.data_ptr()) if amp.shape[1] else None,
                                         ctypes.c_void_p(g_det.data_ptr()) if det.shape[1] else None,
-                                        ctypes.c_void_p(g_u.data_ptr()) if u.numel() else None, None, ctypes.c_void_p(g_psi0.data_ptr()),
+                                        ctypes.c_void_p(g_u.data_ptr()) if u.numel() else None,
+                                        ctypes.c_void_p(g_tsave.data_ptr()) if time_grad else None, ctypes.c_void_p(g_psi0.data_ptr()),
                                         ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), tape, stream))
         torch.cuda.current_stream(dev).synchronize()  # (the host-side arrays in `keep` may go once the queue has drained)
-    return {"expect": expect[0].sum(dim=1), "g_amp": g_amp[0], "g_det": g_det[0], "g_u": g_u, "g_psi0": g_psi0,
-            "stats": {"degree": info.degree, "total_factors": info.total_factors, "kernel_family": _native.KERNEL_FAMILIES[info.kernel_family],
-                      "kernel_fwd": info.kernel_fwd.decode(), "kernel_bwd": info.kernel_bwd.decode(), "tape_mode": info.tape_mode}}
+    out = {"expect": expect[0].sum(dim=1), "g_amp": g_amp[0], "g_det": g_det[0], "g_u": g_u, "g_psi0": g_psi0,
+           "stats": {"degree": info.degree, "total_factors": info.total_factors, "kernel_family": _native.KERNEL_FAMILIES[info.kernel_family],
+                     "kernel_fwd": info.kernel_fwd.decode(), "kernel_bwd": info.kernel_bwd.decode(), "tape_mode": info.tape_mode}}
+    if time_grad:
+        out["g_tsave"] = g_tsave
+    return out
 
 
-def run_virtual_native(prob: ShardedProblem, psi0: Tensor, tsave, obs_diag: Optional[Tensor] = None):
+def run_virtual_native(prob: ShardedProblem, psi0: Tensor, tsave, obs_diag: Optional[Tensor] = None, solver=None):
     """All 2^g ranks on this device, the whole trajectory in ONE native call (partners are read in place).
-    Returns (final state (2^N,), <O>(t_k) or None, stats)."""
+    solver: a solver.SolverType (or its native code), default KRYLOV_SE.  Returns (final state (2^N,), <O>(t_k) or None, stats)."""
     dloc = 1 << prob.n_local
     final, expect, stats = _native_forward(prob, psi0.reshape(prob.world, dloc), tsave, 0,
-                                           None if obs_diag is None else obs_diag.reshape(prob.world, dloc), None, None)
+                                           None if obs_diag is None else obs_diag.reshape(prob.world, dloc), None, None, solver=solver)
     return final.reshape(-1), expect, stats
 
 
@@ -462,7 +495,7 @@ def _hypercube_exchange(prob: ShardedProblem, psi0_local: Tensor, rank: int, gro
 
     g = prob.n_gpu_bits
     recv = [torch.empty_like(psi0_local, dtype=torch.complex128) for _ in range(g)]  # recv[k]: slab of rank ^ (1 << k)
-    state = {"works": [], "error": None, "staged": []}
+    state = {"works": [], "error": None, "staged": [], "posts": 0}  # posts: phase-0 calls = slab exchanges of this run
     lookup: list = []
     via_host = dist.get_backend(group) == "gloo"  # tests on one GPU: gloo moves host buffers
 
@@ -477,6 +510,7 @@ def _hypercube_exchange(prob: ShardedProblem, psi0_local: Tensor, rank: int, gro
     def exchange(_user, phase, src, nbytes):
         try:
             if phase == 0:
+                state["posts"] += 1
                 x = view_of(src, nbytes)
                 if via_host:
                     x = x.cpu()  # (synchronises: fine for the gloo tests)
@@ -504,7 +538,8 @@ def _hypercube_exchange(prob: ShardedProblem, psi0_local: Tensor, rank: int, gro
     return recv, exchange, lookup, state
 
 
-def run_distributed_native(prob: ShardedProblem, psi0_local: Tensor, tsave, group=None, obs_diag_local: Optional[Tensor] = None):
+def run_distributed_native(prob: ShardedProblem, psi0_local: Tensor, tsave, group=None, obs_diag_local: Optional[Tensor] = None,
+                           solver=None):
     """One process per GPU: the library runs the whole trajectory of this rank's slab in one call and asks — through the
     exchange callback — for the hypercube slab exchange before every completing pass; <O>(t_k) is all-reduced once at the end.
     Returns (final slab, <O>(t_k), stats)."""
@@ -516,7 +551,8 @@ def run_distributed_native(prob: ShardedProblem, psi0_local: Tensor, tsave, grou
     recv, exchange, lookup, state = _hypercube_exchange(prob, psi0_local, rank, group)
     try:
         final, expect, stats = _native_forward(prob, psi0_local.reshape(1, -1), tsave, rank,
-                                               None if obs_diag_local is None else obs_diag_local.reshape(1, -1), recv, exchange, lookup)
+                                               None if obs_diag_local is None else obs_diag_local.reshape(1, -1), recv, exchange, lookup,
+                                               solver=solver)
     except RuntimeError:
         if state["error"] is not None:
             raise state["error"]
@@ -529,19 +565,27 @@ def run_distributed_native(prob: ShardedProblem, psi0_local: Tensor, tsave, grou
 # ---------------------------------------------------------------------------------------------------------------------
 # gradients: exact discrete adjoint of the sharded factor chain
 # ---------------------------------------------------------------------------------------------------------------------
-def grad_virtual_native(prob: ShardedProblem, psi0: Tensor, tsave, obs_diag: Tensor, grad_expect) -> dict:
+def grad_virtual_native(prob: ShardedProblem, psi0: Tensor, tsave, obs_diag: Tensor, grad_expect, time_grad: bool = False,
+                        solver=None) -> dict:
     """Value and gradients of  sum_k grad_expect[k] <O>(t_k)  with all 2^g ranks on this device and the WHOLE reverse sweep driven by
     the library (the Python-scheduled `grad_virtual` below stays as the CPU-testable reference of the same
-    algorithm).  Returns {"expect", "g_amp", "g_det", "g_u", "g_psi0" (2^N,)} as numpy / torch like grad_virtual."""
+    algorithm).  Returns {"expect", "g_amp", "g_det", "g_u", "g_psi0" (2^N,)} as numpy / torch like grad_virtual; time_grad: also
+    "g_tsave" (n_tsave,) numpy.  solver: a solver.SolverType (or its native code), default KRYLOV_SE."""
     dloc = 1 << prob.n_local
-    out = _native_value_and_grad(prob, psi0.reshape(prob.world, dloc), tsave, 0, obs_diag.reshape(prob.world, dloc), grad_expect, None, None)
-    return {"expect": out["expect"], "g_amp": out["g_amp"].cpu().numpy(), "g_det": out["g_det"].cpu().numpy(),
-            "g_u": out["g_u"].cpu().numpy(), "g_psi0": out["g_psi0"].reshape(-1), "stats": out["stats"]}
+    out = _native_value_and_grad(prob, psi0.reshape(prob.world, dloc), tsave, 0, obs_diag.reshape(prob.world, dloc), grad_expect, None, None,
+                                 time_grad=time_grad, solver=solver)
+    res = {"expect": out["expect"], "g_amp": out["g_amp"].cpu().numpy(), "g_det": out["g_det"].cpu().numpy(),
+           "g_u": out["g_u"].cpu().numpy(), "g_psi0": out["g_psi0"].reshape(-1), "stats": out["stats"]}
+    if time_grad:
+        res["g_tsave"] = out["g_tsave"].cpu().numpy()
+    return res
 
 
-def grad_distributed_native(prob: ShardedProblem, psi0_local: Tensor, tsave, obs_diag_local: Tensor, grad_expect, group=None) -> dict:
+def grad_distributed_native(prob: ShardedProblem, psi0_local: Tensor, tsave, obs_diag_local: Tensor, grad_expect, group=None,
+                            time_grad: bool = False, solver=None) -> dict:
     """One process per GPU: every rank runs the native forward + reverse sweep on its slab; state AND cotangent slabs travel through
-    the hypercube exchange callback; the (tiny) expectation values and gradient arrays are all-reduced ONCE at the end."""
+    the hypercube exchange callback; the (tiny) expectation values and gradient arrays are all-reduced ONCE at the end (time_grad:
+    "g_tsave" rides in the same all-reduce).  stats["exchange_posts"]: slab exchanges posted by this run, forward and reverse."""
     import torch.distributed as dist
 
     rank, world = dist.get_rank(group), dist.get_world_size(group)
@@ -550,18 +594,22 @@ def grad_distributed_native(prob: ShardedProblem, psi0_local: Tensor, tsave, obs
     recv, exchange, lookup, state = _hypercube_exchange(prob, psi0_local, rank, group)
     try:
         out = _native_value_and_grad(prob, psi0_local.reshape(1, -1), tsave, rank, obs_diag_local.reshape(1, -1), grad_expect,
-                                     recv, exchange, lookup)
+                                     recv, exchange, lookup, time_grad=time_grad, solver=solver)
     except RuntimeError:
         if state["error"] is not None:
             raise state["error"]
         raise
     flat = torch.cat([out["expect"].reshape(-1), torch.view_as_real(out["g_amp"].contiguous()).reshape(-1), out["g_det"].reshape(-1),
-                      out["g_u"].reshape(-1)])
+                      out["g_u"].reshape(-1)] + ([out["g_tsave"]] if time_grad else []))
     dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
-    n_e, n_a, n_d = out["expect"].numel(), 2 * out["g_amp"].numel(), out["g_det"].numel()
-    return {"expect": flat[:n_e], "g_amp": torch.view_as_complex(flat[n_e:n_e + n_a].clone().reshape(*out["g_amp"].shape, 2)).cpu().numpy(),
-            "g_det": flat[n_e + n_a:n_e + n_a + n_d].reshape(out["g_det"].shape).cpu().numpy(),
-            "g_u": flat[n_e + n_a + n_d:].cpu().numpy(), "g_psi0": out["g_psi0"].reshape(-1), "stats": out["stats"]}
+    n_e, n_a, n_d, n_u = out["expect"].numel(), 2 * out["g_amp"].numel(), out["g_det"].numel(), out["g_u"].numel()
+    res = {"expect": flat[:n_e], "g_amp": torch.view_as_complex(flat[n_e:n_e + n_a].clone().reshape(*out["g_amp"].shape, 2)).cpu().numpy(),
+           "g_det": flat[n_e + n_a:n_e + n_a + n_d].reshape(out["g_det"].shape).cpu().numpy(),
+           "g_u": flat[n_e + n_a + n_d:n_e + n_a + n_d + n_u].cpu().numpy(), "g_psi0": out["g_psi0"].reshape(-1),
+           "stats": dict(out["stats"], exchange_posts=state["posts"])}
+    if time_grad:
+        res["g_tsave"] = flat[n_e + n_a + n_d + n_u:].cpu().numpy()
+    return res
 
 
 class _VirtualFabric:
@@ -608,7 +656,7 @@ class _DistFabric:
 
 
 def _value_and_grad(prob: ShardedProblem, tsave, fabric, psi_slabs: list, obs_slabs: list, grad_expect,
-                    ops_factory: Optional[Callable]) -> dict:
+                    ops_factory: Optional[Callable], time_grad: bool = False) -> dict:
     """Forward with a tape of every factor input (slab-sized entries), then the reverse sweep.
 
     Loss: L = sum_k grad_expect[k] * <psi(t_k)|O|psi(t_k)> for the diagonal observable O.  Per factor
@@ -617,7 +665,13 @@ def _value_and_grad(prob: ShardedProblem, tsave, fabric, psi_slabs: list, obs_sl
       dL/dRe c = Re(beta z1), dL/dIm c = Im(beta z2),  z1 = <F mu, x>, z2 = <F_signed mu, x>   -> amplitude terms
     where the flips of the local qubits are formed by a local pass without diagonal (F_k mu), and the flip of a GPU qubit is
     the partner rank's cotangent slab, i.e. a plain inner product.  mu <- (conj(gamma) + conj(beta) H) mu is the forward pass
-    with conjugated scalars (H is Hermitian).  Contractions are per-rank partial sums; the gradient arrays are all-reduced."""
+    with conjugated scalars (H is Hermitian).  Contractions are per-rank partial sums; the gradient arrays are all-reduced.
+
+    time_grad: also "g_tsave" (n_tsave,), the gradient w.r.t. the evaluation times.  Interval k = nsub[k] exponentials of duration
+    (t_{k+1} - t_k) / nsub[k] with the tables interpolated at t_{k+1}.  Duration: dL/dtau_sub = Im<mu, H x_out> at the output of every
+    sub-exponential, formed as Im<H mu, x_out> (H Hermitian) because the partners' cotangent slabs are here anyway (the exchange of
+    the adjoint pass that follows) while their x_out would take one more exchange; + to t_{k+1}, - to t_k.  Interpolation: the
+    coefficient gradients times the slope of the tables at t_{k+1} (zero where the interpolation clamps)."""
     plan = ShardedPlan(prob, np.asarray(tsave), _design_native)
     g, nl = prob.n_gpu_bits, prob.n_local
     dloc = 1 << nl
@@ -673,8 +727,12 @@ def _value_and_grad(prob: ShardedProblem, tsave, fabric, psi_slabs: list, obs_sl
     mus = [2.0 * gexp[T] * o * x for o, x in zip(obs_slabs, xs)]
     scratch = [torch.empty_like(x) for x in xs]
     fidx = len(tape)
+    g_ts = np.zeros(T + 1)  # per-rank partial sums, like g_amp / g_det until the all-reduce
+    x_out = xs              # output of the factor walked next (= the input of the one walked last)
     for k in reversed(range(T)):
         calls = step_calls[k]
+        h_calls = [plan.hamiltonian_call(k, r) for r in fabric.ranks] if time_grad else None
+        tau_sum = 0.0
         acc_loc = np.zeros(n_loc_terms, dtype=np.complex128)  # (dL/dRe c, dL/dIm c) of the local part of each term
         acc_q = np.zeros(g, dtype=np.complex128)               # same for the flip of each GPU qubit
         rsum = [torch.zeros(dloc, dtype=torch.float64, device=device) for _ in fabric.ranks]
@@ -682,6 +740,11 @@ def _value_and_grad(prob: ShardedProblem, tsave, fabric, psi_slabs: list, obs_sl
             fidx -= 1
             x_in = tape[fidx]
             rem = fabric.exchange(mus, partners_of)
+            if time_grad and i % plan.degree == plan.degree - 1:  # output of a sub-exponential
+                for j in range(len(fabric.ranks)):
+                    h_mu = ops[j].apply(h_calls[j], mus[j], rem[j], scratch[j])
+                    tau_sum += float(torch.vdot(h_mu, x_out[j]).imag)
+            x_out = x_in
             new_mus = []
             for j, r in enumerate(fabric.ranks):
                 c, mu, x = calls[j][i], mus[j], x_in[j]
@@ -720,6 +783,15 @@ def _value_and_grad(prob: ShardedProblem, tsave, fabric, psi_slabs: list, obs_sl
             if arr.shape[0]:
                 arr[:, i1] += (1.0 - frac) * gt
                 arr[:, i2] += frac * gt
+        if time_grad:
+            slope = 0.0  # d coefficient / d t_{k+1}, linear in the (per-rank partial) coefficient gradients
+            if ka:
+                d_amp = (prob.amp_tables[:, i2] - prob.amp_tables[:, i1]) / prob.dt
+                slope += float((g_term.real * d_amp.real + g_term.imag * d_amp.imag).sum())
+            if kd:
+                slope += float((g_dterm * (prob.det_tables[:, i2] - prob.det_tables[:, i1]) / prob.dt).sum())
+            g_ts[k + 1] += tau_sum / plan.nsub[k] + slope
+            g_ts[k] -= tau_sum / plan.nsub[k]
         if gexp[k] != 0.0:
             mus = [mu + 2.0 * gexp[k] * o * x for mu, o, x in zip(mus, obs_slabs, tape[fidx])]
 
@@ -740,31 +812,36 @@ def _value_and_grad(prob: ShardedProblem, tsave, fabric, psi_slabs: list, obs_sl
             else:
                 v = pair[a - g, b - g]
             g_u[_pair_index(n, a, b)] += v
-    packed = torch.as_tensor(np.concatenate([g_amp.real.ravel(), g_amp.imag.ravel(), g_det.ravel(), g_u]), device=device)
+    parts = [g_amp.real.ravel(), g_amp.imag.ravel(), g_det.ravel(), g_u] + ([g_ts] if time_grad else [])
+    packed = torch.as_tensor(np.concatenate(parts), device=device)
     packed = fabric.allreduce_(packed).cpu().numpy()
     na = ka * ns
     g_amp = (packed[:na] + 1j * packed[na:2 * na]).reshape(ka, ns)
     g_det = packed[2 * na:2 * na + kd * ns].reshape(kd, ns)
-    g_u = packed[2 * na + kd * ns:]
-    return {"final": xs, "expect": torch.stack(expect), "g_amp": g_amp, "g_det": g_det, "g_u": g_u, "g_psi0": mus}
+    g_u = packed[2 * na + kd * ns:2 * na + kd * ns + len(g_u)]
+    out = {"final": xs, "expect": torch.stack(expect), "g_amp": g_amp, "g_det": g_det, "g_u": g_u, "g_psi0": mus}
+    if time_grad:
+        out["g_tsave"] = packed[2 * na + kd * ns + len(g_u):]
+    return out
 
 
 def grad_virtual(prob: ShardedProblem, psi0: Tensor, tsave, obs_diag: Tensor, grad_expect,
-                 ops_factory: Optional[Callable] = None) -> dict:
+                 ops_factory: Optional[Callable] = None, time_grad: bool = False) -> dict:
     """All G ranks inside this process: value and gradients of L = sum_k grad_expect[k] <O>(t_k).  Returns expect [n_t],
-    g_amp [K_a, n] (dL/dRe + i dL/dIm), g_det [K_d, n], g_u [pairs], final / g_psi0 (2^N,)."""
+    g_amp [K_a, n] (dL/dRe + i dL/dIm), g_det [K_d, n], g_u [pairs], final / g_psi0 (2^N,); time_grad: also g_tsave [n_t]."""
     dloc = 1 << prob.n_local
     fabric = _VirtualFabric(prob)
     out = _value_and_grad(prob, tsave, fabric, [psi0[r * dloc:(r + 1) * dloc] for r in fabric.ranks],
-                          [obs_diag[r * dloc:(r + 1) * dloc] for r in fabric.ranks], grad_expect, ops_factory)
+                          [obs_diag[r * dloc:(r + 1) * dloc] for r in fabric.ranks], grad_expect, ops_factory, time_grad)
     out["final"], out["g_psi0"] = torch.cat(out["final"]), torch.cat(out["g_psi0"])
     return out
 
 
 def grad_distributed(prob: ShardedProblem, psi0_local: Tensor, tsave, obs_diag_local: Tensor, grad_expect, group=None,
-                     ops_factory: Optional[Callable] = None) -> dict:
-    """One process per GPU: same as ``grad_virtual`` with this rank's slabs; the gradient arrays are identical on all ranks."""
+                     ops_factory: Optional[Callable] = None, time_grad: bool = False) -> dict:
+    """One process per GPU: same as ``grad_virtual`` with this rank's slabs; the gradient arrays (g_tsave included: it travels in
+    the same all-reduce) are identical on all ranks."""
     fabric = _DistFabric(prob, group)
-    out = _value_and_grad(prob, tsave, fabric, [psi0_local], [obs_diag_local], grad_expect, ops_factory)
+    out = _value_and_grad(prob, tsave, fabric, [psi0_local], [obs_diag_local], grad_expect, ops_factory, time_grad)
     out["final"], out["g_psi0"] = out["final"][0], out["g_psi0"][0]
     return out
