@@ -61,6 +61,7 @@ extern "C" {
 #define RYDIFF_MAX_QUBITS 30
 #define RYDIFF_MAX_PAIR_TERMS 28
 #define RYDIFF_MAX_TERMS 64
+#define RYDIFF_MAX_PAULI_STRINGS 1024 /* Pauli strings of one call, over all Pauli observables (after any frame rotation) */
 
 enum { RYDIFF_OK = 0, RYDIFF_EINVAL = -1, RYDIFF_EWORKSPACE = -2, RYDIFF_EHIP = -3, RYDIFF_ENOTIMPL = -4 };
 
@@ -196,6 +197,26 @@ typedef struct RydProblem {
      * caller sizes it to the HBM that is free (rydiff_plan reports the workspace for the value given): what the full tape of
      * need_tape = 2 does for a run that fits, this does for the part of a run that fits. */
     int32_t tape_steps;
+
+    /* PAULI-STRING observables, evaluated at every tsave next to the diagonal ones and differentiated by rydiff_backward:
+     *   O_o = sum_{s = pauli_first[o]}^{pauli_first[o+1]-1} w_s P_s,   w_s real,   P_s = (x)_j sigma_j,  sigma_j in {I, X, Y, Z}
+     * in the basis order of the register (index bit 0 = first basis state r, bit 1 = g): X = [[0,1],[1,0]], Y = [[0,-i],[i,0]],
+     * Z = diag(+1,-1).  A string is two qubit masks in the convention of amp_masks (bit j = qubit j; qubit 0 = most significant
+     * bit of the amplitude index): pauli_x = the qubits carrying X or Y, pauli_z = the qubits carrying Z or Y.  With xm, zm the
+     * same masks moved to amplitude-index bits (qubit j <-> bit N-1-j) and ny = popcount(x & z), since Y = i X Z:
+     *   (P psi)[y] = i^ny * (-1)^popcount((y ^ xm) & zm) * psi[y ^ xm],     <O> = sum_s w_s sum_y Re( conj(psi[y]) (P_s psi)[y] )
+     * No 2^N table: strings with x = 0 are diagonal observables given by one integer.  expect_out and grad_expect become
+     * [n_obs + n_pauli_obs][n_tsave][B], the diagonal observables first.  The arrays are HOST memory (the planner groups the strings by
+     * flip mask); they reach the device as kernel arguments, so forward / backward with a RydPlanInfo stay asynchronous.
+     * Values are produced while the state is on the device: allowed with final_state_only and with states_out == NULL and no tape.
+     * The gradient rides the grad_states route of rydiff_backward (the cotangent 2 * sum_o g_o O_o psi_k is formed per save point
+     * in the workspace).  Not together with shard_bits > 0 (RYDIFF_ENOTIMPL); pair terms are fine.  n_pauli_obs = 0: nothing changes. */
+    int32_t n_pauli_obs;            /* 0: none */
+    int32_t n_pauli_strings;        /* 0 .. RYDIFF_MAX_PAULI_STRINGS */
+    const int32_t* pauli_first;     /* HOST [n_pauli_obs + 1], non-decreasing, pauli_first[0] = 0, pauli_first[n_pauli_obs] = n_pauli_strings */
+    const uint32_t* pauli_x;        /* HOST [n_pauli_strings] */
+    const uint32_t* pauli_z;        /* HOST [n_pauli_strings] */
+    const double* pauli_w;          /* HOST [n_pauli_strings] */
 } RydProblem;
 
 /* Result of rydiff_plan(): everything that depends on the VALUES in the coefficient tables. */
@@ -248,7 +269,7 @@ int rydiff_plan(const RydProblem* p, int need_tape, int need_backward, void* scr
  *   states_out  DEVICE complex128 [n_tsave][B][2^N], or NULL (trajectory kept in the workspace tape if need_tape).
  *               With need_tape = 2 / 3 AND states_out the factor outputs go to the (granted) workspace tape and the states at the
  *               save points are copied out of it — stored states plus a later gradient without (or with less) recomputation.
- *   expect_out  DEVICE float64 [n_obs][n_tsave][B], or NULL */
+ *   expect_out  DEVICE float64 [n_obs + n_pauli_obs][n_tsave][B] (diagonal observables first), or NULL */
 int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi0, void* states_out, double* expect_out,
                    void* workspace, size_t workspace_bytes, int need_tape, void* stream);
 
@@ -259,7 +280,7 @@ int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi
  *   states       DEVICE: the states_out of the forward call, or NULL to use the workspace tape (with need_tape = 2 / 3 the
  *                granted workspace tape is used even when states is given)
  *   grad_states  DEVICE complex128 [n_tsave][B][2^N] or NULL
- *   grad_expect  DEVICE float64 [n_obs][n_tsave][B] or NULL
+ *   grad_expect  DEVICE float64 [n_obs + n_pauli_obs][n_tsave][B] or NULL
  *   g_amp        DEVICE complex128 [coeff_batch][n_amp_terms][n_samples] or NULL   (overwritten)
  *   g_det        DEVICE float64    [coeff_batch][n_det_terms][n_samples] or NULL   (overwritten)
  *   g_u          DEVICE float64 [N(N-1)/2] or NULL  (dist_grad, backend.py:456-460 / hamiltonian.py:341-344)

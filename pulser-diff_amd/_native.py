@@ -27,6 +27,7 @@ PLAN_SCRATCH_BYTES = 1024
 KERNEL_FAMILIES = ("lanes", "persistent", "direct", "chained-tiles")
 MAX_QUBITS = 30
 MAX_TERMS = 64
+MAX_PAULI_STRINGS = 1024
 
 
 class RydProblem(ctypes.Structure):
@@ -64,6 +65,12 @@ class RydProblem(ctypes.Structure):
         ("det_ones_terms", ctypes.c_uint64),
         ("dp5_piece_refine", ctypes.c_void_p),
         ("tape_steps", ctypes.c_int32),
+        ("n_pauli_obs", ctypes.c_int32),
+        ("n_pauli_strings", ctypes.c_int32),
+        ("pauli_first", ctypes.c_void_p),
+        ("pauli_x", ctypes.c_void_p),
+        ("pauli_z", ctypes.c_void_p),
+        ("pauli_w", ctypes.c_void_p),
     ]
 
 

@@ -34,6 +34,7 @@ from .result import SampledResult
 from .simconfig import SimConfig
 from .simresults import CoherentResults, NoisyResults, SimulationResults
 from .solver import ProblemSpec, SolverType, evolve, sesolve, tolerance_from_options
+from .observables import PauliObservable
 from .utils import DiagonalObservable
 
 
@@ -242,6 +243,11 @@ class TorchEmulator:
     def build_operator(self, operations) -> Tensor:
         return self._hamiltonian.build_operator(operations)
 
+    def build_observable(self, operations) -> PauliObservable:
+        """``build_operator`` as a sum of Pauli strings (no 2^N x 2^N tensor: any register size), for ``run(observables=[...])``,
+        ``results.expect`` and ``QuantumModel.expectation``."""
+        return self._hamiltonian.build_observable(operations)
+
     def get_hamiltonian(self, time: float) -> Tensor:
         """backend.py:401-427 (explicit matrix; small registers)."""
         if time > self._tot_duration:
@@ -259,8 +265,9 @@ class TorchEmulator:
             observables: Optional[list] = None, store_states: bool = True, **options: Any) -> SimulationResults:
         """Simulates the sequence with the native solver and returns ``CoherentResults``.
 
-        ``observables`` (extension): diagonal observables (``DiagonalObservable`` or dense diagonal tensors) to be
-        evaluated natively at every evaluation time; ``store_states=False`` keeps the trajectory out of the results.
+        ``observables`` (extension): diagonal observables (``DiagonalObservable`` or dense diagonal tensors) and sums of Pauli
+        strings (``PauliObservable``, e.g. from ``build_observable``) to be evaluated natively at every evaluation time;
+        ``store_states=False`` keeps the trajectory out of the results.
         """
         if time_grad:
             self._eval_times_array.requires_grad_(True)  # backend.py:453-455
@@ -285,8 +292,16 @@ class TorchEmulator:
 
         dev = self._compute_device
         ham = self._hamiltonian
-        obs_tensors, obs_objs = [], []
+        obs_tensors, obs_objs, pauli_objs = [], [], []
         for obs in observables or []:
+            if isinstance(obs, PauliObservable):
+                if ham.basis_name == "all":
+                    raise NotImplementedError("Pauli observables are not available in the three-level all-basis; use "
+                                              "results.expect on stored states.")
+                if obs.n_qubits != ham._size:
+                    raise ValueError(f"PauliObservable on {obs.n_qubits} qubits handed to a register of {ham._size}")
+                pauli_objs.append(obs)
+                continue
             if isinstance(obs, DiagonalObservable):
                 diag = obs.diag
             elif isinstance(obs, Tensor) and obs.ndim == 2:
@@ -295,7 +310,7 @@ class TorchEmulator:
                     raise ValueError("Only diagonal observables can be evaluated natively; use results.expect on the states.")
                 diag = torch.diagonal(dense).real
             else:
-                raise TypeError("observables must be DiagonalObservable objects or diagonal (dim, dim) tensors")
+                raise TypeError("observables must be DiagonalObservable / PauliObservable objects or diagonal (dim, dim) tensors")
             obs_tensors.append(diag.to(dev, torch.float64))
             obs_objs.append(obs)
         obs_diag = torch.stack(obs_tensors) if obs_tensors else None
@@ -321,12 +336,12 @@ class TorchEmulator:
                 return CoherentResults(rho, ham._size, ham.basis_name, self._eval_times_array, self._meas_basis, meas_errors,
                                        atom_order=tuple(ham._qdict), stats=stats, density=True)
             result = sesolve(ham, psi0.to(dev), self._eval_times_array, solver=solver, options=options, obs_diag=obs_diag,
-                             store_states=store_states)
+                             store_states=store_states, pauli_obs=pauli_objs)
             states_tbd = result.states.permute(0, 2, 1) if result.states.numel() else result.states
             return CoherentResults(states_tbd, ham._size, ham.basis_name, self._eval_times_array, self._meas_basis,
                                    meas_errors, atom_order=tuple(ham._qdict),
-                                   native_expect=result.expect if obs_diag is not None else None,
-                                   native_observables=obs_objs, stats=result.stats)
+                                   native_expect=result.expect if (obs_diag is not None or pauli_objs) else None,
+                                   native_observables=obs_objs + pauli_objs, stats=result.stats)
 
         # does the noise ask for averaging over several runs?  (backend.py:531-569)
         no_resampling = noise <= {"dephasing", "relaxation", "SPAM", "depolarizing", "eff_noise", "amplitude"} and (

@@ -44,6 +44,19 @@ struct Groups {
     int nq[kMaxGroups] = {0};             // detuning groups: qubits in the group (count is 0 for a ones-counting group)
 };
 
+// Pauli-string observables as the kernels read them (pauli_kernels.hpp): the strings of every observable grouped by flip mask
+struct PauliGroup {
+    uint32_t xm;            // flip mask in amplitude-index bits
+    uint32_t first, count;  // its strings in the string table
+    uint32_t layout;        // who evaluates it: tile layout 0 / 1 (k_pauli_expect_tile) or kPauliDirect (k_pauli_expect_direct)
+};
+constexpr uint32_t kPauliDirect = 255;
+struct PauliString {
+    double wr, wi;  // w_s * i^ny
+    uint32_t zm;    // sign mask in amplitude-index bits
+    uint32_t pad;
+};
+
 struct Plan {
     int N = 0;       // qubits of the whole register
     int NL = 0;      // qubits that index a vector of this call: N, or N - shard_bits for a state-sharded run (slabs)
@@ -63,6 +76,17 @@ struct Plan {
     std::vector<double> pair_tab;
     double pair_radius = 0.0;  // Gershgorin radius of the pair terms (sum over terms of the largest absolute row sum)
     size_t off_pair = 0;
+    // Pauli-string observables: groups of observable o are [pauli_gfirst[o], pauli_gfirst[o + 1])
+    int n_pobs = 0;
+    std::vector<int32_t> pauli_gfirst;
+    std::vector<PauliGroup> pauli_groups;
+    std::vector<PauliString> pauli_strings;
+    bool pauli_work[3] = {false, false, false};  // some group is evaluated in tile layout 0 / in tile layout 1 / by the direct kernel
+    size_t off_pauli = 0, off_pauli_traj = 0, off_pauli_cot = 0;
+    size_t pauli_gfirst_bytes() const { return (pauli_gfirst.size() * sizeof(int32_t) + 7) / 8 * 8; }
+    size_t pauli_bytes() const {
+        return n_pobs ? pauli_gfirst_bytes() + pauli_groups.size() * sizeof(PauliGroup) + pauli_strings.size() * sizeof(PauliString) : 0;
+    }
 
     // workspace offsets (bytes)
     size_t off_meta_idx = 0, off_coef = 0, off_stats = 0, off_udiag = 0, off_buf0 = 0, off_buf1 = 0;
@@ -114,6 +138,84 @@ inline bool build_groups(int N, int n_terms, const uint32_t* masks, Groups& g, s
             return false;
         }
     }
+    return true;
+}
+
+inline uint32_t to_index_mask(uint32_t qubit_mask, int N) {
+    uint32_t m = 0;
+    for (int j = 0; j < N; ++j)
+        if (qubit_mask >> j & 1u) m |= 1u << (N - 1 - j);
+    return m;
+}
+
+// RydProblem.pauli_* -> per-observable groups of strings that share a flip mask (one partner load per group)
+inline bool build_pauli(const RydProblem* p, Plan& pl, std::string& err) {
+    pl.n_pobs = 0;
+    pl.pauli_gfirst.clear();
+    pl.pauli_groups.clear();
+    pl.pauli_strings.clear();
+    if (p->n_pauli_obs < 0 || p->n_pauli_strings < 0) {
+        err = "negative Pauli observable / string count";
+        return false;
+    }
+    if (p->n_pauli_obs == 0) {
+        if (p->n_pauli_strings != 0) {
+            err = "Pauli strings without a Pauli observable";
+            return false;
+        }
+        return true;
+    }
+    const int no = p->n_pauli_obs, ns = p->n_pauli_strings;
+    if (ns > RYDIFF_MAX_PAULI_STRINGS || no > RYDIFF_MAX_PAULI_STRINGS) {
+        err = "too many Pauli strings / observables (max " + std::to_string(RYDIFF_MAX_PAULI_STRINGS) + ")";
+        return false;
+    }
+    if (!p->pauli_first || (ns > 0 && (!p->pauli_x || !p->pauli_z || !p->pauli_w))) {
+        err = "missing Pauli observable arrays (pauli_first / pauli_x / pauli_z / pauli_w)";
+        return false;
+    }
+    if (p->pauli_first[0] != 0 || p->pauli_first[no] != ns) {
+        err = "pauli_first must start at 0 and end at n_pauli_strings";
+        return false;
+    }
+    for (int o = 0; o < no; ++o)
+        if (p->pauli_first[o + 1] < p->pauli_first[o]) {
+            err = "pauli_first must be non-decreasing";
+            return false;
+        }
+    if (p->shard_bits > 0) {
+        err = "Pauli-string observables: not implemented together with state sharding";
+        return false;
+    }
+    const int N = p->n_qubits;
+    for (int s = 0; s < ns; ++s) {
+        if (N < 32 && (((p->pauli_x[s] | p->pauli_z[s]) >> N) != 0)) {
+            err = "Pauli string " + std::to_string(s) + " addresses a qubit >= n_qubits";
+            return false;
+        }
+        if (!std::isfinite(p->pauli_w[s])) {
+            err = "Pauli string " + std::to_string(s) + " has a non-finite weight";
+            return false;
+        }
+    }
+    pl.n_pobs = no;
+    pl.pauli_gfirst.assign(no + 1, 0);
+    for (int o = 0; o < no; ++o) {
+        pl.pauli_gfirst[o] = int32_t(pl.pauli_groups.size());
+        std::vector<int> order;
+        for (int s = p->pauli_first[o]; s < p->pauli_first[o + 1]; ++s) order.push_back(s);
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return p->pauli_x[a] < p->pauli_x[b]; });
+        for (size_t i = 0; i < order.size(); ++i) {
+            const int s = order[i];
+            if (i == 0 || p->pauli_x[s] != p->pauli_x[order[i - 1]])
+                pl.pauli_groups.push_back({to_index_mask(p->pauli_x[s], N), uint32_t(pl.pauli_strings.size()), 0u, kPauliDirect});
+            pl.pauli_groups.back().count += 1;
+            static const double ph[4][2] = {{1, 0}, {0, 1}, {-1, 0}, {0, -1}};  // i^ny
+            const int ny = __builtin_popcount(p->pauli_x[s] & p->pauli_z[s]) & 3;
+            pl.pauli_strings.push_back({p->pauli_w[s] * ph[ny][0], p->pauli_w[s] * ph[ny][1], to_index_mask(p->pauli_z[s], N), 0u});
+        }
+    }
+    pl.pauli_gfirst[no] = int32_t(pl.pauli_groups.size());
     return true;
 }
 
@@ -198,6 +300,7 @@ inline bool build_plan(const RydProblem* p, Plan& pl, std::string& err, double w
         pl.pair_radius += worst;
     }
     pl.N = p->n_qubits;
+    if (!build_pauli(p, pl, err)) return false;
     pl.shard_bits = p->shard_bits;
     if (pl.shard_bits < 0 || pl.shard_bits > 6 || pl.shard_bits >= pl.N) {
         err = "shard_bits must be in [0, min(6, n_qubits - 1)]";
@@ -410,6 +513,9 @@ inline size_t carve(Plan& pl, int tape_mode, bool need_backward, int chain_slots
         pl.off_pm_nsub = take(E * sizeof(int32_t));
     }
     pl.off_pair = take(size_t(pl.n_pair) * 64 * sizeof(double));
+    pl.off_pauli = take(pl.pauli_bytes());
+    // one-launch sweeps: the trajectory the Pauli observables are evaluated on where the caller keeps none
+    pl.off_pauli_traj = take((pl.n_pobs && pl.N <= 12) ? size_t(pl.T + 1) * pl.state_bytes : 0);
     pl.total_fwd = off;
     pl.tape_mode = tape_mode;
     if (tape_mode == 2) pl.off_tape = take(size_t(total_factors + 1) * pl.state_bytes);
@@ -420,6 +526,8 @@ inline size_t carve(Plan& pl, int tape_mode, bool need_backward, int chain_slots
         pl.off_chain = take(size_t(chain_slots > 0 ? chain_slots : 1) * pl.state_bytes);
         pl.off_ge = take(size_t(pl.Bc) * E * 64 /* kGradReplicas */ * (pl.NC + 1) * sizeof(double));
         pl.off_wtot = take(pl.dim * (pl.shard_bits ? size_t(pl.B) : 1) * sizeof(double));  // sharded: one weight slab per rank of the call
+        // Pauli cotangent grad_states[k] + 2 sum_o g_o O_o psi_k: one state, reused in stream order (one-launch adjoints: every k)
+        pl.off_pauli_cot = take(pl.n_pobs ? size_t(pl.N <= 12 ? pl.T + 1 : 1) * pl.state_bytes : 0);
         pl.off_meta2 = take(std::max(E * 40, size_t(pl.T + 1) * sizeof(int32_t)));  // StageBwdDev records, or the save-point flags of the one-launch adjoint
     }
     return off;

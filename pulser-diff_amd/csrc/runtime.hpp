@@ -149,6 +149,10 @@ int upload_words(hipStream_t stream, void* dst, const void* src, size_t bytes) {
     return RYDIFF_OK;
 }
 
+struct Runtime;
+void assign_pauli_layouts(Runtime& rt);                                  // pauli_launch.hpp
+int upload_pauli_tables(const Plan& pl, char* ws, hipStream_t stream);  // pauli_launch.hpp
+
 std::mutex g_poly_mutex;
 std::vector<PolyDesign> g_poly_cache;
 
@@ -405,6 +409,11 @@ int prepare(const RydProblem* p, const RydPlanInfo* info, void* workspace, size_
         if (rc) return rc;
         rt.parg.tab = reinterpret_cast<const double2*>(ws + pl.off_pair);
     }
+    if (pl.n_pobs) {
+        assign_pauli_layouts(rt);
+        rc = upload_pauli_tables(pl, ws, stream);
+        if (rc) return rc;
+    }
     if (pl.NC > 0) {
         ExpandArgs ea{};
         ea.amp = static_cast<const double2*>(p->amp_tables);
@@ -508,20 +517,35 @@ void shard_groups(const Plan& pl, int (&grp)[kShardMaxBits]) {
     }
 }
 
+// Cotangents of the Pauli-string observables: they ride the grad_states route — k_pauli_apply (pauli_launch.hpp) writes
+// grad_states[k] + 2 sum_o g_o O_o psi_k into a workspace buffer and the injecting launch reads that instead of grad_states[k]
+struct PauliInject {
+    const Runtime* rt = nullptr;
+    char* ws = nullptr;
+    hipStream_t stream = nullptr;
+    const double2* gstate = nullptr;  // the caller's grad_states or nullptr
+    const double* gexp = nullptr;     // &grad_expect[n_obs][0][0]
+    double2* buf = nullptr;           // one state (one-launch adjoints: n_tsave states)
+    std::function<const double2*(int)> state_at;  // the state at save point k
+};
+const double2* pauli_cotangent(const PauliInject& pi, int k);
+
 // cotangents handed to the backward call (fused injection, see ChainArgs / FactorBwdArgs)
 struct InjectSource {
     const double2* gstate = nullptr;  // grad_states [n_tsave][B][dim] or nullptr
     const double* gexp = nullptr;     // grad_expect [n_obs][n_tsave][B] or nullptr
     const double* obs = nullptr;      // [n_obs][dim]
     int n_obs = 0;
-    bool any() const { return gstate || gexp; }
+    const PauliInject* pauli = nullptr;  // Pauli observables with a cotangent: replaces gstate
+    bool any() const { return gstate || gexp || pauli; }
 };
 
 // the cotangents injected at save point k (fields of ChainArgs / Chain2BwdArgs / FactorBwdArgs); k < 0 or nothing handed in: none
 template <class Args>
 void fill_inject(Args& a, const InjectSource& inj, int k, const Plan& pl) {
     if (k < 0 || !inj.any()) return;
-    a.inj_gstate = inj.gstate ? inj.gstate + size_t(k) * pl.B * pl.dim : nullptr;
+    if (inj.pauli) a.inj_gstate = pauli_cotangent(*inj.pauli, k);  // (enqueued ahead of the launch these arguments are for)
+    else a.inj_gstate = inj.gstate ? inj.gstate + size_t(k) * pl.B * pl.dim : nullptr;
     a.inj_gexp = inj.gexp ? inj.gexp + size_t(k) * pl.B : nullptr;
     a.inj_obs = inj.obs;
     a.inj_n_obs = inj.n_obs;
@@ -582,6 +606,7 @@ struct ForwardCtx : SweepCtx {
     const double* obs = nullptr;
     double* expect_out = nullptr;
     bool want_exp = false;
+    double* pauli_out = nullptr;   // &expect_out[n_obs][0][0] where Pauli observables are evaluated
 };
 
 struct BackwardCtx : SweepCtx {
@@ -594,6 +619,7 @@ struct BackwardCtx : SweepCtx {
     double* wtot = nullptr;           // U_ij gradient weights, or nullptr
     bool want_tau = false;            // g_tsave given: dL/dtau of every exponential
     InjectSource inj;
+    PauliInject pauli;                // what inj.pauli points to
     bool taped(int k) const { return full_tape() || (partial_tape() && k >= tmap.k0); }  // every factor input of interval k is on the tape
     const double2* state_at(int k) const { return tape + size_t(full_tape() ? fprefix[k] : k) * sv; }  // the state at tsave[k]
 };

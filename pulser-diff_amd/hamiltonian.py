@@ -30,6 +30,7 @@ from typing import Callable, Union
 import torch
 from torch import Tensor
 
+from .observables import PauliObservable
 from .simconfig import SUPPORTED_NOISES, NoiseModel
 from .solver import ProblemSpec, SolverType
 from .utils import basis_state, kron
@@ -341,6 +342,63 @@ class Hamiltonian:
             single = self._site_operator(operator)
             placed.update({self._qid_index[q]: single for q in ids})
         return self._embed(placed)
+
+    def build_observable(self, operations: Union[list, tuple]) -> PauliObservable:
+        """``build_operator`` with every 2x2 factor expanded in Paulis: same arguments (names of ``op_matrix``, plus "X", "Y", "Z",
+        or a 2x2 tensor; atom ids or "global"), a ``PauliObservable`` out.  The result must be Hermitian (real weights)."""
+        if self.basis_name == "all":
+            raise NotImplementedError("Pauli observables are not available in the three-level all-basis.")
+        n = self._size
+
+        def pauli_coeffs(operator) -> dict:
+            if isinstance(operator, str) and operator in ("X", "Y", "Z") and operator not in self.op_matrix:
+                return {operator: 1.0 + 0.0j}
+            m = self._site_operator(operator)
+            m = torch.as_tensor(m)
+            m = (m.to_dense() if m.is_sparse else m).to(CD)
+            if tuple(m.shape) != (2, 2):
+                raise ValueError("build_observable takes 2x2 single-atom operators")
+            a, b, c, d = (complex(v) for v in (m[0, 0], m[0, 1], m[1, 0], m[1, 1]))
+            coef = {"I": 0.5 * (a + d), "X": 0.5 * (b + c), "Y": 0.5j * (b - c), "Z": 0.5 * (a - d)}
+            return {k: v for k, v in coef.items() if v != 0.0}
+
+        def product(site_coeffs: dict) -> dict:
+            """{(x mask, z mask): complex weight} of the tensor product with `site_coeffs[k]` on atom k."""
+            parts = {(0, 0): 1.0 + 0.0j}
+            for k, coef in site_coeffs.items():
+                nxt: dict = {}
+                for (x, z), w in parts.items():
+                    for name, v in coef.items():
+                        key = (x | ((1 << k) if name in "XY" else 0), z | ((1 << k) if name in "ZY" else 0))
+                        nxt[key] = nxt.get(key, 0.0) + w * v
+                parts = nxt
+            return parts
+
+        entries = operations if isinstance(operations, list) else [operations]
+        placed: dict = {}
+        total: dict = {}
+        for operator, where in entries:
+            if isinstance(where, str) and where == "global":  # as build_operator: the sum over all atoms, and the evaluation ends there
+                single = pauli_coeffs(operator)
+                for k in range(n):
+                    for key, v in product({k: single}).items():
+                        total[key] = total.get(key, 0.0) + v
+                break
+            ids = list(where)
+            if len(set(ids)) != len(ids):
+                raise ValueError("Duplicate atom ids in argument list.")
+            strangers = set(ids) - self._qdict.keys()
+            if strangers:
+                raise ValueError("Invalid qubit names: " f"{strangers}")
+            single = pauli_coeffs(operator)
+            placed.update({self._qid_index[q]: single for q in ids})
+        else:
+            total = product(placed)
+        scale = max((abs(v) for v in total.values()), default=0.0)
+        if any(abs(v.imag) > 1e-14 * max(scale, 1.0) for v in map(complex, total.values())):
+            raise ValueError("The operator is not Hermitian (its Pauli weights are not real): build_observable takes observables; "
+                             "use results.expect with build_operator on stored states for anything else.")
+        return PauliObservable._from_masks(n, {k: complex(v).real for k, v in total.items()})
 
     def _construct_hamiltonian(self, update: bool = True) -> None:
         """hamiltonian.py:320-497 for the ising / ground-rydberg mode: structure instead of matrices."""

@@ -21,6 +21,7 @@ from .backend import TorchEmulator
 from .simconfig import SimConfig
 from .simresults import SimulationResults
 from .solver import SolverType
+from .observables import PauliObservable
 from .utils import DiagonalObservable, total_magnetization, total_magnetization_diag
 from .waveform_funcs import constant_waveform
 
@@ -173,6 +174,8 @@ class QuantumModel(Module):
         if obs is None:
             n_qubits = len(self._qubit_order)
             obs = DiagonalObservable(total_magnetization_diag(n_qubits))
+            evaluation_times, results = self._run(observables=[obs])
+        elif isinstance(obs, PauliObservable):  # a sum of Pauli strings: evaluated and differentiated natively, no stored trajectory
             evaluation_times, results = self._run(observables=[obs])
         else:
             evaluation_times, results = self._run()

@@ -1,0 +1,214 @@
+"""Observables that are real-weighted sums of Pauli strings, ``O = sum_s w_s P_s`` — what the native solver evaluates and
+differentiates next to diagonal tables (``include/rydiff.h``: ``RydProblem.pauli_*``; ``csrc/pauli_kernels.hpp``).
+
+Conventions (the header's): a string is two qubit masks, bit j = qubit j (qubit 0 = first atom = most significant bit of the
+amplitude index): ``x`` = the qubits carrying X or Y, ``z`` = the qubits carrying Z or Y.  The 2x2 matrices are the ones of
+``utils.py`` (``XMAT / YMAT / ZMAT``) in the index order of the basis.  With ``xm``, ``zm`` the masks moved to index bits and
+``ny = popcount(x & z)``::
+
+    (P psi)[y] = i^ny * (-1)^popcount((y ^ xm) & zm) * psi[y ^ xm]
+"""
+from __future__ import annotations
+
+import math
+from typing import Iterable, Mapping, Sequence, Union
+
+import numpy as np
+import torch
+from torch import Tensor
+
+MAX_PAULI_STRINGS = 1024  # RYDIFF_MAX_PAULI_STRINGS
+MAX_DENSE_QUBITS = 14
+_I_POW = (1.0, 1j, -1.0, -1j)
+
+
+def _term_masks(n_qubits: int, paulis: Union[str, Mapping[int, str]]) -> tuple[int, int]:
+    if isinstance(paulis, str):
+        if len(paulis) != n_qubits:
+            raise ValueError(f"Pauli string {paulis!r} must name one of I, X, Y, Z for each of the {n_qubits} qubits")
+        paulis = {j: c for j, c in enumerate(paulis)}
+    x = z = 0
+    for j, c in paulis.items():
+        j = int(j)
+        if not 0 <= j < n_qubits:
+            raise ValueError(f"qubit {j} is outside the register of {n_qubits} qubits")
+        c = str(c).upper()
+        if c not in "IXYZ" or len(c) != 1:
+            raise ValueError(f"{c!r} is not one of I, X, Y, Z")
+        if c in "XY":
+            x |= 1 << j
+        if c in "ZY":
+            z |= 1 << j
+    return x, z
+
+
+class PauliObservable:
+    """``PauliObservable(n_qubits, [(weight, {qubit: "X" | "Y" | "Z"}), (weight, "XIZY"), ...])``; equal strings are merged."""
+
+    def __init__(self, n_qubits: int, terms: Iterable = ()):
+        self.n_qubits = int(n_qubits)
+        if self.n_qubits < 1:
+            raise ValueError("n_qubits must be positive")
+        self._terms: dict[tuple[int, int], float] = {}
+        for weight, paulis in terms:
+            if isinstance(weight, complex) and abs(weight.imag) > 0.0:
+                raise ValueError("Pauli observables take real weights")
+            key = _term_masks(self.n_qubits, paulis)
+            self._terms[key] = self._terms.get(key, 0.0) + float(weight.real if isinstance(weight, complex) else weight)
+
+    @classmethod
+    def _from_masks(cls, n_qubits: int, terms: Mapping[tuple[int, int], float]) -> "PauliObservable":
+        out = cls(n_qubits)
+        out._terms = {k: float(v) for k, v in terms.items() if v != 0.0}
+        return out
+
+    # ---- algebra ------------------------------------------------------------------------------------------------------
+    def __add__(self, other: "PauliObservable") -> "PauliObservable":
+        if not isinstance(other, PauliObservable):
+            return NotImplemented
+        if other.n_qubits != self.n_qubits:
+            raise ValueError("Pauli observables on registers of different size")
+        terms = dict(self._terms)
+        for k, v in other._terms.items():
+            terms[k] = terms.get(k, 0.0) + v
+        return PauliObservable._from_masks(self.n_qubits, terms)
+
+    def __mul__(self, scalar) -> "PauliObservable":
+        if isinstance(scalar, PauliObservable) or (isinstance(scalar, complex) and scalar.imag != 0.0):
+            return NotImplemented
+        s = float(scalar.real if isinstance(scalar, complex) else scalar)
+        return PauliObservable._from_masks(self.n_qubits, {k: s * v for k, v in self._terms.items()})
+
+    __rmul__ = __mul__
+
+    def __neg__(self) -> "PauliObservable":
+        return self * -1.0
+
+    def __sub__(self, other: "PauliObservable") -> "PauliObservable":
+        return self + (-other)
+
+    def __len__(self) -> int:
+        return len(self._terms)
+
+    @property
+    def terms(self) -> list[tuple[float, int, int]]:
+        """``[(weight, x_mask, z_mask), ...]`` in a fixed order."""
+        return [(w, x, z) for (x, z), w in sorted(self._terms.items())]
+
+    # ---- what a dense tensor offers (simresults.expect validates ``shape``) --------------------------------------------------
+    @property
+    def shape(self) -> tuple:
+        return (2**self.n_qubits, 2**self.n_qubits)
+
+    @property
+    def is_sparse(self) -> bool:
+        return False
+
+    def index_masks(self) -> list[tuple[float, int, int, complex]]:
+        """``[(weight, xm, zm, i^ny), ...]`` with the masks on amplitude-index bits (qubit j -> bit N-1-j)."""
+        n = self.n_qubits
+        flip = lambda m: sum(1 << (n - 1 - j) for j in range(n) if m >> j & 1)  # noqa: E731
+        return [(w, flip(x), flip(z), _I_POW[bin(x & z).count("1") & 3]) for w, x, z in self.terms]
+
+    def to_dense(self) -> Tensor:
+        if self.n_qubits > MAX_DENSE_QUBITS:
+            raise ValueError(f"dense operators are limited to {MAX_DENSE_QUBITS} qubits")
+        dim = 2**self.n_qubits
+        y = torch.arange(dim)
+        mat = torch.zeros(dim, dim, dtype=torch.complex128)
+        for w, xm, zm, ph in self.index_masks():
+            yp = y ^ xm
+            mat[y, yp] += w * ph * _parity_sign(yp & zm)
+        return mat
+
+    def masks(self) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """``(pauli_first, pauli_x, pauli_z, pauli_w)`` of this one observable as the C ABI takes them."""
+        return pack_pauli([self], self.n_qubits)
+
+    def rotated(self, phi: float) -> "PauliObservable":
+        """``V O V^dagger`` for ``V = exp(i phi #ones)`` (the frame ``sesolve`` evolves in under one constant drive phase): per
+        flipped qubit ``X -> cos X + sin Y``, ``Y -> cos Y - sin X``; Z and I unchanged."""
+        c, s = math.cos(float(phi)), math.sin(float(phi))
+        out: dict[tuple[int, int], float] = {}
+        for (x, z), w in self._terms.items():
+            parts = {(x, z): w}
+            for j in range(self.n_qubits):
+                if not x >> j & 1:
+                    continue
+                nxt: dict[tuple[int, int], float] = {}
+                for (px, pz), pw in parts.items():
+                    nxt[(px, pz)] = nxt.get((px, pz), 0.0) + c * pw
+                    other = (px, pz ^ (1 << j))
+                    nxt[other] = nxt.get(other, 0.0) + (-s if pz >> j & 1 else s) * pw
+                parts = nxt
+            for k, v in parts.items():
+                out[k] = out.get(k, 0.0) + v
+        return PauliObservable._from_masks(self.n_qubits, {k: v for k, v in out.items() if abs(v) > 0.0})
+
+    def rotated_count(self) -> int:
+        """Strings of ``rotated(phi)`` for a generic phi: 2^k for a string with k flipped qubits (before merging)."""
+        return sum(2 ** bin(x).count("1") for (x, _z) in self._terms)
+
+
+def _parity_sign(v: Tensor) -> Tensor:
+    """(-1)^popcount(v) for an integer tensor, as float64."""
+    p = torch.zeros_like(v)
+    for j in range(32):
+        p ^= (v >> j) & 1
+    return 1.0 - 2.0 * p.to(torch.float64)
+
+
+def pack_pauli(observables: Sequence[PauliObservable], n_qubits: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """The host arrays of ``RydProblem.pauli_first / pauli_x / pauli_z / pauli_w`` for a list of observables."""
+    first, xs, zs, ws = [0], [], [], []
+    for obs in observables:
+        if obs.n_qubits != n_qubits:
+            raise ValueError(f"Pauli observable on {obs.n_qubits} qubits handed to a register of {n_qubits}")
+        for w, x, z in obs.terms:
+            xs.append(x)
+            zs.append(z)
+            ws.append(w)
+        first.append(len(xs))
+    packed = (np.asarray(first, dtype=np.int32), np.asarray(xs, dtype=np.uint32), np.asarray(zs, dtype=np.uint32),
+              np.asarray(ws, dtype=np.float64))
+    check_pauli(packed, n_qubits)
+    return packed
+
+
+def check_pauli(packed, n_qubits: int) -> None:
+    """The C ABI sees raw pointers: counts, mask bits and the string cap are checked here (ValueError, never a bad device read)."""
+    first, x, z, w = (np.asarray(a) for a in packed)
+    if first.ndim != 1 or len(first) < 2 or first[0] != 0 or np.any(np.diff(first) < 0):
+        raise ValueError("pauli_first must be a non-decreasing array starting at 0 with one entry per observable plus one")
+    if not (len(x) == len(z) == len(w) == int(first[-1])):
+        raise ValueError(f"pauli_x / pauli_z / pauli_w must hold pauli_first[-1] = {int(first[-1])} strings each")
+    if len(x) > MAX_PAULI_STRINGS:
+        raise ValueError(f"too many Pauli strings: {len(x)} (at most {MAX_PAULI_STRINGS} per call)")
+    if len(x) and (int(np.max(x.astype(np.uint64) | z.astype(np.uint64))) >> n_qubits) != 0:
+        raise ValueError(f"a Pauli string addresses a qubit at or above n_qubits = {n_qubits}")
+    if len(w) and not np.all(np.isfinite(w)):
+        raise ValueError("Pauli weights must be finite")
+
+
+def expect_pauli(obs: PauliObservable, states: Tensor) -> Tensor:
+    """``<O>`` by index arithmetic in torch (no 2^N x 2^N operator): kets ``(n_t, dim, B)`` or density matrices
+    ``(n_t, dim, dim, B)``, on any device.  One gather per distinct flip mask."""
+    dim = 2**obs.n_qubits
+    if states.ndim not in (3, 4) or states.shape[1] != dim:
+        raise ValueError(f"PauliObservable on {obs.n_qubits} qubits expects kets (n_t, {dim}, B) or density matrices (n_t, {dim}, {dim}, B)")
+    dev = states.device
+    y = torch.arange(dim, device=dev)
+    by_flip: dict[int, Tensor] = {}
+    for w, xm, zm, ph in obs.index_masks():
+        coef = (w * ph) * _parity_sign((y ^ xm) & zm).to(torch.complex128)
+        by_flip[xm] = by_flip[xm] + coef if xm in by_flip else coef
+    cdt = states.dtype if states.is_complex() else torch.complex128
+    out = torch.zeros(states.shape[0], dtype=cdt, device=dev)
+    for xm, coef in by_flip.items():
+        yp = y ^ xm
+        coef = coef.to(cdt)
+        if states.ndim == 3:  # sum_y conj(psi[y]) coef[y] psi[y ^ xm]
+            out = out + (states.conj() * coef[None, :, None] * states[:, yp, :]).sum(dim=(1, 2))
+        else:  # tr(O rho) = sum_y O[y, y ^ xm] rho[y ^ xm, y]
+            out = out + (coef[None, :, None] * states[:, yp, y, :]).sum(dim=(1, 2))
+    return out

@@ -19,6 +19,7 @@ import torch
 from torch import Tensor
 
 from .result import SampledResult, TorchResult
+from .observables import PauliObservable
 from .utils import DiagonalObservable, expect
 
 
@@ -108,7 +109,7 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
         legal_shape = (self._dim**self._size, self._dim**self._size)
         out = []
         for obs in obs_list:
-            if not isinstance(obs, (Tensor, DiagonalObservable)):
+            if not isinstance(obs, (Tensor, DiagonalObservable, PauliObservable)):
                 raise TypeError(f"Incompatible type {type(obs)} of observable. Type must be ArrayLike or qutip.Qobj.")
             if tuple(obs.shape) != legal_shape:
                 raise ValueError("Incompatible shape of observable." + f"Expected {legal_shape}, got {tuple(obs.shape)}.")

@@ -20,6 +20,7 @@ import torch
 from torch import Tensor
 
 from . import _native
+from .observables import PauliObservable, check_pauli, pack_pauli
 
 
 class SolverType(enum.Enum):
@@ -64,6 +65,23 @@ class ProblemSpec:
     det_ones: tuple = ()          # () or one bool per detuning term: the term counts the ones of its mask with minus its coefficient
     # DP5_SE: optional uint8 array [n_samples - 1], multiplier of the Magnus sub-steps per sample interval (RydProblem.dp5_piece_refine)
     piece_refine: Optional[Any] = None
+    # Pauli-string observables evaluated (and differentiated) natively next to obs_diag: a list of PauliObservable, or the packed
+    # host arrays (pauli_first, pauli_x, pauli_z, pauli_w) of RydProblem; their values follow the diagonal ones in `expect`
+    pauli: Optional[Any] = None
+
+    def packed_pauli(self):
+        """The four host arrays of RydProblem.pauli_* (None: no Pauli observables)."""
+        if self.pauli is None:
+            return None
+        pauli = self.pauli
+        if len(pauli) and all(isinstance(o, PauliObservable) for o in pauli):
+            return pack_pauli(list(pauli), self.n_qubits)
+        if len(pauli) != 4:
+            raise ValueError("ProblemSpec.pauli: a list of PauliObservable or (pauli_first, pauli_x, pauli_z, pauli_w)")
+        packed = (np.ascontiguousarray(pauli[0], dtype=np.int32), np.ascontiguousarray(pauli[1], dtype=np.uint32),
+                  np.ascontiguousarray(pauli[2], dtype=np.uint32), np.ascontiguousarray(pauli[3], dtype=np.float64))
+        check_pauli(packed, self.n_qubits)
+        return packed
 
     def solver_code(self) -> int:
         if self.solver not in _SOLVER_CODE:
@@ -146,6 +164,15 @@ class _Call:
             if self.piece_refine.shape != (spec.n_samples - 1,):
                 raise ValueError(f"piece_refine must have n_samples - 1 = {spec.n_samples - 1} entries, got {self.piece_refine.shape}")
             p.dp5_piece_refine = self.piece_refine.ctypes.data
+        self.pauli = spec.packed_pauli()  # (validated: counts, mask bits, the string cap)
+        if self.pauli is not None and len(self.pauli[0]) > 1:
+            first, px, pz, pw = self.pauli
+            p.n_pauli_obs = len(first) - 1
+            p.n_pauli_strings = len(px)
+            p.pauli_first = first.ctypes.data
+            p.pauli_x = px.ctypes.data if len(px) else None
+            p.pauli_z = pz.ctypes.data if len(px) else None
+            p.pauli_w = pw.ctypes.data if len(px) else None
         self.problem = p
 
 
@@ -171,6 +198,7 @@ def _check_shapes(spec: ProblemSpec, amp: Tensor, det: Tensor, u_pairs: Tensor, 
         raise ValueError(f"u_pairs must hold N(N-1)/2 = {n_pairs} values, got {u_pairs.numel()}")
     if obs is not None and obs.numel() and (obs.ndim != 2 or obs.shape[1] != 2 ** nq):
         raise ValueError(f"obs_diag must have shape (n_obs, {2 ** nq}), got {tuple(obs.shape)}")
+    spec.packed_pauli()  # raises ValueError on a mask bit at or above N, inconsistent counts, too many strings
     if batch > 65535:
         raise ValueError("batch must be <= 65535 (split the columns / trajectories into several calls)")
 
@@ -297,7 +325,7 @@ class _RydbergEvolve(torch.autograd.Function):
                         raise
             states = (torch.empty((n_t, batch, dim), dtype=torch.complex128, device=dev) if spec.store_states
                       else torch.empty((0, batch, dim), dtype=torch.complex128, device=dev))
-            n_obs = call.problem.n_obs
+            n_obs = call.problem.n_obs + call.problem.n_pauli_obs  # diagonal observables first
             expect = torch.empty((n_obs, n_t, batch), dtype=torch.float64, device=dev)
             _native.check(L.rydiff_forward(ctypes.byref(call.problem), ctypes.byref(info), _ptr(psi_c),
                                            _ptr(states) if spec.store_states else None,
@@ -315,6 +343,7 @@ class _RydbergEvolve(torch.autograd.Function):
         ctx.save_for_backward(amp_c, det_c, u_c, psi_c, obs_c if obs_c is not None else torch.empty(0, device=dev),
                               states)
         ctx.has_obs = obs_c is not None
+        ctx.has_expect = n_obs > 0
         ctx.set_materialize_grads(False)
         ctx.stats = {"degree": info.degree, "total_factors": info.total_factors, "rho": info.rho_design,
                      "spectral": (info.spectral_lo, info.spectral_hi), "n_stages": info.n_stages,
@@ -359,7 +388,7 @@ class _RydbergEvolve(torch.autograd.Function):
                 workspace = torch.empty(info.workspace_bytes, dtype=torch.uint8, device=dev)  # sized by the forward call's plan
                 states_ptr = _ptr(states)
             _native.check(L.rydiff_backward(ctypes.byref(call.problem), ctypes.byref(info), states_ptr, _ptr(g_states),
-                                            _ptr(g_expect) if (g_expect is not None and obs is not None) else None,
+                                            _ptr(g_expect) if (g_expect is not None and ctx.has_expect) else None,
                                             _ptr(g_amp), _ptr(g_det), _ptr(g_u), _ptr(g_ts), _ptr(g_psi),
                                             _ptr(workspace), workspace.numel(), int(ctx.need_tape), stream))
             if ctx.need_tape:
@@ -384,7 +413,7 @@ class SolveResult:
     """What the reference reads from pyqtorch's result object: ``.states`` iterable over time (backend.py:513-521)."""
 
     states: Tensor  # (n_t, dim, B) view, like pyqtorch
-    expect: Tensor  # (n_obs, n_t, B) diagonal observables evaluated natively
+    expect: Tensor  # (n_obs + n_pauli, n_t, B) observables evaluated natively, the diagonal ones first
     stats: dict
 
 
@@ -395,11 +424,13 @@ def evolve(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsave: Tenso
 
 
 def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverType.DP5_SE,
-            options: Optional[dict] = None, obs_diag: Optional[Tensor] = None, store_states: bool = True) -> SolveResult:
+            options: Optional[dict] = None, obs_diag: Optional[Tensor] = None, store_states: bool = True,
+            pauli_obs: Optional[Sequence[PauliObservable]] = None) -> SolveResult:
     """Drop-in for ``pyqtorch.sesolve(H=..., psi0, tsave, solver, options)`` at ``backend.py:488-494``.
 
     ``problem`` is the structured Hamiltonian (``pulser_diff_amd.hamiltonian.Hamiltonian``) instead of the opaque
-    callable; ``psi0`` is ``(dim, B)`` as in the reference.
+    callable; ``psi0`` is ``(dim, B)`` as in the reference.  ``pauli_obs``: Pauli-string observables evaluated natively; their
+    values follow the diagonal ones in ``SolveResult.expect``.
     """
     options = dict(options or {})
     spec = problem.problem_spec(solver=solver, tol=tolerance_from_options(options), store_states=store_states)
@@ -415,8 +446,22 @@ def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverTyp
         if obs_diag is not None:
             obs_diag = torch.zeros(obs_diag.shape[0], 1 << spec.n_qubits, dtype=obs_diag.dtype,
                                    device=obs_diag.device).index_copy(1, embed, obs_diag)
+    pauli_obs = list(pauli_obs or [])
+    if pauli_obs and embed is not None:
+        raise NotImplementedError("Pauli observables are not available in the three-level all-basis; use results.expect on stored states.")
     rot = None
     phi = getattr(problem, "frame_phase", None)
+    if pauli_obs and phi is not None and not spec.pair_terms:
+        # off-diagonal observables DO see the frame: the library gets V O V^dagger (a string with k flipped qubits becomes 2^k).
+        # Where that would exceed the cap of strings per call the frame stays off for this call (complex tables: slower kernels,
+        # same numbers).
+        rotated = [o.rotated(float(phi)) for o in pauli_obs]
+        if sum(len(o) for o in rotated) <= _native.MAX_PAULI_STRINGS:
+            pauli_obs = rotated
+        else:
+            phi = None
+    if pauli_obs:
+        spec.pauli = pauli_obs
     if phi is not None and embed is None and not spec.pair_terms:
         # one constant drive phase: evolve in the frame that rotates with it (hamiltonian.py: frame_phase) — real tables, V psi0 in,
         # V^dagger psi(t) out; diagonal observables do not see the frame

@@ -13,6 +13,8 @@ from math import pi, prod, sin
 import torch
 from torch import Tensor
 
+from .observables import PauliObservable, expect_pauli
+
 # pyqtorch.matrices restated (imported by the reference at utils.py:7, hamiltonian.py:17)
 IMAT = torch.eye(2, dtype=torch.complex128)
 XMAT = torch.tensor([[0, 1], [1, 0]], dtype=torch.complex128)
@@ -76,6 +78,10 @@ def total_magnetization(n_qubits: int, use_sparse: bool = False) -> Tensor:
 
 def expect(obs, states: Tensor) -> Tensor:
     """utils.py:68-86.  states: (n_t, dim, B) kets or (n_t, dim, dim, B) density matrices."""
+    if isinstance(obs, PauliObservable):  # matrix-free: index arithmetic, no 2^N x 2^N operator
+        if states.is_sparse:
+            states = states.to_dense()
+        return expect_pauli(obs, states)
     if isinstance(obs, DiagonalObservable):
         d = obs.diag.to(states.device)
         if states.ndim == 4:  # density matrices: tr(O rho) = sum_x O[x] rho[x, x]
