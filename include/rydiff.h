@@ -62,6 +62,7 @@ extern "C" {
 #define RYDIFF_MAX_PAIR_TERMS 28
 #define RYDIFF_MAX_TERMS 64
 #define RYDIFF_MAX_PAULI_STRINGS 1024 /* Pauli strings of one call, over all Pauli observables (after any frame rotation) */
+#define RYDIFF_MAX_OVERLAPS 16 /* state-overlap observables (target states) of one call */
 
 enum { RYDIFF_OK = 0, RYDIFF_EINVAL = -1, RYDIFF_EWORKSPACE = -2, RYDIFF_EHIP = -3, RYDIFF_ENOTIMPL = -4 };
 
@@ -198,6 +199,20 @@ typedef struct RydProblem {
      * need_tape = 2 does for a run that fits, this does for the part of a run that fits. */
     int32_t tape_steps;
 
+    /* STATE-OVERLAP observables: the complex overlaps with given target states, evaluated at every tsave behind the Pauli
+     * observables (below) and differentiated by rydiff_backward:
+     *   c_o[k][b] = sum_y conj(phi_{o,b}[y]) psi_b(t_k)[y]          (state fidelity |c|^2, gate fidelity |sum_b c_b| / dim)
+     * expect_out and grad_expect become [n_obs + n_pauli_obs + 2 * n_overlaps][n_tsave][B]: overlap o owns two consecutive rows
+     * behind the Pauli rows, Re c_o then Im c_o.  The cotangent added to psi_b(t_k) is (gRe + i gIm) * phi_{o,b} (gRe, gIm: the two
+     * rows of grad_expect), formed per save point in the workspace next to the Pauli one and injected through the grad_states route.
+     * The targets are constants (no gradient) and need not be normalised.  Allowed with final_state_only, with states_out == NULL
+     * and no tape, and next to diagonal observables, Pauli observables and pair terms; not together with shard_bits > 0
+     * (RYDIFF_ENOTIMPL).  n_overlaps = 0: nothing changes.  (The fields sit in front of the Pauli block, which stays the tail of the
+     * struct; library and bindings are built from one header and rydiff_sizeof_problem() guards against a stale pair.) */
+    int32_t n_overlaps;             /* 0: none; at most RYDIFF_MAX_OVERLAPS */
+    int32_t overlap_batch;          /* 1: all trajectories share each target; B (= batch): one target per trajectory */
+    const void* overlap_targets;    /* DEVICE complex128 [n_overlaps][overlap_batch][2^N] */
+
     /* PAULI-STRING observables, evaluated at every tsave next to the diagonal ones and differentiated by rydiff_backward:
      *   O_o = sum_{s = pauli_first[o]}^{pauli_first[o+1]-1} w_s P_s,   w_s real,   P_s = (x)_j sigma_j,  sigma_j in {I, X, Y, Z}
      * in the basis order of the register (index bit 0 = first basis state r, bit 1 = g): X = [[0,1],[1,0]], Y = [[0,-i],[i,0]],
@@ -269,7 +284,8 @@ int rydiff_plan(const RydProblem* p, int need_tape, int need_backward, void* scr
  *   states_out  DEVICE complex128 [n_tsave][B][2^N], or NULL (trajectory kept in the workspace tape if need_tape).
  *               With need_tape = 2 / 3 AND states_out the factor outputs go to the (granted) workspace tape and the states at the
  *               save points are copied out of it — stored states plus a later gradient without (or with less) recomputation.
- *   expect_out  DEVICE float64 [n_obs + n_pauli_obs][n_tsave][B] (diagonal observables first), or NULL */
+ *   expect_out  DEVICE float64 [n_obs + n_pauli_obs + 2 * n_overlaps][n_tsave][B] (diagonal observables first, then the Pauli
+ *               ones, then Re / Im of every overlap), or NULL */
 int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi0, void* states_out, double* expect_out,
                    void* workspace, size_t workspace_bytes, int need_tape, void* stream);
 
@@ -280,7 +296,7 @@ int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi
  *   states       DEVICE: the states_out of the forward call, or NULL to use the workspace tape (with need_tape = 2 / 3 the
  *                granted workspace tape is used even when states is given)
  *   grad_states  DEVICE complex128 [n_tsave][B][2^N] or NULL
- *   grad_expect  DEVICE float64 [n_obs + n_pauli_obs][n_tsave][B] or NULL
+ *   grad_expect  DEVICE float64 [n_obs + n_pauli_obs + 2 * n_overlaps][n_tsave][B] or NULL
  *   g_amp        DEVICE complex128 [coeff_batch][n_amp_terms][n_samples] or NULL   (overwritten)
  *   g_det        DEVICE float64    [coeff_batch][n_det_terms][n_samples] or NULL   (overwritten)
  *   g_u          DEVICE float64 [N(N-1)/2] or NULL  (dist_grad, backend.py:456-460 / hamiltonian.py:341-344)

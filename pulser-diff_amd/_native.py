@@ -28,6 +28,7 @@ KERNEL_FAMILIES = ("lanes", "persistent", "direct", "chained-tiles")
 MAX_QUBITS = 30
 MAX_TERMS = 64
 MAX_PAULI_STRINGS = 1024
+MAX_OVERLAPS = 16
 
 
 class RydProblem(ctypes.Structure):
@@ -65,6 +66,9 @@ class RydProblem(ctypes.Structure):
         ("det_ones_terms", ctypes.c_uint64),
         ("dp5_piece_refine", ctypes.c_void_p),
         ("tape_steps", ctypes.c_int32),
+        ("n_overlaps", ctypes.c_int32),
+        ("overlap_batch", ctypes.c_int32),
+        ("overlap_targets", ctypes.c_void_p),
         ("n_pauli_obs", ctypes.c_int32),
         ("n_pauli_strings", ctypes.c_int32),
         ("pauli_first", ctypes.c_void_p),

@@ -34,7 +34,7 @@ from .result import SampledResult
 from .simconfig import SimConfig
 from .simresults import CoherentResults, NoisyResults, SimulationResults
 from .solver import ProblemSpec, SolverType, evolve, sesolve, tolerance_from_options
-from .observables import PauliObservable
+from .observables import PauliObservable, StateOverlap
 from .utils import DiagonalObservable
 
 
@@ -266,8 +266,9 @@ class TorchEmulator:
         """Simulates the sequence with the native solver and returns ``CoherentResults``.
 
         ``observables`` (extension): diagonal observables (``DiagonalObservable`` or dense diagonal tensors) and sums of Pauli
-        strings (``PauliObservable``, e.g. from ``build_observable``) to be evaluated natively at every evaluation time;
-        ``store_states=False`` keeps the trajectory out of the results.
+        strings (``PauliObservable``, e.g. from ``build_observable``) and overlaps with target states (``StateOverlap``; read with
+        ``results.overlap``) to be evaluated natively at every evaluation time; ``store_states=False`` keeps the trajectory out of
+        the results.
         """
         if time_grad:
             self._eval_times_array.requires_grad_(True)  # backend.py:453-455
@@ -292,8 +293,13 @@ class TorchEmulator:
 
         dev = self._compute_device
         ham = self._hamiltonian
-        obs_tensors, obs_objs, pauli_objs = [], [], []
+        obs_tensors, obs_objs, pauli_objs, overlap_objs = [], [], [], []
         for obs in observables or []:
+            if isinstance(obs, StateOverlap):
+                if tuple(obs.shape) != (ham.dim ** ham._size,) * 2:
+                    raise ValueError(f"StateOverlap targets of dimension {obs.shape[0]} handed to states of dimension {ham.dim ** ham._size}")
+                overlap_objs.append(obs)
+                continue
             if isinstance(obs, PauliObservable):
                 if ham.basis_name == "all":
                     raise NotImplementedError("Pauli observables are not available in the three-level all-basis; use "
@@ -310,7 +316,7 @@ class TorchEmulator:
                     raise ValueError("Only diagonal observables can be evaluated natively; use results.expect on the states.")
                 diag = torch.diagonal(dense).real
             else:
-                raise TypeError("observables must be DiagonalObservable / PauliObservable objects or diagonal (dim, dim) tensors")
+                raise TypeError("observables must be DiagonalObservable / PauliObservable / StateOverlap objects or diagonal (dim, dim) tensors")
             obs_tensors.append(diag.to(dev, torch.float64))
             obs_objs.append(obs)
         obs_diag = torch.stack(obs_tensors) if obs_tensors else None
@@ -331,17 +337,20 @@ class TorchEmulator:
                                           "state different from the ground.")
 
         def run_coherent() -> CoherentResults:
+            if overlap_objs and solver == SolverType.DP5_ME:
+                raise NotImplementedError("StateOverlap observables are defined on kets: not available in master-equation runs.")
             if solver == SolverType.DP5_ME:  # density matrices (backend.py:495-509); without collapse noise L = 0
                 rho, stats = mesolve(ham, psi0.to(dev), self._eval_times_array, ham.config, options)
                 return CoherentResults(rho, ham._size, ham.basis_name, self._eval_times_array, self._meas_basis, meas_errors,
                                        atom_order=tuple(ham._qdict), stats=stats, density=True)
             result = sesolve(ham, psi0.to(dev), self._eval_times_array, solver=solver, options=options, obs_diag=obs_diag,
-                             store_states=store_states, pauli_obs=pauli_objs)
+                             store_states=store_states, pauli_obs=pauli_objs, overlap_obs=overlap_objs)
             states_tbd = result.states.permute(0, 2, 1) if result.states.numel() else result.states
             return CoherentResults(states_tbd, ham._size, ham.basis_name, self._eval_times_array, self._meas_basis,
                                    meas_errors, atom_order=tuple(ham._qdict),
                                    native_expect=result.expect if (obs_diag is not None or pauli_objs) else None,
-                                   native_observables=obs_objs + pauli_objs, stats=result.stats)
+                                   native_observables=obs_objs + pauli_objs, stats=result.stats,
+                                   native_overlaps=result.overlaps, overlap_observables=overlap_objs)
 
         # does the noise ask for averaging over several runs?  (backend.py:531-569)
         no_resampling = noise <= {"dephasing", "relaxation", "SPAM", "depolarizing", "eff_noise", "amplitude"} and (
@@ -358,6 +367,8 @@ class TorchEmulator:
             reps = [r for _, r in drawn]
         else:
             reps = [1] * self.config.runs
+        if overlap_objs:
+            raise NotImplementedError("StateOverlap observables are not available in noisy runs that average over realisations.")
         return self._run_noisy(psi0, solver, options, reps, bad_atom_configs, meas_errors)
 
     def _run_noisy(self, psi0: Tensor, solver: SolverType, options: dict, reps: list, bad_atom_configs,

@@ -1,5 +1,5 @@
 // pauli_launch.hpp — Pauli-string observables (pauli_kernels.hpp): where the tables live, the evaluation launches of the forward
-// sweeps and the cotangent the adjoint sweeps inject at a save point.
+// sweeps and the Pauli part of the cotangent the adjoint sweeps inject at a save point (overlap_launch.hpp: observable_cotangent).
 #pragma once
 
 namespace {
@@ -128,13 +128,6 @@ void launch_pauli_apply(const PauliInject& pi, const double2* psi, const int32_t
     a.B = pl.B;
     a.dim = uint32_t(pl.dim);
     hipLaunchKernelGGL(k_pauli_apply, dim3(unsigned((pl.dim + 255) / 256), unsigned(pl.B), unsigned(nk)), dim3(256), 0, pi.stream, a);
-}
-
-// launch-per-factor adjoint sweeps: the cotangent injected at save point k, written into the one reused workspace buffer right
-// before the launch that reads it (stream order keeps the previous reader ahead of this write)
-const double2* pauli_cotangent(const PauliInject& pi, int k) {
-    launch_pauli_apply(pi, pi.state_at(k), nullptr, 0, k, 1, pi.buf);
-    return pi.buf;
 }
 
 }  // namespace

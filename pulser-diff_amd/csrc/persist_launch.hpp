@@ -191,13 +191,13 @@ int forward_persist(const ForwardCtx& c) {
     pa.expect = c.expect_out;
     pa.n_obs = c.want_exp ? rt.pl.n_obs : 0;
     const Plan& pl = rt.pl;
-    if (c.pauli_out && !pa.states) {  // the caller keeps no trajectory: the Pauli observables read one in the workspace
+    if ((c.pauli_out || c.overlap_out) && !pa.states) {  // the caller keeps no trajectory: the Pauli / overlap observables read one in the workspace
         pa.states = reinterpret_cast<double2*>(c.ws + pl.off_pauli_traj);
         HIP_TRY(hipMemcpyAsync(pa.states, c.psi0, pl.state_bytes, hipMemcpyDeviceToDevice, c.stream));
     }
     rc = (rt.flags & 1) ? launch_persist<true>(rt, pa, c.stream) : launch_persist<false>(rt, pa, c.stream);
     if (rc) return rc;
-    return launch_pauli_expect(c, pa.states, c.sv, 0, pl.T + 1, BatchSlice{0, pl.B, false});  // one launch over the stored trajectory
+    return launch_observables_expect(c, pa.states, c.sv, 0, pl.T + 1, BatchSlice{0, pl.B, false});  // one launch over the stored trajectory
 }
 
 // The whole reverse sweep in one launch (k_persist_bwd / k_lanes_bwd); the cotangent w.r.t. psi0 ends up in c.lam[0].
@@ -229,8 +229,8 @@ int backward_persist(const BackwardCtx& c) {
     pa.save_entry = reinterpret_cast<const int32_t*>(c.ws + pl.off_pm_first);
     pa.chainbuf = c.chainbuf;
     pa.gstate = c.inj.gstate;
-    if (c.inj.pauli) {  // grad_states[k] + 2 sum_o g_o O_o psi_k for every save point, in one launch
-        launch_pauli_apply(c.pauli, c.tape, c.full_tape() ? pa.save_entry : nullptr, 1, 0, pl.T + 1, c.pauli.buf);
+    if (c.inj.pauli) {  // grad_states[k] + 2 sum_o g_o O_o psi_k + sum_o (gRe + i gIm)_o phi_o for every save point, one launch per kind
+        launch_observable_cotangent(c.pauli, c.tape, c.full_tape() ? pa.save_entry : nullptr, 1, 0, pl.T + 1, c.pauli.buf);
         LAUNCH_CHECK();
         pa.gstate = c.pauli.buf;
     }

@@ -82,7 +82,9 @@ struct Plan {
     std::vector<PauliGroup> pauli_groups;
     std::vector<PauliString> pauli_strings;
     bool pauli_work[3] = {false, false, false};  // some group is evaluated in tile layout 0 / in tile layout 1 / by the direct kernel
-    size_t off_pauli = 0, off_pauli_traj = 0, off_pauli_cot = 0;
+    size_t off_pauli = 0, off_pauli_traj = 0, off_pauli_cot = 0;  // (the trajectory and the cotangent buffer serve the overlaps too)
+    // state-overlap observables (overlap_kernels.hpp): targets stay where the caller has them
+    int n_ov = 0, ov_batch = 1;
     size_t pauli_gfirst_bytes() const { return (pauli_gfirst.size() * sizeof(int32_t) + 7) / 8 * 8; }
     size_t pauli_bytes() const {
         return n_pobs ? pauli_gfirst_bytes() + pauli_groups.size() * sizeof(PauliGroup) + pauli_strings.size() * sizeof(PauliString) : 0;
@@ -219,6 +221,32 @@ inline bool build_pauli(const RydProblem* p, Plan& pl, std::string& err) {
     return true;
 }
 
+// RydProblem.overlap_*: counts, target batch (1 or B), pointer
+inline bool build_overlaps(const RydProblem* p, Plan& pl, std::string& err) {
+    pl.n_ov = 0;
+    pl.ov_batch = 1;
+    if (p->n_overlaps < 0 || p->n_overlaps > RYDIFF_MAX_OVERLAPS) {
+        err = "n_overlaps must be in [0, " + std::to_string(RYDIFF_MAX_OVERLAPS) + "]";
+        return false;
+    }
+    if (p->n_overlaps == 0) return true;
+    if (p->overlap_batch != 1 && p->overlap_batch != p->batch) {
+        err = "overlap_batch must be 1 or batch";
+        return false;
+    }
+    if (!p->overlap_targets) {
+        err = "missing overlap_targets";
+        return false;
+    }
+    if (p->shard_bits > 0) {
+        err = "state-overlap observables: not implemented together with state sharding";
+        return false;
+    }
+    pl.n_ov = p->n_overlaps;
+    pl.ov_batch = p->overlap_batch;
+    return true;
+}
+
 // `width`: half spectral width of the generator when it is already known (<= 0: not yet) — the continuous solver's
 // sub-step shrinks with it.
 inline bool build_plan(const RydProblem* p, Plan& pl, std::string& err, double width = -1.0) {
@@ -301,6 +329,7 @@ inline bool build_plan(const RydProblem* p, Plan& pl, std::string& err, double w
     }
     pl.N = p->n_qubits;
     if (!build_pauli(p, pl, err)) return false;
+    if (!build_overlaps(p, pl, err)) return false;
     pl.shard_bits = p->shard_bits;
     if (pl.shard_bits < 0 || pl.shard_bits > 6 || pl.shard_bits >= pl.N) {
         err = "shard_bits must be in [0, min(6, n_qubits - 1)]";
@@ -514,8 +543,8 @@ inline size_t carve(Plan& pl, int tape_mode, bool need_backward, int chain_slots
     }
     pl.off_pair = take(size_t(pl.n_pair) * 64 * sizeof(double));
     pl.off_pauli = take(pl.pauli_bytes());
-    // one-launch sweeps: the trajectory the Pauli observables are evaluated on where the caller keeps none
-    pl.off_pauli_traj = take((pl.n_pobs && pl.N <= 12) ? size_t(pl.T + 1) * pl.state_bytes : 0);
+    // one-launch sweeps: the trajectory the Pauli and overlap observables are evaluated on where the caller keeps none
+    pl.off_pauli_traj = take(((pl.n_pobs || pl.n_ov) && pl.N <= 12) ? size_t(pl.T + 1) * pl.state_bytes : 0);
     pl.total_fwd = off;
     pl.tape_mode = tape_mode;
     if (tape_mode == 2) pl.off_tape = take(size_t(total_factors + 1) * pl.state_bytes);
@@ -526,8 +555,9 @@ inline size_t carve(Plan& pl, int tape_mode, bool need_backward, int chain_slots
         pl.off_chain = take(size_t(chain_slots > 0 ? chain_slots : 1) * pl.state_bytes);
         pl.off_ge = take(size_t(pl.Bc) * E * 64 /* kGradReplicas */ * (pl.NC + 1) * sizeof(double));
         pl.off_wtot = take(pl.dim * (pl.shard_bits ? size_t(pl.B) : 1) * sizeof(double));  // sharded: one weight slab per rank of the call
-        // Pauli cotangent grad_states[k] + 2 sum_o g_o O_o psi_k: one state, reused in stream order (one-launch adjoints: every k)
-        pl.off_pauli_cot = take(pl.n_pobs ? size_t(pl.N <= 12 ? pl.T + 1 : 1) * pl.state_bytes : 0);
+        // observable cotangent grad_states[k] + 2 sum_o g_o O_o psi_k + sum_o (gRe + i gIm)_o phi_o: one state, reused in stream order
+        // (one-launch adjoints: every k)
+        pl.off_pauli_cot = take((pl.n_pobs || pl.n_ov) ? size_t(pl.N <= 12 ? pl.T + 1 : 1) * pl.state_bytes : 0);
         pl.off_meta2 = take(std::max(E * 40, size_t(pl.T + 1) * sizeof(int32_t)));  // StageBwdDev records, or the save-point flags of the one-launch adjoint
     }
     return off;

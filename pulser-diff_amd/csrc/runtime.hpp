@@ -517,18 +517,22 @@ void shard_groups(const Plan& pl, int (&grp)[kShardMaxBits]) {
     }
 }
 
-// Cotangents of the Pauli-string observables: they ride the grad_states route — k_pauli_apply (pauli_launch.hpp) writes
-// grad_states[k] + 2 sum_o g_o O_o psi_k into a workspace buffer and the injecting launch reads that instead of grad_states[k]
+// Cotangents of the Pauli-string and state-overlap observables: they ride the grad_states route — k_pauli_apply (pauli_launch.hpp)
+// writes grad_states[k] + 2 sum_o g_o O_o psi_k into a workspace buffer, k_overlap_apply (overlap_launch.hpp) adds
+// sum_o (gRe + i gIm)_o phi_o to it (or to grad_states[k] where no Pauli observable has a cotangent), and the injecting launch reads
+// that buffer instead of grad_states[k]
 struct PauliInject {
     const Runtime* rt = nullptr;
     char* ws = nullptr;
     hipStream_t stream = nullptr;
     const double2* gstate = nullptr;  // the caller's grad_states or nullptr
-    const double* gexp = nullptr;     // &grad_expect[n_obs][0][0]
+    const double* gexp = nullptr;     // &grad_expect[n_obs][0][0], or nullptr: no Pauli observables
+    const double* ov_gexp = nullptr;  // &grad_expect[n_obs + n_pobs][0][0], or nullptr: no overlaps
+    const double2* ov_targets = nullptr;
     double2* buf = nullptr;           // one state (one-launch adjoints: n_tsave states)
     std::function<const double2*(int)> state_at;  // the state at save point k
 };
-const double2* pauli_cotangent(const PauliInject& pi, int k);
+const double2* observable_cotangent(const PauliInject& pi, int k);  // overlap_launch.hpp
 
 // cotangents handed to the backward call (fused injection, see ChainArgs / FactorBwdArgs)
 struct InjectSource {
@@ -536,7 +540,7 @@ struct InjectSource {
     const double* gexp = nullptr;     // grad_expect [n_obs][n_tsave][B] or nullptr
     const double* obs = nullptr;      // [n_obs][dim]
     int n_obs = 0;
-    const PauliInject* pauli = nullptr;  // Pauli observables with a cotangent: replaces gstate
+    const PauliInject* pauli = nullptr;  // Pauli / overlap observables with a cotangent: replaces gstate
     bool any() const { return gstate || gexp || pauli; }
 };
 
@@ -544,7 +548,7 @@ struct InjectSource {
 template <class Args>
 void fill_inject(Args& a, const InjectSource& inj, int k, const Plan& pl) {
     if (k < 0 || !inj.any()) return;
-    if (inj.pauli) a.inj_gstate = pauli_cotangent(*inj.pauli, k);  // (enqueued ahead of the launch these arguments are for)
+    if (inj.pauli) a.inj_gstate = observable_cotangent(*inj.pauli, k);  // (enqueued ahead of the launch these arguments are for)
     else a.inj_gstate = inj.gstate ? inj.gstate + size_t(k) * pl.B * pl.dim : nullptr;
     a.inj_gexp = inj.gexp ? inj.gexp + size_t(k) * pl.B : nullptr;
     a.inj_obs = inj.obs;
@@ -607,6 +611,7 @@ struct ForwardCtx : SweepCtx {
     double* expect_out = nullptr;
     bool want_exp = false;
     double* pauli_out = nullptr;   // &expect_out[n_obs][0][0] where Pauli observables are evaluated
+    double* overlap_out = nullptr; // &expect_out[n_obs + n_pobs][0][0] where overlaps are evaluated
 };
 
 struct BackwardCtx : SweepCtx {

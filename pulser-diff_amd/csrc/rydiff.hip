@@ -42,6 +42,7 @@ using namespace rydiff;
 #include "persist_kernels.hpp"
 #include "lane_kernels.hpp"
 #include "pauli_kernels.hpp"
+#include "overlap_kernels.hpp"
 static_assert(sizeof(PersistFactor) == 48, "plan.hpp sizes the factor table with 48 bytes per entry");
 
 #include "runtime.hpp"
@@ -49,6 +50,7 @@ static_assert(sizeof(PersistFactor) == 48, "plan.hpp sizes the factor table with
 #include "direct_launch.hpp"
 #include "chain_launch.hpp"
 #include "pair_launch.hpp"
+#include "overlap_launch.hpp"
 #include "persist_launch.hpp"
 
 namespace {
@@ -139,7 +141,7 @@ int forward_chained(const ForwardCtx& c) {
             if (c.copy_out && step_of_end[i])
                 HIP_TRY(hipMemcpyAsync(c.copy_out + size_t(step_of_end[i]) * sv + size_t(bs.first) * pl.dim, out + size_t(bs.first) * pl.dim,
                                        size_t(bs.count) * pl.dim * sizeof(double2), hipMemcpyDeviceToDevice, stream));
-            if (step_of_end[i]) return launch_pauli_expect(c, out, 0, step_of_end[i], 1, bs);
+            if (step_of_end[i]) return launch_observables_expect(c, out, 0, step_of_end[i], 1, bs);
             return RYDIFF_OK;
         };
         auto exp_slot = [&](int i, ChainStep& cs) {
@@ -195,7 +197,7 @@ int forward_direct(const ForwardCtx& c) {
             const int rc = launch_expect(c, cur, k + 1);
             if (rc) return rc;
         }
-        if (const int rc = launch_pauli_expect(c, cur, 0, k + 1, 1, BatchSlice{0, pl.B, false})) return rc;
+        if (const int rc = launch_observables_expect(c, cur, 0, k + 1, 1, BatchSlice{0, pl.B, false})) return rc;
     }
     if (c.final_dst) HIP_TRY(hipMemcpyAsync(c.final_dst, cur, pl.state_bytes, hipMemcpyDeviceToDevice, c.stream));
     return RYDIFF_OK;
@@ -454,13 +456,15 @@ int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi
     c.expect_out = expect_out;
     c.want_exp = expect_out && pl.n_obs > 0;
     c.pauli_out = (expect_out && pl.n_pobs) ? expect_out + size_t(pl.n_obs) * (pl.T + 1) * pl.B : nullptr;
-    if (c.want_exp || c.pauli_out) HIP_TRY(hipMemsetAsync(expect_out, 0, size_t(pl.n_obs + pl.n_pobs) * (pl.T + 1) * pl.B * sizeof(double), stream));
+    c.overlap_out = (expect_out && pl.n_ov) ? expect_out + size_t(pl.n_obs + pl.n_pobs) * (pl.T + 1) * pl.B : nullptr;
+    if (c.want_exp || c.pauli_out || c.overlap_out)
+        HIP_TRY(hipMemsetAsync(expect_out, 0, size_t(pl.n_obs + pl.n_pobs + 2 * pl.n_ov) * (pl.T + 1) * pl.B * sizeof(double), stream));
     if (c.want_exp) {
         rc = launch_expect(c, c.start, 0);
         if (rc) return rc;
     }
-    if (persist_enabled(rt)) return forward_persist(c);  // (evaluates the Pauli observables on the whole trajectory afterwards)
-    rc = launch_pauli_expect(c, c.start, 0, 0, 1, BatchSlice{0, pl.B, false});
+    if (persist_enabled(rt)) return forward_persist(c);  // (evaluates the Pauli / overlap observables on the whole trajectory afterwards)
+    rc = launch_observables_expect(c, c.start, 0, 0, 1, BatchSlice{0, pl.B, false});
     if (rc) return rc;
     return chain_enabled(rt) ? forward_chained(c) : forward_direct(c);
 }
@@ -495,12 +499,14 @@ int rydiff_backward(const RydProblem* p, const RydPlanInfo* info, const void* st
     c.inj.gexp = have_gexp ? grad_expect : nullptr;
     c.inj.obs = p->obs_diag;
     c.inj.n_obs = have_gexp ? pl.n_obs : 0;
-    if (grad_expect && pl.n_pobs) {
+    if (grad_expect && (pl.n_pobs || pl.n_ov)) {
         c.pauli.rt = &rt;
         c.pauli.ws = c.ws;
         c.pauli.stream = stream;
         c.pauli.gstate = c.inj.gstate;
-        c.pauli.gexp = grad_expect + size_t(pl.n_obs) * (pl.T + 1) * pl.B;
+        c.pauli.gexp = pl.n_pobs ? grad_expect + size_t(pl.n_obs) * (pl.T + 1) * pl.B : nullptr;
+        c.pauli.ov_gexp = pl.n_ov ? grad_expect + size_t(pl.n_obs + pl.n_pobs) * (pl.T + 1) * pl.B : nullptr;
+        c.pauli.ov_targets = static_cast<const double2*>(p->overlap_targets);
         c.pauli.buf = reinterpret_cast<double2*>(c.ws + pl.off_pauli_cot);
         c.pauli.state_at = [&c](int k) { return c.state_at(k); };
         c.inj.pauli = &c.pauli;
@@ -516,7 +522,7 @@ int rydiff_backward(const RydProblem* p, const RydPlanInfo* info, const void* st
         // cotangent at the final time; the cotangents of the earlier save points are added by the launch that completes the
         // adjoint state there (fused injection: no separate launches, and no host-side look at grad_expect)
         hipLaunchKernelGGL(k_inject, dim3(unsigned((pl.dim + 255) / 256), pl.B), dim3(256), 0, stream, c.lam[0],
-                           c.inj.pauli ? pauli_cotangent(c.pauli, pl.T) : (c.inj.gstate ? c.inj.gstate + size_t(pl.T) * c.sv : nullptr), c.state_at(pl.T), c.inj.obs, c.inj.gexp, pl.n_obs,
+                           c.inj.pauli ? observable_cotangent(c.pauli, pl.T) : (c.inj.gstate ? c.inj.gstate + size_t(pl.T) * c.sv : nullptr), c.state_at(pl.T), c.inj.obs, c.inj.gexp, pl.n_obs,
                            pl.T + 1, pl.T, pl.B, uint32_t(pl.dim), 1, rt.obs_ostride(), rt.obs_bstride());
         LAUNCH_CHECK();
         // chained passes in trajectory-per-XCD placement: every group of trajectories runs its whole sweep before the next one starts

@@ -21,7 +21,7 @@ from .backend import TorchEmulator
 from .simconfig import SimConfig
 from .simresults import SimulationResults
 from .solver import SolverType
-from .observables import PauliObservable
+from .observables import PauliObservable, StateOverlap
 from .utils import DiagonalObservable, total_magnetization, total_magnetization_diag
 from .waveform_funcs import constant_waveform
 
@@ -148,7 +148,7 @@ class QuantumModel(Module):
             self._seq._set_register(self.register)
             self.built_seq = self._seq.build(**values) if self._seq.is_parametrized() else self._seq
 
-    def _run(self, observables=None) -> tuple[Tensor, SimulationResults]:
+    def _run(self, observables=None, store_states: Optional[bool] = None) -> tuple[Tensor, SimulationResults]:
         """model.py:405-414 — but the emulator PERSISTS between epochs: while the built sequence keeps its structure (the usual
         case: only parameter values move) its coefficient tables are refreshed in place instead of building a new emulator."""
         sim = getattr(self, "_sim", None)
@@ -162,7 +162,8 @@ class QuantumModel(Module):
         elif self.noise_config is not None and any(n in self.noise_config.noise for n in ("doppler", "amplitude", "SPAM")):
             self._sim.set_config(self.noise_config)  # stochastic noise: a fresh realisation per epoch, as a new emulator would draw
         results = self._sim.run(time_grad=self.time_grad, dist_grad=self.dist_grad, solver=self.solver,
-                                observables=observables, **self.options)
+                                observables=observables, **({} if store_states is None else {"store_states": store_states}),
+                                **self.options)
         return self._sim.evaluation_times, results
 
     def forward(self) -> tuple[Tensor, Tensor]:
@@ -180,3 +181,10 @@ class QuantumModel(Module):
         else:
             evaluation_times, results = self._run()
         return evaluation_times, results.expect([obs])[0]
+
+    def overlap(self, target) -> tuple[Tensor, Tensor]:
+        """Evaluation times and the complex overlaps ``<target_b | psi_b(t)>``, ``(n_t, B)``, evaluated and differentiated natively:
+        no trajectory is stored or handed to autograd.  ``target``: a ``StateOverlap`` or its targets, ``(dim,)`` or ``(dim, B)``."""
+        obs = target if isinstance(target, StateOverlap) else StateOverlap(target)
+        evaluation_times, results = self._run(observables=[obs], store_states=False)
+        return evaluation_times, results.overlap(obs)

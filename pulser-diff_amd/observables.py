@@ -18,6 +18,7 @@ import torch
 from torch import Tensor
 
 MAX_PAULI_STRINGS = 1024  # RYDIFF_MAX_PAULI_STRINGS
+MAX_OVERLAPS = 16  # RYDIFF_MAX_OVERLAPS
 MAX_DENSE_QUBITS = 14
 _I_POW = (1.0, 1j, -1.0, -1j)
 
@@ -212,3 +213,76 @@ def expect_pauli(obs: PauliObservable, states: Tensor) -> Tensor:
         else:  # tr(O rho) = sum_y O[y, y ^ xm] rho[y ^ xm, y]
             out = out + (coef[None, :, None] * states[:, yp, y, :]).sum(dim=(1, 2))
     return out
+
+
+class StateOverlap:
+    """The complex overlap ``c[k][b] = <phi_b | psi_b(t_k)>`` with a target state — what fidelities are made of (state fidelity
+    ``|c|^2``, gate fidelity ``|sum_b c_b| / dim``); evaluated and differentiated natively at every evaluation time
+    (``include/rydiff.h``: ``RydProblem.overlap_*``; ``csrc/overlap_kernels.hpp``), no stored trajectory.
+
+    ``targets``: ``(dim,)`` — one target shared by every trajectory of the batch — or ``(dim, B)``, one target per trajectory, in
+    the reference's layout of kets (basis index first).  Targets are constants (no gradient) and need not be normalised.
+    As an operator the observable is the projector ``|phi><phi|``: ``shape`` is ``(dim, dim)`` and ``results.expect`` gives
+    ``sum_b |c_b|^2``; the overlaps themselves come from ``results.overlap``."""
+
+    def __init__(self, targets):
+        t = torch.as_tensor(targets)
+        if not (t.is_complex() or t.is_floating_point()):
+            raise TypeError(f"StateOverlap targets must be complex (or real floating point) amplitudes, got {t.dtype}")
+        if t.ndim == 1:
+            t = t.unsqueeze(1)
+        if t.ndim != 2 or t.shape[0] < 2 or t.shape[1] < 1:
+            raise ValueError(f"StateOverlap targets must have shape (dim,) or (dim, B) with dim >= 2, got {tuple(t.shape)}")
+        self.targets = t.detach().to(torch.complex128)  # (dim, 1 | B)
+
+    @property
+    def shape(self) -> tuple:
+        return (self.targets.shape[0], self.targets.shape[0])
+
+    @property
+    def batch(self) -> int:
+        return int(self.targets.shape[1])
+
+    @property
+    def is_sparse(self) -> bool:
+        return False
+
+    def to(self, device) -> "StateOverlap":
+        """Moves the targets (in place: the object keeps its identity, which is how results find its native values)."""
+        self.targets = self.targets.to(device)
+        return self
+
+
+def overlap_states(obs: StateOverlap, states: Tensor) -> Tensor:
+    """``c[k][b] = sum_y conj(phi_b[y]) psi[k][y][b]`` in torch on stored kets ``(n_t, dim, B)``; complex ``(n_t, B)``."""
+    if states.is_sparse:
+        states = states.to_dense()
+    if states.ndim == 4:
+        raise NotImplementedError("StateOverlap is defined on kets; density matrices (master-equation runs) are not supported")
+    dim = obs.targets.shape[0]
+    if states.ndim != 3 or states.shape[1] != dim:
+        raise ValueError(f"StateOverlap with targets of dimension {dim} expects kets (n_t, {dim}, B), got {tuple(states.shape)}")
+    if obs.batch not in (1, states.shape[2]):
+        raise ValueError(f"StateOverlap holds {obs.batch} targets but the states have batch {states.shape[2]}")
+    phi = obs.targets.to(states.device)
+    return (phi.conj()[None, :, :] * states.to(torch.complex128)).sum(dim=1)
+
+
+def pack_overlaps(observables: Sequence[StateOverlap], dim: int, batch: int, device=None) -> Tensor:
+    """The ``(n_ov, 1 | B, dim)`` complex128 tensor of ``RydProblem.overlap_targets`` (``ProblemSpec.overlaps``): batch 1 when every
+    observable shares its target over the trajectories, else ``B`` (shared targets repeated)."""
+    observables = list(observables)
+    if not observables:
+        raise ValueError("no StateOverlap observable to pack")
+    if len(observables) > MAX_OVERLAPS:
+        raise ValueError(f"too many StateOverlap observables: {len(observables)} (at most {MAX_OVERLAPS} per call)")
+    for o in observables:
+        if not isinstance(o, StateOverlap):
+            raise TypeError(f"expected StateOverlap objects, got {type(o)}")
+        if o.targets.shape[0] != dim:
+            raise ValueError(f"StateOverlap targets of dimension {o.targets.shape[0]} handed to states of dimension {dim}")
+        if o.batch not in (1, batch):
+            raise ValueError(f"StateOverlap holds {o.batch} targets: must be 1 or the batch size {batch}")
+    bt = max(o.batch for o in observables)
+    rows = [o.targets.to(device).transpose(0, 1).expand(bt, dim) for o in observables]
+    return torch.stack(rows).contiguous()

@@ -19,7 +19,7 @@ import torch
 from torch import Tensor
 
 from .result import SampledResult, TorchResult
-from .observables import PauliObservable
+from .observables import PauliObservable, StateOverlap, overlap_states
 from .utils import DiagonalObservable, expect
 
 
@@ -55,7 +55,8 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
     def __init__(self, states_tbd: Tensor, size: int, basis_name: str, sim_times: Tensor, meas_basis: str,
                  meas_errors: Optional[Mapping[str, float]] = None, atom_order: tuple = (),
                  native_expect: Optional[Tensor] = None, native_observables: Optional[list] = None,
-                 stats: Optional[dict] = None, density: bool = False) -> None:
+                 stats: Optional[dict] = None, density: bool = False, native_overlaps: Optional[Tensor] = None,
+                 overlap_observables: Optional[list] = None) -> None:
         super().__init__(size, basis_name, sim_times)
         if self._basis_name == "all":  # simresults.py:381-383
             if meas_basis not in {"ground-rydberg", "digital"}:
@@ -71,6 +72,8 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
         self._atom_order = atom_order
         self._native_expect = native_expect  # (n_obs, n_t, B)
         self._native_observables = list(native_observables or [])
+        self._native_overlaps = native_overlaps  # complex (n_ov, n_t, B)
+        self._overlap_observables = list(overlap_observables or [])
         self.solver_stats = dict(stats or {})
 
     # ---- sequence protocol over per-time results (pulser.result.Results)
@@ -109,7 +112,7 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
         legal_shape = (self._dim**self._size, self._dim**self._size)
         out = []
         for obs in obs_list:
-            if not isinstance(obs, (Tensor, DiagonalObservable, PauliObservable)):
+            if not isinstance(obs, (Tensor, DiagonalObservable, PauliObservable, StateOverlap)):
                 raise TypeError(f"Incompatible type {type(obs)} of observable. Type must be ArrayLike or qutip.Qobj.")
             if tuple(obs.shape) != legal_shape:
                 raise ValueError("Incompatible shape of observable." + f"Expected {legal_shape}, got {tuple(obs.shape)}.")
@@ -117,8 +120,23 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
             if hit and self._native_expect is not None:
                 out.append(self._native_expect[hit[0]].sum(dim=-1).to(torch.complex128))
                 continue
+            if isinstance(obs, StateOverlap):  # the projector |phi><phi|: sum_b |c_b|^2
+                out.append((self.overlap(obs).abs() ** 2).sum(dim=-1).to(torch.complex128))
+                continue
             out.append(expect(obs, self.states))
         return out
+
+    def overlap(self, obs: StateOverlap) -> Tensor:
+        """``<phi_b | psi_b(t_k)>``, complex ``(n_t, B)``: the native values when ``obs`` was handed to ``run(observables=...)``,
+        else computed from the stored states."""
+        if not isinstance(obs, StateOverlap):
+            raise TypeError(f"overlap takes a StateOverlap, got {type(obs)}")
+        if self._density:
+            raise NotImplementedError("StateOverlap is defined on kets; this is a master-equation run.")
+        hit = [k for k, o in enumerate(self._overlap_observables) if o is obs]
+        if hit and self._native_overlaps is not None:
+            return self._native_overlaps[hit[0]]
+        return overlap_states(obs, self.states)
 
     def sample_state(self, t: float, n_samples: int = 1000, t_tol: float = 1.0e-3) -> Counter:
         """simresults.py:497-540: ideal samples, then the detection errors of the SPAM model (a measured 0 flips with

@@ -20,7 +20,7 @@ import torch
 from torch import Tensor
 
 from . import _native
-from .observables import PauliObservable, check_pauli, pack_pauli
+from .observables import PauliObservable, StateOverlap, check_pauli, pack_overlaps, pack_pauli
 
 
 class SolverType(enum.Enum):
@@ -68,6 +68,13 @@ class ProblemSpec:
     # Pauli-string observables evaluated (and differentiated) natively next to obs_diag: a list of PauliObservable, or the packed
     # host arrays (pauli_first, pauli_x, pauli_z, pauli_w) of RydProblem; their values follow the diagonal ones in `expect`
     pauli: Optional[Any] = None
+    # state-overlap observables (RydProblem.overlap_*): the packed targets, a complex128 DEVICE tensor (n_ov, 1 | B, 2^N)
+    # (observables.pack_overlaps); Re / Im of every overlap follow the Pauli rows in `expect`.  Constants: no gradient.
+    overlaps: Optional[Tensor] = None
+
+    @property
+    def n_overlaps(self) -> int:
+        return 0 if self.overlaps is None else int(self.overlaps.shape[0])
 
     def packed_pauli(self):
         """The four host arrays of RydProblem.pauli_* (None: no Pauli observables)."""
@@ -173,10 +180,36 @@ class _Call:
             p.pauli_x = px.ctypes.data if len(px) else None
             p.pauli_z = pz.ctypes.data if len(px) else None
             p.pauli_w = pw.ctypes.data if len(px) else None
+        self.overlaps = None
+        if spec.overlaps is not None:
+            _check_overlaps(spec, batch)
+            self.overlaps = spec.overlaps.contiguous()
+            p.n_overlaps = self.overlaps.shape[0]
+            p.overlap_batch = self.overlaps.shape[1]
+            p.overlap_targets = self.overlaps.data_ptr()
         self.problem = p
 
 
-def _check_shapes(spec: ProblemSpec, amp: Tensor, det: Tensor, u_pairs: Tensor, obs: Optional[Tensor], batch: int) -> None:
+def _check_overlaps(spec: ProblemSpec, batch: int, device: Optional[torch.device] = None) -> None:
+    """ProblemSpec.overlaps against the spec: shape (n_ov, 1 | batch, 2^N), complex128, count within the cap, on `device`."""
+    ov = spec.overlaps
+    if ov is None:
+        return
+    dim = 2 ** spec.n_qubits
+    if not isinstance(ov, Tensor) or ov.dtype != torch.complex128:
+        raise ValueError(f"overlaps must be a complex128 tensor, got {getattr(ov, 'dtype', type(ov))}")
+    if ov.ndim != 3 or ov.shape[2] != dim or ov.shape[0] < 1:
+        raise ValueError(f"overlaps must have shape (n_overlaps, 1 or batch, {dim}), got {tuple(ov.shape)}")
+    if ov.shape[0] > _native.MAX_OVERLAPS:
+        raise ValueError(f"too many overlap observables: {ov.shape[0]} (at most {_native.MAX_OVERLAPS} per call)")
+    if ov.shape[1] not in (1, batch):
+        raise ValueError(f"overlaps: the target batch must be 1 or the batch size {batch}, got {ov.shape[1]}")
+    if device is not None and ov.device != torch.device(device):
+        raise ValueError(f"overlaps must live on the device of the states ({device}), got {ov.device}")
+
+
+def _check_shapes(spec: ProblemSpec, amp: Tensor, det: Tensor, u_pairs: Tensor, obs: Optional[Tensor], batch: int,
+                  device: Optional[torch.device] = None) -> None:
     """The C ABI sees raw pointers only: every buffer is checked against the spec here, so that a mismatch is a ValueError and
     never an out-of-bounds device read."""
     ka, kd, n, nq = len(spec.amp_masks), len(spec.det_masks), spec.n_samples, spec.n_qubits
@@ -199,6 +232,7 @@ def _check_shapes(spec: ProblemSpec, amp: Tensor, det: Tensor, u_pairs: Tensor, 
     if obs is not None and obs.numel() and (obs.ndim != 2 or obs.shape[1] != 2 ** nq):
         raise ValueError(f"obs_diag must have shape (n_obs, {2 ** nq}), got {tuple(obs.shape)}")
     spec.packed_pauli()  # raises ValueError on a mask bit at or above N, inconsistent counts, too many strings
+    _check_overlaps(spec, batch, device)
     if batch > 65535:
         raise ValueError("batch must be <= 65535 (split the columns / trajectories into several calls)")
 
@@ -260,7 +294,7 @@ class _RydbergEvolve(torch.autograd.Function):
         batch, dim = psi_c.shape
         if dim != 2 ** spec.n_qubits:
             raise ValueError(f"Incompatible shape of initial state.Expected {2 ** spec.n_qubits}, got {dim}.")
-        _check_shapes(spec, amp_c, det_c, u_c, obs_c, batch)
+        _check_shapes(spec, amp_c, det_c, u_c, obs_c, batch, dev)
         n_t = len(ts_host)
         # (real_amp_grad only matters to the adjoint launches; set here as well so that the plan's kernel_bwd names what will run)
         call = _Call(spec, amp_c, det_c, u_c, ts_host, batch, obs_c, real_amp_grad=not amp.is_complex())
@@ -325,7 +359,8 @@ class _RydbergEvolve(torch.autograd.Function):
                         raise
             states = (torch.empty((n_t, batch, dim), dtype=torch.complex128, device=dev) if spec.store_states
                       else torch.empty((0, batch, dim), dtype=torch.complex128, device=dev))
-            n_obs = call.problem.n_obs + call.problem.n_pauli_obs  # diagonal observables first
+            # diagonal observables first, then the Pauli ones, then Re / Im of every overlap
+            n_obs = call.problem.n_obs + call.problem.n_pauli_obs + 2 * call.problem.n_overlaps
             expect = torch.empty((n_obs, n_t, batch), dtype=torch.float64, device=dev)
             _native.check(L.rydiff_forward(ctypes.byref(call.problem), ctypes.byref(info), _ptr(psi_c),
                                            _ptr(states) if spec.store_states else None,
@@ -415,22 +450,35 @@ class SolveResult:
     states: Tensor  # (n_t, dim, B) view, like pyqtorch
     expect: Tensor  # (n_obs + n_pauli, n_t, B) observables evaluated natively, the diagonal ones first
     stats: dict
+    overlaps: Optional[Tensor] = None  # complex (n_ov, n_t, B): <phi_o,b | psi_b(t_k)> evaluated natively (differentiable), or None
+
+
+def split_expect(expect: Tensor, n_overlaps: int) -> tuple[Tensor, Optional[Tensor]]:
+    """The `expect` output of ``evolve`` -> (diagonal and Pauli rows, complex overlaps (n_ov, n_t, B) or None)."""
+    if not n_overlaps:
+        return expect, None
+    n_real = expect.shape[0] - 2 * n_overlaps
+    pairs = expect[n_real:].reshape(n_overlaps, 2, *expect.shape[1:])
+    return expect[:n_real], torch.complex(pairs[:, 0], pairs[:, 1])
 
 
 def evolve(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Tensor,
            spec: ProblemSpec, obs_diag: Optional[Tensor] = None) -> tuple[Tensor, Tensor]:
-    """Low-level entry: psi0 is (B, dim); returns states (n_t, B, dim) and expect (n_obs, n_t, B)."""
+    """Low-level entry: psi0 is (B, dim); returns states (n_t, B, dim) and expect (n_obs + n_pauli + 2 n_overlaps, n_t, B)
+    (``split_expect`` takes the overlap rows of ``spec.overlaps`` out as complex numbers)."""
     return _RydbergEvolve.apply(amp_tables, det_tables, u_pairs, tsave, psi0, obs_diag, spec)
 
 
 def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverType.DP5_SE,
             options: Optional[dict] = None, obs_diag: Optional[Tensor] = None, store_states: bool = True,
-            pauli_obs: Optional[Sequence[PauliObservable]] = None) -> SolveResult:
+            pauli_obs: Optional[Sequence[PauliObservable]] = None,
+            overlap_obs: Optional[Sequence[StateOverlap]] = None) -> SolveResult:
     """Drop-in for ``pyqtorch.sesolve(H=..., psi0, tsave, solver, options)`` at ``backend.py:488-494``.
 
     ``problem`` is the structured Hamiltonian (``pulser_diff_amd.hamiltonian.Hamiltonian``) instead of the opaque
     callable; ``psi0`` is ``(dim, B)`` as in the reference.  ``pauli_obs``: Pauli-string observables evaluated natively; their
-    values follow the diagonal ones in ``SolveResult.expect``.
+    values follow the diagonal ones in ``SolveResult.expect``.  ``overlap_obs``: ``StateOverlap`` observables evaluated natively
+    into ``SolveResult.overlaps``.
     """
     options = dict(options or {})
     spec = problem.problem_spec(solver=solver, tol=tolerance_from_options(options), store_states=store_states)
@@ -446,6 +494,14 @@ def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverTyp
         if obs_diag is not None:
             obs_diag = torch.zeros(obs_diag.shape[0], 1 << spec.n_qubits, dtype=obs_diag.dtype,
                                    device=obs_diag.device).index_copy(1, embed, obs_diag)
+    overlap_obs = list(overlap_obs or [])
+    targets = None
+    if overlap_obs:
+        # (n_ov, 1 | B, dim) in the basis the states are stored in; three levels: scattered like psi0, zeros on the unused codes
+        targets = pack_overlaps(overlap_obs, psi_bd.shape[1] if embed is None else embed.numel(), psi_bd.shape[0], psi_bd.device)
+        if embed is not None:
+            targets = torch.zeros(*targets.shape[:2], 1 << spec.n_qubits, dtype=targets.dtype,
+                                  device=targets.device).index_copy(2, embed, targets)
     pauli_obs = list(pauli_obs or [])
     if pauli_obs and embed is not None:
         raise NotImplementedError("Pauli observables are not available in the three-level all-basis; use results.expect on stored states.")
@@ -472,10 +528,15 @@ def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverTyp
             ones += ((x >> j) & 1).to(torch.float64)
         rot = torch.exp(1j * float(phi) * ones)
         psi_bd = psi_bd * rot[None, :]
+        if targets is not None:  # <phi|psi> = <V phi|V psi>: the targets go into the frame with psi0
+            targets = targets * rot[None, None, :]
+    if targets is not None:
+        spec.overlaps = targets.contiguous()
     states, expect = evolve(amp_tables, problem.det_tables, problem.u_pairs, tsave, psi_bd, spec, obs_diag)
     if rot is not None and states.numel():
         states = states * rot.conj()[None, None, :]
     if embed is not None and states.numel():
         states = states.index_select(2, embed)
+    expect, overlaps = split_expect(expect, len(overlap_obs))
     return SolveResult(states.permute(0, 2, 1) if states.numel() else states, expect,
-                       dict(spec.options.get("_last_stats", {})))
+                       dict(spec.options.get("_last_stats", {})), overlaps)

@@ -13,7 +13,7 @@ from math import pi, prod, sin
 import torch
 from torch import Tensor
 
-from .observables import PauliObservable, expect_pauli
+from .observables import PauliObservable, StateOverlap, expect_pauli, overlap_states
 
 # pyqtorch.matrices restated (imported by the reference at utils.py:7, hamiltonian.py:17)
 IMAT = torch.eye(2, dtype=torch.complex128)
@@ -82,6 +82,8 @@ def expect(obs, states: Tensor) -> Tensor:
         if states.is_sparse:
             states = states.to_dense()
         return expect_pauli(obs, states)
+    if isinstance(obs, StateOverlap):  # the projector |phi><phi|: sum_b |<phi_b|psi_b>|^2
+        return (overlap_states(obs, states).abs() ** 2).sum(dim=-1).to(torch.complex128)
     if isinstance(obs, DiagonalObservable):
         d = obs.diag.to(states.device)
         if states.ndim == 4:  # density matrices: tr(O rho) = sum_x O[x] rho[x, x]
