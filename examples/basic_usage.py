@@ -2,7 +2,7 @@
 """The flows of the reference's docs/basic_usage.ipynb on the MI355X-native backend (needs a GPU):
 
   1. simulate a sequence and read states / expectation values           (notebook section 1.1)
-  2. derivatives w.r.t. time, pulse parameters and atom positions       (1.2: deriv_time / deriv_param)
+  2. derivatives w.r.t. time, pulse parameters and atom positions       (1.2: deriv_time / deriv_param, and at every time)
   3. optimise pulse parameters with QuantumModel + Adam                 (2.1)
   4. the same sequence with stochastic noise                            (SimConfig)
   5. collapse-operator noise: the master equation, SolverType.DP5_ME    (2.5)
@@ -16,7 +16,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch
 
 from pulser_diff_amd import QuantumModel, SimConfig, SolverType, TorchEmulator
-from pulser_diff_amd.derivative import deriv_param, deriv_time
+from pulser_diff_amd.derivative import deriv_param, deriv_param_all_times, deriv_time
 from pulser_diff_amd.pulses import BlackmanWaveform, MockDevice, Pulse, RampWaveform, Register, Sequence
 from pulser_diff_amd.utils import total_magnetization
 
@@ -43,6 +43,15 @@ d_omega, d_area = deriv_param(exp_val, [omega, area], times, 1200)  # t in ns, l
 (d_q0,) = deriv_param(exp_val, [q0], times, 1200)
 print(f"2. d<Z>/dt(0.8us) = {dt_f[80].item():+.4f};  at t = 1.2us: d/domega = {d_omega.item():+.4f}, d/darea = {d_area.item():+.4f}, "
       f"d/dq0 = ({d_q0[0].item():+.4f}, {d_q0[1].item():+.4f})")
+# the notebook's "derivative at each time" loop (for t in times: deriv_param(f=exp_val, x=diff_params, times=times, t=t)) as ONE
+# forward-mode sweep: the state and one tangent state per scalar parameter advance together (rydiff_forward_tangent)
+sens = deriv_param_all_times(sim, [omega, area, q0], [obs])
+g_omega, g_area, g_q0 = (g[0] for g in sens.grads)  # (n_t, *parameter shape) each
+k_max = int(g_omega[:, 0].abs().argmax())
+k12 = int(torch.argmin(torch.abs(times.detach() - 1.2)))  # the evaluation time deriv_param picked for t = 1200 ns
+print(f"   all {len(times)} times in one {sens.route} sweep: d<Z>/domega(1.2us) = {g_omega[k12, 0].item():+.4f}, d<Z>/darea(1.2us) = "
+      f"{g_area[k12, 0].item():+.4f}, d<Z>/dq0(1.2us) = ({g_q0[k12, 0].item():+.4f}, {g_q0[k12, 1].item():+.4f}); "
+      f"|d<Z>/domega| peaks at t = {times[k_max].item():.2f} us ({g_omega[k_max, 0].item():+.4f})")
 
 # ---- 3. optimisation ------------------------------------------------------------------------------------------------
 reg2 = Register.rectangle(1, 2, spacing=8, prefix="q")

@@ -307,6 +307,44 @@ int rydiff_backward(const RydProblem* p, const RydPlanInfo* info, const void* st
                     const double* grad_expect, void* g_amp, double* g_det, double* g_u, double* g_tsave, void* g_psi0,
                     void* workspace, size_t workspace_bytes, int need_tape, void* stream);
 
+/* Forward-mode (tangent) sweep: the Jacobian-vector twin of rydiff_backward.  One sweep carries the state AND n_dir tangent
+ * states through every factor pass and emits d<O>(t_k)/d(theta_d) for every evaluation time, every observable row and every
+ * direction d, at roughly (1 + n_dir) forward passes instead of one reverse sweep per evaluation time.  A direction is given by
+ * the tangents of the problem's inputs: tables laid out like the tables themselves with the direction as the outermost index.
+ * The plan constants (polynomial roots, spectral shift, sub-steps) are frozen — the discrete map that rydiff_backward
+ * differentiates:   y = (gamma + beta H) x   =>   dy_d = (gamma + beta H) dx_d + beta dH_d x,   dH_d = H built from the tangent
+ * coefficients (same groups, masks, conjugation and diagonal rules).  Tangents w.r.t. tsave are not part of it (g_tsave of
+ * rydiff_backward delivers all of them in one reverse sweep). */
+#define RYDIFF_MAX_TANGENTS 8
+typedef struct RydTangent {
+    int32_t n_dir;          /* 1..RYDIFF_MAX_TANGENTS */
+    const void*   d_amp;    /* DEVICE complex128 [n_dir][coeff_batch][n_amp_terms][n_samples] or NULL (zero) */
+    const double* d_det;    /* DEVICE float64    [n_dir][coeff_batch][n_det_terms][n_samples] or NULL */
+    const double* d_u;      /* DEVICE float64    [n_dir][N(N-1)/2] or NULL */
+    const void*   d_psi0;   /* DEVICE complex128 [n_dir][B][2^N] or NULL */
+} RydTangent;
+
+/* sizeof(RydTangent) as this library was compiled (see rydiff_sizeof_problem). */
+size_t rydiff_sizeof_tangent(void);
+
+/* Device workspace of rydiff_forward_tangent for n_dir directions (sized as if every tangent pointer were given); 0 on an
+ * error (rydiff_last_error).  `info`: from rydiff_plan(p, 0, 0, ...).  Host only. */
+size_t rydiff_tangent_workspace_bytes(const RydProblem* p, const RydPlanInfo* info, int n_dir);
+
+/* The tangent sweep.  Asynchronous like rydiff_forward with a plan: it only enqueues work on `stream`.
+ *   info         HOST: result of rydiff_plan(p, 0, 0, ...) for the SAME table values (required)
+ *   psi0         DEVICE complex128 [B][2^N]
+ *   expect_out   DEVICE float64 [rows][n_tsave][B] or NULL: the values, rows = n_obs + n_pauli_obs + 2 * n_overlaps in the order
+ *                of rydiff_forward
+ *   dexpect_out  DEVICE float64 [n_dir][rows][n_tsave][B] (required): diagonal rows 2 sum_y o[y] Re(conj psi[y] dpsi_d[y]), Pauli
+ *                rows 2 sum_s w_s Re<psi|P_s|dpsi_d>, overlap rows Re / Im <phi_o|dpsi_d>; every save point, k = 0 included
+ *   workspace    DEVICE, >= rydiff_tangent_workspace_bytes(p, info, n_dir)
+ * Both solvers, coeff_batch 1 or B, dp5_piece_refine honoured (same plan); kernel_variant is ignored: the sweep has one kernel
+ * family (launch per factor, one amplitude per thread).  Not implemented (RYDIFF_ENOTIMPL): state-sharded runs, pair terms,
+ * conditioned / ones-counting terms.  Every argument is validated before anything touches a device. */
+int rydiff_forward_tangent(const RydProblem* p, const RydPlanInfo* info, const RydTangent* tangent, const void* psi0,
+                           double* expect_out, double* dexpect_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* One matrix-free application y = H(coefficients) x on DEVICE buffers, for get_hamiltonian-style
  * checks (backend.py:401-427) and micro-benchmarks.  c_amp: HOST complex (re,im) per amp term,
  * c_det: HOST value per det term (already interpolated, reference units as above). */

@@ -29,6 +29,7 @@ MAX_QUBITS = 30
 MAX_TERMS = 64
 MAX_PAULI_STRINGS = 1024
 MAX_OVERLAPS = 16
+MAX_TANGENTS = 8
 
 
 class RydProblem(ctypes.Structure):
@@ -100,6 +101,18 @@ class RydPlanInfo(ctypes.Structure):
     ]
 
 
+class RydTangent(ctypes.Structure):
+    """Directions of one forward-mode sweep (include/rydiff.h): tangent tables laid out like the tables, direction outermost."""
+
+    _fields_ = [
+        ("n_dir", ctypes.c_int32),
+        ("d_amp", ctypes.c_void_p),
+        ("d_det", ctypes.c_void_p),
+        ("d_u", ctypes.c_void_p),
+        ("d_psi0", ctypes.c_void_p),
+    ]
+
+
 EXPORTS = (
     "rydiff_plan",
     "rydiff_forward",
@@ -111,6 +124,9 @@ EXPORTS = (
     "rydiff_version",
     "rydiff_sizeof_problem",
     "rydiff_sizeof_plan_info",
+    "rydiff_sizeof_tangent",
+    "rydiff_tangent_workspace_bytes",
+    "rydiff_forward_tangent",
 )
 
 _lib = None
@@ -153,7 +169,14 @@ def lib() -> ctypes.CDLL:
     L.rydiff_version.restype = ctypes.c_char_p
     L.rydiff_sizeof_problem.restype = ctypes.c_size_t
     L.rydiff_sizeof_plan_info.restype = ctypes.c_size_t
-    if (L.rydiff_sizeof_problem(), L.rydiff_sizeof_plan_info()) != (ctypes.sizeof(RydProblem), ctypes.sizeof(RydPlanInfo)):
+    L.rydiff_sizeof_tangent.restype = ctypes.c_size_t
+    L.rydiff_tangent_workspace_bytes.argtypes = [ctypes.POINTER(RydProblem), ctypes.POINTER(RydPlanInfo), i32]
+    L.rydiff_tangent_workspace_bytes.restype = ctypes.c_size_t
+    L.rydiff_forward_tangent.argtypes = [ctypes.POINTER(RydProblem), ctypes.POINTER(RydPlanInfo), ctypes.POINTER(RydTangent), vp, vp, vp,
+                                         vp, ctypes.c_size_t, vp]
+    L.rydiff_forward_tangent.restype = i32
+    if (L.rydiff_sizeof_problem(), L.rydiff_sizeof_plan_info(), L.rydiff_sizeof_tangent()) != (
+            ctypes.sizeof(RydProblem), ctypes.sizeof(RydPlanInfo), ctypes.sizeof(RydTangent)):
         raise RuntimeError(f"{_LIB_PATH} was built from another include/rydiff.h than this binding mirrors (struct sizes differ): rebuild it")
     _lib = L
     return L

@@ -382,6 +382,29 @@ int plan_runtime(const RydProblem* p, const RydPlanInfo* info, void* scratch, si
     return RYDIFF_OK;
 }
 
+// K0 on one set of tables: per-exponential coefficient records [Bc][E][NC] into `coef`, from the StageDev records already in the
+// workspace.  A nullptr table is a zero table (its terms are left out of the sums): the tangent sweep hands in tangent tables.
+int launch_expand(const Plan& pl, char* ws, const double2* amp, const double* det, double* coef, hipStream_t stream) {
+    const size_t E = pl.stages.size();
+    ExpandArgs ea{};
+    ea.amp = amp;
+    ea.det = det;
+    ea.st = reinterpret_cast<const StageDev*>(ws + pl.off_meta_idx);
+    ea.coef = coef;
+    ea.E = int(E);
+    ea.n_samples = pl.n_samples;
+    ea.Ka = amp ? pl.Ka : 0;
+    ea.Kd = det ? pl.Kd : 0;
+    ea.NC = pl.NC;
+    ea.ga = pl.ga.n;
+    ea.gd = pl.gd.n;
+    for (int g = 0; g < pl.ga.n; ++g) ea.amem[g] = pl.ga.members[g];
+    for (int g = 0; g < pl.gd.n; ++g) ea.dmem[g] = pl.gd.members[g];
+    hipLaunchKernelGGL(k_expand_coeffs, dim3((unsigned(E) + 127) / 128, pl.Bc), dim3(128), 0, stream, ea);
+    LAUNCH_CHECK();
+    return RYDIFF_OK;
+}
+
 // common prologue of forward / backward: plan_runtime, upload metadata, expand coefficients, udiag.
 // With `info` given nothing in here waits for the device.
 int prepare(const RydProblem* p, const RydPlanInfo* info, void* workspace, size_t workspace_bytes, int need_tape,
@@ -415,23 +438,9 @@ int prepare(const RydProblem* p, const RydPlanInfo* info, void* workspace, size_
         if (rc) return rc;
     }
     if (pl.NC > 0) {
-        ExpandArgs ea{};
-        ea.amp = static_cast<const double2*>(p->amp_tables);
-        ea.det = p->det_tables;
-        ea.st = reinterpret_cast<const StageDev*>(ws + pl.off_meta_idx);
-        ea.coef = reinterpret_cast<double*>(ws + pl.off_coef);
-        ea.E = int(E);
-        ea.n_samples = pl.n_samples;
-        ea.Ka = pl.Ka;
-        ea.Kd = pl.Kd;
-        ea.NC = pl.NC;
-        ea.ga = pl.ga.n;
-        ea.gd = pl.gd.n;
-        for (int g = 0; g < pl.ga.n; ++g) ea.amem[g] = pl.ga.members[g];
-        for (int g = 0; g < pl.gd.n; ++g) ea.dmem[g] = pl.gd.members[g];
-        dim3 grid((unsigned(E) + 127) / 128, pl.Bc);
-        hipLaunchKernelGGL(k_expand_coeffs, grid, dim3(128), 0, stream, ea);
-        LAUNCH_CHECK();
+        const int rc2 = launch_expand(pl, ws, static_cast<const double2*>(p->amp_tables), p->det_tables,
+                                      reinterpret_cast<double*>(ws + pl.off_coef), stream);
+        if (rc2) return rc2;
     }
     double* udiag = reinterpret_cast<double*>(ws + pl.off_udiag);
     if (pl.N > 1) {

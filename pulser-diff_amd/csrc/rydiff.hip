@@ -43,6 +43,7 @@ using namespace rydiff;
 #include "lane_kernels.hpp"
 #include "pauli_kernels.hpp"
 #include "overlap_kernels.hpp"
+#include "tangent_kernels.hpp"
 static_assert(sizeof(PersistFactor) == 48, "plan.hpp sizes the factor table with 48 bytes per entry");
 
 #include "runtime.hpp"
@@ -51,6 +52,7 @@ static_assert(sizeof(PersistFactor) == 48, "plan.hpp sizes the factor table with
 #include "chain_launch.hpp"
 #include "pair_launch.hpp"
 #include "overlap_launch.hpp"
+#include "tangent_launch.hpp"
 #include "persist_launch.hpp"
 
 namespace {
@@ -370,6 +372,7 @@ const char* rydiff_last_error(void) { return g_last_error.c_str(); }
 const char* rydiff_version(void) { return "rydiff 0.4 (gfx950)"; }
 size_t rydiff_sizeof_problem(void) { return sizeof(RydProblem); }
 size_t rydiff_sizeof_plan_info(void) { return sizeof(RydPlanInfo); }
+size_t rydiff_sizeof_tangent(void) { return sizeof(RydTangent); }
 
 #ifdef RYDIFF_TIMELINE
 int rydiff_debug_timeline(unsigned long long* host_buf, int n_entries) {  // tuning builds only
@@ -534,6 +537,90 @@ int rydiff_backward(const RydProblem* p, const RydPlanInfo* info, const void* st
     }
     if (g_psi0) HIP_TRY(hipMemcpyAsync(g_psi0, c.lam[cl], pl.state_bytes, hipMemcpyDeviceToDevice, stream));
     return scatter_gradients(c, g_amp, g_det, g_u, g_tsave);
+}
+
+size_t rydiff_tangent_workspace_bytes(const RydProblem* p, const RydPlanInfo* info, int n_dir) {
+    Runtime rt;
+    TangentLayout lay;
+    return tangent_plan(p, info, n_dir, rt, lay) ? 0 : lay.total;
+}
+
+// Forward-mode sweep: the state and n_dir tangents through every factor once (tangent_kernels.hpp), observable tangents at every
+// save point.  One kernel family: launch per factor, one amplitude per thread.
+int rydiff_forward_tangent(const RydProblem* p, const RydPlanInfo* info, const RydTangent* tg, const void* psi0, double* expect_out,
+                           double* dexpect_out, void* workspace, size_t workspace_bytes, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    // ---- host-only validation: nothing below this block runs unless all of it passes ----
+    if (!p) return fail(RYDIFF_EINVAL, "null problem");
+    if (!tg) return fail(RYDIFF_EINVAL, "null tangent");
+    int rc = tangent_validate(p, info, tg->n_dir);  // n_dir, the plan, what the sweep does not implement
+    if (rc) return rc;
+    if (!tg->d_amp && !tg->d_det && !tg->d_u && !tg->d_psi0)
+        return fail(RYDIFF_EINVAL, "tangent: all of d_amp, d_det, d_u, d_psi0 are NULL (nothing to differentiate)");
+    if (!dexpect_out) return fail(RYDIFF_EINVAL, "null dexpect_out");
+    if (!psi0) return fail(RYDIFF_EINVAL, "null psi0");
+    Runtime rt0;
+    TangentLayout lay;
+    rc = tangent_plan(p, info, tg->n_dir, rt0, lay);
+    if (rc) return rc;
+    if (!workspace) return fail(RYDIFF_EINVAL, "null workspace");
+    if (workspace_bytes < lay.total)
+        return fail(RYDIFF_EWORKSPACE, "tangent workspace too small: need " + std::to_string(lay.total) + " bytes, got " + std::to_string(workspace_bytes));
+    // ---- device work ----
+    RydProblem q = *p;
+    q.kernel_variant = 0;
+    Runtime rt;
+    rc = prepare(&q, info, workspace, workspace_bytes, 0, false, stream, rt);  // metadata, coefficient records, udiag, Pauli tables
+    if (rc) return rc;
+    const Plan& pl = rt.pl;
+    const int D = tg->n_dir;
+    char* ws = static_cast<char*>(workspace);
+    rc = tangent_tables(rt, &q, tg, ws, lay, stream);
+    if (rc) return rc;
+    const size_t sv = size_t(pl.B) * pl.dim;
+    double2* vec[2] = {reinterpret_cast<double2*>(ws + lay.off_vec[0]), reinterpret_cast<double2*>(ws + lay.off_vec[1])};
+    HIP_TRY(hipMemcpyAsync(vec[0], psi0, pl.state_bytes, hipMemcpyDeviceToDevice, stream));
+    const int Dp = tangent_padded(D);  // the kernel's direction count: a padded direction starts at zero and stays there
+    if (tg->d_psi0) {
+        HIP_TRY(hipMemcpyAsync(vec[0] + sv, tg->d_psi0, size_t(D) * pl.state_bytes, hipMemcpyDeviceToDevice, stream));
+        if (Dp > D) HIP_TRY(hipMemsetAsync(vec[0] + size_t(1 + D) * sv, 0, size_t(Dp - D) * pl.state_bytes, stream));
+    } else {
+        HIP_TRY(hipMemsetAsync(vec[0] + sv, 0, size_t(Dp) * pl.state_bytes, stream));
+    }
+    const size_t rows = size_t(pl.n_obs + pl.n_pobs + 2 * pl.n_ov);
+    const size_t row = size_t(pl.T + 1) * pl.B;
+    if (rows) HIP_TRY(hipMemsetAsync(dexpect_out, 0, size_t(D) * rows * row * sizeof(double), stream));
+    ForwardCtx c{{rt, &q, ws, stream, sv}};
+    c.psi0 = c.start = vec[0];
+    c.obs = q.obs_diag;
+    c.expect_out = expect_out;
+    c.want_exp = expect_out && pl.n_obs > 0;
+    c.pauli_out = (expect_out && pl.n_pobs) ? expect_out + size_t(pl.n_obs) * row : nullptr;
+    c.overlap_out = (expect_out && pl.n_ov) ? expect_out + size_t(pl.n_obs + pl.n_pobs) * row : nullptr;
+    if (expect_out && rows) HIP_TRY(hipMemsetAsync(expect_out, 0, rows * row * sizeof(double), stream));
+    auto save_point = [&](const double2* v, int k) -> int {  // values (the existing reductions on psi) and tangents of every row
+        if (c.want_exp)
+            if (const int r = launch_expect(c, v, k)) return r;
+        if (const int r = launch_observables_expect(c, v, 0, k, 1, BatchSlice{0, pl.B, false})) return r;
+        return launch_expect_tangent(c, v, D, k, dexpect_out);
+    };
+    rc = save_point(vec[0], 0);
+    if (rc) return rc;
+    TangentFactorArgs fa{};
+    fill_tangent_factor(fa, rt, ws, lay, tg->d_u != nullptr);
+    std::vector<ChainItem> chain;
+    int cur = 0;
+    for (int k = 0; k < pl.T; ++k) {
+        build_step_chain(rt, k, chain);
+        for (const ChainItem& it : chain) {
+            rc = launch_factor_tangent(fa, rt, ws, lay, D, vec[cur], vec[cur ^ 1], it.stage, it.s, stream);
+            if (rc) return rc;
+            cur ^= 1;
+        }
+        rc = save_point(vec[cur], k + 1);
+        if (rc) return rc;
+    }
+    return RYDIFF_OK;
 }
 
 int rydiff_apply_factor(const RydProblem* p, const double* c_amp_reim, const double* c_det, const double* gamma_reim,

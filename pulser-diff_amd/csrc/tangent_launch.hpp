@@ -1,0 +1,183 @@
+// tangent_launch.hpp — forward-mode (tangent) sweep (tangent_kernels.hpp): argument validation, the workspace regions behind the
+// forward plan's, the tangent coefficient records / interaction diagonals, and the launches of one factor pass and of the
+// observable tangents at one save point.
+#pragma once
+
+namespace {
+
+// Everything rydiff_forward_tangent refuses, checked on the host before anything touches a device.
+int tangent_validate(const RydProblem* p, const RydPlanInfo* info, int n_dir) {
+    if (!p) return fail(RYDIFF_EINVAL, "null problem");
+    if (n_dir < 1 || n_dir > RYDIFF_MAX_TANGENTS)
+        return fail(RYDIFF_EINVAL, "n_dir must be in [1, " + std::to_string(RYDIFF_MAX_TANGENTS) + "], got " + std::to_string(n_dir));
+    if (!info) return fail(RYDIFF_EINVAL, "the tangent sweep needs the plan of rydiff_plan(p, 0, 0, ...): null info");
+    if (p->shard_bits > 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented for state-sharded runs (shard_bits > 0)");
+    if (p->n_pair_terms > 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented with dense pair terms (n_pair_terms > 0)");
+    if (p->amp_conditioned_terms || p->det_ones_terms)
+        return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented with conditioned flips / ones-counting terms (three-level registers)");
+    return RYDIFF_OK;
+}
+
+// Workspace of the tangent sweep: the forward plan's regions (udiag, coefficient records, Pauli tables ...) and behind them
+struct TangentLayout {
+    size_t off_vec[2] = {0, 0};  // ping-pong: [1 + D][B][dim] amplitudes each
+    size_t off_dcoef = 0;        // [D][Bc][E][NC] doubles
+    size_t off_dudiag = 0;       // [D][dim] doubles
+    size_t total = 0;
+    long dcoef_dstride = 0;      // doubles
+};
+
+// k_factor_tangent is instantiated for 1, 2, 3, 4, 6 and 8 directions; 5 and 7 run the next one with a zero direction (zero tangent
+// vector, zero records: it stays zero and nothing reads it)
+int tangent_padded(int n_dir) { return n_dir == 5 ? 6 : (n_dir == 7 ? 8 : n_dir); }
+
+TangentLayout tangent_layout(const Plan& pl, size_t base, int n_dir) {
+    n_dir = tangent_padded(n_dir);
+    TangentLayout t;
+    size_t off = align_up(base);
+    auto take = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + bytes);
+        return o;
+    };
+    const size_t vecs = size_t(1 + n_dir) * pl.state_bytes;
+    t.off_vec[0] = take(vecs);
+    t.off_vec[1] = take(vecs);
+    t.dcoef_dstride = long(pl.Bc) * long(pl.stages.size()) * pl.NC;
+    t.off_dcoef = take(size_t(n_dir) * size_t(std::max<long>(t.dcoef_dstride, 1)) * sizeof(double));
+    t.off_dudiag = take(size_t(n_dir) * pl.dim * sizeof(double));
+    t.total = off;
+    return t;
+}
+
+// host-only planning of a tangent call: validation, the forward plan from `info`, the layout
+int tangent_plan(const RydProblem* p, const RydPlanInfo* info, int n_dir, Runtime& rt, TangentLayout& lay) {
+    int rc = tangent_validate(p, info, n_dir);
+    if (rc) return rc;
+    RydProblem q = *p;
+    q.kernel_variant = 0;  // ignored: one kernel family
+    double lo, hi, dummy_scratch = 0.0;
+    size_t need = 0;
+    int need_tape = 0;
+    rc = plan_runtime(&q, info, &dummy_scratch, sizeof(dummy_scratch), need_tape, false, nullptr, rt, lo, hi, need);  // (with info: host only)
+    if (rc) return rc;
+    lay = tangent_layout(rt.pl, need, n_dir);
+    return RYDIFF_OK;
+}
+
+// tangent coefficient records (k_expand_coeffs on the tangent tables, same StageDev records) and tangent interaction diagonals
+int tangent_tables(const Runtime& rt, const RydProblem* p, const RydTangent* tg, char* ws, const TangentLayout& lay, hipStream_t stream) {
+    const Plan& pl = rt.pl;
+    const int Dp = tangent_padded(tg->n_dir);
+    if (pl.NC > 0) {
+        for (int d = 0; d < tg->n_dir; ++d) {
+            const int rc = launch_expand(pl, ws, tg->d_amp ? static_cast<const double2*>(tg->d_amp) + size_t(d) * pl.Bc * pl.Ka * pl.n_samples : nullptr,
+                                         tg->d_det ? tg->d_det + size_t(d) * pl.Bc * pl.Kd * pl.n_samples : nullptr,
+                                         reinterpret_cast<double*>(ws + lay.off_dcoef) + size_t(d) * lay.dcoef_dstride, stream);
+            if (rc) return rc;
+        }
+        if (Dp > tg->n_dir)  // padded directions: zero records
+            HIP_TRY(hipMemsetAsync(reinterpret_cast<double*>(ws + lay.off_dcoef) + size_t(tg->n_dir) * lay.dcoef_dstride, 0,
+                                   size_t(Dp - tg->n_dir) * lay.dcoef_dstride * sizeof(double), stream));
+    }
+    if (tg->d_u && pl.N > 1) {
+        const int npairs = pl.N * (pl.N - 1) / 2;
+        double* dud = reinterpret_cast<double*>(ws + lay.off_dudiag);
+        for (int d = 0; d < tg->n_dir; ++d) {
+            hipLaunchKernelGGL(k_build_udiag, dim3(unsigned((pl.dim + 255) / 256)), dim3(256), 0, stream, dud + size_t(d) * pl.dim,
+                               tg->d_u + size_t(d) * npairs, pl.N, uint32_t(pl.dim));
+            LAUNCH_CHECK();
+        }
+        if (Dp > tg->n_dir) HIP_TRY(hipMemsetAsync(dud + size_t(tg->n_dir) * pl.dim, 0, size_t(Dp - tg->n_dir) * pl.dim * sizeof(double), stream));
+    }
+    return RYDIFF_OK;
+}
+
+template <int D>
+void launch_factor_tangent_n(const TangentFactorArgs& a, dim3 grid, hipStream_t stream) {
+    hipLaunchKernelGGL((k_factor_tangent<D>), grid, dim3(256), 0, stream, a);
+}
+
+// what every factor launch of one call shares
+void fill_tangent_factor(TangentFactorArgs& a, const Runtime& rt, char* ws, const TangentLayout& lay, bool have_du) {
+    const Plan& pl = rt.pl;
+    a.vstride = size_t(pl.B) * pl.dim;
+    a.udiag = reinterpret_cast<const double*>(ws + pl.off_udiag);
+    a.dudiag = (have_du && pl.N > 1) ? reinterpret_cast<const double*>(ws + lay.off_dudiag) : nullptr;
+    a.coef_bstride = rt.coef_bstride();
+    a.dcoef_dstride = lay.dcoef_dstride;
+    a.dim = uint32_t(pl.dim);
+    a.ga = pl.ga.n;
+    a.gd = pl.gd.n;
+    fill_detuning(a.dmask, a.dcnt, pl);
+    a.nflip = 0;
+    for (int q = 0; q < pl.ga.n; ++q)
+        for (uint32_t m = pl.ga.amp_index_mask[q]; m; m &= m - 1) {
+            a.fbg[a.nflip++] = uint32_t(__builtin_ctz(m)) | (uint32_t(q) << 8);
+        }
+}
+
+int launch_factor_tangent(TangentFactorArgs& a, const Runtime& rt, char* ws, const TangentLayout& lay, int n_dir, const double2* xin,
+                          double2* xout, int stage, const FactorScalars& s, hipStream_t stream) {
+    const Plan& pl = rt.pl;
+    a.xin = xin;
+    a.xout = xout;
+    a.coef = rt.coef(ws, stage);
+    a.dcoef = reinterpret_cast<const double*>(ws + lay.off_dcoef) + size_t(stage) * pl.NC;
+    a.gr = s.gr;
+    a.gi = s.gi;
+    a.br = s.br;
+    a.bi = s.bi;
+    const dim3 grid(unsigned((pl.dim + 255) / 256), unsigned(pl.B));
+    switch (tangent_padded(n_dir)) {
+        case 1: launch_factor_tangent_n<1>(a, grid, stream); break;
+        case 2: launch_factor_tangent_n<2>(a, grid, stream); break;
+        case 3: launch_factor_tangent_n<3>(a, grid, stream); break;
+        case 4: launch_factor_tangent_n<4>(a, grid, stream); break;
+        case 6: launch_factor_tangent_n<6>(a, grid, stream); break;
+        case 8: launch_factor_tangent_n<8>(a, grid, stream); break;
+        default: return fail(RYDIFF_EINVAL, "internal: n_dir out of range");
+    }
+    LAUNCH_CHECK();
+    return RYDIFF_OK;
+}
+
+// observable tangents of every row at save point k: vec = [1 + D][B][dim] with the state first; dexp = dexpect_out
+int launch_expect_tangent(const ForwardCtx& c, const double2* vec, int n_dir, int k, double* dexp) {
+    const Plan& pl = c.rt.pl;
+    const size_t vstride = size_t(pl.B) * pl.dim;
+    const size_t row = size_t(pl.T + 1) * pl.B;
+    const size_t dstride = size_t(pl.n_obs + pl.n_pobs + 2 * pl.n_ov) * row;
+    const unsigned red_blocks = unsigned(std::min<size_t>((pl.dim + 255) / 256, 1024));
+    if (pl.n_obs > 0) {
+        hipLaunchKernelGGL(k_expect_tangent, dim3(red_blocks, unsigned(pl.B), unsigned(n_dir)), dim3(256), 0, c.stream, vec, vec + vstride, vstride,
+                           c.p->obs_diag, dexp, dstride, pl.n_obs, pl.T + 1, k, pl.B, uint32_t(pl.dim));
+        LAUNCH_CHECK();
+    }
+    if (pl.n_pobs > 0) {
+        PauliTangentArgs a{};
+        a.psi = vec;
+        a.dpsi = vec + vstride;
+        a.vstride = vstride;
+        a.t = pauli_tables(pl, c.ws);
+        a.out = dexp + size_t(pl.n_obs) * row;
+        a.out_dstride = dstride;
+        a.n_pobs = pl.n_pobs;
+        a.n_tsave = pl.T + 1;
+        a.k = k;
+        a.B = pl.B;
+        a.dim = uint32_t(pl.dim);
+        hipLaunchKernelGGL(k_pauli_expect_tangent, dim3(red_blocks, unsigned(pl.B), unsigned(pl.n_pobs * n_dir)), dim3(256), 0, c.stream, a);
+        LAUNCH_CHECK();
+    }
+    if (pl.n_ov > 0) {  // Re / Im <phi_o|dpsi_d>: k_overlap_expect as it is, on the tangent, into direction d's overlap rows
+        for (int d = 0; d < n_dir; ++d) {
+            ForwardCtx t = c;
+            t.overlap_out = dexp + size_t(d) * dstride + size_t(pl.n_obs + pl.n_pobs) * row;
+            if (const int rc = launch_overlap_expect(t, vec + size_t(1 + d) * vstride, 0, k, 1, BatchSlice{0, pl.B, false})) return rc;
+        }
+    }
+    return RYDIFF_OK;
+}
+
+}  // namespace

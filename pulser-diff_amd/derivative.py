@@ -59,3 +59,11 @@ def deriv_param(f: Tensor, x: list, times: Optional[Tensor] = None, t=None):
     cotangent = torch.zeros(len(f), dtype=torch.float64, device=f.device)
     cotangent[index] = 1.0
     return torch.autograd.grad(f, x, grad_outputs=cotangent, retain_graph=True)
+
+
+def deriv_param_all_times(sim, x: list, observables: list, **kw):
+    """``deriv_param`` at EVERY evaluation time in one call: ``sim.run_sensitivities(x, observables, **kw)`` — one native
+    forward-mode sweep that carries a tangent state per scalar entry of ``x`` instead of one reverse sweep per evaluation time
+    (``basic_usage.ipynb``: ``for t in times: deriv_param(f=exp_val, x=diff_params, times=eval_times, t=t)``).  Returns
+    ``Sensitivities``: ``values`` (n_obs, n_t), ``grads[i]`` (n_obs, n_t, *x[i].shape), ``route``."""
+    return sim.run_sensitivities(x, observables, **kw)

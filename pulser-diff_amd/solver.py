@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import ctypes
 import enum
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Any, Optional, Sequence
 
 import numpy as np
@@ -540,3 +540,89 @@ def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverTyp
     expect, overlaps = split_expect(expect, len(overlap_obs))
     return SolveResult(states.permute(0, 2, 1) if states.numel() else states, expect,
                        dict(spec.options.get("_last_stats", {})), overlaps)
+
+
+def _tangent_chunk(t: Optional[Tensor], d0: int, d1: int, shape: tuple, dtype: torch.dtype, name: str, dev) -> Optional[Tensor]:
+    """Directions d0:d1 of one tangent input as the contiguous device buffer the C ABI reads (None stays None)."""
+    if t is None:
+        return None
+    _require_cuda(t, name)
+    if tuple(t.shape[1:]) != tuple(shape):
+        raise ValueError(f"{name} must have shape (n_dir, {', '.join(str(s) for s in shape)}), got {tuple(t.shape)}")
+    return t[d0:d1].detach().to(dev, dtype).contiguous()
+
+
+def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Tensor, spec: ProblemSpec,
+                   obs_diag: Optional[Tensor] = None, d_amp: Optional[Tensor] = None, d_det: Optional[Tensor] = None,
+                   d_u: Optional[Tensor] = None, d_psi0: Optional[Tensor] = None) -> tuple[Tensor, Tensor]:
+    """Forward-mode twin of ``evolve`` (``rydiff_forward_tangent``): ONE sweep carries the state and the tangent states of up to 8
+    directions through every factor and returns the observable values ``expect`` (rows, n_t, B) and their directional derivatives
+    ``dexpect`` (n_dir, rows, n_t, B) at EVERY evaluation time — rows = diagonal observables, then the Pauli observables and Re / Im
+    of the overlaps of ``spec``, as in ``evolve``.  A direction d is the tangent of the inputs: ``d_amp[d]`` shaped like
+    ``amp_tables``, ``d_det[d]`` like ``det_tables``, ``d_u[d]`` like ``u_pairs``, ``d_psi0[d]`` like ``psi0`` (B, dim); an
+    input left out has tangent zero.  More than 8 directions run in chunks of 8.  No autograd graph hangs off the outputs."""
+    L = _native.lib()
+    dev = psi0.device
+    for t, name in ((amp_tables, "amp_tables"), (det_tables, "det_tables"), (u_pairs, "u_pairs"), (psi0, "psi0")):
+        _require_cuda(t, name)
+    given = [t for t in (d_amp, d_det, d_u, d_psi0) if t is not None]
+    if not given:
+        raise ValueError("evolve_tangent needs at least one of d_amp, d_det, d_u, d_psi0")
+    n_dir = int(given[0].shape[0])
+    if n_dir < 1 or any(int(t.shape[0]) != n_dir for t in given):
+        raise ValueError("d_amp, d_det, d_u, d_psi0 must agree on the number of directions (their first axis), at least one")
+    amp_c = amp_tables.detach().to(torch.complex128).contiguous()
+    det_c = det_tables.detach().to(torch.float64).contiguous()
+    u_c = u_pairs.detach().to(torch.float64).contiguous()
+    psi_c = psi0.detach().to(torch.complex128).contiguous()
+    obs_c = None if obs_diag is None else obs_diag.detach().to(torch.float64).contiguous()
+    ts_host = tsave.detach().to("cpu", torch.float64).numpy()
+    if psi_c.ndim != 2:
+        raise ValueError(f"psi0 must be (batch, 2^N), got shape {tuple(psi_c.shape)}")
+    batch, dim = psi_c.shape
+    if dim != 2 ** spec.n_qubits:
+        raise ValueError(f"Incompatible shape of initial state.Expected {2 ** spec.n_qubits}, got {dim}.")
+    _check_shapes(spec, amp_c, det_c, u_c, obs_c, batch, dev)
+    n_t = len(ts_host)
+    call = _Call(spec, amp_c, det_c, u_c, ts_host, batch, obs_c)
+    call.problem.kernel_variant = 0  # the tangent sweep has one kernel family
+    p = call.problem
+    rows = p.n_obs + p.n_pauli_obs + 2 * p.n_overlaps
+    expect = torch.empty((rows, n_t, batch), dtype=torch.float64, device=dev)
+    dexpect = torch.empty((n_dir, rows, n_t, batch), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        scratch = torch.empty(_native.PLAN_SCRATCH_BYTES, dtype=torch.uint8, device=dev)
+        info = _native.RydPlanInfo()
+        _native.check(L.rydiff_plan(ctypes.byref(p), 0, 0, _ptr(scratch), stream, ctypes.byref(info)))
+        workspace = None
+        values_done = False
+        for d0 in range(0, n_dir, _native.MAX_TANGENTS):
+            d1 = min(n_dir, d0 + _native.MAX_TANGENTS)
+            bufs = (_tangent_chunk(d_amp, d0, d1, amp_c.shape, torch.complex128, "d_amp", dev) if amp_c.numel() else None,
+                    _tangent_chunk(d_det, d0, d1, det_c.shape, torch.float64, "d_det", dev) if det_c.numel() else None,
+                    _tangent_chunk(d_u, d0, d1, u_c.shape, torch.float64, "d_u", dev) if u_c.numel() else None,
+                    _tangent_chunk(d_psi0, d0, d1, psi_c.shape, torch.complex128, "d_psi0", dev))
+            out = dexpect[d0:d1]
+            if all(b is None for b in bufs):  # tangents of inputs this problem does not have: the derivative is zero
+                out.zero_()
+                continue
+            tg = _native.RydTangent()
+            tg.n_dir = d1 - d0
+            tg.d_amp, tg.d_det, tg.d_u, tg.d_psi0 = (None if b is None else b.data_ptr() for b in bufs)
+            need = L.rydiff_tangent_workspace_bytes(ctypes.byref(p), ctypes.byref(info), tg.n_dir)
+            if need == 0:  # refused: the sweep's own (host-only) validation reports why, with its error code
+                _native.check(L.rydiff_forward_tangent(ctypes.byref(p), ctypes.byref(info), ctypes.byref(tg), _ptr(psi_c), None, _ptr(out),
+                                                       None, 0, stream))
+                raise RuntimeError("rydiff_tangent_workspace_bytes returned 0: " + _native.last_error())
+            if workspace is None or workspace.numel() < need:
+                workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+            want_values = rows > 0 and not values_done
+            values_done = True
+            _native.check(L.rydiff_forward_tangent(ctypes.byref(p), ctypes.byref(info), ctypes.byref(tg), _ptr(psi_c),
+                                                   _ptr(expect) if want_values else None, _ptr(out), _ptr(workspace),
+                                                   workspace.numel(), stream))
+    if rows and not values_done:  # no chunk reached the library (tangents of inputs the problem does not have)
+        with torch.no_grad():
+            expect = evolve(amp_c, det_c, u_c, tsave.detach(), psi_c, replace(spec, store_states=False), obs_c)[1]
+    return expect, dexpect
