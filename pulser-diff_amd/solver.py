@@ -273,6 +273,12 @@ def _ptr(t: Optional[Tensor]):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _new_workspace(nbytes: int, dev) -> Tensor:
+    """Every byte buffer the library is handed (workspaces, the plan scratch) comes from here: uninitialised device memory.  The
+    library writes whatever it reads; tests/test_gpu_workspace_contents.py replaces this seam to hand it hostile contents."""
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+
+
 class _RydbergEvolve(torch.autograd.Function):
     """states, expect = evolve(amp_tables, det_tables, u_pairs, tsave, psi0; obs_diag, spec)."""
 
@@ -305,7 +311,7 @@ class _RydbergEvolve(torch.autograd.Function):
         need_tape = int(bool(needs_grad and not spec.store_states))
         with torch.cuda.device(dev):
             stream = _stream_ptr(dev)
-            scratch = torch.empty(_native.PLAN_SCRATCH_BYTES, dtype=torch.uint8, device=dev)
+            scratch = _new_workspace(_native.PLAN_SCRATCH_BYTES, dev)
             info = _native.RydPlanInfo()
             # with the trajectory kept in the workspace tape, size the workspace for the backward sweep right away
             # (every register size has a tape-mode adjoint: the launch-per-factor sweeps from 12 qubits on, the one-launch
@@ -339,7 +345,7 @@ class _RydbergEvolve(torch.autograd.Function):
             workspace = None
             for attempt in range(3):
                 try:
-                    workspace = torch.empty(info.workspace_bytes, dtype=torch.uint8, device=dev)
+                    workspace = _new_workspace(info.workspace_bytes, dev)
                     break
                 except torch.OutOfMemoryError:
                     # The fit test above counts the caching allocator's free blocks as reusable, but a cached block that is a little
@@ -420,7 +426,7 @@ class _RydbergEvolve(torch.autograd.Function):
                 workspace = ctx.tape_workspace  # sized for forward + backward by the forward call
                 states_ptr = None
             else:
-                workspace = torch.empty(info.workspace_bytes, dtype=torch.uint8, device=dev)  # sized by the forward call's plan
+                workspace = _new_workspace(info.workspace_bytes, dev)  # sized by the forward call's plan
                 states_ptr = _ptr(states)
             _native.check(L.rydiff_backward(ctypes.byref(call.problem), ctypes.byref(info), states_ptr, _ptr(g_states),
                                             _ptr(g_expect) if (g_expect is not None and ctx.has_expect) else None,
@@ -592,7 +598,7 @@ def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsav
     dexpect = torch.empty((n_dir, rows, n_t, batch), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         stream = _stream_ptr(dev)
-        scratch = torch.empty(_native.PLAN_SCRATCH_BYTES, dtype=torch.uint8, device=dev)
+        scratch = _new_workspace(_native.PLAN_SCRATCH_BYTES, dev)
         info = _native.RydPlanInfo()
         _native.check(L.rydiff_plan(ctypes.byref(p), 0, 0, _ptr(scratch), stream, ctypes.byref(info)))
         workspace = None
@@ -616,7 +622,7 @@ def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsav
                                                        None, 0, stream))
                 raise RuntimeError("rydiff_tangent_workspace_bytes returned 0: " + _native.last_error())
             if workspace is None or workspace.numel() < need:
-                workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+                workspace = _new_workspace(need, dev)
             want_values = rows > 0 and not values_done
             values_done = True
             _native.check(L.rydiff_forward_tangent(ctypes.byref(p), ctypes.byref(info), ctypes.byref(tg), _ptr(psi_c),

@@ -93,6 +93,167 @@ def magnus_cf4_dense(terms, psi0, tsave, h_max=2.5e-3):
     return torch.stack(out)
 
 
+DP5_DEFAULT_H_MAX = 2.5e-3 * (1e-9 / 1e-10) ** 0.25  # the native default (tol 1e-9), as tests/test_gpu_tangent.py's oracle test
+
+
+def map_exponentials(terms, tsave, solver, h_max=DP5_DEFAULT_H_MAX):
+    """The exponentials exp(-i tau H(t)) of the oracle's discrete map, per save interval, in the order they are applied: a list
+    (one entry per interval) of lists of (t, tau).  KRYLOV_SE: one per interval at the right endpoint (R.krylov_map_dense);
+    DP5_SE: the two CF4 exponentials per piece and sub-step, the cuts and the sub-step count of magnus_cf4_dense."""
+    import math
+
+    name = getattr(solver, "name", str(solver))
+    ts = [float(t) for t in tsave]
+    out = []
+    for a, b in zip(ts[:-1], ts[1:]):
+        if name == "KRYLOV_SE":
+            out.append([(b, b - a)])
+            continue
+        if name != "DP5_SE":
+            raise ValueError(f"no dense map for solver {name}")
+        dt, n = terms.dt, terms.n_samples
+        pts = [a]
+        i = math.floor(a / dt) + 1
+        while i <= n - 2 and i * dt < b - 1e-13:
+            if i * dt > a + 1e-13:
+                pts.append(i * dt)
+            i += 1
+        pts.append(b)
+        steps = []
+        for p0, p1 in zip(pts[:-1], pts[1:]):
+            hf = p1 - p0
+            S = max(1, math.ceil(hf / h_max - 1e-9))
+            for sub in range(S):
+                for theta in (1.0 / 6.0, 5.0 / 6.0):
+                    steps.append((p0 + (sub + theta) / S * hf, hf / (2.0 * S)))
+        out.append(steps)
+    return out
+
+
+def accurate_matrix_exp(m):
+    """exp of a (batch of) square matrices to rounding error at every size of the argument.  torch.linalg.matrix_exp takes its
+    degree-4 polynomial up to a 1-norm of 4.99e-2, where that polynomial is no longer exact to double precision: measured against
+    the eigendecomposition of a Hermitian generator its error grows from 7e-14 at 1-norm 1e-2 to 1.9e-10 at 4.9e-2 and is back at
+    2e-15 from 5.1e-2 on.  Arguments below 6e-2 therefore get a plain degree-14 Taylor sum (remainder < 1e-30) instead."""
+    out = torch.linalg.matrix_exp(m)
+    small = torch.linalg.matrix_norm(m, 1) < 6e-2
+    if bool(small.any()):
+        ms = m[small] if m.ndim > 2 else m
+        eye = torch.eye(m.shape[-1], dtype=m.dtype).expand_as(ms)
+        acc = eye.clone()
+        for k in range(14, 0, -1):  # Horner: 1 + m/1 (1 + m/2 (1 + ... m/14))
+            acc = eye + ms @ acc / k
+        if m.ndim > 2:
+            out[small] = acc
+        else:
+            out = acc
+    return out
+
+
+def _direction_terms(terms, d_amp, d_det, d_u):
+    """The HamTerms whose dense H is dH of one direction (H is linear in the tables and in U); a tangent left out is zero."""
+    amp_terms, det_terms = terms.amp_terms(), terms.det_terms()
+    u = torch.zeros_like(terms.u_pairs) if d_u is None else d_u.to(torch.float64)
+    out = R.HamTerms(terms.n_qubits, u, None, None, terms.dt, terms.n_samples)
+    if d_amp is not None:
+        out.extra_amp = [(d_amp[k].to(torch.complex128), tg) for k, (_, tg) in enumerate(amp_terms)]
+    if d_det is not None:
+        out.extra_det = [(d_det[k].to(torch.float64), tg) for k, (_, tg) in enumerate(det_terms)]
+    return out
+
+
+def shifted_terms(terms, d_amp, d_det, d_u, s):
+    """terms + sum_j s[j] * direction_j as HamTerms (tables in the order of amp_terms() / det_terms(); d_amp (n_dir, Ka, n),
+    d_det (n_dir, Kd, n), d_u (n_dir, n_pairs)); differentiable in s."""
+    amps = [c + sum(s[j] * d_amp[j][k] for j in range(len(s))) for k, (c, _) in enumerate(terms.amp_terms())]
+    dets = [c + sum(s[j] * d_det[j][k] for j in range(len(s))) for k, (c, _) in enumerate(terms.det_terms())]
+    out = R.HamTerms(terms.n_qubits, terms.u_pairs + sum(s[j] * d_u[j] for j in range(len(s))), None, None, terms.dt, terms.n_samples)
+    out.extra_amp = [(c, tg) for c, (_, tg) in zip(amps, terms.amp_terms())]
+    out.extra_det = [(c, tg) for c, (_, tg) in zip(dets, terms.det_terms())]
+    return out
+
+
+def tangent_dense_reference(terms, d_amp, d_det, d_u, psi0, d_psi0, tsave, solver, h_max=DP5_DEFAULT_H_MAX):
+    """Plain dense forward mode of the oracle's discrete map, no autograd: every exponential exp(A), A = -i tau H(t), of the map
+    (map_exponentials) is advanced together with its directional derivative through the block identity
+        exp([[A, dA], [0, A]]) = [[e^A, L], [0, e^A]],   psi' = e^A psi,   dpsi' = e^A dpsi + L psi,
+    with dA = -i tau * dense_hamiltonian(the direction's tables and U, t).
+      terms   HamTerms shared by the trajectories, or a list of B HamTerms (per-trajectory tables)
+      d_amp   (n_dir, Ka, n) complex | (n_dir, B, Ka, n) per trajectory | None;  d_det likewise, real;  d_u (n_dir, n_pairs) | None
+      psi0    (dim, B);  d_psi0 (n_dir, dim, B) | None
+    Returns the states (n_t, dim, B) and the tangent states (n_t, n_dir, dim, B), complex128 on the CPU."""
+    per_traj = isinstance(terms, (list, tuple))
+    psi0 = psi0.to(torch.complex128)
+    dim, batch = psi0.shape
+    given = [t for t in (d_amp, d_det, d_u, d_psi0) if t is not None]
+    n_dir = int(given[0].shape[0])
+    groups = [(terms[b], [b]) for b in range(batch)] if per_traj else [(terms, list(range(batch)))]
+    n_t = len(tsave)
+    states = torch.zeros(n_t, dim, batch, dtype=torch.complex128)
+    tangents = torch.zeros(n_t, n_dir, dim, batch, dtype=torch.complex128)
+    have_dh = d_amp is not None or d_det is not None or d_u is not None
+
+    def table(t, d, b):  # direction d of a table tangent, for trajectory b
+        if t is None:
+            return None
+        return t[d, b] if t.ndim == 4 else t[d]
+
+    for g_terms, cols in groups:
+        dirs = [_direction_terms(g_terms, table(d_amp, d, cols[0]), table(d_det, d, cols[0]), None if d_u is None else d_u[d])
+                for d in range(n_dir)] if have_dh else []
+        psi = psi0[:, cols]
+        dpsi = (d_psi0[:, :, cols].to(torch.complex128) if d_psi0 is not None
+                else torch.zeros(n_dir, dim, len(cols), dtype=torch.complex128))
+        states[0][:, cols] = psi
+        tangents[0][:, :, cols] = dpsi
+        for k, steps in enumerate(map_exponentials(g_terms, tsave, solver, h_max)):
+            for t, tau in steps:
+                a = -1j * tau * R.dense_hamiltonian(g_terms, t)
+                if have_dh:
+                    blk = torch.zeros(n_dir, 2 * dim, 2 * dim, dtype=torch.complex128)
+                    blk[:, :dim, :dim] = a
+                    blk[:, dim:, dim:] = a
+                    for d in range(n_dir):
+                        blk[d, :dim, dim:] = -1j * tau * R.dense_hamiltonian(dirs[d], t)
+                    e = accurate_matrix_exp(blk)
+                    ea, el = e[0, :dim, :dim], e[:, :dim, dim:]
+                    dpsi = ea @ dpsi + el @ psi
+                else:
+                    ea = accurate_matrix_exp(a)
+                    dpsi = ea @ dpsi
+                psi = ea @ psi
+            states[k + 1][:, cols] = psi
+            tangents[k + 1][:, :, cols] = dpsi
+    return states, tangents
+
+
+def tangent_rows_reference(states, tangents, obs_diag=None, paulis=(), overlaps=()):
+    """The rows of evolve_tangent from dense states (n_t, dim, B) and tangent states (n_t, n_dir, dim, B), float64 on the CPU:
+    values (rows, n_t, B) and their directional derivatives (n_dir, rows, n_t, B).  Rows: the diagonal observables
+    (obs_diag (n_obs, dim)), 2 Re(psi^H O dpsi) each, then the dense PauliObservable.to_dense() ones, then Re and Im of
+    <phi|dpsi> for every overlap target ((dim,) or (dim, B))."""
+    val, der = [], []
+    for o in ([] if obs_diag is None else obs_diag):
+        o = o.to(torch.float64)
+        val.append((states.abs() ** 2 * o[None, :, None]).sum(1))
+        der.append(2.0 * (states.conj()[:, None] * o[None, None, :, None] * tangents).sum(2).real)
+    for p in paulis:
+        m = p.to_dense()
+        val.append(torch.einsum("tib,ij,tjb->tb", states.conj(), m, states).real)
+        der.append(2.0 * torch.einsum("tib,ij,tdjb->tdb", states.conj(), m, tangents).real)
+    for phi in overlaps:
+        phi = phi.to(torch.complex128)
+        phi = phi[:, None] if phi.ndim == 1 else phi
+        c = (phi.conj()[None] * states).sum(1)
+        dc = (phi.conj()[None, None] * tangents).sum(2)
+        val += [c.real, c.imag]
+        der += [dc.real, dc.imag]
+    n_t, n_dir, _, batch = tangents.shape
+    if not val:
+        return torch.zeros(0, n_t, batch, dtype=torch.float64), torch.zeros(n_dir, 0, n_t, batch, dtype=torch.float64)
+    return torch.stack(val), torch.stack(der).permute(2, 0, 1, 3).contiguous()  # (rows, n_t, n_dir, B) -> (n_dir, rows, n_t, B)
+
+
 def pack_terms(terms: R.HamTerms) -> dict:
     """HamTerms -> plain arrays (golden fixtures store their inputs next to the expected outputs)."""
     amp_terms, det_terms = terms.amp_terms(), terms.det_terms()

@@ -10,7 +10,10 @@ import torch
 import pulser_diff_amd as P
 from pulser_diff_amd import _native, pulses as pl
 from pulser_diff_amd.derivative import deriv_param_all_times
+from oracle import restatement as R
 from pulser_diff_amd.solver import ProblemSpec, SolverType, _Call
+from tests.helpers import (DP5_DEFAULT_H_MAX, magnus_cf4_dense, map_exponentials, random_terms, shifted_terms, tangent_dense_reference,
+                           tangent_rows_reference)
 
 
 def _basic_usage_emulator(q0, omega, area, phase, config=None):
@@ -185,3 +188,90 @@ def test_python_side_refusals():
                                  config=P.SimConfig(noise="SPAM", runs=2, eta=0.1))
     with pytest.raises(NotImplementedError, match="noisy"):
         deriv_param_all_times(spam, [prm["omega"]], [obs])
+
+
+STATE_ATOL = 1e-13  # the same exponentials applied in the same order: rounding only
+
+
+def _randn(gen, *shape, cplx=False):
+    return torch.randn(*shape, generator=gen, dtype=torch.complex128 if cplx else torch.float64)
+
+
+@pytest.mark.parametrize("solver", [SolverType.KRYLOV_SE, SolverType.DP5_SE], ids=["KRYLOV_SE", "DP5_SE"])
+def test_dense_tangent_reference_against_reverse_mode_autograd(solver):
+    """tests.helpers.tangent_dense_reference (block-exponential forward mode, no autograd) against reverse-mode autograd through
+    the oracle's map (R.krylov_map_dense / magnus_cf4_dense) on terms + s * direction: 4 qubits, B = 2, 3 directions, all four
+    tangent inputs.  tsave is off the sample grid with every DP5 piece at least 2 ns long, on a register 6.5 um apart:
+    torch.linalg.matrix_exp, which the reverse-mode side goes through, loses accuracy for arguments of 1-norm 5e-3 .. 4.99e-2
+    (tests.helpers.accurate_matrix_exp; with pieces of 1.3 ns at 8 um the two sides differ by 4.5e-10, and it is the reverse-mode
+    side that is off), so the test asserts that no exponential of the map falls there.  Measured: 5e-16 (KRYLOV_SE), 4e-15 (DP5_SE).
+    For a seeded random cotangent w over the states, sum Re(conj(w) * tangent_d) must equal d/ds_d of
+    sum Re(conj(w) * states(s)) at 1e-12 relative; the states themselves must be the oracle's.  A second run with one HamTerms
+    per trajectory (tables that differ) must reproduce, column by column, the runs with each trajectory's tables shared."""
+    n, n_dir, batch = 4, 3, 2
+    terms = random_terms(n, 21, 0.005, seed=61, local=True, phase=True, spacing=6.5)
+    tsave = torch.tensor([0.0, 0.022, 0.048, 0.092], dtype=torch.float64)
+    for steps in map_exponentials(terms, tsave, solver):
+        for t, tau in steps:  # the reverse-mode side's matrix_exp is exact to rounding on every exponential of this map
+            assert tau * float(torch.linalg.matrix_norm(R.dense_hamiltonian(terms, t), 1)) > 5.5e-2
+    gen = torch.Generator().manual_seed(1234)
+    dim = 2**n
+    psi0 = _randn(gen, dim, batch, cplx=True)
+    psi0 = psi0 / psi0.norm(dim=0, keepdim=True)
+    ka, kd = len(terms.amp_terms()), len(terms.det_terms())
+    d_amp = 0.5 * _randn(gen, n_dir, ka, 21, cplx=True)
+    d_det = 0.5 * _randn(gen, n_dir, kd, 21)
+    d_u = 0.5 * _randn(gen, n_dir, n * (n - 1) // 2)
+    d_psi = _randn(gen, n_dir, dim, batch, cplx=True) / np.sqrt(dim)
+    w = _randn(gen, len(tsave), dim, batch, cplx=True)
+
+    def oracle_states(s):
+        shifted = shifted_terms(terms, d_amp, d_det, d_u, s)
+        start = psi0 + sum(s[j] * d_psi[j] for j in range(n_dir))
+        if solver == SolverType.KRYLOV_SE:
+            return R.krylov_map_dense(shifted, start, tsave)
+        return magnus_cf4_dense(shifted, start, tsave, h_max=DP5_DEFAULT_H_MAX)
+
+    s0 = torch.zeros(n_dir, dtype=torch.float64, requires_grad=True)
+    ref_states = oracle_states(s0)
+    (want,) = torch.autograd.grad((w.conj() * ref_states).real.sum(), s0)
+    states, tangents = tangent_dense_reference(terms, d_amp, d_det, d_u, psi0, d_psi, tsave, solver)
+    assert tuple(states.shape) == (len(tsave), dim, batch) and tuple(tangents.shape) == (len(tsave), n_dir, dim, batch)
+    state_err = float((states - ref_states.detach()).abs().max())
+    print(f"max |states - oracle states| = {state_err:.2e}")
+    assert state_err <= STATE_ATOL
+    for d in range(n_dir):
+        got = float((w.conj() * tangents[:, d]).real.sum())
+        rel = abs(got - float(want[d])) / max(abs(got), abs(float(want[d])))
+        print(f"direction {d}: forward {got:+.15e}  reverse {float(want[d]):+.15e}  rel {rel:.2e}")
+        assert abs(float(want[d])) > 1e-2  # cannot pass on zeros
+        assert rel <= 1e-12
+    # per-trajectory tables: the list form against one shared run per trajectory
+    other = random_terms(n, 21, 0.005, seed=62, local=True, phase=True, spacing=6.5)
+    d_amp_b = torch.stack([d_amp, 0.5 * _randn(gen, n_dir, ka, 21, cplx=True)], dim=1)
+    d_det_b = torch.stack([d_det, 0.5 * _randn(gen, n_dir, kd, 21)], dim=1)
+    st2, tg2 = tangent_dense_reference([terms, other], d_amp_b, d_det_b, d_u, psi0, d_psi, tsave, solver)
+    for b, tb in enumerate((terms, other)):
+        st1, tg1 = tangent_dense_reference(tb, d_amp_b[:, b], d_det_b[:, b], d_u, psi0[:, b:b + 1], d_psi[:, :, b:b + 1], tsave, solver)
+        assert torch.equal(st2[:, :, b:b + 1], st1) and torch.equal(tg2[:, :, :, b:b + 1], tg1)
+    assert float((tg2[..., 1] - tangents[..., 1]).abs().max()) > 1e-3  # the second trajectory's tables really differ
+
+
+def test_dense_tangent_rows_are_the_derivatives_of_the_values():
+    """tests.helpers.tangent_rows_reference: its derivative rows against autograd through its own value rows on psi + s * dpsi
+    (diagonal, dense Pauli and overlap rows, shared and per-trajectory targets), 1e-13 relative to the largest entry."""
+    n, n_dir, batch, n_t = 3, 2, 2, 2
+    dim = 2**n
+    gen = torch.Generator().manual_seed(99)
+    states = _randn(gen, n_t, dim, batch, cplx=True)
+    tangents = _randn(gen, n_t, n_dir, dim, batch, cplx=True)
+    diag = _randn(gen, 2, dim)
+    paulis = [P.PauliObservable(n, [(0.7, {0: "X", 2: "Y"}), (-0.4, {1: "Z"})]), P.PauliObservable(n, [(1.0, {1: "Y"})])]
+    targets = [_randn(gen, dim, cplx=True), _randn(gen, dim, batch, cplx=True)]
+    val, der = tangent_rows_reference(states, tangents, diag, paulis, targets)
+    assert tuple(val.shape) == (2 + 2 + 4, n_t, batch) and tuple(der.shape) == (n_dir, 8, n_t, batch)
+    for d in range(n_dir):
+        s = torch.zeros((), dtype=torch.float64, requires_grad=True)
+        jac = torch.autograd.functional.jacobian(
+            lambda s_: tangent_rows_reference(states + s_ * tangents[:, d], tangents, diag, paulis, targets)[0], s)
+        assert float((jac - der[d]).abs().max()) <= 1e-13 * float(der[d].abs().max())
