@@ -253,7 +253,9 @@ typedef struct RydPlanInfo {
     char kernel_fwd[80];             /* reporting only: the instantiation the forward factor passes of THIS problem run on, as a profiler
                                         prints it, e.g. "k_chain<12,10,false,false,true,false>" (tile bits, log2 threads, complex tables,
                                         adjoint, loop-free, L2-resident) — bench.py names its roofline kernel from here */
-    char kernel_bwd[80];             /* the same for the adjoint factor passes (empty when need_backward was 0) */
+    char kernel_bwd[80];             /* the same for the adjoint factor passes (empty when need_backward was 0); where a one-launch forward
+                                        sweep is followed by the launch-per-factor adjoint (12 qubits, or a save interval of more than 64
+                                        factors) this names that adjoint's kernel */
 } RydPlanInfo;
 
 #define RYDIFF_PLAN_SCRATCH_BYTES 1024

@@ -92,7 +92,14 @@ void describe_kernels(const Runtime& rt, const RydProblem* p, bool backward, Ryd
         }
     } else {
         std::snprintf(info->kernel_fwd, sizeof(info->kernel_fwd), info->kernel_family == 0 ? "k_lanes_fwd (N=%d)" : "k_persist<%d,...>", pl.N);
-        if (backward) std::snprintf(info->kernel_bwd, sizeof(info->kernel_bwd), info->kernel_family == 0 ? "k_lanes_bwd (N=%d)" : "k_persist_bwd<%d,...>", pl.N);
+        // (12 qubits, more than kPersistGroups groups, or an interval of more than kStageChunk factors without the lanes' full tape:
+        // the launch-per-factor adjoint reads what the one-launch forward sweep left)
+        if (backward && persist_bwd_enabled(rt))
+            std::snprintf(info->kernel_bwd, sizeof(info->kernel_bwd), info->kernel_family == 0 ? "k_lanes_bwd (N=%d)" : "k_persist_bwd<%d,...>", pl.N);
+        else if (backward && direct_global_ok(rt))
+            std::snprintf(info->kernel_bwd, sizeof(info->kernel_bwd), "k_factor_bwd_direct_global<%d,%s>", pl.N, b(pl.N <= 13));
+        else if (backward)
+            std::snprintf(info->kernel_bwd, sizeof(info->kernel_bwd), "k_factor_bwd_direct");
     }
 }
 

@@ -30,6 +30,45 @@ def random_terms(n_qubits: int, n_samples: int, dt: float, seed: int, local: boo
     return terms
 
 
+RHO_CAP = 6.0  # kRhoCap (csrc/plan.hpp): an exponential with tau * half_width above it is split into ceil(tau * half_width / 6) sub-exponentials
+# Save-interval lengths in units of RHO_CAP / half_width; every entry at least 0.1 away from an integer, so that the sub-step
+# counts ceil(ratio) do not hinge on rounding.  MIXED: (1, 2, 1, 3, 2) sub-exponentials; TWOS: (1, 2, 1, 2, 2).
+SUBSTEP_RATIOS = {"MIXED": (0.6, 1.6, 0.3, 2.5, 1.4), "TWOS": (0.6, 1.6, 0.3, 1.9, 1.4)}
+SUBSTEP_COUNTS = {"MIXED": (1, 2, 1, 3, 2), "TWOS": (1, 2, 1, 2, 2)}
+
+
+def gershgorin_half_width(terms) -> float:
+    """CPU restatement of the library's spectral bound (k_table_stats / run_stats, csrc) for a HamTerms without pair terms, or for a
+    list of them (one table set per trajectory on one register: every maximum runs over all of them).  With c_q / det_q the flip
+    and detuning coefficients summed per qubit,  flip = max over samples of sum_q |c_q|,  d+ / d- = max over samples of
+    sum_q max(+-2 det_q, 0),  U+ / U- = sum of the positive / negative pair interactions:
+        half width = (U+ + U- + d+ + d-) / 2 + flip,
+    an upper bound of (lambda_max - lambda_min) / 2 of H(t) at every sample (and, H being linear in the tables, in between)."""
+    sets = list(terms) if isinstance(terms, (list, tuple)) else [terms]
+    flip = dpos = dneg = 0.0
+    for tr in sets:
+        c_q = torch.zeros(tr.n_qubits, tr.n_samples, dtype=torch.complex128)
+        d_q = torch.zeros(tr.n_qubits, tr.n_samples, dtype=torch.float64)
+        for c, targets in tr.amp_terms():
+            for q in targets:
+                c_q[q] += c.detach().to(torch.complex128)
+        for d, targets in tr.det_terms():
+            for q in targets:
+                d_q[q] += 2.0 * d.detach().to(torch.float64)
+        flip = max(flip, float(c_q.abs().sum(0).max()))
+        dpos = max(dpos, float(d_q.clamp(min=0).sum(0).max()))
+        dneg = max(dneg, float((-d_q).clamp(min=0).sum(0).max()))
+    u = sets[0].u_pairs.detach().to(torch.float64)
+    return 0.5 * (float(u.clamp(min=0).sum()) + float((-u).clamp(min=0).sum()) + dpos + dneg) + flip
+
+
+def substepped_tsave(half_width: float, ratios) -> torch.Tensor:
+    """Save times 0 = t_0 < t_1 < ... with t_{k+1} - t_k = ratios[k] * RHO_CAP / half_width: interval k then takes
+    ceil(ratios[k]) sub-exponentials.  Not rounded to any sample grid."""
+    tau = torch.tensor(ratios, dtype=torch.float64) * (RHO_CAP / float(half_width))
+    return torch.cat([torch.zeros(1, dtype=torch.float64), torch.cumsum(tau, 0)])
+
+
 def mask_of(targets) -> int:
     m = 0
     for q in targets:

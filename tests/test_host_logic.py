@@ -12,7 +12,7 @@ import pulser_diff_amd as P
 from oracle import restatement as R
 from pulser_diff_amd import _native, pulses as pl
 from pulser_diff_amd.solver import SolverType, tolerance_from_options
-from tests.helpers import random_terms
+from tests.helpers import RHO_CAP, SUBSTEP_COUNTS, SUBSTEP_RATIOS, gershgorin_half_width, random_terms, substepped_tsave
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -577,3 +577,36 @@ def test_freeze_gc_moves_live_objects_out_of_the_collectors_way():
         assert gc.get_freeze_count() > before
     finally:
         gc.unfreeze()
+
+
+@pytest.mark.parametrize("n_qubits", [4, 6])
+def test_restated_spectral_bound_holds_and_the_substep_patterns_give_their_counts(n_qubits):
+    """tests.helpers.gershgorin_half_width (the library's bound, restated) bounds the spread of the spectrum of the oracle's dense
+    H(t) at every sample — also over two table sets — and is not idle (within a factor 3 of the widest spectrum); the two patterns of
+    tests/test_gpu_substepped_intervals.py give save intervals whose ceil(tau * half_width / 6) are the stated sub-step counts, every
+    tau * half_width / 6 at least 0.1 away from an integer."""
+    import dataclasses
+    import math
+
+    terms = random_terms(n_qubits, 15, 0.01, seed=4100 + n_qubits, local=True, phase=True)
+    weaker = dataclasses.replace(terms, amp_coeff=0.8 * terms.amp_coeff, extra_amp=[(0.8 * c, tg) for c, tg in terms.extra_amp])
+    hw = gershgorin_half_width(terms)
+    assert gershgorin_half_width([terms, weaker]) == hw and gershgorin_half_width(weaker) < hw
+    widest = 0.0
+    for tr in (terms, weaker):
+        for i in range(tr.n_samples - 1):  # (the last sample only enters by extrapolation: R.interp_indices)
+            for t in (i * tr.dt, (i + 0.37) * tr.dt):
+                ev = torch.linalg.eigvalsh(R.dense_hamiltonian(tr, t))
+                spread = 0.5 * float(ev[-1] - ev[0])
+                assert spread <= hw * (1 + 1e-12), (i, spread, hw)
+                widest = max(widest, spread)
+    assert widest > hw / 3.0
+    flipped = dataclasses.replace(terms, u_pairs=-terms.u_pairs)  # negative interactions widen the range like positive ones
+    assert abs(gershgorin_half_width(flipped) - hw) <= 1e-12 * hw
+    for name, ratios in SUBSTEP_RATIOS.items():
+        ts = substepped_tsave(hw, ratios)
+        assert ts.dtype == torch.float64 and float(ts[0]) == 0.0 and len(ts) == len(ratios) + 1
+        rho = (ts[1:] - ts[:-1]) * hw
+        assert tuple(math.ceil(float(r) / RHO_CAP) for r in rho) == SUBSTEP_COUNTS[name]
+        assert all(abs(float(r) / RHO_CAP - round(float(r) / RHO_CAP)) >= 0.1 - 1e-12 for r in rho)
+        assert max(SUBSTEP_COUNTS[name]) > 1
