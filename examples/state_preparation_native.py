@@ -57,3 +57,6 @@ def infidelity(m):
 (best_loss, best_params, best_epoch), _ = train(model, infidelity, epochs, lr=5.0)
 load_parameters(model, best_params)
 print(f"best loss {best_loss:.6f} at epoch {best_epoch};  state fidelity now {100 * (1 - float(infidelity(model).detach())):.2f} %")
+# measurement shots of the trained run, drawn natively as well: still no stored states ('1' = Rydberg; the target is all-Rydberg)
+shots = model.sample_final_state(1000)
+print("1000 shots of the final state:", ", ".join(f"{bits}: {count}" for bits, count in shots.most_common(4)))

@@ -193,6 +193,30 @@ typedef struct RydProblem {
      * knows where that is (pulser-diff_amd/hamiltonian.py: piece_refinement) and the library does not have to read them back. */
     const uint8_t* dp5_piece_refine;
 
+    /* MEASUREMENT SHOTS: amplitude indices sampled from |psi_b(t_k)|^2 at chosen save points by rydiff_forward, while the state is
+     * on the device — no stored trajectory, no 2^N probabilities on the host.  The caller supplies the uniforms (its own generator and
+     * seeding), which makes the rule deterministic.  For sampled save point k, trajectory b, shot s with uniform u:
+     *   p[y] = |psi_b(t_k)[y]|^2,   C[x] = sum_{y <= x} p[y],   S = C[2^N - 1];   result = the smallest x with C[x] > u * S
+     * with u clamped into [0, 1) (anything not > 0, NaN included, counts as 0).  Where rounding leaves no such x the result is the
+     * largest x with p[x] > 0; an x with p[x] == 0 is never returned; S == 0 gives RYDIFF_SHOT_NONE.  The state need not be
+     * normalised; result s belongs to uniform s (no sorting asked of the caller).  The cumulative sums are formed in float64 in a fixed
+     * order (bit-reproducible; within (2^N - 1) * 2^-53 * S of the exact ones).
+     * Honoured by rydiff_forward in every kernel family and with every tape mode — final_state_only, states_out == NULL without a
+     * tape, next to diagonal / Pauli / overlap observables, pair terms, conditioned and ones-counting terms.  rydiff_backward ignores
+     * the values (shots carry no gradient) but must be given the same counts as the forward call: rydiff_plan adds the scratch they
+     * need to workspace_bytes (two doubles per 2^10 amplitudes and trajectory, and up to 12 qubits the trajectory the one-launch sweeps
+     * are sampled from where the caller keeps none).  Not together with shard_bits > 0 and not in rydiff_forward_tangent
+     * (RYDIFF_ENOTIMPL).  Traffic per sampled save point and trajectory: one read of the state plus at most n_shots * 16 KiB; the state
+     * is never written.  n_shots = 0: nothing changes.  (The fields sit in front of tape_steps and the overlap block, so the Pauli block
+     * stays the tail of the struct.) */
+#define RYDIFF_MAX_SHOTS (1 << 20)   /* shots per (sampled save point, trajectory) */
+#define RYDIFF_SHOT_NONE 0xFFFFFFFFu /* the sampled state was identically zero */
+    int32_t n_shots;              /* 0: none */
+    int32_t n_shot_times;         /* 1 .. n_tsave */
+    const int32_t* shot_times;    /* HOST [n_shot_times]: save-point indices, strictly increasing, 0 .. n_tsave-1 */
+    const double* shot_uniforms;  /* DEVICE float64 [n_shot_times][B][n_shots], in any order */
+    uint32_t* shots_out;          /* DEVICE [n_shot_times][B][n_shots]: amplitude indices */
+
     /* need_tape = 3 (PARTIAL tape) only: the number of TRAILING tsave intervals whose factor outputs are all kept in the workspace
      * tape (1 .. n_tsave - 1); the earlier intervals keep their save-point states only and are recomputed by the adjoint sweep.  The
      * caller sizes it to the HBM that is free (rydiff_plan reports the workspace for the value given): what the full tape of
@@ -287,7 +311,8 @@ int rydiff_plan(const RydProblem* p, int need_tape, int need_backward, void* scr
  *               With need_tape = 2 / 3 AND states_out the factor outputs go to the (granted) workspace tape and the states at the
  *               save points are copied out of it — stored states plus a later gradient without (or with less) recomputation.
  *   expect_out  DEVICE float64 [n_obs + n_pauli_obs + 2 * n_overlaps][n_tsave][B] (diagonal observables first, then the Pauli
- *               ones, then Re / Im of every overlap), or NULL */
+ *               ones, then Re / Im of every overlap), or NULL
+ * With RydProblem.n_shots > 0 the measurement shots of the save points in shot_times go to RydProblem.shots_out on the way. */
 int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi0, void* states_out, double* expect_out,
                    void* workspace, size_t workspace_bytes, int need_tape, void* stream);
 

@@ -30,6 +30,8 @@ MAX_TERMS = 64
 MAX_PAULI_STRINGS = 1024
 MAX_OVERLAPS = 16
 MAX_TANGENTS = 8
+MAX_SHOTS = 1 << 20  # shots per (sampled save point, trajectory)
+SHOT_NONE = 0xFFFFFFFF  # the sampled state was identically zero
 
 
 class RydProblem(ctypes.Structure):
@@ -66,6 +68,11 @@ class RydProblem(ctypes.Structure):
         ("amp_conditioned_terms", ctypes.c_uint64),
         ("det_ones_terms", ctypes.c_uint64),
         ("dp5_piece_refine", ctypes.c_void_p),
+        ("n_shots", ctypes.c_int32),
+        ("n_shot_times", ctypes.c_int32),
+        ("shot_times", ctypes.c_void_p),
+        ("shot_uniforms", ctypes.c_void_p),
+        ("shots_out", ctypes.c_void_p),
         ("tape_steps", ctypes.c_int32),
         ("n_overlaps", ctypes.c_int32),
         ("overlap_batch", ctypes.c_int32),

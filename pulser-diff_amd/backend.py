@@ -35,6 +35,7 @@ from .simconfig import SimConfig
 from .simresults import CoherentResults, NoisyResults, SimulationResults
 from .solver import ProblemSpec, SolverType, evolve, evolve_tangent, sesolve, tolerance_from_options
 from .observables import PauliObservable, StateOverlap
+from .shots import MAX_SHOTS, ShotRequest, indices_to_bitstrings
 from .utils import DiagonalObservable
 
 
@@ -287,14 +288,25 @@ class TorchEmulator:
 
     # ---- run (backend.py:430-611) -------------------------------------------------------------------------
     def run(self, time_grad: bool = False, dist_grad: bool = False, solver: SolverType = SolverType.DP5_SE,
-            observables: Optional[list] = None, store_states: bool = True, **options: Any) -> SimulationResults:
+            observables: Optional[list] = None, store_states: bool = True, shots: Union[None, int, ShotRequest] = None,
+            native_shots: bool = False, **options: Any) -> SimulationResults:
         """Simulates the sequence with the native solver and returns ``CoherentResults``.
 
         ``observables`` (extension): diagonal observables (``DiagonalObservable`` or dense diagonal tensors) and sums of Pauli
         strings (``PauliObservable``, e.g. from ``build_observable``) and overlaps with target states (``StateOverlap``; read with
         ``results.overlap``) to be evaluated natively at every evaluation time; ``store_states=False`` keeps the trajectory out of
         the results.
+
+        ``shots`` (extension): measurement shots drawn natively while the state is on the device — an int (that many at the final
+        evaluation time) or a ``ShotRequest`` (``times="all"``: every evaluation time).  ``results.sample_state`` /
+        ``sample_final_state`` return them when asked for a sampled time and exactly that many samples, also with
+        ``store_states=False``.  Coherent Schroedinger runs only.  ``native_shots=True`` (extension, noisy runs that average over
+        realisations): the per-run measurements are drawn natively as well and no run's states are stored.
         """
+        if shots is not None and not isinstance(shots, ShotRequest):
+            if isinstance(shots, bool) or not isinstance(shots, (int, np.integer)):
+                raise TypeError(f"shots must be an int or a ShotRequest, got {type(shots)}")
+            shots = ShotRequest(int(shots))
         if time_grad:
             self._eval_times_array.requires_grad_(True)  # backend.py:453-455
         if dist_grad:
@@ -355,18 +367,21 @@ class TorchEmulator:
         def run_coherent() -> CoherentResults:
             if overlap_objs and solver == SolverType.DP5_ME:
                 raise NotImplementedError("StateOverlap observables are defined on kets: not available in master-equation runs.")
+            if shots is not None and solver == SolverType.DP5_ME:
+                raise NotImplementedError("Native measurement shots are not available in master-equation runs; "
+                                          "sample_state draws from the stored density matrices.")
             if solver == SolverType.DP5_ME:  # density matrices (backend.py:495-509); without collapse noise L = 0
                 rho, stats = mesolve(ham, psi0.to(dev), self._eval_times_array, ham.config, options)
                 return CoherentResults(rho, ham._size, ham.basis_name, self._eval_times_array, self._meas_basis, meas_errors,
                                        atom_order=tuple(ham._qdict), stats=stats, density=True)
             result = sesolve(ham, psi0.to(dev), self._eval_times_array, solver=solver, options=options, obs_diag=obs_diag,
-                             store_states=store_states, pauli_obs=pauli_objs, overlap_obs=overlap_objs)
+                             store_states=store_states, pauli_obs=pauli_objs, overlap_obs=overlap_objs, shots=shots)
             states_tbd = result.states.permute(0, 2, 1) if result.states.numel() else result.states
             return CoherentResults(states_tbd, ham._size, ham.basis_name, self._eval_times_array, self._meas_basis,
                                    meas_errors, atom_order=tuple(ham._qdict),
                                    native_expect=result.expect if (obs_diag is not None or pauli_objs) else None,
                                    native_observables=obs_objs + pauli_objs, stats=result.stats,
-                                   native_overlaps=result.overlaps, overlap_observables=overlap_objs)
+                                   native_overlaps=result.overlaps, overlap_observables=overlap_objs, native_shots=result.shots)
 
         # does the noise ask for averaging over several runs?  (backend.py:531-569)
         no_resampling = noise <= {"dephasing", "relaxation", "SPAM", "depolarizing", "eff_noise", "amplitude"} and (
@@ -385,7 +400,10 @@ class TorchEmulator:
             reps = [1] * self.config.runs
         if overlap_objs:
             raise NotImplementedError("StateOverlap observables are not available in noisy runs that average over realisations.")
-        return self._run_noisy(psi0, solver, options, reps, bad_atom_configs, meas_errors)
+        if shots is not None:
+            raise NotImplementedError("A ShotRequest belongs to one coherent run; noisy runs that average over realisations return "
+                                      "their measurements as NoisyResults (native_shots=True draws them natively).")
+        return self._run_noisy(psi0, solver, options, reps, bad_atom_configs, meas_errors, native_shots=native_shots)
 
     # ---- sensitivities at every evaluation time (extension) ---------------------------------------------------
     def _table_tangents(self, x: list) -> tuple:
@@ -513,10 +531,12 @@ class TorchEmulator:
         return Sensitivities(values, grads, "tangent", times)
 
     def _run_noisy(self, psi0: Tensor, solver: SolverType, options: dict, reps: list, bad_atom_configs,
-                   meas_errors) -> NoisyResults:
+                   meas_errors, native_shots: bool = False) -> NoisyResults:
         """backend.py:571-611 with the stochastic runs as the BATCH axis of the native solver: every run is one more
         trajectory with its own coefficient tables, all advanced by the same launches; the per-run measurements
-        (``samples_per_run`` x repetitions, then detection errors) are drawn on the GPU from |psi(t)|^2."""
+        (``samples_per_run`` x repetitions, then detection errors) are drawn on the GPU from |psi(t)|^2.  ``native_shots``
+        (Schroedinger runs): the solver draws them itself at every evaluation time and stores no states, so the runs of one
+        batch are bounded by its workspace instead of the saved trajectories."""
         ham, dev = self._hamiltonian, self._compute_device
         if psi0.shape[1] != 1:
             raise NotImplementedError("Noisy runs start from a single initial state.")
@@ -525,6 +545,7 @@ class TorchEmulator:
         n, n_t = ham._size, int(self._eval_times_array.shape[0])
         dim = 2**n
         master = solver == SolverType.DP5_ME  # collapse operators on top: every realisation is a density matrix
+        native_shots = bool(native_shots) and not master  # (density matrices keep the route through stored states)
         u_pairs = ham.u_pairs.detach()
         # the XY exchange lives in dense pair terms (they used to be dropped here, i.e. noisy XY runs evolved without
         # any interaction).  A badly prepared atom takes no part in it (hamiltonian.py:393-397 skips its pairs), so the pair terms
@@ -553,10 +574,19 @@ class TorchEmulator:
         else:
             def spec_of(run: int) -> ProblemSpec:
                 return ProblemSpec(n, ham.dt, ham.n_samples, amp_masks, det_masks, solver=solver,
-                                   tol=tolerance_from_options(options), store_states=True, pair_terms=xy_terms_of(run))
+                                   tol=tolerance_from_options(options), store_states=not native_shots, pair_terms=xy_terms_of(run))
             start = psi0.to(dev).T.contiguous()
         # bound the saved states of one batch (n_t x runs x 2^N, or 4^N, amplitudes)
         chunk = 1 if per_run_pairs else max(1, min(loop_runs, int(self._noisy_state_budget // max(n_t * start.shape[1] * 16, 1))))
+        max_shots = self.config.samples_per_run * max(reps)
+        if native_shots:
+            if max_shots > MAX_SHOTS:
+                raise ValueError(f"native_shots: samples_per_run x repetitions = {max_shots} exceeds {MAX_SHOTS} shots per run and time; "
+                                 "use the default route")
+            # no stored states: one trajectory costs its share of the workspace — a handful of state vectors, up to 12 qubits the
+            # trajectory the one-launch sweep is sampled from — plus its uniforms and shots
+            per_run = (8 + (n_t if n <= 12 else 0)) * dim * 16 + n_t * max_shots * 12
+            chunk = 1 if per_run_pairs else max(1, min(loop_runs, 65535, int(self._noisy_state_budget // per_run)))
         eps = meas_errors["epsilon"] if meas_errors else 0.0
         eps_p = meas_errors["epsilon_prime"] if meas_errors else 0.0
         bit_weights = (1 << torch.arange(n, device=dev, dtype=torch.int64))
@@ -569,18 +599,26 @@ class TorchEmulator:
         for r0 in range(0, loop_runs, chunk):
             r1 = min(loop_runs, r0 + chunk)
             with torch.no_grad():
-                states, _ = evolve(amp[r0:r1], det[r0:r1], u_pairs, tsave, start.repeat(r1 - r0, 1), spec_of(r0), None)
-                if master:  # populations = diagonal of rho
+                spec = spec_of(r0)
+                if native_shots:
+                    spec.shots = ShotRequest(max_shots, times="all")
+                states, _ = evolve(amp[r0:r1], det[r0:r1], u_pairs, tsave, start.repeat(r1 - r0, 1), spec, None)
+                if native_shots:
+                    probs = None
+                elif master:  # populations = diagonal of rho
                     probs = states.reshape(n_t, r1 - r0, dim, dim).diagonal(dim1=2, dim2=3).real.clamp_min(0.0)
                 else:
                     probs = states.real**2 + states.imag**2  # (n_t, runs, dim), basis order r = 0, g = 1
                 del states
                 for b in range(r1 - r0):
                     n_shots = self.config.samples_per_run * reps[r0 + b]
-                    idx = torch.multinomial(probs[:, b, :], n_shots, replacement=True)  # (n_t, shots)
                     # measured bitstring (result.py:70-120): ground-rydberg '1' = r = index bit 0, i.e. the complement of the index;
                     # digital / XY '1' = h / d = index bit 1: the index itself
-                    shots = (dim - 1) - idx if ham.basis_name == "ground-rydberg" else idx
+                    if native_shots:  # (n_t, shots): the first n_shots of the run's native shots (shot s belongs to uniform s)
+                        shots = indices_to_bitstrings(spec.shots.indices[:, b, :n_shots], ham.basis_name, self._meas_basis, n)
+                    else:
+                        idx = torch.multinomial(probs[:, b, :], n_shots, replacement=True)  # (n_t, shots)
+                        shots = (dim - 1) - idx if ham.basis_name == "ground-rydberg" else idx
                     if eps > 0 or eps_p > 0:
                         bits = (shots.unsqueeze(-1) >> torch.arange(n, device=dev)) & 1
                         flip = torch.rand(bits.shape, device=dev) < torch.where(bits == 1, eps_p, eps)

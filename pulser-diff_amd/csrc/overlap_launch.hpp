@@ -41,10 +41,12 @@ int launch_overlap_expect(const ForwardCtx& c, const double2* psi, size_t kstrid
     return RYDIFF_OK;
 }
 
-// every native observable that is evaluated by a launch of its own (Pauli strings, overlaps) on the states of k0 .. k0 + nk - 1
+// every native observable that is evaluated by a launch of its own (Pauli strings, overlaps) on the states of k0 .. k0 + nk - 1,
+// and the measurement shots of the sampled save points among them
 int launch_observables_expect(const ForwardCtx& c, const double2* psi, size_t kstride, int k0, int nk, const BatchSlice& bs) {
     if (const int rc = launch_pauli_expect(c, psi, kstride, k0, nk, bs)) return rc;
-    return launch_overlap_expect(c, psi, kstride, k0, nk, bs);
+    if (const int rc = launch_overlap_expect(c, psi, kstride, k0, nk, bs)) return rc;
+    return launch_shots(c, psi, kstride, k0, nk, bs);
 }
 
 // out[kk] = grad_states[k0 + kk] + 2 sum_o g_o O_o psi_{k0 + kk} + sum_o (gRe + i gIm)_o phi_o,  kk < nk  (the state at save point k

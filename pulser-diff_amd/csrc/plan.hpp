@@ -85,6 +85,11 @@ struct Plan {
     size_t off_pauli = 0, off_pauli_traj = 0, off_pauli_cot = 0;  // (the trajectory and the cotangent buffer serve the overlaps too)
     // state-overlap observables (overlap_kernels.hpp): targets stay where the caller has them
     int n_ov = 0, ov_batch = 1;
+    // measurement shots (shots_kernels.hpp): the sampled save points; scratch = chunk sums and their prefix, [B][shot_chunks()] doubles each
+    int n_shots = 0;
+    std::vector<int32_t> shot_times;
+    size_t off_shot_sums = 0, off_shot_prefix = 0;
+    size_t shot_chunks() const { return std::max<size_t>(dim >> 10, 1); }  // 2^10 amplitudes per chunk (kShotChunkBits)
     size_t pauli_gfirst_bytes() const { return (pauli_gfirst.size() * sizeof(int32_t) + 7) / 8 * 8; }
     size_t pauli_bytes() const {
         return n_pobs ? pauli_gfirst_bytes() + pauli_groups.size() * sizeof(PauliGroup) + pauli_strings.size() * sizeof(PauliString) : 0;
@@ -247,6 +252,37 @@ inline bool build_overlaps(const RydProblem* p, Plan& pl, std::string& err) {
     return true;
 }
 
+// RydProblem.n_shots / shot_*: counts against the caps, pointers, the list of sampled save points
+inline bool build_shots(const RydProblem* p, Plan& pl, std::string& err) {
+    pl.n_shots = 0;
+    pl.shot_times.clear();
+    if (p->n_shots < 0 || p->n_shots > RYDIFF_MAX_SHOTS) {
+        err = "n_shots must be in [0, " + std::to_string(RYDIFF_MAX_SHOTS) + "]";
+        return false;
+    }
+    if (p->n_shots == 0) return true;
+    if (p->n_shot_times < 1 || p->n_shot_times > p->n_tsave) {
+        err = "n_shot_times must be in [1, n_tsave]";
+        return false;
+    }
+    if (!p->shot_times || !p->shot_uniforms || !p->shots_out) {
+        err = "missing shot arrays (shot_times / shot_uniforms / shots_out)";
+        return false;
+    }
+    for (int i = 0; i < p->n_shot_times; ++i)
+        if (p->shot_times[i] < 0 || p->shot_times[i] >= p->n_tsave || (i > 0 && p->shot_times[i] <= p->shot_times[i - 1])) {
+            err = "shot_times must be strictly increasing save-point indices in [0, n_tsave)";
+            return false;
+        }
+    if (p->shard_bits > 0) {
+        err = "measurement shots: not implemented together with state sharding";
+        return false;
+    }
+    pl.n_shots = p->n_shots;
+    pl.shot_times.assign(p->shot_times, p->shot_times + p->n_shot_times);
+    return true;
+}
+
 // `width`: half spectral width of the generator when it is already known (<= 0: not yet) — the continuous solver's
 // sub-step shrinks with it.
 inline bool build_plan(const RydProblem* p, Plan& pl, std::string& err, double width = -1.0) {
@@ -330,6 +366,7 @@ inline bool build_plan(const RydProblem* p, Plan& pl, std::string& err, double w
     pl.N = p->n_qubits;
     if (!build_pauli(p, pl, err)) return false;
     if (!build_overlaps(p, pl, err)) return false;
+    if (!build_shots(p, pl, err)) return false;
     pl.shard_bits = p->shard_bits;
     if (pl.shard_bits < 0 || pl.shard_bits > 6 || pl.shard_bits >= pl.N) {
         err = "shard_bits must be in [0, min(6, n_qubits - 1)]";
@@ -543,8 +580,11 @@ inline size_t carve(Plan& pl, int tape_mode, bool need_backward, int chain_slots
     }
     pl.off_pair = take(size_t(pl.n_pair) * 64 * sizeof(double));
     pl.off_pauli = take(pl.pauli_bytes());
-    // one-launch sweeps: the trajectory the Pauli and overlap observables are evaluated on where the caller keeps none
-    pl.off_pauli_traj = take(((pl.n_pobs || pl.n_ov) && pl.N <= 12) ? size_t(pl.T + 1) * pl.state_bytes : 0);
+    // one-launch sweeps: the trajectory the Pauli and overlap observables are evaluated on (and the shots drawn from) where the
+    // caller keeps none
+    pl.off_pauli_traj = take(((pl.n_pobs || pl.n_ov || pl.n_shots) && pl.N <= 12) ? size_t(pl.T + 1) * pl.state_bytes : 0);
+    pl.off_shot_sums = take(pl.n_shots ? size_t(pl.B) * pl.shot_chunks() * sizeof(double) : 0);
+    pl.off_shot_prefix = take(pl.n_shots ? size_t(pl.B) * pl.shot_chunks() * sizeof(double) : 0);
     pl.total_fwd = off;
     pl.tape_mode = tape_mode;
     if (tape_mode == 2) pl.off_tape = take(size_t(total_factors + 1) * pl.state_bytes);

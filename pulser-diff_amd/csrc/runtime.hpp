@@ -621,6 +621,8 @@ struct ForwardCtx : SweepCtx {
     bool want_exp = false;
     double* pauli_out = nullptr;   // &expect_out[n_obs][0][0] where Pauli observables are evaluated
     double* overlap_out = nullptr; // &expect_out[n_obs + n_pobs][0][0] where overlaps are evaluated
+    const double* shot_u = nullptr;  // RydProblem.shot_uniforms / shots_out where shots are drawn (rydiff_forward with n_shots > 0)
+    uint32_t* shots_out = nullptr;
 };
 
 struct BackwardCtx : SweepCtx {

@@ -43,6 +43,7 @@ using namespace rydiff;
 #include "lane_kernels.hpp"
 #include "pauli_kernels.hpp"
 #include "overlap_kernels.hpp"
+#include "shots_kernels.hpp"
 #include "tangent_kernels.hpp"
 static_assert(sizeof(PersistFactor) == 48, "plan.hpp sizes the factor table with 48 bytes per entry");
 
@@ -51,6 +52,7 @@ static_assert(sizeof(PersistFactor) == 48, "plan.hpp sizes the factor table with
 #include "direct_launch.hpp"
 #include "chain_launch.hpp"
 #include "pair_launch.hpp"
+#include "shots_launch.hpp"
 #include "overlap_launch.hpp"
 #include "tangent_launch.hpp"
 #include "persist_launch.hpp"
@@ -467,13 +469,17 @@ int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi
     c.want_exp = expect_out && pl.n_obs > 0;
     c.pauli_out = (expect_out && pl.n_pobs) ? expect_out + size_t(pl.n_obs) * (pl.T + 1) * pl.B : nullptr;
     c.overlap_out = (expect_out && pl.n_ov) ? expect_out + size_t(pl.n_obs + pl.n_pobs) * (pl.T + 1) * pl.B : nullptr;
+    if (pl.n_shots) {  // drawn wherever launch_observables_expect sees a sampled save point
+        c.shot_u = p->shot_uniforms;
+        c.shots_out = p->shots_out;
+    }
     if (c.want_exp || c.pauli_out || c.overlap_out)
         HIP_TRY(hipMemsetAsync(expect_out, 0, size_t(pl.n_obs + pl.n_pobs + 2 * pl.n_ov) * (pl.T + 1) * pl.B * sizeof(double), stream));
     if (c.want_exp) {
         rc = launch_expect(c, c.start, 0);
         if (rc) return rc;
     }
-    if (persist_enabled(rt)) return forward_persist(c);  // (evaluates the Pauli / overlap observables on the whole trajectory afterwards)
+    if (persist_enabled(rt)) return forward_persist(c);  // (evaluates the Pauli / overlap observables and draws the shots on the whole trajectory afterwards)
     rc = launch_observables_expect(c, c.start, 0, 0, 1, BatchSlice{0, pl.B, false});
     if (rc) return rc;
     return chain_enabled(rt) ? forward_chained(c) : forward_direct(c);

@@ -148,7 +148,7 @@ class QuantumModel(Module):
             self._seq._set_register(self.register)
             self.built_seq = self._seq.build(**values) if self._seq.is_parametrized() else self._seq
 
-    def _run(self, observables=None, store_states: Optional[bool] = None) -> tuple[Tensor, SimulationResults]:
+    def _run(self, observables=None, store_states: Optional[bool] = None, shots=None) -> tuple[Tensor, SimulationResults]:
         """model.py:405-414 — but the emulator PERSISTS between epochs: while the built sequence keeps its structure (the usual
         case: only parameter values move) its coefficient tables are refreshed in place instead of building a new emulator."""
         sim = getattr(self, "_sim", None)
@@ -163,7 +163,7 @@ class QuantumModel(Module):
             self._sim.set_config(self.noise_config)  # stochastic noise: a fresh realisation per epoch, as a new emulator would draw
         results = self._sim.run(time_grad=self.time_grad, dist_grad=self.dist_grad, solver=self.solver,
                                 observables=observables, **({} if store_states is None else {"store_states": store_states}),
-                                **self.options)
+                                **({} if shots is None else {"shots": shots}), **self.options)
         return self._sim.evaluation_times, results
 
     def forward(self) -> tuple[Tensor, Tensor]:
@@ -181,6 +181,13 @@ class QuantumModel(Module):
         else:
             evaluation_times, results = self._run()
         return evaluation_times, results.expect([obs])[0]
+
+    def sample_final_state(self, n_samples: int = 1000):
+        """Bitstring counts (a ``Counter``) of ``n_samples`` measurement shots of the final state at the current parameters, drawn
+        natively while the state is on the device: no trajectory is stored (``TorchEmulator.run(shots=...)``)."""
+        with torch.no_grad():
+            _, results = self._run(store_states=False, shots=int(n_samples))
+        return results.sample_final_state(int(n_samples))
 
     def overlap(self, target) -> tuple[Tensor, Tensor]:
         """Evaluation times and the complex overlaps ``<target_b | psi_b(t)>``, ``(n_t, B)``, evaluated and differentiated natively:

@@ -20,6 +20,7 @@ from torch import Tensor
 
 from .result import SampledResult, TorchResult
 from .observables import PauliObservable, StateOverlap, overlap_states
+from .shots import ShotRequest, bitstring_counts, indices_to_bitstrings
 from .utils import DiagonalObservable, expect
 
 
@@ -56,7 +57,7 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
                  meas_errors: Optional[Mapping[str, float]] = None, atom_order: tuple = (),
                  native_expect: Optional[Tensor] = None, native_observables: Optional[list] = None,
                  stats: Optional[dict] = None, density: bool = False, native_overlaps: Optional[Tensor] = None,
-                 overlap_observables: Optional[list] = None) -> None:
+                 overlap_observables: Optional[list] = None, native_shots: Optional[ShotRequest] = None) -> None:
         super().__init__(size, basis_name, sim_times)
         if self._basis_name == "all":  # simresults.py:381-383
             if meas_basis not in {"ground-rydberg", "digital"}:
@@ -74,6 +75,7 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
         self._native_observables = list(native_observables or [])
         self._native_overlaps = native_overlaps  # complex (n_ov, n_t, B)
         self._overlap_observables = list(overlap_observables or [])
+        self._native_shots = native_shots  # filled by the solver: amplitude indices (n_shot_times, B, n_shots)
         self.solver_stats = dict(stats or {})
 
     # ---- sequence protocol over per-time results (pulser.result.Results)
@@ -141,13 +143,38 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
     def sample_state(self, t: float, n_samples: int = 1000, t_tol: float = 1.0e-3) -> Counter:
         """simresults.py:497-540: ideal samples, then the detection errors of the SPAM model (a measured 0 flips with
         probability epsilon, a measured 1 with probability epsilon_prime), independently per shot and per atom."""
-        sampled_state = self[self._get_index_from_time(t, t_tol)].get_samples(n_samples)
+        t_index = self._get_index_from_time(t, t_tol)
+        sampled_state = self._native_sample(t_index, n_samples)
+        if sampled_state is None:
+            if self._states_tbd.numel() == 0:
+                raise RuntimeError(
+                    "States were not stored for this run (store_states=False) and it drew no native shots for this time and count: "
+                    f"request them with run(..., shots=ShotRequest({n_samples}, times=[{t_index}])) — an int samples the final time, "
+                    'times="all" every evaluation time — and ask sample_state for exactly that many samples.')
+            sampled_state = self[t_index].get_samples(n_samples)
         if self._meas_errors is None or (self._meas_errors["epsilon"] == 0.0 and self._meas_errors["epsilon_prime"] == 0):
             return sampled_state
         return apply_detection_errors(sampled_state, self._meas_errors["epsilon"], self._meas_errors["epsilon_prime"])
 
     def sample_final_state(self, N_samples: int = 1000) -> Counter:
         return self.sample_state(float(self._sim_times[-1]), N_samples)
+
+    @property
+    def native_shots(self) -> Optional[ShotRequest]:
+        """The ``ShotRequest`` of ``run(..., shots=...)`` with the shots the solver drew (``.indices``), or None."""
+        return self._native_shots
+
+    def _native_sample(self, t_index: int, n_samples: int) -> Optional[Counter]:
+        """The native shots of evaluation time ``t_index`` as bitstring counts, when that time was sampled with exactly
+        ``n_samples`` shots (first column of the initial state, like ``TorchResult.get_samples``); else None."""
+        req = self._native_shots
+        if req is None or self._density or req.n_shots != n_samples:
+            return None
+        pos = req.position_of(t_index)
+        if pos is None:
+            return None
+        outcomes = indices_to_bitstrings(req.indices[pos, 0], self._basis_name, self._meas_basis, self._size)
+        return bitstring_counts(outcomes, self._size)
 
 
 def apply_detection_errors(counts: Counter, eps: float, eps_p: float) -> Counter:

@@ -13,7 +13,7 @@ from __future__ import annotations
 import ctypes
 import enum
 from dataclasses import dataclass, field, replace
-from typing import Any, Optional, Sequence
+from typing import Any, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -21,6 +21,7 @@ from torch import Tensor
 
 from . import _native
 from .observables import PauliObservable, StateOverlap, check_pauli, pack_overlaps, pack_pauli
+from .shots import ShotRequest
 
 
 class SolverType(enum.Enum):
@@ -71,6 +72,9 @@ class ProblemSpec:
     # state-overlap observables (RydProblem.overlap_*): the packed targets, a complex128 DEVICE tensor (n_ov, 1 | B, 2^N)
     # (observables.pack_overlaps); Re / Im of every overlap follow the Pauli rows in `expect`.  Constants: no gradient.
     overlaps: Optional[Tensor] = None
+    # measurement shots drawn natively at chosen save points (RydProblem.n_shots / shot_*): the request object receives the amplitude
+    # indices (shots.ShotRequest.indices); a non-differentiable by-product, allowed next to a gradient
+    shots: Optional[ShotRequest] = None
 
     @property
     def n_overlaps(self) -> int:
@@ -188,6 +192,18 @@ class _Call:
             p.overlap_batch = self.overlaps.shape[1]
             p.overlap_targets = self.overlaps.data_ptr()
         self.problem = p
+        self.shot_buffers = None
+
+    def set_shots(self, times: np.ndarray, uniforms: Tensor, out: Tensor) -> None:
+        """RydProblem.n_shots / shot_*: sampled save points (host int32), uniforms (device float64) and the output (device, 32-bit),
+        both (n_shot_times, batch, n_shots).  rydiff_backward is handed the same fields: the counts size the workspace."""
+        self.shot_buffers = (np.ascontiguousarray(times, dtype=np.int32), uniforms, out)
+        p = self.problem
+        p.n_shots = uniforms.shape[2]
+        p.n_shot_times = len(self.shot_buffers[0])
+        p.shot_times = self.shot_buffers[0].ctypes.data
+        p.shot_uniforms = uniforms.data_ptr()
+        p.shots_out = out.data_ptr()
 
 
 def _check_overlaps(spec: ProblemSpec, batch: int, device: Optional[torch.device] = None) -> None:
@@ -307,6 +323,16 @@ class _RydbergEvolve(torch.autograd.Function):
         # the kernel variant this call resolved to (spec field, else the CALLING thread's default): the backward pass runs on the
         # autograd engine's device thread, where that thread-local default is not visible
         ctx.kernel_variant = int(call.problem.kernel_variant)
+        ctx.shot_buffers = None
+        if spec.shots is not None:
+            if not isinstance(spec.shots, ShotRequest):
+                raise TypeError(f"ProblemSpec.shots must be a ShotRequest, got {type(spec.shots)}")
+            shot_times = spec.shots.resolve_times(n_t)
+            with torch.cuda.device(dev):
+                shot_u = spec.shots.draw_uniforms(len(shot_times), batch, dev)
+                shot_out = torch.empty(shot_u.shape, dtype=torch.int32, device=dev)
+            call.set_shots(shot_times, shot_u, shot_out)
+            ctx.shot_buffers = call.shot_buffers
         needs_grad = any(ctx.needs_input_grad[:5])
         need_tape = int(bool(needs_grad and not spec.store_states))
         with torch.cuda.device(dev):
@@ -372,6 +398,10 @@ class _RydbergEvolve(torch.autograd.Function):
                                            _ptr(states) if spec.store_states else None,
                                            _ptr(expect) if n_obs else None, _ptr(workspace),
                                            workspace.numel(), need_tape, stream))
+            if spec.shots is not None:
+                spec.shots.indices = shot_out.to(torch.int64) & 0xFFFFFFFF  # (the library writes unsigned 32-bit indices)
+                spec.shots.time_indices = tuple(int(k) for k in shot_times)
+                spec.shots.last_uniforms = shot_u
         ctx.spec = spec
         ctx.info = info
         ctx.tsave_host = ts_host
@@ -407,6 +437,8 @@ class _RydbergEvolve(torch.autograd.Function):
         call = _Call(spec, amp_c, det_c, u_c, ctx.tsave_host, batch, obs, real_amp_grad=not ctx.in_dtypes[0].is_complex)
         call.problem.kernel_variant = ctx.kernel_variant  # same kernel family as the forward pass (see forward)
         call.problem.tape_steps = ctx.tape_steps
+        if ctx.shot_buffers is not None:  # ignored by the adjoint sweep, but the counts are part of the workspace layout
+            call.set_shots(*ctx.shot_buffers)
         need = ctx.needs_input_grad
         if g_states is not None and g_states.numel() == 0:
             g_states = None
@@ -457,6 +489,7 @@ class SolveResult:
     expect: Tensor  # (n_obs + n_pauli, n_t, B) observables evaluated natively, the diagonal ones first
     stats: dict
     overlaps: Optional[Tensor] = None  # complex (n_ov, n_t, B): <phi_o,b | psi_b(t_k)> evaluated natively (differentiable), or None
+    shots: Optional[ShotRequest] = None  # the request handed to sesolve(shots=...), holding the native shots (.indices)
 
 
 def split_expect(expect: Tensor, n_overlaps: int) -> tuple[Tensor, Optional[Tensor]]:
@@ -471,23 +504,28 @@ def split_expect(expect: Tensor, n_overlaps: int) -> tuple[Tensor, Optional[Tens
 def evolve(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Tensor,
            spec: ProblemSpec, obs_diag: Optional[Tensor] = None) -> tuple[Tensor, Tensor]:
     """Low-level entry: psi0 is (B, dim); returns states (n_t, B, dim) and expect (n_obs + n_pauli + 2 n_overlaps, n_t, B)
-    (``split_expect`` takes the overlap rows of ``spec.overlaps`` out as complex numbers)."""
+    (``split_expect`` takes the overlap rows of ``spec.overlaps`` out as complex numbers).  ``spec.shots`` (a ``ShotRequest``)
+    receives its measurement shots as a by-product; the return value does not change."""
     return _RydbergEvolve.apply(amp_tables, det_tables, u_pairs, tsave, psi0, obs_diag, spec)
 
 
 def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverType.DP5_SE,
             options: Optional[dict] = None, obs_diag: Optional[Tensor] = None, store_states: bool = True,
             pauli_obs: Optional[Sequence[PauliObservable]] = None,
-            overlap_obs: Optional[Sequence[StateOverlap]] = None) -> SolveResult:
+            overlap_obs: Optional[Sequence[StateOverlap]] = None, shots: Union[None, int, ShotRequest] = None) -> SolveResult:
     """Drop-in for ``pyqtorch.sesolve(H=..., psi0, tsave, solver, options)`` at ``backend.py:488-494``.
 
     ``problem`` is the structured Hamiltonian (``pulser_diff_amd.hamiltonian.Hamiltonian``) instead of the opaque
     callable; ``psi0`` is ``(dim, B)`` as in the reference.  ``pauli_obs``: Pauli-string observables evaluated natively; their
     values follow the diagonal ones in ``SolveResult.expect``.  ``overlap_obs``: ``StateOverlap`` observables evaluated natively
-    into ``SolveResult.overlaps``.
+    into ``SolveResult.overlaps``.  ``shots``: a ``ShotRequest`` (or an int: that many shots at the final time) filled natively and
+    returned as ``SolveResult.shots``; its indices are in the basis order of the native register (three-level registers: two qubits
+    per atom, see ``shots.indices_to_bitstrings``).
     """
     options = dict(options or {})
     spec = problem.problem_spec(solver=solver, tol=tolerance_from_options(options), store_states=store_states)
+    if shots is not None:
+        spec.shots = shots if isinstance(shots, ShotRequest) else ShotRequest(int(shots))
     psi_bd = psi0.reshape(psi0.shape[0], -1).transpose(0, 1)
     amp_tables = problem.amp_tables.real if getattr(problem, "amp_is_real", False) else problem.amp_tables
     embed = None
@@ -545,7 +583,7 @@ def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverTyp
         states = states.index_select(2, embed)
     expect, overlaps = split_expect(expect, len(overlap_obs))
     return SolveResult(states.permute(0, 2, 1) if states.numel() else states, expect,
-                       dict(spec.options.get("_last_stats", {})), overlaps)
+                       dict(spec.options.get("_last_stats", {})), overlaps, spec.shots)
 
 
 def _tangent_chunk(t: Optional[Tensor], d0: int, d1: int, shape: tuple, dtype: torch.dtype, name: str, dev) -> Optional[Tensor]:
@@ -567,6 +605,8 @@ def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsav
     of the overlaps of ``spec``, as in ``evolve``.  A direction d is the tangent of the inputs: ``d_amp[d]`` shaped like
     ``amp_tables``, ``d_det[d]`` like ``det_tables``, ``d_u[d]`` like ``u_pairs``, ``d_psi0[d]`` like ``psi0`` (B, dim); an
     input left out has tangent zero.  More than 8 directions run in chunks of 8.  No autograd graph hangs off the outputs."""
+    if spec.shots is not None:
+        raise NotImplementedError("evolve_tangent draws no measurement shots (rydiff_forward_tangent: RYDIFF_ENOTIMPL); request them from evolve")
     L = _native.lib()
     dev = psi0.device
     for t, name in ((amp_tables, "amp_tables"), (det_tables, "det_tables"), (u_pairs, "u_pairs"), (psi0, "psi0")):
