@@ -63,6 +63,8 @@ extern "C" {
 #define RYDIFF_MAX_TERMS 64
 #define RYDIFF_MAX_PAULI_STRINGS 1024 /* Pauli strings of one call, over all Pauli observables (after any frame rotation) */
 #define RYDIFF_MAX_OVERLAPS 16 /* state-overlap observables (target states) of one call */
+#define RYDIFF_MAX_RDMS 8        /* reduced density matrices of one call */
+#define RYDIFF_MAX_RDM_QUBITS 6  /* qubits of one reduced density matrix */
 
 enum { RYDIFF_OK = 0, RYDIFF_EINVAL = -1, RYDIFF_EWORKSPACE = -2, RYDIFF_EHIP = -3, RYDIFF_ENOTIMPL = -4 };
 
@@ -217,6 +219,25 @@ typedef struct RydProblem {
     const double* shot_uniforms;  /* DEVICE float64 [n_shot_times][B][n_shots], in any order */
     uint32_t* shots_out;          /* DEVICE [n_shot_times][B][n_shots]: amplitude indices */
 
+    /* REDUCED DENSITY MATRICES: the state of a subsystem A of m distinct qubits (1 <= m <= RYDIFF_MAX_RDM_QUBITS), the rest E traced out,
+     * evaluated at every tsave behind the overlap rows and differentiated by rydiff_backward:
+     *   rho_o[a][a'] = sum_e psi[idx(a, e)] conj(psi[idx(a', e)])          (= Tr_E |psi><psi|, not normalised by the library)
+     * rdm_masks[o]: the qubits of A in the convention of amp_masks (bit j = qubit j); a enumerates their settings with the
+     * lowest-numbered qubit most significant.  expect_out and grad_expect become
+     *   [n_obs + n_pauli_obs + 2 * n_overlaps + 2 * sum_o 4^{m_o}][n_tsave][B]:
+     * RDM o owns 2 * 4^{m_o} consecutive rows behind the overlap rows, entry (a, a') at offset 2 * (a * 2^m + a'), Re then Im.  All
+     * entries are written: the lower triangle is the conjugate of the upper one and Im rho[a][a] is an exact 0.  Every entry is an
+     * independent output for rydiff_backward: with G = gRe + i gIm (2^m x 2^m, the RDM's rows of grad_expect at (k, b)) the
+     * cotangent added to psi_b(t_k) is ((G + G^dagger)_A (x) 1_E) psi_b(t_k), formed per save point in the workspace buffer of the
+     * Pauli and overlap cotangents (after them) and injected through the grad_states route.  Honoured by rydiff_forward in every
+     * kernel family and with every tape mode — final_state_only, states_out == NULL without a tape — next to diagonal, Pauli and
+     * overlap observables, shots, pair terms and conditioned terms.  Not together with shard_bits > 0 and not in
+     * rydiff_forward_tangent (RYDIFF_ENOTIMPL).  RYDIFF_EINVAL: a count outside [0, RYDIFF_MAX_RDMS], an empty mask, more than
+     * RYDIFF_MAX_RDM_QUBITS bits in a mask, bits at or above N.  Cost per RDM and state: one read of the state, 8 * 2^(N+m) flops.
+     * n_rdms = 0: nothing changes.  (The fields sit in front of tape_steps and the overlap block, so the Pauli block stays the tail of the struct.) */
+    int32_t n_rdms;                 /* 0: none; at most RYDIFF_MAX_RDMS */
+    const uint32_t* rdm_masks;      /* HOST [n_rdms] */
+
     /* need_tape = 3 (PARTIAL tape) only: the number of TRAILING tsave intervals whose factor outputs are all kept in the workspace
      * tape (1 .. n_tsave - 1); the earlier intervals keep their save-point states only and are recomputed by the adjoint sweep.  The
      * caller sizes it to the HBM that is free (rydiff_plan reports the workspace for the value given): what the full tape of
@@ -310,8 +331,8 @@ int rydiff_plan(const RydProblem* p, int need_tape, int need_backward, void* scr
  *   states_out  DEVICE complex128 [n_tsave][B][2^N], or NULL (trajectory kept in the workspace tape if need_tape).
  *               With need_tape = 2 / 3 AND states_out the factor outputs go to the (granted) workspace tape and the states at the
  *               save points are copied out of it — stored states plus a later gradient without (or with less) recomputation.
- *   expect_out  DEVICE float64 [n_obs + n_pauli_obs + 2 * n_overlaps][n_tsave][B] (diagonal observables first, then the Pauli
- *               ones, then Re / Im of every overlap), or NULL
+ *   expect_out  DEVICE float64 [n_obs + n_pauli_obs + 2 * n_overlaps + 2 * sum_o 4^{m_o}][n_tsave][B] (diagonal observables first,
+ *               then the Pauli ones, then Re / Im of every overlap, then Re / Im of every reduced-density-matrix entry), or NULL
  * With RydProblem.n_shots > 0 the measurement shots of the save points in shot_times go to RydProblem.shots_out on the way. */
 int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi0, void* states_out, double* expect_out,
                    void* workspace, size_t workspace_bytes, int need_tape, void* stream);
@@ -323,7 +344,7 @@ int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi
  *   states       DEVICE: the states_out of the forward call, or NULL to use the workspace tape (with need_tape = 2 / 3 the
  *                granted workspace tape is used even when states is given)
  *   grad_states  DEVICE complex128 [n_tsave][B][2^N] or NULL
- *   grad_expect  DEVICE float64 [n_obs + n_pauli_obs + 2 * n_overlaps][n_tsave][B] or NULL
+ *   grad_expect  DEVICE float64 [n_obs + n_pauli_obs + 2 * n_overlaps + 2 * sum_o 4^{m_o}][n_tsave][B] or NULL
  *   g_amp        DEVICE complex128 [coeff_batch][n_amp_terms][n_samples] or NULL   (overwritten)
  *   g_det        DEVICE float64    [coeff_batch][n_det_terms][n_samples] or NULL   (overwritten)
  *   g_u          DEVICE float64 [N(N-1)/2] or NULL  (dist_grad, backend.py:456-460 / hamiltonian.py:341-344)

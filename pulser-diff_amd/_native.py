@@ -29,6 +29,8 @@ MAX_QUBITS = 30
 MAX_TERMS = 64
 MAX_PAULI_STRINGS = 1024
 MAX_OVERLAPS = 16
+MAX_RDMS = 8
+MAX_RDM_QUBITS = 6
 MAX_TANGENTS = 8
 MAX_SHOTS = 1 << 20  # shots per (sampled save point, trajectory)
 SHOT_NONE = 0xFFFFFFFF  # the sampled state was identically zero
@@ -73,6 +75,8 @@ class RydProblem(ctypes.Structure):
         ("shot_times", ctypes.c_void_p),
         ("shot_uniforms", ctypes.c_void_p),
         ("shots_out", ctypes.c_void_p),
+        ("n_rdms", ctypes.c_int32),
+        ("rdm_masks", ctypes.c_void_p),
         ("tape_steps", ctypes.c_int32),
         ("n_overlaps", ctypes.c_int32),
         ("overlap_batch", ctypes.c_int32),

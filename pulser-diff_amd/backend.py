@@ -34,7 +34,7 @@ from .result import SampledResult
 from .simconfig import SimConfig
 from .simresults import CoherentResults, NoisyResults, SimulationResults
 from .solver import ProblemSpec, SolverType, evolve, evolve_tangent, sesolve, tolerance_from_options
-from .observables import PauliObservable, StateOverlap
+from .observables import PauliObservable, ReducedDensityMatrix, StateOverlap
 from .shots import MAX_SHOTS, ShotRequest, indices_to_bitstrings
 from .utils import DiagonalObservable
 
@@ -261,6 +261,16 @@ class TorchEmulator:
         ``results.expect`` and ``QuantumModel.expectation``."""
         return self._hamiltonian.build_observable(operations)
 
+    def build_reduced_density_matrix(self, atom_ids) -> ReducedDensityMatrix:
+        """The ``ReducedDensityMatrix`` of the atoms ``atom_ids`` (register ids, in the order the matrix index should have), for
+        ``run(observables=[...])`` and ``results.reduced_density_matrix`` / ``results.entanglement_entropy``."""
+        index = self._hamiltonian._qid_index
+        ids = list(atom_ids)
+        missing = [q for q in ids if q not in index]
+        if missing:
+            raise ValueError(f"atom id(s) {missing} are not in the register ({list(index)})")
+        return ReducedDensityMatrix([index[q] for q in ids])
+
     def get_hamiltonian(self, time: float) -> Tensor:
         """backend.py:401-427 (explicit matrix; small registers)."""
         if time > self._tot_duration:
@@ -294,8 +304,9 @@ class TorchEmulator:
 
         ``observables`` (extension): diagonal observables (``DiagonalObservable`` or dense diagonal tensors) and sums of Pauli
         strings (``PauliObservable``, e.g. from ``build_observable``) and overlaps with target states (``StateOverlap``; read with
-        ``results.overlap``) to be evaluated natively at every evaluation time; ``store_states=False`` keeps the trajectory out of
-        the results.
+        ``results.overlap``) and states of subsystems (``ReducedDensityMatrix``, e.g. from ``build_reduced_density_matrix``; read
+        with ``results.reduced_density_matrix`` / ``results.entanglement_entropy``) to be evaluated natively at every evaluation
+        time; ``store_states=False`` keeps the trajectory out of the results.
 
         ``shots`` (extension): measurement shots drawn natively while the state is on the device — an int (that many at the final
         evaluation time) or a ``ShotRequest`` (``times="all"``: every evaluation time).  ``results.sample_state`` /
@@ -321,8 +332,15 @@ class TorchEmulator:
 
         dev = self._compute_device
         ham = self._hamiltonian
-        obs_tensors, obs_objs, pauli_objs, overlap_objs = [], [], [], []
+        obs_tensors, obs_objs, pauli_objs, overlap_objs, rdm_objs = [], [], [], [], []
         for obs in observables or []:
+            if isinstance(obs, ReducedDensityMatrix):
+                if ham.basis_name == "all":
+                    raise NotImplementedError("ReducedDensityMatrix is not available in the three-level all-basis; trace the "
+                                              "stored states instead.")
+                obs.check(ham._size)
+                rdm_objs.append(obs)
+                continue
             if isinstance(obs, StateOverlap):
                 if tuple(obs.shape) != (ham.dim ** ham._size,) * 2:
                     raise ValueError(f"StateOverlap targets of dimension {obs.shape[0]} handed to states of dimension {ham.dim ** ham._size}")
@@ -344,7 +362,8 @@ class TorchEmulator:
                     raise ValueError("Only diagonal observables can be evaluated natively; use results.expect on the states.")
                 diag = torch.diagonal(dense).real
             else:
-                raise TypeError("observables must be DiagonalObservable / PauliObservable / StateOverlap objects or diagonal (dim, dim) tensors")
+                raise TypeError("observables must be DiagonalObservable / PauliObservable / StateOverlap / ReducedDensityMatrix objects or "
+                                "diagonal (dim, dim) tensors")
             obs_tensors.append(diag.to(dev, torch.float64))
             obs_objs.append(obs)
         obs_diag = torch.stack(obs_tensors) if obs_tensors else None
@@ -367,6 +386,8 @@ class TorchEmulator:
         def run_coherent() -> CoherentResults:
             if overlap_objs and solver == SolverType.DP5_ME:
                 raise NotImplementedError("StateOverlap observables are defined on kets: not available in master-equation runs.")
+            if rdm_objs and solver == SolverType.DP5_ME:
+                raise NotImplementedError("ReducedDensityMatrix observables are defined on kets: not available in master-equation runs.")
             if shots is not None and solver == SolverType.DP5_ME:
                 raise NotImplementedError("Native measurement shots are not available in master-equation runs; "
                                           "sample_state draws from the stored density matrices.")
@@ -375,13 +396,14 @@ class TorchEmulator:
                 return CoherentResults(rho, ham._size, ham.basis_name, self._eval_times_array, self._meas_basis, meas_errors,
                                        atom_order=tuple(ham._qdict), stats=stats, density=True)
             result = sesolve(ham, psi0.to(dev), self._eval_times_array, solver=solver, options=options, obs_diag=obs_diag,
-                             store_states=store_states, pauli_obs=pauli_objs, overlap_obs=overlap_objs, shots=shots)
+                             store_states=store_states, pauli_obs=pauli_objs, overlap_obs=overlap_objs, shots=shots, rdm_obs=rdm_objs)
             states_tbd = result.states.permute(0, 2, 1) if result.states.numel() else result.states
             return CoherentResults(states_tbd, ham._size, ham.basis_name, self._eval_times_array, self._meas_basis,
                                    meas_errors, atom_order=tuple(ham._qdict),
                                    native_expect=result.expect if (obs_diag is not None or pauli_objs) else None,
                                    native_observables=obs_objs + pauli_objs, stats=result.stats,
-                                   native_overlaps=result.overlaps, overlap_observables=overlap_objs, native_shots=result.shots)
+                                   native_overlaps=result.overlaps, overlap_observables=overlap_objs, native_shots=result.shots,
+                                   native_rdms=result.rdms, rdm_observables=rdm_objs)
 
         # does the noise ask for averaging over several runs?  (backend.py:531-569)
         no_resampling = noise <= {"dephasing", "relaxation", "SPAM", "depolarizing", "eff_noise", "amplitude"} and (
@@ -400,6 +422,8 @@ class TorchEmulator:
             reps = [1] * self.config.runs
         if overlap_objs:
             raise NotImplementedError("StateOverlap observables are not available in noisy runs that average over realisations.")
+        if rdm_objs:
+            raise NotImplementedError("ReducedDensityMatrix observables are not available in noisy runs that average over realisations.")
         if shots is not None:
             raise NotImplementedError("A ShotRequest belongs to one coherent run; noisy runs that average over realisations return "
                                       "their measurements as NoisyResults (native_shots=True draws them natively).")
@@ -464,6 +488,9 @@ class TorchEmulator:
         observables = list(observables)
         full = ham.dim ** ham._size
         for obs in observables:
+            if isinstance(obs, ReducedDensityMatrix):
+                raise NotImplementedError("run_sensitivities does not take ReducedDensityMatrix observables (the tangent sweep "
+                                          "evaluates none); differentiate results.reduced_density_matrix through run().")
             if not isinstance(obs, (DiagonalObservable, PauliObservable)) and not (isinstance(obs, Tensor) and obs.ndim == 2):
                 raise TypeError("observables must be DiagonalObservable / PauliObservable objects or diagonal (dim, dim) tensors")
             if tuple(obs.shape) != (full, full):

@@ -85,6 +85,10 @@ struct Plan {
     size_t off_pauli = 0, off_pauli_traj = 0, off_pauli_cot = 0;  // (the trajectory and the cotangent buffer serve the overlaps too)
     // state-overlap observables (overlap_kernels.hpp): targets stay where the caller has them
     int n_ov = 0, ov_batch = 1;
+    // reduced density matrices (rdm_kernels.hpp): subsystem masks over amplitude-index bits, qubits, first row (behind the overlap rows)
+    int n_rdm = 0, rdm_rows = 0;
+    uint32_t rdm_am[RYDIFF_MAX_RDMS] = {0};
+    int rdm_m[RYDIFF_MAX_RDMS] = {0}, rdm_row[RYDIFF_MAX_RDMS] = {0};
     // measurement shots (shots_kernels.hpp): the sampled save points; scratch = chunk sums and their prefix, [B][shot_chunks()] doubles each
     int n_shots = 0;
     std::vector<int32_t> shot_times;
@@ -252,6 +256,54 @@ inline bool build_overlaps(const RydProblem* p, Plan& pl, std::string& err) {
     return true;
 }
 
+// RydProblem.n_rdms / rdm_masks: count, every mask non-empty, at most RYDIFF_MAX_RDM_QUBITS qubits, all inside the register
+inline bool build_rdms(const RydProblem* p, Plan& pl, std::string& err) {
+    pl.n_rdm = pl.rdm_rows = 0;
+    if (p->n_rdms < 0 || p->n_rdms > RYDIFF_MAX_RDMS) {
+        err = "n_rdms must be in [0, " + std::to_string(RYDIFF_MAX_RDMS) + "]";
+        return false;
+    }
+    if (p->n_rdms == 0) return true;
+    if (!p->rdm_masks) {
+        err = "missing rdm_masks";
+        return false;
+    }
+    int rows = 0;
+    for (int o = 0; o < p->n_rdms; ++o) {
+        const uint32_t qm = p->rdm_masks[o];
+        int m = 0;
+        uint32_t am = 0;
+        for (int j = 0; j < 32; ++j)
+            if (qm >> j & 1u) {
+                if (j >= p->n_qubits) {
+                    err = "rdm_masks[" + std::to_string(o) + "] addresses a qubit outside the register";
+                    return false;
+                }
+                am |= 1u << (p->n_qubits - 1 - j);
+                ++m;
+            }
+        if (m == 0) {
+            err = "rdm_masks[" + std::to_string(o) + "] is empty";
+            return false;
+        }
+        if (m > RYDIFF_MAX_RDM_QUBITS) {
+            err = "rdm_masks[" + std::to_string(o) + "] holds more than " + std::to_string(RYDIFF_MAX_RDM_QUBITS) + " qubits";
+            return false;
+        }
+        pl.rdm_am[o] = am;
+        pl.rdm_m[o] = m;
+        pl.rdm_row[o] = rows;
+        rows += 2 << (2 * m);
+    }
+    if (p->shard_bits > 0) {
+        err = "reduced density matrices: not implemented together with state sharding";
+        return false;
+    }
+    pl.n_rdm = p->n_rdms;
+    pl.rdm_rows = rows;
+    return true;
+}
+
 // RydProblem.n_shots / shot_*: counts against the caps, pointers, the list of sampled save points
 inline bool build_shots(const RydProblem* p, Plan& pl, std::string& err) {
     pl.n_shots = 0;
@@ -366,6 +418,7 @@ inline bool build_plan(const RydProblem* p, Plan& pl, std::string& err, double w
     pl.N = p->n_qubits;
     if (!build_pauli(p, pl, err)) return false;
     if (!build_overlaps(p, pl, err)) return false;
+    if (!build_rdms(p, pl, err)) return false;
     if (!build_shots(p, pl, err)) return false;
     pl.shard_bits = p->shard_bits;
     if (pl.shard_bits < 0 || pl.shard_bits > 6 || pl.shard_bits >= pl.N) {
@@ -582,7 +635,7 @@ inline size_t carve(Plan& pl, int tape_mode, bool need_backward, int chain_slots
     pl.off_pauli = take(pl.pauli_bytes());
     // one-launch sweeps: the trajectory the Pauli and overlap observables are evaluated on (and the shots drawn from) where the
     // caller keeps none
-    pl.off_pauli_traj = take(((pl.n_pobs || pl.n_ov || pl.n_shots) && pl.N <= 12) ? size_t(pl.T + 1) * pl.state_bytes : 0);
+    pl.off_pauli_traj = take(((pl.n_pobs || pl.n_ov || pl.n_rdm || pl.n_shots) && pl.N <= 12) ? size_t(pl.T + 1) * pl.state_bytes : 0);
     pl.off_shot_sums = take(pl.n_shots ? size_t(pl.B) * pl.shot_chunks() * sizeof(double) : 0);
     pl.off_shot_prefix = take(pl.n_shots ? size_t(pl.B) * pl.shot_chunks() * sizeof(double) : 0);
     pl.total_fwd = off;
@@ -597,7 +650,7 @@ inline size_t carve(Plan& pl, int tape_mode, bool need_backward, int chain_slots
         pl.off_wtot = take(pl.dim * (pl.shard_bits ? size_t(pl.B) : 1) * sizeof(double));  // sharded: one weight slab per rank of the call
         // observable cotangent grad_states[k] + 2 sum_o g_o O_o psi_k + sum_o (gRe + i gIm)_o phi_o: one state, reused in stream order
         // (one-launch adjoints: every k)
-        pl.off_pauli_cot = take((pl.n_pobs || pl.n_ov) ? size_t(pl.N <= 12 ? pl.T + 1 : 1) * pl.state_bytes : 0);
+        pl.off_pauli_cot = take((pl.n_pobs || pl.n_ov || pl.n_rdm) ? size_t(pl.N <= 12 ? pl.T + 1 : 1) * pl.state_bytes : 0);
         pl.off_meta2 = take(std::max(E * 40, size_t(pl.T + 1) * sizeof(int32_t)));  // StageBwdDev records, or the save-point flags of the one-launch adjoint
     }
     return off;

@@ -529,7 +529,7 @@ void shard_groups(const Plan& pl, int (&grp)[kShardMaxBits]) {
 // Cotangents of the Pauli-string and state-overlap observables: they ride the grad_states route — k_pauli_apply (pauli_launch.hpp)
 // writes grad_states[k] + 2 sum_o g_o O_o psi_k into a workspace buffer, k_overlap_apply (overlap_launch.hpp) adds
 // sum_o (gRe + i gIm)_o phi_o to it (or to grad_states[k] where no Pauli observable has a cotangent), and the injecting launch reads
-// that buffer instead of grad_states[k]
+// that buffer instead of grad_states[k]; k_rdm_apply (rdm_launch.hpp) adds sum_o ((G + G^dagger)_{A_o} (x) 1) psi_k the same way
 struct PauliInject {
     const Runtime* rt = nullptr;
     char* ws = nullptr;
@@ -538,6 +538,7 @@ struct PauliInject {
     const double* gexp = nullptr;     // &grad_expect[n_obs][0][0], or nullptr: no Pauli observables
     const double* ov_gexp = nullptr;  // &grad_expect[n_obs + n_pobs][0][0], or nullptr: no overlaps
     const double2* ov_targets = nullptr;
+    const double* rdm_gexp = nullptr; // &grad_expect[n_obs + n_pobs + 2 n_ov][0][0], or nullptr: no reduced density matrices
     double2* buf = nullptr;           // one state (one-launch adjoints: n_tsave states)
     std::function<const double2*(int)> state_at;  // the state at save point k
 };
@@ -621,6 +622,7 @@ struct ForwardCtx : SweepCtx {
     bool want_exp = false;
     double* pauli_out = nullptr;   // &expect_out[n_obs][0][0] where Pauli observables are evaluated
     double* overlap_out = nullptr; // &expect_out[n_obs + n_pobs][0][0] where overlaps are evaluated
+    double* rdm_out = nullptr;     // &expect_out[n_obs + n_pobs + 2 n_ov][0][0] where reduced density matrices are evaluated
     const double* shot_u = nullptr;  // RydProblem.shot_uniforms / shots_out where shots are drawn (rydiff_forward with n_shots > 0)
     uint32_t* shots_out = nullptr;
 };

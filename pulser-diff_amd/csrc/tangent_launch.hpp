@@ -16,6 +16,7 @@ int tangent_validate(const RydProblem* p, const RydPlanInfo* info, int n_dir) {
     if (p->amp_conditioned_terms || p->det_ones_terms)
         return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented with conditioned flips / ones-counting terms (three-level registers)");
     if (p->n_shots > 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: measurement shots are not implemented (n_shots > 0): draw them in rydiff_forward");
+    if (p->n_rdms > 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: reduced density matrices are not implemented (n_rdms > 0)");
     return RYDIFF_OK;
 }
 

@@ -21,7 +21,7 @@ from .backend import TorchEmulator
 from .simconfig import SimConfig
 from .simresults import SimulationResults
 from .solver import SolverType
-from .observables import PauliObservable, StateOverlap
+from .observables import PauliObservable, ReducedDensityMatrix, StateOverlap
 from .utils import DiagonalObservable, total_magnetization, total_magnetization_diag
 from .waveform_funcs import constant_waveform
 
@@ -195,3 +195,10 @@ class QuantumModel(Module):
         obs = target if isinstance(target, StateOverlap) else StateOverlap(target)
         evaluation_times, results = self._run(observables=[obs], store_states=False)
         return evaluation_times, results.overlap(obs)
+
+    def reduced_density_matrix(self, qubits) -> tuple[Tensor, Tensor]:
+        """Evaluation times and the state of the subsystem ``qubits`` (indices in register order, or a ``ReducedDensityMatrix``),
+        complex ``(n_t, B, 2^m, 2^m)``, evaluated and differentiated natively: no trajectory is stored or handed to autograd."""
+        obs = qubits if isinstance(qubits, ReducedDensityMatrix) else ReducedDensityMatrix(qubits)
+        evaluation_times, results = self._run(observables=[obs], store_states=False)
+        return evaluation_times, results.reduced_density_matrix(obs)

@@ -19,6 +19,8 @@ from torch import Tensor
 
 MAX_PAULI_STRINGS = 1024  # RYDIFF_MAX_PAULI_STRINGS
 MAX_OVERLAPS = 16  # RYDIFF_MAX_OVERLAPS
+MAX_RDMS = 8  # RYDIFF_MAX_RDMS
+MAX_RDM_QUBITS = 6  # RYDIFF_MAX_RDM_QUBITS
 MAX_DENSE_QUBITS = 14
 _I_POW = (1.0, 1j, -1.0, -1j)
 
@@ -286,3 +288,94 @@ def pack_overlaps(observables: Sequence[StateOverlap], dim: int, batch: int, dev
     bt = max(o.batch for o in observables)
     rows = [o.targets.to(device).transpose(0, 1).expand(bt, dim) for o in observables]
     return torch.stack(rows).contiguous()
+
+
+class ReducedDensityMatrix:
+    """The state of a subsystem, ``rho_A[a][a'] = sum_e psi[idx(a, e)] conj(psi[idx(a', e)])`` (``Tr_E |psi><psi|``, not normalised),
+    for ``A`` = ``qubits``: 1 to 6 distinct qubit indices in any order; evaluated and differentiated natively at every evaluation time
+    (``include/rydiff.h``: ``RydProblem.n_rdms / rdm_masks``; ``csrc/rdm_kernels.hpp``), no stored trajectory.
+
+    The matrix index ``a`` enumerates the settings of ``qubits`` with the FIRST listed qubit most significant, in the basis order of
+    the register (r = 0, g = 1).  The library works in ascending qubit order; other orders are a permutation of the small matrix,
+    applied in torch.  Read the values with ``results.reduced_density_matrix`` / ``SolveResult.rdms``: complex ``(n_t, B, 2^m, 2^m)``."""
+
+    def __init__(self, qubits):
+        qs = tuple(int(q) for q in qubits)
+        if not 1 <= len(qs) <= MAX_RDM_QUBITS:
+            raise ValueError(f"a reduced density matrix takes 1 to {MAX_RDM_QUBITS} qubits, got {len(qs)}")
+        if len(set(qs)) != len(qs):
+            raise ValueError(f"the qubits of a reduced density matrix must be distinct, got {qs}")
+        if min(qs) < 0:
+            raise ValueError(f"negative qubit index in {qs}")
+        self.qubits = qs
+
+    @property
+    def n_sub(self) -> int:
+        return len(self.qubits)
+
+    @property
+    def shape(self) -> tuple:
+        return (2 ** self.n_sub, 2 ** self.n_sub)
+
+    @property
+    def is_sparse(self) -> bool:
+        return False
+
+    @property
+    def mask(self) -> int:
+        """Bit j = qubit j, the convention of ``amp_masks``."""
+        return sum(1 << q for q in self.qubits)
+
+    def check(self, n_qubits: int) -> None:
+        if max(self.qubits) >= n_qubits:
+            raise ValueError(f"qubit {max(self.qubits)} is outside the register of {n_qubits} qubits")
+
+    def native_index(self) -> Tensor:
+        """``perm`` with ``rho_user = rho_native[perm][:, perm]``: for every index in the order of ``qubits`` the index in ascending
+        qubit order (lowest-numbered qubit most significant), which is how the library lays the matrix out."""
+        m = self.n_sub
+        rank = {q: i for i, q in enumerate(sorted(self.qubits))}  # position in ascending order, 0 = most significant
+        perm = torch.zeros(2 ** m, dtype=torch.long)
+        for au in range(2 ** m):
+            an = 0
+            for i, q in enumerate(self.qubits):
+                if au >> (m - 1 - i) & 1:
+                    an |= 1 << (m - 1 - rank[q])
+            perm[au] = an
+        return perm
+
+
+def reduced_density_matrix(obs: ReducedDensityMatrix, states: Tensor) -> Tensor:
+    """The torch route on stored kets ``(n_t, dim, B)``: complex ``(n_t, B, 2^m, 2^m)``, differentiable."""
+    if not isinstance(obs, ReducedDensityMatrix):
+        raise TypeError(f"expected a ReducedDensityMatrix, got {type(obs)}")
+    if states.is_sparse:
+        states = states.to_dense()
+    if states.ndim == 4:
+        raise NotImplementedError("ReducedDensityMatrix is defined on kets; density matrices (master-equation runs) are not supported")
+    if states.ndim != 3:
+        raise ValueError(f"expected kets (n_t, dim, B), got {tuple(states.shape)}")
+    n_t, dim, batch = states.shape
+    n = dim.bit_length() - 1
+    if dim != 1 << n:
+        raise ValueError(f"ReducedDensityMatrix needs a register of qubits (dim a power of two), got dim {dim}")
+    obs.check(n)
+    m = obs.n_sub
+    rest = [q for q in range(n) if q not in obs.qubits]
+    st = states.to(torch.complex128).reshape((n_t,) + (2,) * n + (batch,))
+    st = st.permute([0] + [1 + q for q in obs.qubits] + [1 + q for q in rest] + [n + 1]).reshape(n_t, 2 ** m, 2 ** (n - m), batch)
+    return torch.einsum("taeb,tceb->tbac", st, st.conj())
+
+
+def pack_rdms(observables: Sequence[ReducedDensityMatrix], n_qubits: int) -> np.ndarray:
+    """The uint32 masks of ``RydProblem.rdm_masks`` (``ProblemSpec.rdms``)."""
+    observables = list(observables)
+    if not observables:
+        raise ValueError("no ReducedDensityMatrix to pack")
+    if len(observables) > MAX_RDMS:
+        raise ValueError(f"too many reduced density matrices: {len(observables)} (at most {MAX_RDMS} per call)")
+    for o in observables:
+        if not isinstance(o, ReducedDensityMatrix):
+            raise TypeError(f"expected ReducedDensityMatrix objects, got {type(o)}")
+        o.check(n_qubits)
+    return np.asarray([o.mask for o in observables], dtype=np.uint32)

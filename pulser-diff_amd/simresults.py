@@ -19,9 +19,9 @@ import torch
 from torch import Tensor
 
 from .result import SampledResult, TorchResult
-from .observables import PauliObservable, StateOverlap, overlap_states
+from .observables import PauliObservable, ReducedDensityMatrix, StateOverlap, overlap_states, reduced_density_matrix
 from .shots import ShotRequest, bitstring_counts, indices_to_bitstrings
-from .utils import DiagonalObservable, expect
+from .utils import DiagonalObservable, expect, von_neumann_entropy
 
 
 class SimulationResults(ABC):
@@ -57,7 +57,8 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
                  meas_errors: Optional[Mapping[str, float]] = None, atom_order: tuple = (),
                  native_expect: Optional[Tensor] = None, native_observables: Optional[list] = None,
                  stats: Optional[dict] = None, density: bool = False, native_overlaps: Optional[Tensor] = None,
-                 overlap_observables: Optional[list] = None, native_shots: Optional[ShotRequest] = None) -> None:
+                 overlap_observables: Optional[list] = None, native_shots: Optional[ShotRequest] = None,
+                 native_rdms: Optional[list] = None, rdm_observables: Optional[list] = None) -> None:
         super().__init__(size, basis_name, sim_times)
         if self._basis_name == "all":  # simresults.py:381-383
             if meas_basis not in {"ground-rydberg", "digital"}:
@@ -75,6 +76,8 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
         self._native_observables = list(native_observables or [])
         self._native_overlaps = native_overlaps  # complex (n_ov, n_t, B)
         self._overlap_observables = list(overlap_observables or [])
+        self._native_rdms = native_rdms  # per observable: complex (n_t, B, 2^m, 2^m)
+        self._rdm_observables = list(rdm_observables or [])
         self._native_shots = native_shots  # filled by the solver: amplitude indices (n_shot_times, B, n_shots)
         self.solver_stats = dict(stats or {})
 
@@ -139,6 +142,25 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
         if hit and self._native_overlaps is not None:
             return self._native_overlaps[hit[0]]
         return overlap_states(obs, self.states)
+
+    def reduced_density_matrix(self, obs: ReducedDensityMatrix) -> Tensor:
+        """``Tr_E |psi_b(t_k)><psi_b(t_k)|`` on the qubits of ``obs``, complex ``(n_t, B, 2^m, 2^m)``: the native values when ``obs``
+        was handed to ``run(observables=...)``, else computed from the stored states."""
+        if not isinstance(obs, ReducedDensityMatrix):
+            raise TypeError(f"reduced_density_matrix takes a ReducedDensityMatrix, got {type(obs)}")
+        if self._density:
+            raise NotImplementedError("ReducedDensityMatrix is defined on kets; this is a master-equation run.")
+        if self._basis_name == "all":
+            raise NotImplementedError("ReducedDensityMatrix is not available in the three-level all-basis.")
+        hit = [k for k, o in enumerate(self._rdm_observables) if o is obs]
+        if hit and self._native_rdms is not None:
+            return self._native_rdms[hit[0]]
+        return reduced_density_matrix(obs, self.states)
+
+    def entanglement_entropy(self, obs: ReducedDensityMatrix, base: float = 2) -> Tensor:
+        """Von Neumann entropy of the subsystem of ``obs`` at every evaluation time, real ``(n_t, B)`` (``base=2``: bits); for a pure
+        register state the entanglement entropy between the subsystem and the rest."""
+        return von_neumann_entropy(self.reduced_density_matrix(obs), base)
 
     def sample_state(self, t: float, n_samples: int = 1000, t_tol: float = 1.0e-3) -> Counter:
         """simresults.py:497-540: ideal samples, then the detection errors of the SPAM model (a measured 0 flips with

@@ -20,7 +20,7 @@ import torch
 from torch import Tensor
 
 from . import _native
-from .observables import PauliObservable, StateOverlap, check_pauli, pack_overlaps, pack_pauli
+from .observables import PauliObservable, ReducedDensityMatrix, StateOverlap, check_pauli, pack_overlaps, pack_pauli, pack_rdms
 from .shots import ShotRequest
 
 
@@ -72,6 +72,9 @@ class ProblemSpec:
     # state-overlap observables (RydProblem.overlap_*): the packed targets, a complex128 DEVICE tensor (n_ov, 1 | B, 2^N)
     # (observables.pack_overlaps); Re / Im of every overlap follow the Pauli rows in `expect`.  Constants: no gradient.
     overlaps: Optional[Tensor] = None
+    # reduced density matrices (RydProblem.n_rdms / rdm_masks): a list of ReducedDensityMatrix, or the packed uint32 qubit masks
+    # (observables.pack_rdms); Re / Im of every entry follow the overlap rows in `expect` (split_observables takes them out)
+    rdms: Optional[Any] = None
     # measurement shots drawn natively at chosen save points (RydProblem.n_shots / shot_*): the request object receives the amplitude
     # indices (shots.ShotRequest.indices); a non-differentiable by-product, allowed next to a gradient
     shots: Optional[ShotRequest] = None
@@ -79,6 +82,26 @@ class ProblemSpec:
     @property
     def n_overlaps(self) -> int:
         return 0 if self.overlaps is None else int(self.overlaps.shape[0])
+
+    def packed_rdms(self) -> Optional[np.ndarray]:
+        """The host array of RydProblem.rdm_masks (None: no reduced density matrices); validated like the library does."""
+        if self.rdms is None:
+            return None
+        rdms = list(self.rdms)
+        if rdms and all(isinstance(o, ReducedDensityMatrix) for o in rdms):
+            return pack_rdms(rdms, self.n_qubits)
+        masks = [int(v) for v in rdms]
+        if not 1 <= len(masks) <= _native.MAX_RDMS:
+            raise ValueError(f"ProblemSpec.rdms: 1 to {_native.MAX_RDMS} reduced density matrices per call, got {len(masks)}")
+        for v in masks:
+            if v <= 0 or v >> self.n_qubits or bin(v).count("1") > _native.MAX_RDM_QUBITS:
+                raise ValueError(f"ProblemSpec.rdms: mask {v:#x} must name 1 to {_native.MAX_RDM_QUBITS} qubits below {self.n_qubits}")
+        return np.asarray(masks, dtype=np.uint32)
+
+    def rdm_rows(self) -> int:
+        """Rows of `expect` the reduced density matrices take: 2 * sum_o 4^{m_o}."""
+        masks = self.packed_rdms()
+        return 0 if masks is None else sum(2 * 4 ** bin(int(v)).count("1") for v in masks)
 
     def packed_pauli(self):
         """The four host arrays of RydProblem.pauli_* (None: no Pauli observables)."""
@@ -191,6 +214,10 @@ class _Call:
             p.n_overlaps = self.overlaps.shape[0]
             p.overlap_batch = self.overlaps.shape[1]
             p.overlap_targets = self.overlaps.data_ptr()
+        self.rdm_masks = spec.packed_rdms()
+        if self.rdm_masks is not None:
+            p.n_rdms = len(self.rdm_masks)
+            p.rdm_masks = self.rdm_masks.ctypes.data
         self.problem = p
         self.shot_buffers = None
 
@@ -249,6 +276,7 @@ def _check_shapes(spec: ProblemSpec, amp: Tensor, det: Tensor, u_pairs: Tensor, 
         raise ValueError(f"obs_diag must have shape (n_obs, {2 ** nq}), got {tuple(obs.shape)}")
     spec.packed_pauli()  # raises ValueError on a mask bit at or above N, inconsistent counts, too many strings
     _check_overlaps(spec, batch, device)
+    spec.packed_rdms()  # raises ValueError on an empty mask, too many qubits, a bit at or above N, too many matrices
     if batch > 65535:
         raise ValueError("batch must be <= 65535 (split the columns / trajectories into several calls)")
 
@@ -391,8 +419,8 @@ class _RydbergEvolve(torch.autograd.Function):
                         raise
             states = (torch.empty((n_t, batch, dim), dtype=torch.complex128, device=dev) if spec.store_states
                       else torch.empty((0, batch, dim), dtype=torch.complex128, device=dev))
-            # diagonal observables first, then the Pauli ones, then Re / Im of every overlap
-            n_obs = call.problem.n_obs + call.problem.n_pauli_obs + 2 * call.problem.n_overlaps
+            # diagonal observables first, then the Pauli ones, then Re / Im of every overlap, then Re / Im of every RDM entry
+            n_obs = call.problem.n_obs + call.problem.n_pauli_obs + 2 * call.problem.n_overlaps + spec.rdm_rows()
             expect = torch.empty((n_obs, n_t, batch), dtype=torch.float64, device=dev)
             _native.check(L.rydiff_forward(ctypes.byref(call.problem), ctypes.byref(info), _ptr(psi_c),
                                            _ptr(states) if spec.store_states else None,
@@ -490,6 +518,7 @@ class SolveResult:
     stats: dict
     overlaps: Optional[Tensor] = None  # complex (n_ov, n_t, B): <phi_o,b | psi_b(t_k)> evaluated natively (differentiable), or None
     shots: Optional[ShotRequest] = None  # the request handed to sesolve(shots=...), holding the native shots (.indices)
+    rdms: Optional[list] = None  # per ReducedDensityMatrix: complex (n_t, B, 2^m, 2^m), evaluated natively (differentiable), or None
 
 
 def split_expect(expect: Tensor, n_overlaps: int) -> tuple[Tensor, Optional[Tensor]]:
@@ -499,6 +528,37 @@ def split_expect(expect: Tensor, n_overlaps: int) -> tuple[Tensor, Optional[Tens
     n_real = expect.shape[0] - 2 * n_overlaps
     pairs = expect[n_real:].reshape(n_overlaps, 2, *expect.shape[1:])
     return expect[:n_real], torch.complex(pairs[:, 0], pairs[:, 1])
+
+
+def split_observables(expect: Tensor, n_overlaps: int, rdms=None) -> tuple[Tensor, Optional[Tensor], Optional[list]]:
+    """``split_expect`` that also takes the reduced-density-matrix rows out: `expect` of ``evolve`` -> (diagonal and Pauli rows,
+    complex overlaps (n_ov, n_t, B) or None, one complex (n_t, B, 2^m, 2^m) per entry of ``rdms`` or None).  ``rdms``: what
+    ``ProblemSpec.rdms`` held — ``ReducedDensityMatrix`` objects (the matrices come back in the order of their ``qubits``) or integer
+    masks (ascending qubit order, the library's)."""
+    rdms = list(rdms or [])
+    if not rdms:
+        return split_expect(expect, n_overlaps) + (None,)
+    ms = [o.n_sub if isinstance(o, ReducedDensityMatrix) else bin(int(o)).count("1") for o in rdms]
+    first = expect.shape[0] - sum(2 * 4 ** m for m in ms)
+    out = []
+    for o, m in zip(rdms, ms):
+        d = 2 ** m
+        rows = expect[first:first + 2 * d * d].reshape(d, d, 2, *expect.shape[1:])  # (a, a', Re | Im, n_t, B)
+        rho = torch.complex(rows[:, :, 0], rows[:, :, 1]).permute(2, 3, 0, 1)
+        if isinstance(o, ReducedDensityMatrix):
+            perm = o.native_index().to(rho.device)
+            rho = rho.index_select(2, perm).index_select(3, perm)
+        out.append(rho)
+        first += 2 * d * d
+    real, ov = split_expect(expect[:expect.shape[0] - sum(2 * 4 ** m for m in ms)], n_overlaps)
+    return real, ov, out
+
+
+def frame_factor(n_sub: int, phi: float) -> Tensor:
+    """``exp(-i phi (ones(a) - ones(a')))``, ``(2^m, 2^m)``: takes a reduced density matrix of the state ``V psi`` in the frame that
+    rotates with a constant drive phase ``phi`` (``V = exp(i phi * number of ones)``) back to the lab frame."""
+    ones = torch.tensor([bin(a).count("1") for a in range(2 ** n_sub)], dtype=torch.float64)
+    return torch.exp(-1j * phi * (ones[:, None] - ones[None, :]))
 
 
 def evolve(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Tensor,
@@ -512,7 +572,8 @@ def evolve(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsave: Tenso
 def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverType.DP5_SE,
             options: Optional[dict] = None, obs_diag: Optional[Tensor] = None, store_states: bool = True,
             pauli_obs: Optional[Sequence[PauliObservable]] = None,
-            overlap_obs: Optional[Sequence[StateOverlap]] = None, shots: Union[None, int, ShotRequest] = None) -> SolveResult:
+            overlap_obs: Optional[Sequence[StateOverlap]] = None, shots: Union[None, int, ShotRequest] = None,
+            rdm_obs: Optional[Sequence[ReducedDensityMatrix]] = None) -> SolveResult:
     """Drop-in for ``pyqtorch.sesolve(H=..., psi0, tsave, solver, options)`` at ``backend.py:488-494``.
 
     ``problem`` is the structured Hamiltonian (``pulser_diff_amd.hamiltonian.Hamiltonian``) instead of the opaque
@@ -520,7 +581,8 @@ def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverTyp
     values follow the diagonal ones in ``SolveResult.expect``.  ``overlap_obs``: ``StateOverlap`` observables evaluated natively
     into ``SolveResult.overlaps``.  ``shots``: a ``ShotRequest`` (or an int: that many shots at the final time) filled natively and
     returned as ``SolveResult.shots``; its indices are in the basis order of the native register (three-level registers: two qubits
-    per atom, see ``shots.indices_to_bitstrings``).
+    per atom, see ``shots.indices_to_bitstrings``).  ``rdm_obs``: ``ReducedDensityMatrix`` observables evaluated natively into
+    ``SolveResult.rdms`` (lab frame, the order of their ``qubits``).
     """
     options = dict(options or {})
     spec = problem.problem_spec(solver=solver, tol=tolerance_from_options(options), store_states=store_states)
@@ -546,6 +608,12 @@ def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverTyp
         if embed is not None:
             targets = torch.zeros(*targets.shape[:2], 1 << spec.n_qubits, dtype=targets.dtype,
                                   device=targets.device).index_copy(2, embed, targets)
+    rdm_obs = list(rdm_obs or [])
+    if rdm_obs:
+        if embed is not None:
+            raise NotImplementedError("ReducedDensityMatrix is not available in the three-level all-basis (an atom is two qubits "
+                                      "there); trace the stored states instead.")
+        spec.rdms = rdm_obs
     pauli_obs = list(pauli_obs or [])
     if pauli_obs and embed is not None:
         raise NotImplementedError("Pauli observables are not available in the three-level all-basis; use results.expect on stored states.")
@@ -581,9 +649,12 @@ def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverTyp
         states = states * rot.conj()[None, None, :]
     if embed is not None and states.numel():
         states = states.index_select(2, embed)
-    expect, overlaps = split_expect(expect, len(overlap_obs))
+    expect, overlaps, rdms = split_observables(expect, len(overlap_obs), rdm_obs)
+    if rdms is not None and rot is not None:
+        # the library saw V psi: rho_lab[a][a'] = rho[a][a'] exp(-i phi (ones(a) - ones(a'))), on the small matrix (differentiable)
+        rdms = [r * frame_factor(o.n_sub, float(phi)).to(r.device) for o, r in zip(rdm_obs, rdms)]
     return SolveResult(states.permute(0, 2, 1) if states.numel() else states, expect,
-                       dict(spec.options.get("_last_stats", {})), overlaps, spec.shots)
+                       dict(spec.options.get("_last_stats", {})), overlaps, spec.shots, rdms)
 
 
 def _tangent_chunk(t: Optional[Tensor], d0: int, d1: int, shape: tuple, dtype: torch.dtype, name: str, dev) -> Optional[Tensor]:
@@ -605,6 +676,9 @@ def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsav
     of the overlaps of ``spec``, as in ``evolve``.  A direction d is the tangent of the inputs: ``d_amp[d]`` shaped like
     ``amp_tables``, ``d_det[d]`` like ``det_tables``, ``d_u[d]`` like ``u_pairs``, ``d_psi0[d]`` like ``psi0`` (B, dim); an
     input left out has tangent zero.  More than 8 directions run in chunks of 8.  No autograd graph hangs off the outputs."""
+    if spec.rdms is not None:
+        raise NotImplementedError("evolve_tangent evaluates no reduced density matrices (rydiff_forward_tangent: RYDIFF_ENOTIMPL); "
+                                  "request them from evolve")
     if spec.shots is not None:
         raise NotImplementedError("evolve_tangent draws no measurement shots (rydiff_forward_tangent: RYDIFF_ENOTIMPL); request them from evolve")
     L = _native.lib()

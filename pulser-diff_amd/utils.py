@@ -8,6 +8,7 @@ N ~ 14.
 from __future__ import annotations
 
 from functools import lru_cache, reduce
+import math
 from math import pi, prod, sin
 
 import torch
@@ -170,3 +171,17 @@ def freeze_gc() -> None:
     gc.collect()
     gc.freeze()
 
+
+
+def purity(rho: Tensor) -> Tensor:
+    """``Re tr rho^2`` of density matrices ``(..., d, d)``: 1 for a pure state, 1/d for the maximally mixed one.  Smooth everywhere —
+    the entanglement loss to recommend for gradient-based optimisation."""
+    return torch.einsum("...ij,...ji->...", rho, rho).real
+
+
+def von_neumann_entropy(rho: Tensor, base: float = 2) -> Tensor:
+    """``-tr rho log rho`` of Hermitian density matrices ``(..., d, d)`` from ``eigvalsh``, eigenvalues clamped at 0 before ``x log x``
+    (``base=2``: bits).  Differentiable, but the gradient is undefined at degenerate spectra (``eigvalsh``) and unbounded at zero
+    eigenvalues (pure states, product states); optimise ``purity`` instead."""
+    ev = torch.linalg.eigvalsh(0.5 * (rho + rho.mH)).clamp_min(0.0)
+    return -torch.special.xlogy(ev, ev).sum(dim=-1) / math.log(base)
