@@ -132,6 +132,8 @@ typedef struct RydProblem {
      *     tape, adjoint with real_amp_grad (automatic: one 20-qubit trajectory)
      *  18 automatic, but one factor per launch (k_chain) everywhere
      *  19 automatic, but one factor per adjoint launch (forward blocks as automatic)
+     *  20 / 21 as 17, with the adjoint block kernel's tape vectors staged through registers / by LDS-DMA (DESIGN.md section 3;
+     *     17 and automatic take the one that measured faster)
      * "automatic" takes the one-launch sweeps up to 12 qubits, the direct kernels while few tiles are in flight
      * (B * 2^N <= 2^18, with gradients 2^19) and the chained passes beyond.  Results do not depend on the variant beyond rounding. */
     int32_t kernel_variant;

@@ -196,6 +196,9 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2(Chain2Args a) {
 // are kept; x_b and t are requested then.  x_b is consumed (factor b's weights, the wtot atomics, the (w + s) part of
 // <P mu_mid, x_b>, mu_out but its tp part) before round B, and t lands during it: t is only needed as tp.  Cotangent injection
 // at a save point (the state there is x_b) as in k_chain; then the next block starts on mu_out: 5R + 3W per two factors.
+// Nothing after the mu_out stores waits on the vector-memory counter: the diagonal of the layout is formed once and kept for the
+// start stage, both stages' coefficients are fetched at the top, and every request of the top is retired before the has_p branch,
+// so the start stage's rounds run while the mu_out stores drain (they used to wait for their acknowledgement).
 struct Chain2BwdArgs {
     const double2* mu;  // complete cotangent at the output of the block being finished (the start vector for the first launch)
     const double2* w;   // P_X mu                              (unused when !has_p)
@@ -233,11 +236,35 @@ struct Chain2BwdArgs {
     long inj_ostride;
 };
 
-template <int LT, int LGT>
+// 16 bytes per lane from global memory straight into LDS (global_load_lds_dwordx4, streaming policy as stream_load): no VGPR
+// destination.  `lds_wave` is the wave's destination base (wave-uniform); lane l lands at lds_wave + l.  Counted on vmcnt.
+__device__ __forceinline__ void stream_load_lds(const double2* g, double2* lds_wave) {
+    __builtin_amdgcn_global_load_lds(reinterpret_cast<const __attribute__((address_space(1))) void*>(reinterpret_cast<uintptr_t>(g)),
+                                     (__attribute__((address_space(3))) void*)lds_wave, 16, 0, /* nt */ 2);
+}
+
+constexpr int kChain2BwdXbLds = 1;  // elements of x_b per thread that the DMA instantiation stages in LDS (the rest: registers)
+
+// bytes of dynamic LDS: two tile buffers, [2][waves] parked partials, and (DMA) the staging area of x_b
+template <int LT, int LGT, bool DMA>
+constexpr size_t chain2_bwd_lds_bytes() {
+    return 2 * (size_t(1) << LT) * sizeof(double2) + 2 * ((size_t(1) << LGT) / 64) * sizeof(double) +
+           (DMA ? size_t(kChain2BwdXbLds) * (size_t(1) << LGT) * sizeof(double2) : 0);
+}
+
+// DMA: the tape vectors are requested at the top of the kernel with mu and w.  They never take part in a partner sum (a thread
+// needs its own elements only), so x_a goes by LDS-DMA straight into this thread's slots of the idle tile buffer (where the
+// register instantiation parks it) and kChain2BwdXbLds elements of x_b into a staging area behind the parked partials, which no
+// put() touches: it lives until the mu_out store.  The other elements of x_b wait in registers.  Every DMA is retired (vmcnt(0))
+// before round A's barrier and read after it, by the wave that issued it.  !DMA: the register-staged kernel described above.
+template <int LT, int LGT, bool DMA>
 __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
     constexpr int NT = 1 << LGT, R = 1 << (LT - LGT), NW = NT / 64;
+    constexpr int XBL = DMA ? kChain2BwdXbLds : 0;
+    static_assert(XBL <= R && (2 * NW * sizeof(double)) % sizeof(double2) == 0);
     extern __shared__ __attribute__((aligned(16))) double2 tiles[];
     double* red = reinterpret_cast<double*>(tiles + 2 * (size_t(1) << LT));  // [2][NW] parked gradient partials: dL/dc, dL/ddelta
+    double2* xbs = tiles + 2 * (size_t(1) << LT) + 2 * NW * sizeof(double) / sizeof(double2);  // (DMA) [XBL][NT] staged x_b
     const unsigned tid = threadIdx.x;
     const unsigned t = blockIdx.x;
     const unsigned bl = blockIdx.y;
@@ -248,7 +275,8 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
     const int midlow = a.hs - a.lo;
     const unsigned xbase = ((t & ((1u << midlow) - 1u)) << a.lo) | ((t >> midlow) << (a.hs + a.hb));
     if (tid < 2 * NW) red[tid] = 0.0;  // published by the barrier of the first round
-    double2 uu[R], ww[R], xa[R], xb[R], tp[R];
+    RYDIFF_TL(0);
+    double2 uu[R], ww[R], xb[R], tp[R];
     unsigned xg[R];
     // the amplitude indices (and the 64-bit offsets derived from them) are taken afresh for each stage's stores, from a copy of
     // tid the compiler cannot see through: otherwise they stay live from the first loads to the last stores and spill
@@ -261,6 +289,23 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
             xg[r] = xbase | (i & lomask) | ((i >> a.lo) << a.hs);
         }
     };
+    // interaction diagonal (as k_chain): its table entries (L2 hits) are requested ahead of the streamed vectors, branch-free, so that
+    // they neither wait for those nor cost a round trip of their own once those have landed
+    double vloc[LT + 1], ut[R];
+    {
+        const double* __restrict__ vrow = a.vr + size_t(t) * 16;
+#pragma unroll
+        for (int b2 = 0; b2 <= LT; ++b2) vloc[b2] = vrow[b2];
+#pragma unroll
+        for (int r = 0; r < R; ++r) ut[r] = a.utt[unsigned(r) * NT + tid];
+    }
+    // ... and so are the drive and detuning coefficients of both stages (the host passes loadable records for the first and the
+    // last launch too)
+    double c_fin = a.coef_fin[bt * a.coef_bstride], c_sta = a.coef_sta[bt * a.coef_bstride], cdet_fin = 0.0, cdet_sta = 0.0;
+    if (a.gd) {  // (uniform)
+        cdet_fin = a.coef_fin[bt * a.coef_bstride + 2];
+        cdet_sta = a.coef_sta[bt * a.coef_bstride + 2];
+    }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const unsigned i = unsigned(r) * NT + tid;
@@ -270,31 +315,42 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
     // w and x_a requested with mu, outside of control flow (the host passes valid pointers for the first launch too)
 #pragma unroll
     for (int r = 0; r < R; ++r) ww[r] = stream_load(a.w + boff + xg[r]);
+    [[maybe_unused]] double2 xa[R];
+    if constexpr (DMA) {
+        const unsigned wv = __builtin_amdgcn_readfirstlane(tid & ~63u);  // a wave's 64 slots of one r are 1 KiB of contiguous LDS
+        double2* xat = tiles + (size_t(1) << LT);                        // the idle buffer of round A (buf ^ 1)
 #pragma unroll
-    for (int r = 0; r < R; ++r) xa[r] = stream_load(a.xa + boff + xg[r]);
-    // interaction diagonal (as k_chain), evaluated once per stage (table reads: L2 hits) so that it is not live across the rounds
-    auto interaction_diagonal = [&](double (&du)[R]) {
-        unsigned tid_o = tid;  // (table addresses taken afresh per stage, as in reindex)
-        asm volatile("" : "+v"(tid_o));
-        const double* __restrict__ vrow = a.vr + size_t(t) * 16;
-        double vloc[LT];
+        for (int r = 0; r < R; ++r) stream_load_lds(a.xa + boff + xg[r], xat + unsigned(r) * NT + wv);
 #pragma unroll
-        for (int b2 = 0; b2 < LT; ++b2) vloc[b2] = vrow[b2];
-        double dlane = vrow[LT];
+        for (int r = 0; r < XBL; ++r) stream_load_lds(a.xb + boff + xg[r], xbs + unsigned(r) * NT + wv);
 #pragma unroll
-        for (int b2 = 0; b2 < LGT; ++b2)
-            if (!(tid >> b2 & 1u)) dlane += vloc[b2];
+        for (int r = XBL; r < R; ++r) xb[r] = stream_load(a.xb + boff + xg[r]);
+    } else {
+#pragma unroll
+        for (int r = 0; r < R; ++r) xa[r] = stream_load(a.xa + boff + xg[r]);
+    }
+    __builtin_amdgcn_sched_barrier(0);  // (every request above is issued before the first wait)
+    auto uniform = [](double v) {  // (workgroup-uniform values: scalar registers)
+        return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+    };
+    c_fin = uniform(c_fin);
+    c_sta = uniform(c_sta);
+    cdet_fin = uniform(cdet_fin);
+    cdet_sta = uniform(cdet_sta);
+    double du[R];  // kept for both stages: the finish and the start stage work in the same layout
+    {
+        double dlane = vloc[LT];
+#pragma unroll
+        for (int b2 = 0; b2 < LGT; ++b2) dlane = (tid >> b2 & 1u) ? dlane : dlane + vloc[b2];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            double d = a.utt[unsigned(r) * NT + tid_o] + dlane;
+            double d = ut[r] + dlane;
 #pragma unroll
             for (int b2 = LGT; b2 < LT; ++b2)
                 if (!(r >> (b2 - LGT) & 1)) d += vloc[b2];
             du[r] = d;
         }
-    };
-    double du[R];  // (the finish stage's copy: taken while the loads are in flight)
-    interaction_diagonal(du);
+    }
     auto cnt = [&](int r) -> double { return a.gd ? double(a.dcnt - popc_i(xg[r] & a.dmask)) : 0.0; };
     int buf = 0;  // LDS buffer the next round writes
     auto put = [&](const double2 (&val)[R]) -> const double2* {
@@ -307,22 +363,38 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
     };
     auto cmul = [](double xr, double xi, const double2& z) { return make_double2(xr * z.x - xi * z.y, xr * z.y + xi * z.x); };
     auto cdot = [](const double2& p, const double2& x) { return make_double2(p.x * x.x + p.y * x.y, p.x * x.y - p.y * x.x); };  // conj(p) x
+    auto xbv = [&](int r) -> double2 { return r < XBL ? xbs[unsigned(r) * NT + tid] : xb[r]; };  // x_b: staged in LDS or in registers
 
+    // Every request of the top is retired here, on both paths (round A's barrier needs all of them anyway: x_a sits in LDS before it).
+    // Left pending on the path of a chain's first launch, which does not use them, they would make the start stage of the OTHER path
+    // wait for the acknowledgement of its mu_out stores: the compiler places its waits after the join of the two paths.
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        asm volatile("" ::"v"(uu[r].x), "v"(uu[r].y), "v"(ww[r].x), "v"(ww[r].y));
+        if constexpr (!DMA) asm volatile("" ::"v"(xa[r].x), "v"(xa[r].y));
+        if (DMA && r >= XBL) asm volatile("" ::"v"(xb[r].x), "v"(xb[r].y));
+    }
     double2 y[R];
     if (a.has_p) {
-        const double* __restrict__ cf = a.coef_fin + bt * a.coef_bstride;
-        const double c = cf[0], cdet = a.gd ? cf[2] : 0.0;
+        const double c = c_fin, cdet = cdet_fin;
         double2 pm[R], mid[R];  // P mu, mu_mid: kept until x_b arrives (mu_out is formed from them, not from mu and H mu)
         double wx[R];           // Re(beta_a conj(mu) x_a): factor a's weight of d(x) (factor b's, Re(beta_b conj(mu_mid) x_b), joins it)
         double zc = 0.0;  // Re(beta_a <P mu, x_a>) + Re(beta_b <P mu_mid, x_b>): dL/dc
         const bool two = a.k_r != 0.0 || a.k_i != 0.0;  // (uniform) a second finishing round: P_Y' e
         {
             // x_a waits out round A in this thread's own slots of the other LDS buffer (not in registers); e replaces it there
+            // (DMA: it is there already, retired by the vmcnt(0) in front of round A's barrier)
             double2* etile = tiles + (size_t(buf ^ 1) << LT);
+            if constexpr (DMA) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            } else {
 #pragma unroll
-            for (int r = 0; r < R; ++r) etile[unsigned(r) * NT + tid] = xa[r];
+                for (int r = 0; r < R; ++r) etile[unsigned(r) * NT + tid] = xa[r];
+            }
             double2 s[R], ds[R];
-            partner_sums<LT, LGT, false>(put(uu), uu, a.fin_mask, tid, s, ds);
+            const double2* mtile = put(uu);
+            RYDIFF_TL(1);
+            partner_sums<LT, LGT, false>(mtile, uu, a.fin_mask, tid, s, ds);
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const double2 xav = etile[unsigned(r) * NT + tid];
@@ -340,21 +412,25 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
         }
         park1<NW>(zc, red, 0);  // factor a's drive contraction is complete: parked now, not kept through round B
         zc = 0.0;
-        // the second tape vector and t (needed as tp = t + P_Y' e only) are requested once round A is done
+        RYDIFF_TL(2);
+        // the second tape vector (!DMA) and t (needed as tp = t + P_Y' e only) are requested once round A is done
+        if constexpr (!DMA) {
 #pragma unroll
-        for (int r = 0; r < R; ++r) xb[r] = stream_load(a.xb + boff + xg[r]);
+            for (int r = 0; r < R; ++r) xb[r] = stream_load(a.xb + boff + xg[r]);
+        }
 #pragma unroll
         for (int r = 0; r < R; ++r) tp[r] = stream_load(a.t + boff + xg[r]);
         reindex();  // (the indices of round A are not kept through the second load)
         double sgd = 0.0;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            const double2 wb = cdot(mid[r], xb[r]);
+            const double2 xbr = xbv(r);
+            const double2 wb = cdot(mid[r], xbr);
             const double wr = wx[r] + (a.cbb_r * wb.x - a.cbb_i * wb.y);
             if (a.wtot) unsafeAtomicAdd(a.wtot + xg[r], wr);  // both factors: one atomic
             sgd += wr * cnt(r);
             const double2 gpm = cmul(a.ga_r, a.ga_i, pm[r]);
-            const double2 q = cdot(gpm, xb[r]);
+            const double2 q = cdot(gpm, xbr);
             zc += a.cbb_r * q.x - a.cbb_i * q.y;
             // mu_out = (gb~ + bb~ H) mu_mid, H mu_mid = d mu_mid + c (ga~ P mu + ba~ tp): all but the tp part now
             const double d = du[r] + cdet * cnt(r);
@@ -363,6 +439,7 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
         }
         // x_b is consumed before round B starts: its partner reads must not be scheduled while P mu and mu_mid are still live
         __builtin_amdgcn_sched_barrier(0);
+        RYDIFF_TL(3);
         if (two) {
             __syncthreads();  // e published
             buf ^= 1;
@@ -387,9 +464,10 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
             const double2 kt = cmul(kc_r, kc_i, tp[r]);
             y[r].x += kt.x;
             y[r].y += kt.y;
-            const double2 q = cdot(cmul(a.ba_r, a.ba_i, tp[r]), xb[r]);  // (one-factor block: ba~ = 0)
+            const double2 q = cdot(cmul(a.ba_r, a.ba_i, tp[r]), xbv(r));  // (one-factor block: ba~ = 0)
             zc += a.cbb_r * q.x - a.cbb_i * q.y;
         }
+        RYDIFF_TL(4);
         park2<NW>(zc, sgd, red, 0, 1);
         reindex();
         if (a.inj_gexp || a.inj_gstate) {  // wave-uniform: the completed cotangent sits at a save point whose state is x_b
@@ -401,8 +479,9 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
                     for (int r = 0; r < R; ++r) {
                         double wsum = 0.0;
                         for (int o = 0; o < a.inj_n_obs; ++o) wsum += a.inj_gexp[o * a.inj_ostride + bt] * a.inj_obs[size_t(o) * a.dim + xg[r]];
-                        y[r].x += 2.0 * wsum * xb[r].x;
-                        y[r].y += 2.0 * wsum * xb[r].y;
+                        const double2 xbr = xbv(r);
+                        y[r].x += 2.0 * wsum * xbr.x;
+                        y[r].y += 2.0 * wsum * xbr.y;
                     }
                 }
             }
@@ -417,9 +496,12 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) stream_store(a.mu_out + boff + xg[r], y[r]);
+        RYDIFF_TL(5);
     } else {
 #pragma unroll
-        for (int r = 0; r < R; ++r) y[r] = uu[r];
+        for (int r = 0; r < R; ++r) {
+            y[r] = uu[r];
+        }
     }
     auto flush = [&]() {  // after the barrier that follows the parks: one atomic per quantity and workgroup
         if (a.has_p && tid < 2) {
@@ -437,14 +519,13 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
     }
 
     // start the next block in this layout: w' = P_Y mu_out, t' = P_Y (D' mu_out + c' w')
-    const double* __restrict__ cf = a.coef_sta + bt * a.coef_bstride;
-    const double c = cf[0], cdet = a.gd ? cf[2] : 0.0;
+    const double c = c_sta, cdet = cdet_sta;
     reindex();
-    interaction_diagonal(du);
     double2 w2[R], ds[R];
     partner_sums<LT, LGT, false, true>(put(y), y, ~0u, tid, w2, ds);
 #pragma unroll
     for (int r = 0; r < R; ++r) stream_store(a.w_out + boff + xg[r], w2[r]);
+    RYDIFF_TL(6);
     double2 z[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -455,5 +536,6 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
     partner_sums<LT, LGT, false, true>(put(z), z, ~0u, tid, t2, ds);
 #pragma unroll
     for (int r = 0; r < R; ++r) stream_store(a.t_out + boff + xg[r], t2[r]);
+    RYDIFF_TL(7);
     flush();  // (the barriers of the start rounds published the parked partials)
 }

@@ -137,18 +137,25 @@ int run_chain2(const Runtime& rt, char* ws, const std::vector<ChainItem>& items,
 
 // ---- adjoint in blocks of two factors (k_chain2_bwd, pair_kernels.hpp) -------------------------------------------------
 // Where the forward blocks are, for the real-drive adjoint (RydProblem.real_amp_grad: no signed sums) on the 2^12 two-layout
-// tiles; variant 19 keeps the one-factor adjoint (k_chain) next to automatic forward blocks.
+// tiles; variant 19 keeps the one-factor adjoint (k_chain) next to automatic forward blocks.  Variants 20 / 21: blocks wherever
+// legal (as 17) with the tape vectors staged through registers / by LDS-DMA (k_chain2_bwd<.., false / true>).
 bool pair_bwd_enabled(const Runtime& rt) {
     const ChainGeom g = chain_geom(rt);
     return !rt.pair_bwd_off && rt.real_amp_grad && pair_enabled(rt) && g.lt == kTileBits && g.layouts == 2;
 }
 
-template <int LGT>
+// Tape staging of the adjoint block kernel.  Automatic stays with the registers: on C3 the LDS-DMA version measured the same per
+// launch (26.3 us both) and within noise on the bench line; it remains selectable for A/B runs.
+constexpr bool kPairBwdDmaDefault = false;
+bool pair_bwd_dma(const Runtime& rt) { return rt.pair_bwd_stage ? rt.pair_bwd_stage > 0 : kPairBwdDmaDefault; }
+
+template <int LGT, bool DMA>
 int launch_chain2_bwd_t(const Chain2BwdArgs& ca, unsigned tiles, hipStream_t stream) {
     constexpr int LT = kTileBits;
-    const size_t lds = 2 * (size_t(1) << LT) * sizeof(double2) + 2 * ((size_t(1) << LGT) / 64) * sizeof(double);  // two tile buffers + [2][waves]
-    if (int rc = set_max_dynamic_lds_once<&k_chain2_bwd<LT, LGT>>(lds)) return rc;
-    hipLaunchKernelGGL((k_chain2_bwd<LT, LGT>), dim3(tiles, unsigned(ca.b_count)), dim3(1 << LGT), lds, stream, ca);
+    constexpr size_t lds = chain2_bwd_lds_bytes<LT, LGT, DMA>();
+    static_assert(lds <= 160 * 1024, "k_chain2_bwd: more LDS than a gfx950 workgroup can have");
+    if (int rc = set_max_dynamic_lds_once<&k_chain2_bwd<LT, LGT, DMA>>(lds)) return rc;
+    hipLaunchKernelGGL((k_chain2_bwd<LT, LGT, DMA>), dim3(tiles, unsigned(ca.b_count)), dim3(1 << LGT), lds, stream, ca);
     LAUNCH_CHECK();
     return RYDIFF_OK;
 }
@@ -223,7 +230,7 @@ int run_chain2_bwd(const Runtime& rt, char* ws, const std::vector<ChainItem>& it
             if (ca.mu_out == cur) return fail(RYDIFF_EINVAL, "internal: cotangent ping-pong clash");
             fill_inject(ca, inj, save_k[fb], pl);  // (inside has_p: every finishing launch completes a cotangent, mu_out)
         }
-        rc = launch_chain2_bwd_t<10>(ca, tiles, stream);
+        rc = pair_bwd_dma(rt) ? launch_chain2_bwd_t<10, true>(ca, tiles, stream) : launch_chain2_bwd_t<10, false>(ca, tiles, stream);
         if (rc) return rc;
         if (ca.has_p) {
             cur = ca.mu_out;  // complete cotangent at the input of forward factor fb

@@ -78,7 +78,7 @@ void describe_kernels(const Runtime& rt, const RydProblem* p, bool backward, Ryd
             if (!bwd && pairs)
                 std::snprintf(info->kernel_fwd, sizeof(info->kernel_fwd), "k_chain2<%d,10>", kTileBits);
             else if (bwd && pairs_bwd)
-                std::snprintf(info->kernel_bwd, sizeof(info->kernel_bwd), "k_chain2_bwd<%d,10>", kTileBits);
+                std::snprintf(info->kernel_bwd, sizeof(info->kernel_bwd), "k_chain2_bwd<%d,10,%s>", kTileBits, b(pair_bwd_dma(rt)));
             else if (chain_geom(rt).lt == kWideTileBits)
                 std::snprintf(bwd ? info->kernel_bwd : info->kernel_fwd, sizeof(info->kernel_fwd), "k_chain_wide<%d,%s,%s,%s>", kWideTileBits,
                               b(cplx), b(bwd != 0), b(fast));

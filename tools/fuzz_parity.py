@@ -60,7 +60,7 @@ for case in range(n_cases):
     cond = (True,) * ka if three else ()
     ones = ((bool(rng.integers(0, 2)),) * kd) if three else ()
     out = {}
-    variants = (1, 0) + ((int(rng.choice([2, 4, 10, 14, 15, 16, 17, 19])),) if n >= 13 else ())  # 10: trajectory-per-XCD placement, 14: wide tiles, 15 / 16: tiles of 2^11 / 2^10 amplitudes, 17: block-of-two passes, 19: forward blocks only  # from 13 qubits also the chained tiles FORCED: auto routes small single trajectories to the direct kernels
+    variants = (1, 0) + ((int(rng.choice([2, 4, 10, 14, 15, 16, 17, 19, 20, 21])),) if n >= 13 else ())  # 10: trajectory-per-XCD placement, 14: wide tiles, 15 / 16: tiles of 2^11 / 2^10 amplitudes, 17: block-of-two passes, 19: forward blocks only, 20 / 21: adjoint blocks staged through registers / by LDS-DMA  # from 13 qubits also the chained tiles FORCED: auto routes small single trajectories to the direct kernels
     for variant in variants:
         _native.set_kernel_variant(variant)
         spec = ProblemSpec(n, dt, ns, am, dm, solver=solver, store_states=store, tape=tape, tape_steps=tape_steps, amp_conditioned=cond, det_ones=ones)
