@@ -65,6 +65,8 @@ extern "C" {
 #define RYDIFF_MAX_OVERLAPS 16 /* state-overlap observables (target states) of one call */
 #define RYDIFF_MAX_RDMS 8        /* reduced density matrices of one call */
 #define RYDIFF_MAX_RDM_QUBITS 6  /* qubits of one reduced density matrix */
+#define RYDIFF_MAX_DM_ATOMS 12   /* atoms of a density-matrix register (RydProblem.dm_atoms): 4^12 amplitudes */
+#define RYDIFF_MAX_DM_DIAG 64    /* diagonal observables of a density-matrix register */
 
 enum { RYDIFF_OK = 0, RYDIFF_EINVAL = -1, RYDIFF_EWORKSPACE = -2, RYDIFF_EHIP = -3, RYDIFF_ENOTIMPL = -4 };
 
@@ -240,6 +242,48 @@ typedef struct RydProblem {
     int32_t n_rdms;                 /* 0: none; at most RYDIFF_MAX_RDMS */
     const uint32_t* rdm_masks;      /* HOST [n_rdms] */
 
+    /* DENSITY-MATRIX observables: dm_atoms = n > 0 declares the register to be the DOUBLED register of a density matrix (the
+     * master-equation path, see the pair terms above): n_qubits == 2n, row qubits 0..n-1, column qubits n..2n-1,
+     *   vec(rho)[x * 2^n + y] = rho[x][y],
+     * and asks for functionals of v = vec(rho_b(t_k)) at every tsave, evaluated while the state is on the device.  Their rows follow
+     * ALL the rows above in expect_out / grad_expect ([n_tsave][B] each), in this order:
+     *   n_dm_diag rows       sum_x o[x] Re v[x (2^n + 1)]                                  (Tr(rho O) for diagonal O)
+     *   n_dm_pauli_obs rows  sum_s w_s Re sum_x i^ny (-1)^popcount((x ^ xm) & zm) v[(x ^ xm) 2^n + x]      (sum_s w_s Re Tr(P_s rho);
+     *                        strings over the n ATOMS in the conventions and limits of the ket Pauli block, xm / zm the masks
+     *                        moved to index bits of an atom index: atom j <-> bit n-1-j)
+     *   n_dm_fid rows        Re sum_{x,y} conj(phi[x]) v[x 2^n + y] phi[y]                  (<phi|rho|phi>; targets are constants, not
+     *                        normalised by the library; dm_fid_batch = 1: shared by the trajectories, B: one per trajectory)
+     *   dm_purity row        sum_i |v_i|^2                                                  (Tr rho^2 for Hermitian rho)
+     * None of them assumes a Hermitian or normalised rho.  rydiff_backward differentiates every row: with g the row's entry of
+     * grad_expect at (k, b), the cotangent added to v (torch's dL/dRe + i dL/dIm) is  g o[x] on the diagonal entries;
+     * g w_s conj(phase_s(x)) at entry (x ^ xm, x);  g phi[x] conj(phi[y]);  2 g v — formed per save point in the workspace buffer of the
+     * Pauli / overlap / RDM cotangents (after them) and injected through the grad_states route.
+     * dm_shots = 1 (needs n_shots > 0): the measurement shots above are drawn from p[x] = max(Re v[x (2^n + 1)], 0), x < 2^n — the
+     * diagonal of rho — instead of |psi|^2; every other word of the shot rule holds (float64 cumulative sums in a fixed order, the
+     * smallest x with C[x] > u * S, the clamping of u, RYDIFF_SHOT_NONE when S == 0, never an x with p[x] == 0).
+     * The ket-style fields keep their meaning on the doubled register.  Honoured by rydiff_forward in every kernel family and with
+     * every tape mode (states_out == NULL without a tape included: rydiff_plan adds the trajectory the one-launch sweeps are
+     * evaluated from).  Not together with shard_bits > 0 and not in rydiff_forward_tangent (RYDIFF_ENOTIMPL).  RYDIFF_EINVAL:
+     * n_qubits != 2 * dm_atoms, dm_atoms outside [0, RYDIFF_MAX_DM_ATOMS], a count out of range (n_dm_diag <= RYDIFF_MAX_DM_DIAG,
+     * strings <= RYDIFF_MAX_PAULI_STRINGS, n_dm_fid <= RYDIFF_MAX_OVERLAPS, dm_purity / dm_shots 0 or 1), a mask bit at or above n,
+     * a NULL table with a non-zero count, dm_shots without n_shots.  Traffic per save point and trajectory: 2^n * 16 B per distinct
+     * flip mask for the diagonal and Pauli rows, ONE read of the 4^n amplitudes for all fidelities and the purity, 2^n * 16 B for
+     * the shots.  dm_atoms = 0: nothing changes, the other dm_* fields are ignored.  (The fields sit in front of tape_steps.) */
+    int32_t dm_atoms;               /* n; 0: none */
+    int32_t n_dm_diag;
+    const double* dm_diag;          /* DEVICE float64 [n_dm_diag][2^n] */
+    int32_t n_dm_pauli_obs;
+    int32_t n_dm_pauli_strings;
+    const int32_t* dm_pauli_first;  /* HOST [n_dm_pauli_obs + 1] */
+    const uint32_t* dm_pauli_x;     /* HOST [n_dm_pauli_strings]: bit j = atom j */
+    const uint32_t* dm_pauli_z;     /* HOST [n_dm_pauli_strings] */
+    const double* dm_pauli_w;       /* HOST [n_dm_pauli_strings] */
+    int32_t n_dm_fid;               /* 0 .. RYDIFF_MAX_OVERLAPS */
+    int32_t dm_fid_batch;           /* 1 or B */
+    const void* dm_fid_targets;     /* DEVICE complex128 [n_dm_fid][dm_fid_batch][2^n] */
+    int32_t dm_purity;              /* 0 or 1 */
+    int32_t dm_shots;               /* 0 or 1 */
+
     /* need_tape = 3 (PARTIAL tape) only: the number of TRAILING tsave intervals whose factor outputs are all kept in the workspace
      * tape (1 .. n_tsave - 1); the earlier intervals keep their save-point states only and are recomputed by the adjoint sweep.  The
      * caller sizes it to the HBM that is free (rydiff_plan reports the workspace for the value given): what the full tape of
@@ -333,8 +377,9 @@ int rydiff_plan(const RydProblem* p, int need_tape, int need_backward, void* scr
  *   states_out  DEVICE complex128 [n_tsave][B][2^N], or NULL (trajectory kept in the workspace tape if need_tape).
  *               With need_tape = 2 / 3 AND states_out the factor outputs go to the (granted) workspace tape and the states at the
  *               save points are copied out of it — stored states plus a later gradient without (or with less) recomputation.
- *   expect_out  DEVICE float64 [n_obs + n_pauli_obs + 2 * n_overlaps + 2 * sum_o 4^{m_o}][n_tsave][B] (diagonal observables first,
- *               then the Pauli ones, then Re / Im of every overlap, then Re / Im of every reduced-density-matrix entry), or NULL
+ *   expect_out  DEVICE float64 [n_obs + n_pauli_obs + 2 * n_overlaps + 2 * sum_o 4^{m_o} + dm rows][n_tsave][B] (diagonal observables
+ *               first, then the Pauli ones, then Re / Im of every overlap, then Re / Im of every reduced-density-matrix entry, then the
+ *               density-matrix rows n_dm_diag + n_dm_pauli_obs + n_dm_fid + dm_purity), or NULL
  * With RydProblem.n_shots > 0 the measurement shots of the save points in shot_times go to RydProblem.shots_out on the way. */
 int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi0, void* states_out, double* expect_out,
                    void* workspace, size_t workspace_bytes, int need_tape, void* stream);
@@ -346,7 +391,7 @@ int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi
  *   states       DEVICE: the states_out of the forward call, or NULL to use the workspace tape (with need_tape = 2 / 3 the
  *                granted workspace tape is used even when states is given)
  *   grad_states  DEVICE complex128 [n_tsave][B][2^N] or NULL
- *   grad_expect  DEVICE float64 [n_obs + n_pauli_obs + 2 * n_overlaps + 2 * sum_o 4^{m_o}][n_tsave][B] or NULL
+ *   grad_expect  DEVICE float64 [n_obs + n_pauli_obs + 2 * n_overlaps + 2 * sum_o 4^{m_o} + dm rows][n_tsave][B] or NULL
  *   g_amp        DEVICE complex128 [coeff_batch][n_amp_terms][n_samples] or NULL   (overwritten)
  *   g_det        DEVICE float64    [coeff_batch][n_det_terms][n_samples] or NULL   (overwritten)
  *   g_u          DEVICE float64 [N(N-1)/2] or NULL  (dist_grad, backend.py:456-460 / hamiltonian.py:341-344)
@@ -391,7 +436,7 @@ size_t rydiff_tangent_workspace_bytes(const RydProblem* p, const RydPlanInfo* in
  *   workspace    DEVICE, >= rydiff_tangent_workspace_bytes(p, info, n_dir)
  * Both solvers, coeff_batch 1 or B, dp5_piece_refine honoured (same plan); kernel_variant is ignored: the sweep has one kernel
  * family (launch per factor, one amplitude per thread).  Not implemented (RYDIFF_ENOTIMPL): state-sharded runs, pair terms,
- * conditioned / ones-counting terms.  Every argument is validated before anything touches a device. */
+ * conditioned / ones-counting terms, density-matrix registers (dm_atoms > 0).  Every argument is validated before anything touches a device. */
 int rydiff_forward_tangent(const RydProblem* p, const RydPlanInfo* info, const RydTangent* tangent, const void* psi0,
                            double* expect_out, double* dexpect_out, void* workspace, size_t workspace_bytes, void* stream);
 

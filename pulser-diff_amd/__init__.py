@@ -10,6 +10,6 @@ from pulser_diff_amd.model import QuantumModel  # noqa: F401
 from pulser_diff_amd.simconfig import SimConfig  # noqa: F401
 from pulser_diff_amd.solver import SolverType  # noqa: F401
 from pulser_diff_amd.utils import DiagonalObservable  # noqa: F401
-from pulser_diff_amd.observables import PauliObservable, ReducedDensityMatrix, StateOverlap  # noqa: F401
+from pulser_diff_amd.observables import PauliObservable, Purity, ReducedDensityMatrix, StateOverlap  # noqa: F401
 
-__all__ = ["TorchEmulator", "SimConfig", "SolverType", "DiagonalObservable", "PauliObservable", "StateOverlap", "ReducedDensityMatrix", "QuantumModel"]
+__all__ = ["TorchEmulator", "SimConfig", "SolverType", "DiagonalObservable", "PauliObservable", "StateOverlap", "ReducedDensityMatrix", "Purity", "QuantumModel"]

@@ -32,6 +32,8 @@ MAX_OVERLAPS = 16
 MAX_RDMS = 8
 MAX_RDM_QUBITS = 6
 MAX_TANGENTS = 8
+MAX_DM_ATOMS = 12  # atoms of a density-matrix register (RydProblem.dm_atoms)
+MAX_DM_DIAG = 64  # diagonal observables of a density-matrix register
 MAX_SHOTS = 1 << 20  # shots per (sampled save point, trajectory)
 SHOT_NONE = 0xFFFFFFFF  # the sampled state was identically zero
 
@@ -77,6 +79,20 @@ class RydProblem(ctypes.Structure):
         ("shots_out", ctypes.c_void_p),
         ("n_rdms", ctypes.c_int32),
         ("rdm_masks", ctypes.c_void_p),
+        ("dm_atoms", ctypes.c_int32),
+        ("n_dm_diag", ctypes.c_int32),
+        ("dm_diag", ctypes.c_void_p),
+        ("n_dm_pauli_obs", ctypes.c_int32),
+        ("n_dm_pauli_strings", ctypes.c_int32),
+        ("dm_pauli_first", ctypes.c_void_p),
+        ("dm_pauli_x", ctypes.c_void_p),
+        ("dm_pauli_z", ctypes.c_void_p),
+        ("dm_pauli_w", ctypes.c_void_p),
+        ("n_dm_fid", ctypes.c_int32),
+        ("dm_fid_batch", ctypes.c_int32),
+        ("dm_fid_targets", ctypes.c_void_p),
+        ("dm_purity", ctypes.c_int32),
+        ("dm_shots", ctypes.c_int32),
         ("tape_steps", ctypes.c_int32),
         ("n_overlaps", ctypes.c_int32),
         ("overlap_batch", ctypes.c_int32),

@@ -34,7 +34,7 @@ from .result import SampledResult
 from .simconfig import SimConfig
 from .simresults import CoherentResults, NoisyResults, SimulationResults
 from .solver import ProblemSpec, SolverType, evolve, evolve_tangent, sesolve, tolerance_from_options
-from .observables import PauliObservable, ReducedDensityMatrix, StateOverlap
+from .observables import PauliObservable, Purity, ReducedDensityMatrix, StateOverlap
 from .shots import MAX_SHOTS, ShotRequest, indices_to_bitstrings
 from .utils import DiagonalObservable
 
@@ -311,7 +311,8 @@ class TorchEmulator:
         ``shots`` (extension): measurement shots drawn natively while the state is on the device — an int (that many at the final
         evaluation time) or a ``ShotRequest`` (``times="all"``: every evaluation time).  ``results.sample_state`` /
         ``sample_final_state`` return them when asked for a sampled time and exactly that many samples, also with
-        ``store_states=False``.  Coherent Schroedinger runs only.  ``native_shots=True`` (extension, noisy runs that average over
+        ``store_states=False``.  Coherent runs: Schroedinger, and master-equation runs without stored states (drawn from the
+        diagonal of rho; with stored states ``sample_state`` draws from the stored density matrices and ``shots=`` is refused).  ``native_shots=True`` (extension, noisy runs that average over
         realisations): the per-run measurements are drawn natively as well and no run's states are stored.
         """
         if shots is not None and not isinstance(shots, ShotRequest):
@@ -332,8 +333,14 @@ class TorchEmulator:
 
         dev = self._compute_device
         ham = self._hamiltonian
-        obs_tensors, obs_objs, pauli_objs, overlap_objs, rdm_objs = [], [], [], [], []
+        obs_tensors, obs_objs, pauli_objs, overlap_objs, rdm_objs, purity_objs = [], [], [], [], [], []
         for obs in observables or []:
+            if isinstance(obs, Purity):
+                if solver != SolverType.DP5_ME:
+                    raise NotImplementedError("Purity is evaluated natively in master-equation runs only (a ket has purity "
+                                              "<psi|psi>^2: results.purity() computes it from the stored states).")
+                purity_objs.append(obs)
+                continue
             if isinstance(obs, ReducedDensityMatrix):
                 if ham.basis_name == "all":
                     raise NotImplementedError("ReducedDensityMatrix is not available in the three-level all-basis; trace the "
@@ -362,8 +369,8 @@ class TorchEmulator:
                     raise ValueError("Only diagonal observables can be evaluated natively; use results.expect on the states.")
                 diag = torch.diagonal(dense).real
             else:
-                raise TypeError("observables must be DiagonalObservable / PauliObservable / StateOverlap / ReducedDensityMatrix objects or "
-                                "diagonal (dim, dim) tensors")
+                raise TypeError("observables must be DiagonalObservable / PauliObservable / StateOverlap / ReducedDensityMatrix / Purity "
+                                "objects or diagonal (dim, dim) tensors")
             obs_tensors.append(diag.to(dev, torch.float64))
             obs_objs.append(obs)
         obs_diag = torch.stack(obs_tensors) if obs_tensors else None
@@ -384,17 +391,32 @@ class TorchEmulator:
                                           "state different from the ground.")
 
         def run_coherent() -> CoherentResults:
-            if overlap_objs and solver == SolverType.DP5_ME:
-                raise NotImplementedError("StateOverlap observables are defined on kets: not available in master-equation runs.")
             if rdm_objs and solver == SolverType.DP5_ME:
-                raise NotImplementedError("ReducedDensityMatrix observables are defined on kets: not available in master-equation runs.")
-            if shots is not None and solver == SolverType.DP5_ME:
-                raise NotImplementedError("Native measurement shots are not available in master-equation runs; "
-                                          "sample_state draws from the stored density matrices.")
+                raise NotImplementedError("ReducedDensityMatrix observables stay refused in master-equation runs: partial traces of a "
+                                          "density matrix are not evaluated natively (diagonal, Pauli, StateOverlap and Purity are).")
+            # A master-equation run that stores its density matrices already serves fidelities (results.fidelity) and samples
+            # (sample_state) from them: the two requests that used to be refused there stay refused with stored states, and are
+            # served natively where no trajectory is kept
+            if overlap_objs and solver == SolverType.DP5_ME and store_states:
+                raise NotImplementedError("StateOverlap observables of master-equation runs are evaluated natively (the fidelity "
+                                          "<phi|rho|phi>) with store_states=False only; with stored states results.fidelity(obs) "
+                                          "computes it from the density matrices without the observable being handed to run().")
+            if shots is not None and solver == SolverType.DP5_ME and store_states:
+                raise NotImplementedError("Native measurement shots of master-equation runs are drawn (from the diagonal of rho) with "
+                                          "store_states=False only; with stored states sample_state draws from the stored density "
+                                          "matrices.")
             if solver == SolverType.DP5_ME:  # density matrices (backend.py:495-509); without collapse noise L = 0
-                rho, stats = mesolve(ham, psi0.to(dev), self._eval_times_array, ham.config, options)
-                return CoherentResults(rho, ham._size, ham.basis_name, self._eval_times_array, self._meas_basis, meas_errors,
-                                       atom_order=tuple(ham._qdict), stats=stats, density=True)
+                # diagonal tables, Pauli strings (unrotated: this path runs in no rotating frame), fidelities, the purity and the
+                # shots are taken from rho while it is on the device; store_states=False keeps the (n_t, 4^N) trajectory out
+                res = mesolve(ham, psi0.to(dev), self._eval_times_array, ham.config, options,
+                              observables=obs_objs + pauli_objs + overlap_objs + purity_objs, shots=shots, store_states=store_states)
+                n_ex, n_ov = len(obs_objs) + len(pauli_objs), len(overlap_objs)
+                return CoherentResults(res.states, ham._size, ham.basis_name, self._eval_times_array, self._meas_basis, meas_errors,
+                                       atom_order=tuple(ham._qdict), stats=res.stats, density=True,
+                                       native_expect=torch.stack(res.expect[:n_ex]) if n_ex else None,
+                                       native_observables=obs_objs + pauli_objs, overlap_observables=overlap_objs,
+                                       native_fidelities=res.expect[n_ex:n_ex + n_ov] if n_ov else None,
+                                       native_purity=res.expect[n_ex + n_ov] if purity_objs else None, native_shots=res.shots)
             result = sesolve(ham, psi0.to(dev), self._eval_times_array, solver=solver, options=options, obs_diag=obs_diag,
                              store_states=store_states, pauli_obs=pauli_objs, overlap_obs=overlap_objs, shots=shots, rdm_obs=rdm_objs)
             states_tbd = result.states.permute(0, 2, 1) if result.states.numel() else result.states
@@ -421,9 +443,11 @@ class TorchEmulator:
         else:
             reps = [1] * self.config.runs
         if overlap_objs:
-            raise NotImplementedError("StateOverlap observables are not available in noisy runs that average over realisations.")
+            raise NotImplementedError("StateOverlap observables stay refused in noisy runs that average over realisations.")
         if rdm_objs:
-            raise NotImplementedError("ReducedDensityMatrix observables are not available in noisy runs that average over realisations.")
+            raise NotImplementedError("ReducedDensityMatrix observables stay refused in noisy runs that average over realisations.")
+        if purity_objs:
+            raise NotImplementedError("Purity observables stay refused in noisy runs that average over realisations.")
         if shots is not None:
             raise NotImplementedError("A ShotRequest belongs to one coherent run; noisy runs that average over realisations return "
                                       "their measurements as NoisyResults (native_shots=True draws them natively).")

@@ -1,0 +1,253 @@
+// dm_kernels.hpp — density-matrix observables (include/rydiff.h: RydProblem.dm_*): functionals of v = vec(rho), rho the state of
+// the doubled register of a master-equation run, v[x * 2^n + y] = rho[x][y]  (gfx950, wave64):
+//   k_dm_trace      diagonal rows  sum_x o[x] Re v[x (2^n + 1)]  and Pauli rows  sum_s w_s Re Tr(P_s rho): per flip mask xm the 2^n
+//                   entries (x ^ xm, x) and nothing else — 2^n * 16 B against 4^n * 16 B for the matrix; one row per grid.z
+//   k_dm_fidelity   <phi_o|rho|phi_o> for every target and the purity sum |v|^2 from ONE read of v: consecutive lanes on consecutive
+//                   y (rows of rho are contiguous: 16-byte loads), phi re-read from cache (2^n <= 4096 entries), the accumulators in
+//                   registers (NO = compile-time bound on the targets, as in k_overlap_expect)
+//   k_dm_shots      one workgroup per trajectory of a sampled save point: the clamped diagonal p[x] = max(Re v[x (2^n + 1)], 0)
+//                   into LDS, a fixed-order float64 prefix (segment sums, one serial scan of the 256 totals), one binary search per
+//                   shot — no float atomics: bit-reproducible
+//   k_dm_apply      cotangent, dense parts:  out = base + sum_o g_o phi_o[x] conj(phi_o[y]) + 2 g_p v   (streaming, no atomics)
+//   k_dm_scatter    cotangent, sparse parts, in place behind k_dm_apply: one thread per (distinct flip mask, x) adds
+//                   sum_o g_o o[x] (xm = 0) + sum_s g w_s conj(phase_s(x)) at entry (x ^ xm, x) — one owner per entry, no atomics
+// The final sums follow the other observable kernels: wave shuffle, LDS, one atomic per block and row.
+#pragma once
+
+struct DmTables {
+    const int32_t* gfirst = nullptr;        // [n_dm_pobs + 1]: groups of observable o
+    const PauliGroup* groups = nullptr;     // per observable, by flip mask (atom-index bits)
+    const PauliString* strings = nullptr;
+    const PauliGroup* agroups = nullptr;    // all observables, by flip mask: the cotangent scatter (pad of a string = its observable)
+    const PauliString* astrings = nullptr;
+};
+
+struct DmTraceArgs {
+    const double2* v;    // state at save point k0, trajectory 0
+    size_t kstride;      // amplitudes between consecutive save points (grid.y covers b_count * n_k states)
+    DmTables t;
+    const double* diag;  // [n_diag][2^n]
+    double* out;         // first density-matrix row of expect_out: [n_diag + n_pobs][n_tsave][B]
+    int n_diag, n_tsave, k0, B, b_first, b_count, n;
+};
+
+// grid (blocks, b_count * n_k, n_diag + n_pobs)
+__global__ __launch_bounds__(256) void k_dm_trace(DmTraceArgs a) {
+    __shared__ double lds[8];
+    const uint32_t D = 1u << a.n;
+    const int b = a.b_first + int(blockIdx.y) % a.b_count;
+    const int kk = int(blockIdx.y) / a.b_count;
+    const int row = blockIdx.z;
+    const double2* __restrict__ v = a.v + size_t(kk) * a.kstride + (size_t(b) << (2 * a.n));
+    double acc = 0.0;
+    if (row < a.n_diag) {
+        const double* __restrict__ o = a.diag + (size_t(row) << a.n);
+        for (uint32_t x = blockIdx.x * 256u + threadIdx.x; x < D; x += gridDim.x * 256u) acc = fma(o[x], v[size_t(x) * (D + 1u)].x, acc);
+    } else {
+        const int ob = row - a.n_diag;
+        for (int g = a.t.gfirst[ob]; g < a.t.gfirst[ob + 1]; ++g) {  // uniform
+            const PauliGroup gr = a.t.groups[g];
+            for (uint32_t x = blockIdx.x * 256u + threadIdx.x; x < D; x += gridDim.x * 256u) {
+                const uint32_t xp = x ^ gr.xm;
+                const double2 q = v[(size_t(xp) << a.n) + x];  // rho[x ^ xm][x]
+                for (uint32_t s = gr.first; s < gr.first + gr.count; ++s) {
+                    const PauliString st = a.t.strings[s];
+                    const double val = st.wr * q.x - st.wi * q.y;  // Re(w i^ny q)
+                    acc += (__popc(xp & st.zm) & 1u) ? -val : val;
+                }
+            }
+        }
+    }
+    block_atomic_add(acc, a.out + (size_t(row) * a.n_tsave + a.k0 + kk) * a.B + b, lds);
+}
+
+struct DmFidArgs {
+    const double2* v;    // state at save point k0, trajectory 0
+    size_t kstride;
+    const double2* phi;  // [n_fid][fid_batch][2^n]
+    double* out;         // first fidelity row of expect_out: [n_fid + purity][n_tsave][B]
+    int n_fid, fid_batch, purity, n_tsave, k0, B, b_first, b_count, n;
+};
+
+// grid (blocks, b_count * n_k)
+template <int NO>
+__global__ __launch_bounds__(256) void k_dm_fidelity(DmFidArgs a) {
+    __shared__ double lds[8];
+    const uint32_t D = 1u << a.n, total = 1u << (2 * a.n);
+    const int b = a.b_first + int(blockIdx.y) % a.b_count;
+    const int kk = int(blockIdx.y) / a.b_count;
+    const double2* __restrict__ v = a.v + size_t(kk) * a.kstride + size_t(b) * total;
+    const double2* __restrict__ phi = a.phi + (a.fid_batch > 1 ? size_t(b) * D : size_t(0));
+    const size_t ostride = size_t(a.fid_batch) * D;
+    double f[NO], pur = 0.0;
+#pragma unroll
+    for (int o = 0; o < NO; ++o) f[o] = 0.0;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+        const double2 q = v[i];
+        const uint32_t x = i >> a.n, y = i & (D - 1u);
+        pur = fma(q.x, q.x, fma(q.y, q.y, pur));
+#pragma unroll
+        for (int o = 0; o < NO; ++o) {
+            if (o < a.n_fid) {  // uniform
+                const double2 px = phi[size_t(o) * ostride + x], py = phi[size_t(o) * ostride + y];
+                const double wr = q.x * py.x - q.y * py.y, wi = q.x * py.y + q.y * py.x;  // rho[x][y] phi[y]
+                f[o] = fma(px.x, wr, fma(px.y, wi, f[o]));                               // Re(conj(phi[x]) ...)
+            }
+        }
+    }
+    double* out = a.out + size_t(a.k0 + kk) * a.B + b;
+    const size_t row = size_t(a.n_tsave) * a.B;
+#pragma unroll
+    for (int o = 0; o < NO; ++o)
+        if (o < a.n_fid) block_atomic_add(f[o], out + size_t(o) * row, lds);
+    if (a.purity) block_atomic_add(pur, out + size_t(a.n_fid) * row, lds);
+}
+
+constexpr uint32_t kDmShotMax = 1u << RYDIFF_MAX_DM_ATOMS;  // probabilities of one density matrix: 32 KiB of LDS
+
+struct DmShotArgs {
+    const double2* v;  // the sampled state, trajectory 0
+    const double* u;   // [B][n_shots] of this sampled save point
+    uint32_t* out;     // [B][n_shots]
+    int n, n_shots, b_first;
+};
+
+// grid (b_count), 256 threads.  Thread t owns a contiguous segment of the diagonal; the segment totals are scanned serially by thread
+// 0, so the last entry of a segment and the offset of the next one are the same number: C is non-decreasing, and C[x] > C[x - 1]
+// only where p[x] > 0.
+__global__ __launch_bounds__(256) void k_dm_shots(DmShotArgs a) {
+    __shared__ double C[kDmShotMax];
+    __shared__ double part[256];
+    __shared__ int last_pos;
+    const uint32_t D = 1u << a.n;
+    const int b = a.b_first + int(blockIdx.x);
+    const double2* __restrict__ v = a.v + (size_t(b) << (2 * a.n));
+    const uint32_t seg = (D + 255u) / 256u;
+    const uint32_t lo = min(threadIdx.x * seg, D), hi = min(lo + seg, D);
+    double run = 0.0;
+    int mine = -1;
+    for (uint32_t x = lo; x < hi; ++x) {
+        const double re = v[size_t(x) * (D + 1u)].x;
+        const double p = re > 0.0 ? re : 0.0;  // (NaN counts as 0)
+        run += p;
+        C[x] = run;
+        if (p > 0.0) mine = int(x);
+    }
+    part[threadIdx.x] = run;
+    if (threadIdx.x == 0) last_pos = -1;
+    __syncthreads();
+    if (mine >= 0) atomicMax(&last_pos, mine);  // (integer: order does not matter)
+    if (threadIdx.x == 0) {
+        double acc = 0.0;
+        for (int w = 0; w < 256; ++w) {
+            const double t = part[w];
+            part[w] = acc;
+            acc += t;
+        }
+    }
+    __syncthreads();
+    const double off = part[threadIdx.x];
+    for (uint32_t x = lo; x < hi; ++x) C[x] = off + C[x];
+    __syncthreads();
+    const double S = C[D - 1u];
+    const int last = last_pos;
+    for (int s = threadIdx.x; s < a.n_shots; s += 256) {
+        const size_t slot = size_t(b) * a.n_shots + s;
+        if (!(S > 0.0) || last < 0) {  // nothing to sample from
+            a.out[slot] = RYDIFF_SHOT_NONE;
+            continue;
+        }
+        double u = a.u[slot];
+        u = u > 0.0 ? fmin(u, 1.0 - 0x1p-53) : 0.0;  // [0, 1); NaN -> 0
+        const double tau = u * S;
+        uint32_t l = 0, h = D;  // the smallest x with C[x] > tau
+        while (l < h) {
+            const uint32_t mid = l + (h - l) / 2;
+            if (C[mid] > tau) h = mid;
+            else l = mid + 1;
+        }
+        a.out[slot] = l < D ? l : uint32_t(last);  // rounding left no cumulative value above the target: the last populated entry
+    }
+}
+
+struct DmApplyArgs {
+    const double2* psi;    // trajectory: the state at save point k is psi + index(k) * B * 4^n, index(k) = entry ? entry[k] : k * kmul
+    const int32_t* entry;
+    int kmul;
+    const double2* base;   // [n_k][B][4^n]: what the cotangent is added to, or nullptr
+    double2* out;          // [n_k][B][4^n]; may be `base`
+    const double2* phi;    // [n_fid][fid_batch][2^n]
+    const double* g_fid;   // fidelity rows of grad_expect: [n_fid][n_tsave][B]
+    const double* g_pur;   // the purity row of grad_expect [n_tsave][B], or nullptr
+    int n_fid, fid_batch, n_tsave, k0, B, n;
+};
+
+// grid (4^n / 256, B, n_k): out[kk][b][x 2^n + y] = base[kk][b][..] + sum_o g_o phi_o[x] conj(phi_o[y]) + 2 g_p v_k[..],  k = k0 + kk
+__global__ __launch_bounds__(256) void k_dm_apply(DmApplyArgs a) {
+    const uint32_t D = 1u << a.n, total = 1u << (2 * a.n);
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= total) return;
+    const int b = blockIdx.y, k = a.k0 + int(blockIdx.z);
+    const size_t sv = size_t(a.B) * total;
+    const size_t off = size_t(blockIdx.z) * sv + size_t(b) * total + i;
+    const uint32_t x = i >> a.n, y = i & (D - 1u);
+    double2 acc = a.base ? a.base[off] : make_double2(0.0, 0.0);
+    const double* g = a.g_fid + size_t(k) * a.B + b;
+    const size_t row = size_t(a.n_tsave) * a.B;
+    const double2* phi = a.phi + (a.fid_batch > 1 ? size_t(b) * D : size_t(0));
+    const size_t ostride = size_t(a.fid_batch) * D;
+    for (int o = 0; o < a.n_fid; ++o) {
+        const double go = g[size_t(o) * row];
+        if (go == 0.0) continue;  // uniform: cotangents usually sit at one or a few save points
+        const double2 px = phi[size_t(o) * ostride + x], py = phi[size_t(o) * ostride + y];
+        acc.x = fma(go, px.x * py.x + px.y * py.y, acc.x);  // phi[x] conj(phi[y])
+        acc.y = fma(go, px.y * py.x - px.x * py.y, acc.y);
+    }
+    const double gp = a.g_pur ? a.g_pur[size_t(k) * a.B + b] : 0.0;
+    if (gp != 0.0) {  // uniform
+        const double2 q = a.psi[size_t(a.entry ? a.entry[k] : k * a.kmul) * sv + size_t(b) * total + i];
+        acc.x = fma(2.0 * gp, q.x, acc.x);
+        acc.y = fma(2.0 * gp, q.y, acc.y);
+    }
+    a.out[off] = acc;
+}
+
+struct DmScatterArgs {
+    double2* out;        // [n_k][B][4^n], already holding everything else
+    DmTables t;
+    const double* diag;  // [n_diag][2^n]
+    const double* gexp;  // first density-matrix row of grad_expect: [n_diag + n_pobs][n_tsave][B]
+    int n_diag, n_tsave, k0, B, n;
+    uint32_t xblocks;    // blocks per group
+};
+
+// grid (xblocks * groups, B, n_k): thread (group, x) owns entry (x ^ xm, x) — distinct groups have distinct masks
+__global__ __launch_bounds__(256) void k_dm_scatter(DmScatterArgs a) {
+    const uint32_t D = 1u << a.n;
+    const uint32_t gi = blockIdx.x / a.xblocks;
+    const uint32_t x = (blockIdx.x % a.xblocks) * 256u + threadIdx.x;
+    if (x >= D) return;
+    const int b = blockIdx.y, k = a.k0 + int(blockIdx.z);
+    const size_t row = size_t(a.n_tsave) * a.B;
+    const double* g = a.gexp + size_t(k) * a.B + b;
+    const PauliGroup gr = a.t.agroups[gi];
+    const uint32_t xp = x ^ gr.xm;
+    double sr = 0.0, si = 0.0;
+    if (gr.xm == 0u)
+        for (int o = 0; o < a.n_diag; ++o) {
+            const double go = g[size_t(o) * row];
+            if (go != 0.0) sr = fma(go, a.diag[(size_t(o) << a.n) + x], sr);
+        }
+    for (uint32_t s = gr.first; s < gr.first + gr.count; ++s) {
+        const PauliString st = a.t.astrings[s];
+        const double go = g[size_t(a.n_diag + int(st.pad)) * row];
+        if (go == 0.0) continue;
+        const bool neg = (__popc(xp & st.zm) & 1u) != 0u;
+        sr += neg ? -go * st.wr : go * st.wr;   // g w conj(i^ny (-1)^...)
+        si += neg ? go * st.wi : -go * st.wi;
+    }
+    if (sr == 0.0 && si == 0.0) return;
+    double2* dst = a.out + (size_t(blockIdx.z) * a.B + b) * (size_t(D) << a.n) + (size_t(xp) << a.n) + x;
+    const double2 cur = *dst;
+    *dst = make_double2(cur.x + sr, cur.y + si);
+}

@@ -1,5 +1,5 @@
 // overlap_launch.hpp — state-overlap observables (overlap_kernels.hpp): the evaluation launches of the forward sweeps, and the
-// observable cotangent (Pauli part, then overlap part, then the reduced-density-matrix part, in one workspace buffer) the adjoint sweeps inject at a save point.
+// observable cotangent (Pauli part, then overlap part, then the reduced-density-matrix part, then the density-matrix rows, in one workspace buffer) the adjoint sweeps inject at a save point.
 #pragma once
 
 namespace {
@@ -41,13 +41,14 @@ int launch_overlap_expect(const ForwardCtx& c, const double2* psi, size_t kstrid
     return RYDIFF_OK;
 }
 
-// every native observable that is evaluated by a launch of its own (Pauli strings, overlaps, reduced density matrices) on the states of k0 .. k0 + nk - 1,
+// every native observable that is evaluated by a launch of its own (Pauli strings, overlaps, reduced density matrices, density-matrix rows) on the states of k0 .. k0 + nk - 1,
 // and the measurement shots of the sampled save points among them
 int launch_observables_expect(const ForwardCtx& c, const double2* psi, size_t kstride, int k0, int nk, const BatchSlice& bs) {
     if (const int rc = launch_pauli_expect(c, psi, kstride, k0, nk, bs)) return rc;
     if (const int rc = launch_overlap_expect(c, psi, kstride, k0, nk, bs)) return rc;
     if (const int rc = launch_rdm_expect(c, psi, kstride, k0, nk, bs)) return rc;
-    return launch_shots(c, psi, kstride, k0, nk, bs);
+    if (const int rc = launch_dm_expect(c, psi, kstride, k0, nk, bs)) return rc;
+    return c.rt.pl.dm_shots ? launch_dm_shots(c, psi, kstride, k0, nk, bs) : launch_shots(c, psi, kstride, k0, nk, bs);
 }
 
 // out[kk] = grad_states[k0 + kk] + 2 sum_o g_o O_o psi_{k0 + kk} + sum_o (gRe + i gIm)_o phi_o + sum_o ((G + G^dagger)_{A_o} (x) 1) psi_{k0 + kk},
@@ -75,13 +76,17 @@ void launch_observable_cotangent(const PauliInject& pi, const double2* psi, cons
         hipLaunchKernelGGL(k_overlap_apply, dim3(unsigned((pl.dim + 255) / 256), unsigned(pl.B), unsigned(nk)), dim3(256), 0, pi.stream, a);
         base = out;
     }
-    if (pi.rdm_gexp) launch_rdm_apply(pi, psi, entry, kmul, k0, nk, base, out);
+    if (pi.rdm_gexp) {
+        launch_rdm_apply(pi, psi, entry, kmul, k0, nk, base, out);
+        base = out;
+    }
+    if (pi.dm_gexp) launch_dm_apply(pi, psi, entry, kmul, k0, nk, base, out);
 }
 
 // launch-per-factor adjoint sweeps: the cotangent injected at save point k, written into the one reused workspace buffer right
 // before the launch that reads it (stream order keeps the previous reader ahead of this write)
 const double2* observable_cotangent(const PauliInject& pi, int k) {
-    launch_observable_cotangent(pi, (pi.gexp || pi.rdm_gexp) ? pi.state_at(k) : nullptr, nullptr, 0, k, 1, pi.buf);
+    launch_observable_cotangent(pi, (pi.gexp || pi.rdm_gexp || (pi.dm_gexp && pi.rt->pl.dm_purity)) ? pi.state_at(k) : nullptr, nullptr, 0, k, 1, pi.buf);
     return pi.buf;
 }
 

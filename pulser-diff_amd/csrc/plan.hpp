@@ -93,6 +93,20 @@ struct Plan {
     int n_shots = 0;
     std::vector<int32_t> shot_times;
     size_t off_shot_sums = 0, off_shot_prefix = 0;
+    // density-matrix observables (dm_kernels.hpp): n atoms (0: none); Pauli strings over the atoms grouped by flip mask per observable
+    // (the evaluation) and over ALL observables (the cotangent scatter: one owner per entry; PauliString.pad = the observable)
+    int dm_n = 0, n_dm_diag = 0, n_dm_pobs = 0, n_dm_fid = 0, dm_fid_batch = 1, dm_purity = 0, dm_shots = 0;
+    std::vector<int32_t> dm_gfirst;
+    std::vector<PauliGroup> dm_groups, dm_agroups;
+    std::vector<PauliString> dm_strings, dm_astrings;
+    size_t off_dm = 0;
+    int dm_rows() const { return n_dm_diag + n_dm_pobs + n_dm_fid + dm_purity; }
+    int ket_rows() const { return n_obs + n_pobs + 2 * n_ov + rdm_rows; }  // rows of expect_out in front of the density-matrix rows
+    size_t dm_gfirst_bytes() const { return (dm_gfirst.size() * sizeof(int32_t) + 7) / 8 * 8; }
+    size_t dm_bytes() const {
+        return dm_gfirst_bytes() + (dm_groups.size() + dm_agroups.size()) * sizeof(PauliGroup) +
+               (dm_strings.size() + dm_astrings.size()) * sizeof(PauliString);
+    }
     size_t shot_chunks() const { return std::max<size_t>(dim >> 10, 1); }  // 2^10 amplitudes per chunk (kShotChunkBits)
     size_t pauli_gfirst_bytes() const { return (pauli_gfirst.size() * sizeof(int32_t) + 7) / 8 * 8; }
     size_t pauli_bytes() const {
@@ -335,6 +349,142 @@ inline bool build_shots(const RydProblem* p, Plan& pl, std::string& err) {
     return true;
 }
 
+// RydProblem.dm_*: the doubled register, counts, masks, tables; the string groups of the evaluation and of the cotangent scatter
+inline bool build_dm(const RydProblem* p, Plan& pl, std::string& err) {
+    pl.dm_n = pl.n_dm_diag = pl.n_dm_pobs = pl.n_dm_fid = pl.dm_purity = pl.dm_shots = 0;
+    pl.dm_fid_batch = 1;
+    pl.dm_gfirst.clear();
+    pl.dm_groups.clear();
+    pl.dm_agroups.clear();
+    pl.dm_strings.clear();
+    pl.dm_astrings.clear();
+    if (p->dm_atoms == 0) return true;
+    const int n = p->dm_atoms;
+    if (n < 0 || n > RYDIFF_MAX_DM_ATOMS) {
+        err = "dm_atoms must be in [0, " + std::to_string(RYDIFF_MAX_DM_ATOMS) + "]";
+        return false;
+    }
+    if (p->n_qubits != 2 * n) {
+        err = "dm_atoms = n declares a doubled register: n_qubits must be 2 * dm_atoms";
+        return false;
+    }
+    if (p->n_dm_diag < 0 || p->n_dm_diag > RYDIFF_MAX_DM_DIAG) {
+        err = "n_dm_diag must be in [0, " + std::to_string(RYDIFF_MAX_DM_DIAG) + "]";
+        return false;
+    }
+    if (p->n_dm_diag > 0 && !p->dm_diag) {
+        err = "missing dm_diag";
+        return false;
+    }
+    const int no = p->n_dm_pauli_obs, ns = p->n_dm_pauli_strings;
+    if (no < 0 || ns < 0 || no > RYDIFF_MAX_PAULI_STRINGS || ns > RYDIFF_MAX_PAULI_STRINGS) {
+        err = "n_dm_pauli_obs / n_dm_pauli_strings must be in [0, " + std::to_string(RYDIFF_MAX_PAULI_STRINGS) + "]";
+        return false;
+    }
+    if (no == 0 && ns != 0) {
+        err = "density-matrix Pauli strings without a Pauli observable";
+        return false;
+    }
+    if (no > 0) {
+        if (!p->dm_pauli_first || (ns > 0 && (!p->dm_pauli_x || !p->dm_pauli_z || !p->dm_pauli_w))) {
+            err = "missing density-matrix Pauli arrays (dm_pauli_first / dm_pauli_x / dm_pauli_z / dm_pauli_w)";
+            return false;
+        }
+        if (p->dm_pauli_first[0] != 0 || p->dm_pauli_first[no] != ns) {
+            err = "dm_pauli_first must start at 0 and end at n_dm_pauli_strings";
+            return false;
+        }
+        for (int o = 0; o < no; ++o)
+            if (p->dm_pauli_first[o + 1] < p->dm_pauli_first[o]) {
+                err = "dm_pauli_first must be non-decreasing";
+                return false;
+            }
+        for (int s = 0; s < ns; ++s) {
+            if (((p->dm_pauli_x[s] | p->dm_pauli_z[s]) >> n) != 0) {
+                err = "density-matrix Pauli string " + std::to_string(s) + " addresses an atom >= dm_atoms";
+                return false;
+            }
+            if (!std::isfinite(p->dm_pauli_w[s])) {
+                err = "density-matrix Pauli string " + std::to_string(s) + " has a non-finite weight";
+                return false;
+            }
+        }
+    }
+    if (p->n_dm_fid < 0 || p->n_dm_fid > RYDIFF_MAX_OVERLAPS) {
+        err = "n_dm_fid must be in [0, " + std::to_string(RYDIFF_MAX_OVERLAPS) + "]";
+        return false;
+    }
+    if (p->n_dm_fid > 0) {
+        if (p->dm_fid_batch != 1 && p->dm_fid_batch != p->batch) {
+            err = "dm_fid_batch must be 1 or batch";
+            return false;
+        }
+        if (!p->dm_fid_targets) {
+            err = "missing dm_fid_targets";
+            return false;
+        }
+    }
+    if ((p->dm_purity != 0 && p->dm_purity != 1) || (p->dm_shots != 0 && p->dm_shots != 1)) {
+        err = "dm_purity and dm_shots must be 0 or 1";
+        return false;
+    }
+    if (p->dm_shots && p->n_shots <= 0) {
+        err = "dm_shots needs n_shots > 0 (and the shot arrays)";
+        return false;
+    }
+    if (p->shard_bits > 0) {
+        err = "density-matrix observables: not implemented together with state sharding";
+        return false;
+    }
+    pl.dm_n = n;
+    pl.n_dm_diag = p->n_dm_diag;
+    pl.n_dm_pobs = no;
+    pl.n_dm_fid = p->n_dm_fid;
+    pl.dm_fid_batch = p->n_dm_fid ? p->dm_fid_batch : 1;
+    pl.dm_purity = p->dm_purity;
+    pl.dm_shots = p->dm_shots;
+    static const double ph[4][2] = {{1, 0}, {0, 1}, {-1, 0}, {0, -1}};  // i^ny
+    auto make_string = [&](int s, uint32_t row) {
+        const int ny = __builtin_popcount(p->dm_pauli_x[s] & p->dm_pauli_z[s]) & 3;
+        return PauliString{p->dm_pauli_w[s] * ph[ny][0], p->dm_pauli_w[s] * ph[ny][1], to_index_mask(p->dm_pauli_z[s], n), row};
+    };
+    // grouped by flip mask: per observable (evaluation), over all of them (cotangent scatter)
+    auto group_strings = [&](std::vector<int>& order, std::vector<PauliGroup>& groups, std::vector<PauliString>& strings,
+                             const std::vector<uint32_t>& row_of) {
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return p->dm_pauli_x[a] < p->dm_pauli_x[b]; });
+        for (size_t i = 0; i < order.size(); ++i) {
+            const int s = order[i];
+            if (i == 0 || p->dm_pauli_x[s] != p->dm_pauli_x[order[i - 1]])
+                groups.push_back({to_index_mask(p->dm_pauli_x[s], n), uint32_t(strings.size()), 0u, kPauliDirect});
+            groups.back().count += 1;
+            strings.push_back(make_string(s, row_of[s]));
+        }
+    };
+    std::vector<uint32_t> row_of(ns, 0u);
+    for (int o = 0; o < no; ++o)
+        for (int s = p->dm_pauli_first[o]; s < p->dm_pauli_first[o + 1]; ++s) row_of[s] = uint32_t(o);
+    pl.dm_gfirst.assign(no + 1, 0);
+    for (int o = 0; o < no; ++o) {
+        pl.dm_gfirst[o] = int32_t(pl.dm_groups.size());
+        std::vector<int> order;
+        for (int s = p->dm_pauli_first[o]; s < p->dm_pauli_first[o + 1]; ++s) order.push_back(s);
+        group_strings(order, pl.dm_groups, pl.dm_strings, row_of);
+    }
+    pl.dm_gfirst[no] = int32_t(pl.dm_groups.size());
+    if (pl.n_dm_diag) pl.dm_agroups.push_back({0u, 0u, 0u, kPauliDirect});  // the diagonal tables ride the xm = 0 group
+    {
+        std::vector<int> order(ns);
+        for (int s = 0; s < ns; ++s) order[s] = s;
+        std::vector<PauliGroup> g;
+        group_strings(order, g, pl.dm_astrings, row_of);
+        for (const PauliGroup& q : g) {
+            if (q.xm == 0u && pl.n_dm_diag) pl.dm_agroups[0] = q;  // (sorted by mask: the strings of xm = 0 come first)
+            else pl.dm_agroups.push_back(q);
+        }
+    }
+    return true;
+}
+
 // `width`: half spectral width of the generator when it is already known (<= 0: not yet) — the continuous solver's
 // sub-step shrinks with it.
 inline bool build_plan(const RydProblem* p, Plan& pl, std::string& err, double width = -1.0) {
@@ -420,6 +570,7 @@ inline bool build_plan(const RydProblem* p, Plan& pl, std::string& err, double w
     if (!build_overlaps(p, pl, err)) return false;
     if (!build_rdms(p, pl, err)) return false;
     if (!build_shots(p, pl, err)) return false;
+    if (!build_dm(p, pl, err)) return false;
     pl.shard_bits = p->shard_bits;
     if (pl.shard_bits < 0 || pl.shard_bits > 6 || pl.shard_bits >= pl.N) {
         err = "shard_bits must be in [0, min(6, n_qubits - 1)]";
@@ -635,7 +786,8 @@ inline size_t carve(Plan& pl, int tape_mode, bool need_backward, int chain_slots
     pl.off_pauli = take(pl.pauli_bytes());
     // one-launch sweeps: the trajectory the Pauli and overlap observables are evaluated on (and the shots drawn from) where the
     // caller keeps none
-    pl.off_pauli_traj = take(((pl.n_pobs || pl.n_ov || pl.n_rdm || pl.n_shots) && pl.N <= 12) ? size_t(pl.T + 1) * pl.state_bytes : 0);
+    pl.off_pauli_traj = take(((pl.n_pobs || pl.n_ov || pl.n_rdm || pl.n_shots || pl.dm_rows()) && pl.N <= 12) ? size_t(pl.T + 1) * pl.state_bytes : 0);
+    pl.off_dm = take(pl.dm_n ? pl.dm_bytes() : 0);  // string tables of the density-matrix observables
     pl.off_shot_sums = take(pl.n_shots ? size_t(pl.B) * pl.shot_chunks() * sizeof(double) : 0);
     pl.off_shot_prefix = take(pl.n_shots ? size_t(pl.B) * pl.shot_chunks() * sizeof(double) : 0);
     pl.total_fwd = off;
@@ -650,7 +802,7 @@ inline size_t carve(Plan& pl, int tape_mode, bool need_backward, int chain_slots
         pl.off_wtot = take(pl.dim * (pl.shard_bits ? size_t(pl.B) : 1) * sizeof(double));  // sharded: one weight slab per rank of the call
         // observable cotangent grad_states[k] + 2 sum_o g_o O_o psi_k + sum_o (gRe + i gIm)_o phi_o: one state, reused in stream order
         // (one-launch adjoints: every k)
-        pl.off_pauli_cot = take((pl.n_pobs || pl.n_ov || pl.n_rdm) ? size_t(pl.N <= 12 ? pl.T + 1 : 1) * pl.state_bytes : 0);
+        pl.off_pauli_cot = take((pl.n_pobs || pl.n_ov || pl.n_rdm || pl.dm_rows()) ? size_t(pl.N <= 12 ? pl.T + 1 : 1) * pl.state_bytes : 0);
         pl.off_meta2 = take(std::max(E * 40, size_t(pl.T + 1) * sizeof(int32_t)));  // StageBwdDev records, or the save-point flags of the one-launch adjoint
     }
     return off;

@@ -154,6 +154,7 @@ int upload_words(hipStream_t stream, void* dst, const void* src, size_t bytes) {
 struct Runtime;
 void assign_pauli_layouts(Runtime& rt);                                  // pauli_launch.hpp
 int upload_pauli_tables(const Plan& pl, char* ws, hipStream_t stream);  // pauli_launch.hpp
+int upload_dm_tables(const Plan& pl, char* ws, hipStream_t stream);     // dm_launch.hpp
 
 std::mutex g_poly_mutex;
 std::vector<PolyDesign> g_poly_cache;
@@ -439,6 +440,10 @@ int prepare(const RydProblem* p, const RydPlanInfo* info, void* workspace, size_
         rc = upload_pauli_tables(pl, ws, stream);
         if (rc) return rc;
     }
+    if (pl.dm_n) {
+        rc = upload_dm_tables(pl, ws, stream);
+        if (rc) return rc;
+    }
     if (pl.NC > 0) {
         const int rc2 = launch_expand(pl, ws, static_cast<const double2*>(p->amp_tables), p->det_tables,
                                       reinterpret_cast<double*>(ws + pl.off_coef), stream);
@@ -531,7 +536,8 @@ void shard_groups(const Plan& pl, int (&grp)[kShardMaxBits]) {
 // Cotangents of the Pauli-string and state-overlap observables: they ride the grad_states route — k_pauli_apply (pauli_launch.hpp)
 // writes grad_states[k] + 2 sum_o g_o O_o psi_k into a workspace buffer, k_overlap_apply (overlap_launch.hpp) adds
 // sum_o (gRe + i gIm)_o phi_o to it (or to grad_states[k] where no Pauli observable has a cotangent), and the injecting launch reads
-// that buffer instead of grad_states[k]; k_rdm_apply (rdm_launch.hpp) adds sum_o ((G + G^dagger)_{A_o} (x) 1) psi_k the same way
+// that buffer instead of grad_states[k]; k_rdm_apply (rdm_launch.hpp) adds sum_o ((G + G^dagger)_{A_o} (x) 1) psi_k the same way, and
+// k_dm_apply / k_dm_scatter (dm_launch.hpp) the cotangents of the density-matrix rows
 struct PauliInject {
     const Runtime* rt = nullptr;
     char* ws = nullptr;
@@ -541,6 +547,9 @@ struct PauliInject {
     const double* ov_gexp = nullptr;  // &grad_expect[n_obs + n_pobs][0][0], or nullptr: no overlaps
     const double2* ov_targets = nullptr;
     const double* rdm_gexp = nullptr; // &grad_expect[n_obs + n_pobs + 2 n_ov][0][0], or nullptr: no reduced density matrices
+    const double* dm_gexp = nullptr;  // the first density-matrix row of grad_expect, or nullptr: no density-matrix rows
+    const double* dm_diag = nullptr;  // RydProblem.dm_diag / dm_fid_targets
+    const double2* dm_phi = nullptr;
     double2* buf = nullptr;           // one state (one-launch adjoints: n_tsave states)
     std::function<const double2*(int)> state_at;  // the state at save point k
 };
@@ -625,6 +634,7 @@ struct ForwardCtx : SweepCtx {
     double* pauli_out = nullptr;   // &expect_out[n_obs][0][0] where Pauli observables are evaluated
     double* overlap_out = nullptr; // &expect_out[n_obs + n_pobs][0][0] where overlaps are evaluated
     double* rdm_out = nullptr;     // &expect_out[n_obs + n_pobs + 2 n_ov][0][0] where reduced density matrices are evaluated
+    double* dm_out = nullptr;      // the first density-matrix row of expect_out where such rows are evaluated
     const double* shot_u = nullptr;  // RydProblem.shot_uniforms / shots_out where shots are drawn (rydiff_forward with n_shots > 0)
     uint32_t* shots_out = nullptr;
 };

@@ -45,6 +45,7 @@ using namespace rydiff;
 #include "overlap_kernels.hpp"
 #include "rdm_kernels.hpp"
 #include "shots_kernels.hpp"
+#include "dm_kernels.hpp"
 #include "tangent_kernels.hpp"
 static_assert(sizeof(PersistFactor) == 48, "plan.hpp sizes the factor table with 48 bytes per entry");
 
@@ -55,6 +56,7 @@ static_assert(sizeof(PersistFactor) == 48, "plan.hpp sizes the factor table with
 #include "pair_launch.hpp"
 #include "shots_launch.hpp"
 #include "rdm_launch.hpp"
+#include "dm_launch.hpp"
 #include "overlap_launch.hpp"
 #include "tangent_launch.hpp"
 #include "persist_launch.hpp"
@@ -472,12 +474,13 @@ int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi
     c.pauli_out = (expect_out && pl.n_pobs) ? expect_out + size_t(pl.n_obs) * (pl.T + 1) * pl.B : nullptr;
     c.overlap_out = (expect_out && pl.n_ov) ? expect_out + size_t(pl.n_obs + pl.n_pobs) * (pl.T + 1) * pl.B : nullptr;
     c.rdm_out = (expect_out && pl.n_rdm) ? expect_out + size_t(pl.n_obs + pl.n_pobs + 2 * pl.n_ov) * (pl.T + 1) * pl.B : nullptr;
+    c.dm_out = (expect_out && pl.dm_rows()) ? expect_out + size_t(pl.ket_rows()) * (pl.T + 1) * pl.B : nullptr;
     if (pl.n_shots) {  // drawn wherever launch_observables_expect sees a sampled save point
         c.shot_u = p->shot_uniforms;
         c.shots_out = p->shots_out;
     }
-    if (c.want_exp || c.pauli_out || c.overlap_out || c.rdm_out)
-        HIP_TRY(hipMemsetAsync(expect_out, 0, size_t(pl.n_obs + pl.n_pobs + 2 * pl.n_ov + pl.rdm_rows) * (pl.T + 1) * pl.B * sizeof(double), stream));
+    if (c.want_exp || c.pauli_out || c.overlap_out || c.rdm_out || c.dm_out)
+        HIP_TRY(hipMemsetAsync(expect_out, 0, size_t(pl.ket_rows() + pl.dm_rows()) * (pl.T + 1) * pl.B * sizeof(double), stream));
     if (c.want_exp) {
         rc = launch_expect(c, c.start, 0);
         if (rc) return rc;
@@ -518,7 +521,7 @@ int rydiff_backward(const RydProblem* p, const RydPlanInfo* info, const void* st
     c.inj.gexp = have_gexp ? grad_expect : nullptr;
     c.inj.obs = p->obs_diag;
     c.inj.n_obs = have_gexp ? pl.n_obs : 0;
-    if (grad_expect && (pl.n_pobs || pl.n_ov || pl.n_rdm)) {
+    if (grad_expect && (pl.n_pobs || pl.n_ov || pl.n_rdm || pl.dm_rows())) {
         c.pauli.rt = &rt;
         c.pauli.ws = c.ws;
         c.pauli.stream = stream;
@@ -527,6 +530,9 @@ int rydiff_backward(const RydProblem* p, const RydPlanInfo* info, const void* st
         c.pauli.ov_gexp = pl.n_ov ? grad_expect + size_t(pl.n_obs + pl.n_pobs) * (pl.T + 1) * pl.B : nullptr;
         c.pauli.ov_targets = static_cast<const double2*>(p->overlap_targets);
         c.pauli.rdm_gexp = pl.n_rdm ? grad_expect + size_t(pl.n_obs + pl.n_pobs + 2 * pl.n_ov) * (pl.T + 1) * pl.B : nullptr;
+        c.pauli.dm_gexp = pl.dm_rows() ? grad_expect + size_t(pl.ket_rows()) * (pl.T + 1) * pl.B : nullptr;
+        c.pauli.dm_diag = p->dm_diag;
+        c.pauli.dm_phi = static_cast<const double2*>(p->dm_fid_targets);
         if (pl.n_rdm && (rc = rdm_apply_prepare())) return rc;
         c.pauli.buf = reinterpret_cast<double2*>(c.ws + pl.off_pauli_cot);
         c.pauli.state_at = [&c](int k) { return c.state_at(k); };

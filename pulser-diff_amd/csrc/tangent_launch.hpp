@@ -17,6 +17,7 @@ int tangent_validate(const RydProblem* p, const RydPlanInfo* info, int n_dir) {
         return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented with conditioned flips / ones-counting terms (three-level registers)");
     if (p->n_shots > 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: measurement shots are not implemented (n_shots > 0): draw them in rydiff_forward");
     if (p->n_rdms > 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: reduced density matrices are not implemented (n_rdms > 0)");
+    if (p->dm_atoms != 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: density-matrix registers are not implemented (dm_atoms > 0)");
     return RYDIFF_OK;
 }
 

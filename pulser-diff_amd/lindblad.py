@@ -19,14 +19,18 @@ linear piece is advanced by commutator-free Magnus steps whose exponentials are 
 from __future__ import annotations
 
 import itertools
-from typing import Optional
+from dataclasses import dataclass, field
+from typing import Optional, Sequence, Union
 
 import numpy as np
 import torch
 from torch import Tensor
 
+from .observables import DensityMatrixObservables, PauliObservable, Purity, StateOverlap, pack_overlaps
+from .shots import ShotRequest
 from .simconfig import NoiseModel
 from .solver import ProblemSpec, SolverType, evolve, tolerance_from_options
+from .utils import DiagonalObservable
 
 CD = torch.complex128
 MAX_ME_QUBITS = 12  # 4^12 amplitudes = 256 MiB per density matrix
@@ -112,9 +116,73 @@ def doubled_pair_terms(pair_terms, n: int, dissipator: Optional[np.ndarray] = No
     return tuple(out)
 
 
-def mesolve(ham, psi0: Tensor, tsave: Tensor, noise: NoiseModel, options: Optional[dict] = None) -> tuple[Tensor, dict]:
+@dataclass
+class MasterEquationResult:
+    """What ``mesolve`` returns.  Unpacks like the pair it used to return: ``rho, stats = mesolve(...)``."""
+
+    states: Tensor  # (n_t, dim, dim, B); empty (0, dim, dim, B) with store_states=False
+    stats: dict
+    expect: list = field(default_factory=list)  # one real (n_t, B) tensor per entry of `observables`, evaluated natively (differentiable)
+    shots: Optional[ShotRequest] = None  # the request, holding the native shots (.indices: basis-state indices of the ATOMS)
+
+    def __iter__(self):
+        return iter((self.states, self.stats))
+
+
+def pack_dm_observables(observables: Sequence, n: int, batch: int, device, shots: bool = False):
+    """``observables`` of a master-equation run -> (``DensityMatrixObservables`` or None, the row of every observable).  Takes
+    ``DiagonalObservable`` / diagonal ``(dim, dim)`` tensors / ``(dim,)`` diagonals, ``PauliObservable``, ``StateOverlap`` (the
+    fidelity ``<phi|rho|phi>``) and ``Purity``.  Strings go to the library as they are: the master equation runs in no rotating
+    frame (``mesolve`` hands ``ham.amp_tables`` over, never ``amp_tables_frame``)."""
+    dim = 2 ** n
+    diags, paulis, overlaps, purity, kinds = [], [], [], False, []
+    for obs in observables:
+        if isinstance(obs, Purity):
+            purity = True
+            kinds.append(("purity", 0))
+        elif isinstance(obs, StateOverlap):
+            kinds.append(("fid", len(overlaps)))
+            overlaps.append(obs)
+        elif isinstance(obs, PauliObservable):
+            if obs.n_qubits != n:
+                raise ValueError(f"PauliObservable on {obs.n_qubits} qubits handed to a register of {n}")
+            kinds.append(("pauli", len(paulis)))
+            paulis.append(obs)
+        else:
+            if isinstance(obs, DiagonalObservable):
+                d = obs.diag
+            elif isinstance(obs, Tensor) and obs.ndim == 2:
+                dense = obs.to_dense() if obs.is_sparse else obs
+                if not torch.equal(torch.diag(torch.diagonal(dense)), dense):
+                    raise ValueError("Only diagonal tensors can be evaluated natively; hand off-diagonal ones over as PauliObservable.")
+                d = torch.diagonal(dense).real
+            elif isinstance(obs, Tensor) and obs.ndim == 1:
+                d = obs.real if obs.is_complex() else obs
+            else:
+                raise TypeError("observables of a master-equation run must be DiagonalObservable / PauliObservable / StateOverlap / "
+                                f"Purity objects or diagonal tensors, got {type(obs)}")
+            if d.shape[0] != dim:
+                raise ValueError(f"diagonal observable of dimension {d.shape[0]} handed to a register of dimension {dim}")
+            kinds.append(("diag", len(diags)))
+            diags.append(d.to(device, torch.float64))
+    if not kinds and not shots:
+        return None, []
+    dm = DensityMatrixObservables(n, diag=torch.stack(diags) if diags else None, pauli=paulis or None,
+                                  targets=pack_overlaps(overlaps, dim, batch, device) if overlaps else None, purity=purity, shots=shots)
+    first = {"diag": 0, "pauli": len(diags), "fid": len(diags) + len(paulis), "purity": len(diags) + len(paulis) + len(overlaps)}
+    return dm, [first[kind] + i for kind, i in kinds]
+
+
+def mesolve(ham, psi0: Tensor, tsave: Tensor, noise: NoiseModel, options: Optional[dict] = None,
+            observables: Optional[Sequence] = None, shots: Union[None, int, ShotRequest] = None,
+            store_states: bool = True) -> MasterEquationResult:
     """Density matrices rho(t_k) of shape (n_t, dim, dim, B) for the structured Hamiltonian ``ham`` and the collapse
-    operators of ``noise``; psi0: (dim, B) kets (rho0 = |psi0><psi0|, ``backend.py:503``)."""
+    operators of ``noise``; psi0: (dim, B) kets (rho0 = |psi0><psi0|, ``backend.py:503``).
+
+    ``observables`` (see ``pack_dm_observables``) are evaluated natively at every evaluation time while rho is on the device
+    (``MasterEquationResult.expect``, differentiable); ``shots``: an int (that many at the final time) or a ``ShotRequest``, drawn
+    natively from the diagonal of rho; ``store_states=False`` keeps the ``(n_t, 4^n)`` trajectory out of the result (``states``
+    is then empty) — gradients of the native values need no stored state."""
     n = ham._size
     if n > MAX_ME_QUBITS:
         raise ValueError(f"The master-equation solver keeps 4^N amplitudes; limited to {MAX_ME_QUBITS} qubits.")
@@ -125,14 +193,18 @@ def mesolve(ham, psi0: Tensor, tsave: Tensor, noise: NoiseModel, options: Option
     pair_terms = doubled_pair_terms(getattr(ham, "pair_terms", ()), n, block)  # dissipators + the XY exchange (if any)
     # default accuracy target one decade below the ket solver's: the calibration of the Magnus step is a little optimistic
     # for non-normal (dissipative) generators
-    spec = ProblemSpec(2 * n, ham.dt, ham.n_samples, am2, dm2, solver=SolverType.DP5_SE,
-                       tol=tolerance_from_options(options) or ME_DEFAULT_TOL, store_states=True, pair_terms=pair_terms,
-                       piece_refine=getattr(ham, "piece_refine", None))  # same time structure on the doubled register
     psi = psi0.to(dev, CD)
     if psi.ndim == 1:
         psi = psi.unsqueeze(1)
     dim = psi.shape[0]
+    if shots is not None and not isinstance(shots, ShotRequest):
+        shots = ShotRequest(int(shots))
+    dm, rows = pack_dm_observables(list(observables or []), n, psi.shape[1], dev, shots=shots is not None)
+    spec = ProblemSpec(2 * n, ham.dt, ham.n_samples, am2, dm2, solver=SolverType.DP5_SE,
+                       tol=tolerance_from_options(options) or ME_DEFAULT_TOL, store_states=bool(store_states), pair_terms=pair_terms,
+                       piece_refine=getattr(ham, "piece_refine", None),  # same time structure on the doubled register
+                       dm=dm, shots=shots)
     rho0 = torch.einsum("xb,yb->bxy", psi, psi.conj()).reshape(psi.shape[1], dim * dim).contiguous()
-    states, _ = evolve(amp2, det2, u2, tsave, rho0, spec, None)  # (n_t, B, dim^2)
+    states, expect = evolve(amp2, det2, u2, tsave, rho0, spec, None)  # (n_t, B, dim^2), (rows, n_t, B)
     rho = states.reshape(states.shape[0], states.shape[1], dim, dim).permute(0, 2, 3, 1)
-    return rho, dict(spec.options.get("_last_stats", {}))
+    return MasterEquationResult(rho, dict(spec.options.get("_last_stats", {})), [expect[r] for r in rows], shots)

@@ -196,6 +196,14 @@ class QuantumModel(Module):
         evaluation_times, results = self._run(observables=[obs], store_states=False)
         return evaluation_times, results.overlap(obs)
 
+    def fidelity(self, target) -> tuple[Tensor, Tensor]:
+        """Evaluation times and the fidelity with ``target``, real ``(n_t, B)``, evaluated and differentiated natively without a stored
+        trajectory: ``|<target|psi(t)>|^2`` for kets, ``<target| rho(t) |target>`` when collapse-operator noise (or
+        ``SolverType.DP5_ME``) makes the run a master-equation one.  ``target``: a ``StateOverlap`` or its targets."""
+        obs = target if isinstance(target, StateOverlap) else StateOverlap(target)
+        evaluation_times, results = self._run(observables=[obs], store_states=False)
+        return evaluation_times, results.fidelity(obs)
+
     def reduced_density_matrix(self, qubits) -> tuple[Tensor, Tensor]:
         """Evaluation times and the state of the subsystem ``qubits`` (indices in register order, or a ``ReducedDensityMatrix``),
         complex ``(n_t, B, 2^m, 2^m)``, evaluated and differentiated natively: no trajectory is stored or handed to autograd."""

@@ -379,3 +379,125 @@ def pack_rdms(observables: Sequence[ReducedDensityMatrix], n_qubits: int) -> np.
             raise TypeError(f"expected ReducedDensityMatrix objects, got {type(o)}")
         o.check(n_qubits)
     return np.asarray([o.mask for o in observables], dtype=np.uint32)
+
+
+class Purity:
+    """``Tr rho^2`` of the register state at every evaluation time — handed to ``run(observables=[...])`` of a master-equation run
+    it is evaluated (as ``sum |rho_xy|^2``) and differentiated natively (``include/rydiff.h``: ``RydProblem.dm_purity``); read it
+    with ``results.purity()``.  Not an operator: ``results.expect`` does not take it."""
+
+
+def fidelity_states(obs: StateOverlap, states: Tensor) -> Tensor:
+    """``<phi_b| rho_b(t_k) |phi_b>`` in torch, real ``(n_t, B)``: stored density matrices ``(n_t, dim, dim, B)``, or kets
+    ``(n_t, dim, B)`` (``|<phi|psi>|^2``).  The real part of the bilinear form, as the library takes it (no Hermiticity assumed)."""
+    if states.is_sparse:
+        states = states.to_dense()
+    if states.ndim == 3:
+        return overlap_states(obs, states).abs() ** 2
+    dim = obs.targets.shape[0]
+    if states.ndim != 4 or states.shape[1] != dim or states.shape[2] != dim:
+        raise ValueError(f"StateOverlap with targets of dimension {dim} expects density matrices (n_t, {dim}, {dim}, B), got {tuple(states.shape)}")
+    if obs.batch not in (1, states.shape[3]):
+        raise ValueError(f"StateOverlap holds {obs.batch} targets but the states have batch {states.shape[3]}")
+    phi = obs.targets.to(states.device).expand(dim, states.shape[3])
+    return torch.einsum("xb,txyb,yb->tb", phi.conj(), states.to(torch.complex128), phi).real
+
+
+def purity_states(states: Tensor) -> Tensor:
+    """``Tr rho^2`` in torch, real ``(n_t, B)``: ``sum |rho_xy|^2`` of stored density matrices ``(n_t, dim, dim, B)`` (the library's
+    row: equal to the trace for Hermitian rho), ``<psi|psi>^2`` of kets ``(n_t, dim, B)``."""
+    if states.is_sparse:
+        states = states.to_dense()
+    if states.ndim == 4:
+        return (states.real ** 2 + states.imag ** 2).sum(dim=(1, 2))
+    if states.ndim != 3:
+        raise ValueError(f"expected kets (n_t, dim, B) or density matrices (n_t, dim, dim, B), got {tuple(states.shape)}")
+    return (states.real ** 2 + states.imag ** 2).sum(dim=1) ** 2
+
+
+MAX_DM_ATOMS = 12  # RYDIFF_MAX_DM_ATOMS
+MAX_DM_DIAG = 64  # RYDIFF_MAX_DM_DIAG
+
+
+class DensityMatrixObservables:
+    """The density-matrix block of ``RydProblem`` (``include/rydiff.h``: ``dm_*``) as ``ProblemSpec.dm`` carries it: the register
+    is the doubled register of ``n_atoms`` atoms, ``vec(rho)[x * 2^n + y] = rho[x][y]``, and these functionals of rho are evaluated
+    (and differentiated) natively at every evaluation time.  Their rows follow all other rows of ``expect``, in this order:
+
+    ``diag``     float64 DEVICE tensor ``(n_diag, 2^n)``: ``sum_x o[x] Re rho[x][x]``
+    ``pauli``    list of ``PauliObservable`` on ``n_atoms`` qubits (or the four packed host arrays): ``Re Tr(O rho)``
+    ``targets``  complex128 DEVICE tensor ``(n_fid, 1 | B, 2^n)`` (``pack_overlaps``): ``Re <phi|rho|phi>``; constants
+    ``purity``   one row ``sum |rho_xy|^2``
+    ``shots``    the shots of ``ProblemSpec.shots`` are drawn from ``max(Re rho[x][x], 0)`` (atom indices ``x < 2^n``)"""
+
+    def __init__(self, n_atoms: int, diag=None, pauli=None, targets=None, purity: bool = False, shots: bool = False):
+        self.n_atoms = int(n_atoms)
+        self.diag = diag
+        self.pauli = pauli
+        self.targets = targets
+        self.purity = bool(purity)
+        self.shots = bool(shots)
+
+    @property
+    def n_diag(self) -> int:
+        return 0 if self.diag is None else int(self.diag.shape[0])
+
+    @property
+    def n_fid(self) -> int:
+        return 0 if self.targets is None else int(self.targets.shape[0])
+
+    def packed_pauli(self):
+        """The four host arrays of ``RydProblem.dm_pauli_*`` (None: no Pauli rows); validated like the library does."""
+        if self.pauli is None or len(self.pauli) == 0:
+            return None
+        if all(isinstance(o, PauliObservable) for o in self.pauli):
+            return pack_pauli(list(self.pauli), self.n_atoms)
+        if len(self.pauli) != 4:
+            raise ValueError("DensityMatrixObservables.pauli: a list of PauliObservable or (pauli_first, pauli_x, pauli_z, pauli_w)")
+        packed = (np.ascontiguousarray(self.pauli[0], dtype=np.int32), np.ascontiguousarray(self.pauli[1], dtype=np.uint32),
+                  np.ascontiguousarray(self.pauli[2], dtype=np.uint32), np.ascontiguousarray(self.pauli[3], dtype=np.float64))
+        check_pauli(packed, self.n_atoms)
+        return packed
+
+    @property
+    def n_pauli(self) -> int:
+        packed = self.packed_pauli()
+        return 0 if packed is None else len(packed[0]) - 1
+
+    def rows(self) -> int:
+        return self.n_diag + self.n_pauli + self.n_fid + int(self.purity)
+
+    def check(self, n_qubits: int, batch: int, device=None) -> None:
+        """Every buffer against the register (the C ABI sees raw pointers): ValueError, never a bad device read."""
+        n, dim = self.n_atoms, 2 ** self.n_atoms
+        if not 1 <= n <= MAX_DM_ATOMS or n_qubits != 2 * n:
+            raise ValueError(f"a density-matrix register of {n} atoms (1 to {MAX_DM_ATOMS}) needs n_qubits = {2 * n}, got {n_qubits}")
+        for name, t, dtype, cap in (("diag", self.diag, torch.float64, MAX_DM_DIAG), ("targets", self.targets, torch.complex128, MAX_OVERLAPS)):
+            if t is None:
+                continue
+            if not isinstance(t, Tensor) or t.dtype != dtype or t.shape[-1] != dim or t.ndim != (2 if name == "diag" else 3):
+                raise ValueError(f"DensityMatrixObservables.{name}: a {dtype} tensor with last dimension {dim}, got "
+                                 f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+            if not 1 <= t.shape[0] <= cap:
+                raise ValueError(f"DensityMatrixObservables.{name}: 1 to {cap} entries, got {t.shape[0]}")
+            if device is not None and t.device != torch.device(device):
+                raise ValueError(f"DensityMatrixObservables.{name} must live on the device of the states ({device}), got {t.device}")
+        if self.targets is not None and self.targets.shape[1] not in (1, batch):
+            raise ValueError(f"DensityMatrixObservables.targets: the target batch must be 1 or the batch size {batch}, got {self.targets.shape[1]}")
+        self.packed_pauli()
+
+
+def dm_trace_indices(obs: PauliObservable):
+    """The index and phase arithmetic of the library's Pauli rows on a density matrix, as numpy arrays per string:
+    ``[(weight, rows, cols, phase), ...]`` with ``Tr(P rho) = sum_x phase[x] * rho[rows[x], cols[x]]``, ``rows = x ^ xm``,
+    ``cols = x``, ``phase[x] = i^ny (-1)^popcount((x ^ xm) & zm)``."""
+    dim = 2 ** obs.n_qubits
+    x = np.arange(dim)
+    out = []
+    for w, xm, zm, ph in obs.index_masks():
+        xp = x ^ xm
+        par = np.zeros(dim, dtype=np.int64)
+        for j in range(obs.n_qubits):
+            par ^= ((xp & zm) >> j) & 1
+        out.append((w, xp, x, ph * (1.0 - 2.0 * par)))
+    return out

@@ -19,7 +19,8 @@ import torch
 from torch import Tensor
 
 from .result import SampledResult, TorchResult
-from .observables import PauliObservable, ReducedDensityMatrix, StateOverlap, overlap_states, reduced_density_matrix
+from .observables import (PauliObservable, ReducedDensityMatrix, StateOverlap, fidelity_states, overlap_states, purity_states,
+                          reduced_density_matrix)
 from .shots import ShotRequest, bitstring_counts, indices_to_bitstrings
 from .utils import DiagonalObservable, expect, von_neumann_entropy
 
@@ -58,7 +59,8 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
                  native_expect: Optional[Tensor] = None, native_observables: Optional[list] = None,
                  stats: Optional[dict] = None, density: bool = False, native_overlaps: Optional[Tensor] = None,
                  overlap_observables: Optional[list] = None, native_shots: Optional[ShotRequest] = None,
-                 native_rdms: Optional[list] = None, rdm_observables: Optional[list] = None) -> None:
+                 native_rdms: Optional[list] = None, rdm_observables: Optional[list] = None,
+                 native_fidelities: Optional[list] = None, native_purity: Optional[Tensor] = None) -> None:
         super().__init__(size, basis_name, sim_times)
         if self._basis_name == "all":  # simresults.py:381-383
             if meas_basis not in {"ground-rydberg", "digital"}:
@@ -78,6 +80,8 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
         self._overlap_observables = list(overlap_observables or [])
         self._native_rdms = native_rdms  # per observable: complex (n_t, B, 2^m, 2^m)
         self._rdm_observables = list(rdm_observables or [])
+        self._native_fidelities = native_fidelities  # master-equation runs, per StateOverlap: real (n_t, B) = <phi|rho|phi>
+        self._native_purity = native_purity  # master-equation runs with a Purity observable: real (n_t, B)
         self._native_shots = native_shots  # filled by the solver: amplitude indices (n_shot_times, B, n_shots)
         self.solver_stats = dict(stats or {})
 
@@ -125,8 +129,8 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
             if hit and self._native_expect is not None:
                 out.append(self._native_expect[hit[0]].sum(dim=-1).to(torch.complex128))
                 continue
-            if isinstance(obs, StateOverlap):  # the projector |phi><phi|: sum_b |c_b|^2
-                out.append((self.overlap(obs).abs() ** 2).sum(dim=-1).to(torch.complex128))
+            if isinstance(obs, StateOverlap):  # the projector |phi><phi|: sum_b |c_b|^2 (kets), sum_b <phi_b|rho_b|phi_b>
+                out.append(self.fidelity(obs).sum(dim=-1).to(torch.complex128))
                 continue
             out.append(expect(obs, self.states))
         return out
@@ -137,11 +141,32 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
         if not isinstance(obs, StateOverlap):
             raise TypeError(f"overlap takes a StateOverlap, got {type(obs)}")
         if self._density:
-            raise NotImplementedError("StateOverlap is defined on kets; this is a master-equation run.")
+            raise NotImplementedError("The complex overlap is defined on kets; this is a master-equation run: results.fidelity(obs) "
+                                      "gives <phi|rho|phi>.")
         hit = [k for k, o in enumerate(self._overlap_observables) if o is obs]
         if hit and self._native_overlaps is not None:
             return self._native_overlaps[hit[0]]
         return overlap_states(obs, self.states)
+
+    def fidelity(self, obs: StateOverlap) -> Tensor:
+        """The fidelity with the target of ``obs``, real ``(n_t, B)``: ``<phi_b| rho_b(t_k) |phi_b>`` in a master-equation run,
+        ``|<phi_b|psi_b(t_k)>|^2`` for kets.  The native values when ``obs`` was handed to ``run(observables=...)``, else computed
+        from the stored states."""
+        if not isinstance(obs, StateOverlap):
+            raise TypeError(f"fidelity takes a StateOverlap, got {type(obs)}")
+        if not self._density:
+            return self.overlap(obs).abs() ** 2
+        hit = [k for k, o in enumerate(self._overlap_observables) if o is obs]
+        if hit and self._native_fidelities is not None:
+            return self._native_fidelities[hit[0]]
+        return fidelity_states(obs, self.states)
+
+    def purity(self) -> Tensor:
+        """``Tr rho^2`` at every evaluation time, real ``(n_t, B)``: the native values of a master-equation run that was handed a
+        ``Purity`` observable, else computed from the stored states (kets: ``<psi|psi>^2``, 1 for a normalised state)."""
+        if self._density and self._native_purity is not None:
+            return self._native_purity
+        return purity_states(self.states)
 
     def reduced_density_matrix(self, obs: ReducedDensityMatrix) -> Tensor:
         """``Tr_E |psi_b(t_k)><psi_b(t_k)|`` on the qubits of ``obs``, complex ``(n_t, B, 2^m, 2^m)``: the native values when ``obs``
@@ -190,7 +215,7 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
         """The native shots of evaluation time ``t_index`` as bitstring counts, when that time was sampled with exactly
         ``n_samples`` shots (first column of the initial state, like ``TorchResult.get_samples``); else None."""
         req = self._native_shots
-        if req is None or self._density or req.n_shots != n_samples:
+        if req is None or req.n_shots != n_samples:  # (master-equation runs: drawn from the diagonal of rho, atom indices as well)
             return None
         pos = req.position_of(t_index)
         if pos is None:

@@ -20,7 +20,8 @@ import torch
 from torch import Tensor
 
 from . import _native
-from .observables import PauliObservable, ReducedDensityMatrix, StateOverlap, check_pauli, pack_overlaps, pack_pauli, pack_rdms
+from .observables import (DensityMatrixObservables, PauliObservable, ReducedDensityMatrix, StateOverlap, check_pauli, pack_overlaps,
+                          pack_pauli, pack_rdms)
 from .shots import ShotRequest
 
 
@@ -78,6 +79,11 @@ class ProblemSpec:
     # measurement shots drawn natively at chosen save points (RydProblem.n_shots / shot_*): the request object receives the amplitude
     # indices (shots.ShotRequest.indices); a non-differentiable by-product, allowed next to a gradient
     shots: Optional[ShotRequest] = None
+    # density-matrix observables (RydProblem.dm_*): the register is the doubled register of a density matrix and these functionals of
+    # rho — diagonal tables, Pauli strings over the atoms, fidelities with target states, the purity — are evaluated and differentiated
+    # natively; their rows follow every other row of `expect` (observables.DensityMatrixObservables).  `dm.shots`: the shots of
+    # `shots` are drawn from the diagonal of rho
+    dm: Optional[DensityMatrixObservables] = None
 
     @property
     def n_overlaps(self) -> int:
@@ -218,6 +224,32 @@ class _Call:
         if self.rdm_masks is not None:
             p.n_rdms = len(self.rdm_masks)
             p.rdm_masks = self.rdm_masks.ctypes.data
+        self.dm_buffers = None
+        if spec.dm is not None:
+            dm = spec.dm
+            dm.check(spec.n_qubits, batch)
+            diag = None if dm.diag is None else dm.diag.contiguous()
+            targets = None if dm.targets is None else dm.targets.contiguous()
+            packed = dm.packed_pauli()
+            self.dm_buffers = (diag, targets, packed)
+            p.dm_atoms = dm.n_atoms
+            if diag is not None:
+                p.n_dm_diag = diag.shape[0]
+                p.dm_diag = diag.data_ptr()
+            if packed is not None:
+                first, px, pz, pw = packed
+                p.n_dm_pauli_obs = len(first) - 1
+                p.n_dm_pauli_strings = len(px)
+                p.dm_pauli_first = first.ctypes.data
+                p.dm_pauli_x = px.ctypes.data if len(px) else None
+                p.dm_pauli_z = pz.ctypes.data if len(px) else None
+                p.dm_pauli_w = pw.ctypes.data if len(px) else None
+            if targets is not None:
+                p.n_dm_fid = targets.shape[0]
+                p.dm_fid_batch = targets.shape[1]
+                p.dm_fid_targets = targets.data_ptr()
+            p.dm_purity = int(dm.purity)
+            p.dm_shots = int(dm.shots)
         self.problem = p
         self.shot_buffers = None
 
@@ -277,6 +309,10 @@ def _check_shapes(spec: ProblemSpec, amp: Tensor, det: Tensor, u_pairs: Tensor, 
     spec.packed_pauli()  # raises ValueError on a mask bit at or above N, inconsistent counts, too many strings
     _check_overlaps(spec, batch, device)
     spec.packed_rdms()  # raises ValueError on an empty mask, too many qubits, a bit at or above N, too many matrices
+    if spec.dm is not None:
+        spec.dm.check(nq, batch, device)
+        if spec.dm.shots and spec.shots is None:
+            raise ValueError("DensityMatrixObservables.shots needs a ShotRequest in ProblemSpec.shots")
     if batch > 65535:
         raise ValueError("batch must be <= 65535 (split the columns / trajectories into several calls)")
 
@@ -420,7 +456,9 @@ class _RydbergEvolve(torch.autograd.Function):
             states = (torch.empty((n_t, batch, dim), dtype=torch.complex128, device=dev) if spec.store_states
                       else torch.empty((0, batch, dim), dtype=torch.complex128, device=dev))
             # diagonal observables first, then the Pauli ones, then Re / Im of every overlap, then Re / Im of every RDM entry
-            n_obs = call.problem.n_obs + call.problem.n_pauli_obs + 2 * call.problem.n_overlaps + spec.rdm_rows()
+            # then the density-matrix rows
+            n_obs = (call.problem.n_obs + call.problem.n_pauli_obs + 2 * call.problem.n_overlaps + spec.rdm_rows()
+                     + (spec.dm.rows() if spec.dm is not None else 0))
             expect = torch.empty((n_obs, n_t, batch), dtype=torch.float64, device=dev)
             _native.check(L.rydiff_forward(ctypes.byref(call.problem), ctypes.byref(info), _ptr(psi_c),
                                            _ptr(states) if spec.store_states else None,
@@ -679,6 +717,9 @@ def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsav
     if spec.rdms is not None:
         raise NotImplementedError("evolve_tangent evaluates no reduced density matrices (rydiff_forward_tangent: RYDIFF_ENOTIMPL); "
                                   "request them from evolve")
+    if spec.dm is not None:
+        raise NotImplementedError("evolve_tangent takes no density-matrix registers (rydiff_forward_tangent: RYDIFF_ENOTIMPL); "
+                                  "differentiate evolve instead")
     if spec.shots is not None:
         raise NotImplementedError("evolve_tangent draws no measurement shots (rydiff_forward_tangent: RYDIFF_ENOTIMPL); request them from evolve")
     L = _native.lib()
