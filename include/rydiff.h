@@ -440,6 +440,32 @@ size_t rydiff_tangent_workspace_bytes(const RydProblem* p, const RydPlanInfo* in
 int rydiff_forward_tangent(const RydProblem* p, const RydPlanInfo* info, const RydTangent* tangent, const void* psi0,
                            double* expect_out, double* dexpect_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Quantum geometry from the tangent sweep: the same sweep as rydiff_forward_tangent, which at every save point also takes the inner
+ * products of the vectors it carries with each other.  With v_0 = psi(t_k) and v_{1+d} = d psi(t_k) / d theta_d,
+ *   G_ij(t_k) = <v_i|v_j> = sum_y conj(v_i[y]) v_j[y]          (conjugate on the LEFT index, so G_ji = conj(G_ij))
+ * from which the caller forms, with N = G_00 (valid for unnormalised states),
+ *   quantum geometric tensor   Q_de = G_{1+d,1+e} / N - G_{1+d,0} G_{0,1+e} / N^2
+ *   quantum Fisher information F = 4 Re Q,       Berry curvature  -2 Im Q
+ * and, together with the overlap rows <phi|dpsi_d>, Gauss-Newton terms of fidelity losses.
+ *   gram_out     DEVICE complex128 [n_tsave][B][1 + n_dir][1 + n_dir] (required): the FULL Hermitian matrix per save point and
+ *                trajectory — the lower triangle is the exact conjugate of the upper one, Im G_ii is an exact 0.  Every entry is
+ *                written, k = 0 included (there G is the Gram matrix of psi0 and d_psi0); neither gram_out nor the workspace needs
+ *                to be cleared.  A direction padded to the kernel's width (n_dir 5, 7) leaves no trace in the output.
+ *   dexpect_out  as in rydiff_forward_tangent, or NULL: the row tangents are skipped
+ *   workspace    DEVICE, >= rydiff_geometry_workspace_bytes(p, info, n_dir): the tangent sweep's regions and, behind them, one
+ *                partial sum per block, trajectory and entry
+ * Fixed order: the sums are formed without atomics — per thread ascending, a fixed wave64 shuffle tree, the block's four waves in
+ * order, the blocks in a fixed tree — so two calls on the same inputs return bit-identical matrices (F subtracts numbers of equal
+ * size and is inverted in natural-gradient solves).  Traffic: one read of (1 + n_dir) * B * 2^N * 16 bytes per save point on top of
+ * the sweep's; nothing of size 2^N is written.  Everything else — expect_out, the solvers, the validation before anything touches
+ * a device, what is RYDIFF_ENOTIMPL (state-sharded runs, pair terms, conditioned / ones-counting terms, shots, reduced density
+ * matrices, dm_atoms > 0) — is rydiff_forward_tangent's; RYDIFF_EINVAL also for a NULL gram_out. */
+size_t rydiff_geometry_workspace_bytes(const RydProblem* p, const RydPlanInfo* info, int n_dir);
+int rydiff_forward_geometry(const RydProblem* p, const RydPlanInfo* info, const RydTangent* tangent, const void* psi0,
+                            double* expect_out, double* dexpect_out /* may be NULL */,
+                            void* gram_out /* DEVICE complex128 [n_tsave][B][1+n_dir][1+n_dir], required */,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* One matrix-free application y = H(coefficients) x on DEVICE buffers, for get_hamiltonian-style
  * checks (backend.py:401-427) and micro-benchmarks.  c_amp: HOST complex (re,im) per amp term,
  * c_det: HOST value per det term (already interpolated, reference units as above). */

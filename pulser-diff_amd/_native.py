@@ -154,6 +154,8 @@ EXPORTS = (
     "rydiff_sizeof_tangent",
     "rydiff_tangent_workspace_bytes",
     "rydiff_forward_tangent",
+    "rydiff_geometry_workspace_bytes",
+    "rydiff_forward_geometry",
 )
 
 _lib = None
@@ -202,6 +204,11 @@ def lib() -> ctypes.CDLL:
     L.rydiff_forward_tangent.argtypes = [ctypes.POINTER(RydProblem), ctypes.POINTER(RydPlanInfo), ctypes.POINTER(RydTangent), vp, vp, vp,
                                          vp, ctypes.c_size_t, vp]
     L.rydiff_forward_tangent.restype = i32
+    L.rydiff_geometry_workspace_bytes.argtypes = [ctypes.POINTER(RydProblem), ctypes.POINTER(RydPlanInfo), i32]
+    L.rydiff_geometry_workspace_bytes.restype = ctypes.c_size_t
+    L.rydiff_forward_geometry.argtypes = [ctypes.POINTER(RydProblem), ctypes.POINTER(RydPlanInfo), ctypes.POINTER(RydTangent), vp, vp, vp,
+                                          vp, vp, ctypes.c_size_t, vp]
+    L.rydiff_forward_geometry.restype = i32
     if (L.rydiff_sizeof_problem(), L.rydiff_sizeof_plan_info(), L.rydiff_sizeof_tangent()) != (
             ctypes.sizeof(RydProblem), ctypes.sizeof(RydPlanInfo), ctypes.sizeof(RydTangent)):
         raise RuntimeError(f"{_LIB_PATH} was built from another include/rydiff.h than this binding mirrors (struct sizes differ): rebuild it")

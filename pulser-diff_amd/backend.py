@@ -33,8 +33,9 @@ from .lindblad import (MAX_ME_QUBITS, ME_DEFAULT_TOL, dissipator_block, doubled_
 from .result import SampledResult
 from .simconfig import SimConfig
 from .simresults import CoherentResults, NoisyResults, SimulationResults
-from .solver import ProblemSpec, SolverType, evolve, evolve_tangent, sesolve, tolerance_from_options
-from .observables import PauliObservable, Purity, ReducedDensityMatrix, StateOverlap
+from .solver import ProblemSpec, SolverType, evolve, evolve_geometry, evolve_tangent, sesolve, tolerance_from_options
+from .observables import PauliObservable, Purity, ReducedDensityMatrix, StateOverlap, pack_overlaps
+from .geometry import QuantumGeometry, quantum_geometric_tensor
 from .shots import MAX_SHOTS, ShotRequest, indices_to_bitstrings
 from .utils import DiagonalObservable
 
@@ -580,6 +581,111 @@ class TorchEmulator:
             grads.append(dvals[d0:d0 + m].permute(1, 2, 0).reshape(len(rows), n_t, *t.shape).to(t.device))
             d0 += m
         return Sensitivities(values, grads, "tangent", times)
+
+    def run_quantum_fisher(self, x: list, observables: list = (), solver: SolverType = SolverType.DP5_SE, dist_grad: bool = False,
+                           **options: Any) -> "QuantumGeometry":
+        """The quantum Fisher information matrix of the state w.r.t. the scalar entries of the tensors in ``x`` at EVERY evaluation
+        time, with the quantum geometric tensor, the Berry curvature and the Gram matrix they are formed from — one native
+        forward-mode sweep that carries the state and one tangent state per scalar and reduces their inner products at every save
+        point (``rydiff_forward_geometry``); no state is stored.  ``x`` is what ``run_sensitivities`` takes.  ``observables``
+        (optional): diagonal observables, ``PauliObservable`` and ``StateOverlap`` objects, whose ``values`` / ``grads`` come out as
+        in ``Sensitivities`` — a ``StateOverlap`` as two rows, Re and Im of ``c = <phi|psi>`` and of its derivatives, so that the
+        Gauss-Newton term ``2 Re(conj(dc_i) dc_j)`` of a fidelity loss can be formed from the same call.  One initial state gives
+        (n_t, D, D) matrices, several columns of it (n_t, B, D, D): the geometry of a batch is per state.  This is the PURE-state
+        quantity: runs whose state is a density matrix or an average are refused, there is no fallback loop."""
+        x = list(x)
+        if not x or not all(isinstance(t, Tensor) for t in x):
+            raise TypeError("x must be a non-empty list of tensors")
+        if any(t is self._eval_times_array for t in x):
+            raise ValueError("run_quantum_fisher differentiates w.r.t. parameters; the evaluation times are not one of them: "
+                             "run(time_grad=True) and deriv_time deliver d f(t_k) / d t_k for every k in one reverse sweep.")
+        noise = set(self.config.noise)
+        no_resampling = noise <= {"dephasing", "relaxation", "SPAM", "depolarizing", "eff_noise", "amplitude"} and (
+            "amplitude" not in noise or self.config.amp_sigma == 0.0)
+        if not no_resampling or ("SPAM" in noise and self.config.eta > 0):
+            raise NotImplementedError("run_quantum_fisher is not available in noisy runs that average over realisations: the average "
+                                      "of pure states is a mixed state, and this is the pure-state quantum Fisher information.")
+        if noise & COLLAPSE_NOISES or solver == SolverType.DP5_ME:
+            raise NotImplementedError("run_quantum_fisher is not available for master-equation runs (collapse-operator noise, DP5_ME): "
+                                      "the state is a density matrix, and the pure-state quantum Fisher information is not the "
+                                      "mixed-state one.")
+        if solver not in (SolverType.DP5_SE, SolverType.KRYLOV_SE):
+            raise ValueError(f"Solver {solver} not available.")
+        ham, dev = self._hamiltonian, self._compute_device
+        if ham.basis_name == "all":
+            raise NotImplementedError("run_quantum_fisher is not available in the three-level all-basis: the native tangent sweep takes "
+                                      "no conditioned flips / ones-counting terms.")
+        if getattr(ham, "pair_terms", ()):
+            raise NotImplementedError("run_quantum_fisher is not available with the XY exchange: the native tangent sweep takes no "
+                                      "dense pair terms.")
+        observables = list(observables)
+        full = ham.dim ** ham._size
+        for obs in observables:
+            if not isinstance(obs, (DiagonalObservable, PauliObservable, StateOverlap)) and not (isinstance(obs, Tensor) and obs.ndim == 2):
+                raise TypeError("observables must be DiagonalObservable / PauliObservable / StateOverlap objects or diagonal (dim, dim) tensors")
+            if tuple(obs.shape) != (full, full):
+                raise ValueError(f"Incompatible shape of observable.Expected {(full, full)}, got {tuple(obs.shape)}.")
+        if dist_grad:
+            self._enable_dist_grad()
+        times = self._eval_times_array.detach()
+        n_t = int(times.shape[0])
+        diag_rows, pauli_objs, overlap_objs, order = [], [], [], []  # order: where observable i sits among the native rows
+        for obs in observables:
+            if isinstance(obs, PauliObservable):
+                if obs.n_qubits != ham._size:
+                    raise ValueError(f"PauliObservable on {obs.n_qubits} qubits handed to a register of {ham._size}")
+                order.append(("p", len(pauli_objs)))
+                pauli_objs.append(obs)
+                continue
+            if isinstance(obs, StateOverlap):
+                order.append(("o", len(overlap_objs)))
+                overlap_objs.append(obs)
+                continue
+            if isinstance(obs, DiagonalObservable):
+                diag = obs.diag
+            else:
+                dense = obs.to_dense() if obs.is_sparse else obs
+                if not torch.equal(torch.diag(torch.diagonal(dense)), dense):
+                    raise ValueError("Only diagonal observables can be evaluated natively; build off-diagonal ones with build_observable.")
+                diag = torch.diagonal(dense).real
+            order.append(("d", len(diag_rows)))
+            diag_rows.append(diag.to(dev, torch.float64))
+        d_amp, d_det, d_u = self._table_tangents(x)
+        n_dir = sum(int(t.numel()) for t in x)
+        psi0 = self.initial_state
+        psi_bd = psi0.reshape(psi0.shape[0], -1).transpose(0, 1).to(dev)
+        batch = int(psi_bd.shape[0])
+        spec = ham.problem_spec(solver=solver, tol=tolerance_from_options(dict(options)), store_states=False)
+        if pauli_objs:
+            spec.pauli = pauli_objs
+        if overlap_objs:  # the complex tables and the unrotated psi0 (as in run_sensitivities): the targets stay in the lab frame too
+            spec.overlaps = pack_overlaps(overlap_objs, int(psi_bd.shape[1]), batch, dev)
+        obs_diag = torch.stack(diag_rows) if diag_rows else None
+        n_real = len(diag_rows) + len(pauli_objs)
+        rows = []
+        for kind, r in order:
+            rows += [r] if kind == "d" else ([len(diag_rows) + r] if kind == "p" else [n_real + 2 * r, n_real + 2 * r + 1])
+        if d_amp is None and d_det is None and d_u is None:
+            # nothing in x reaches the tables: every tangent state is zero — <psi|psi> and the values from one sweep with one zero direction
+            expect, _, g1 = evolve_geometry(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, obs_diag,
+                                            d_psi0=torch.zeros((1,) + tuple(psi_bd.shape), dtype=torch.complex128, device=dev))
+            dexpect = torch.zeros((n_dir,) + tuple(expect.shape), dtype=torch.float64, device=expect.device)
+            gram = torch.zeros((n_t, batch, 1 + n_dir, 1 + n_dir), dtype=torch.complex128, device=g1.device)
+            gram[:, :, 0, 0] = g1[:, :, 0, 0]
+        else:
+            expect, dexpect, gram = evolve_geometry(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, obs_diag,
+                                                    d_amp=d_amp, d_det=d_det, d_u=d_u)
+        if batch == 1:
+            gram = gram[:, 0]
+        values = expect.sum(dim=-1)[rows]            # (n_rows, n_t): summed over the columns of psi0 like results.expect
+        dvals = dexpect.sum(dim=-1)[:, rows]         # (n_dir, n_rows, n_t)
+        grads, d0 = [], 0
+        for t in x:
+            m = int(t.numel())
+            grads.append(dvals[d0:d0 + m].permute(1, 2, 0).reshape(len(rows), n_t, *t.shape).to(t.device))
+            d0 += m
+        qgt = quantum_geometric_tensor(gram)
+        return QuantumGeometry(gram, qgt, 4.0 * qgt.real, -2.0 * qgt.imag, values, grads, "tangent", times)
 
     def _run_noisy(self, psi0: Tensor, solver: SolverType, options: dict, reps: list, bad_atom_configs,
                    meas_errors, native_shots: bool = False) -> NoisyResults:

@@ -47,6 +47,7 @@ using namespace rydiff;
 #include "shots_kernels.hpp"
 #include "dm_kernels.hpp"
 #include "tangent_kernels.hpp"
+#include "gram_kernels.hpp"
 static_assert(sizeof(PersistFactor) == 48, "plan.hpp sizes the factor table with 48 bytes per entry");
 
 #include "runtime.hpp"
@@ -59,6 +60,7 @@ static_assert(sizeof(PersistFactor) == 48, "plan.hpp sizes the factor table with
 #include "dm_launch.hpp"
 #include "overlap_launch.hpp"
 #include "tangent_launch.hpp"
+#include "gram_launch.hpp"
 #include "persist_launch.hpp"
 
 namespace {
@@ -569,11 +571,22 @@ size_t rydiff_tangent_workspace_bytes(const RydProblem* p, const RydPlanInfo* in
     return tangent_plan(p, info, n_dir, rt, lay) ? 0 : lay.total;
 }
 
-// Forward-mode sweep: the state and n_dir tangents through every factor once (tangent_kernels.hpp), observable tangents at every
-// save point.  One kernel family: launch per factor, one amplitude per thread.
-int rydiff_forward_tangent(const RydProblem* p, const RydPlanInfo* info, const RydTangent* tg, const void* psi0, double* expect_out,
-                           double* dexpect_out, void* workspace, size_t workspace_bytes, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+size_t rydiff_geometry_workspace_bytes(const RydProblem* p, const RydPlanInfo* info, int n_dir) {
+    Runtime rt;
+    TangentLayout lay;
+    return tangent_plan(p, info, n_dir, rt, lay) ? 0 : geometry_layout(rt.pl, lay, n_dir).total;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The forward-mode sweep behind rydiff_forward_tangent and rydiff_forward_geometry: the state and n_dir tangents through every
+// factor once (tangent_kernels.hpp); at every save point the observable values, their tangents (dexpect_out, skipped when NULL) and,
+// with `geometry`, the Gram matrix of the (1 + n_dir) vectors (gram_kernels.hpp).  One kernel family: launch per factor, one amplitude
+// per thread.
+int tangent_sweep(const RydProblem* p, const RydPlanInfo* info, const RydTangent* tg, const void* psi0, double* expect_out,
+                  double* dexpect_out, bool geometry, void* gram_out, void* workspace, size_t workspace_bytes, hipStream_t stream) {
     // ---- host-only validation: nothing below this block runs unless all of it passes ----
     if (!p) return fail(RYDIFF_EINVAL, "null problem");
     if (!tg) return fail(RYDIFF_EINVAL, "null tangent");
@@ -581,15 +594,20 @@ int rydiff_forward_tangent(const RydProblem* p, const RydPlanInfo* info, const R
     if (rc) return rc;
     if (!tg->d_amp && !tg->d_det && !tg->d_u && !tg->d_psi0)
         return fail(RYDIFF_EINVAL, "tangent: all of d_amp, d_det, d_u, d_psi0 are NULL (nothing to differentiate)");
-    if (!dexpect_out) return fail(RYDIFF_EINVAL, "null dexpect_out");
+    if (!geometry && !dexpect_out) return fail(RYDIFF_EINVAL, "null dexpect_out");
+    if (geometry && !gram_out) return fail(RYDIFF_EINVAL, "null gram_out");
     if (!psi0) return fail(RYDIFF_EINVAL, "null psi0");
     Runtime rt0;
     TangentLayout lay;
     rc = tangent_plan(p, info, tg->n_dir, rt0, lay);
     if (rc) return rc;
+    GeometryLayout glay;
+    if (geometry) glay = geometry_layout(rt0.pl, lay, tg->n_dir);
+    const size_t need = geometry ? glay.total : lay.total;
     if (!workspace) return fail(RYDIFF_EINVAL, "null workspace");
-    if (workspace_bytes < lay.total)
-        return fail(RYDIFF_EWORKSPACE, "tangent workspace too small: need " + std::to_string(lay.total) + " bytes, got " + std::to_string(workspace_bytes));
+    if (workspace_bytes < need)
+        return fail(RYDIFF_EWORKSPACE, std::string(geometry ? "geometry" : "tangent") + " workspace too small: need " + std::to_string(need) +
+                                           " bytes, got " + std::to_string(workspace_bytes));
     // ---- device work ----
     RydProblem q = *p;
     q.kernel_variant = 0;
@@ -613,7 +631,7 @@ int rydiff_forward_tangent(const RydProblem* p, const RydPlanInfo* info, const R
     }
     const size_t rows = size_t(pl.n_obs + pl.n_pobs + 2 * pl.n_ov);
     const size_t row = size_t(pl.T + 1) * pl.B;
-    if (rows) HIP_TRY(hipMemsetAsync(dexpect_out, 0, size_t(D) * rows * row * sizeof(double), stream));
+    if (rows && dexpect_out) HIP_TRY(hipMemsetAsync(dexpect_out, 0, size_t(D) * rows * row * sizeof(double), stream));
     ForwardCtx c{{rt, &q, ws, stream, sv}};
     c.psi0 = c.start = vec[0];
     c.obs = q.obs_diag;
@@ -626,7 +644,9 @@ int rydiff_forward_tangent(const RydProblem* p, const RydPlanInfo* info, const R
         if (c.want_exp)
             if (const int r = launch_expect(c, v, k)) return r;
         if (const int r = launch_observables_expect(c, v, 0, k, 1, BatchSlice{0, pl.B, false})) return r;
-        return launch_expect_tangent(c, v, D, k, dexpect_out);
+        if (dexpect_out)
+            if (const int r = launch_expect_tangent(c, v, D, k, dexpect_out)) return r;
+        return geometry ? launch_gram(rt, ws, glay, v, D, k, static_cast<double2*>(gram_out), stream) : RYDIFF_OK;
     };
     rc = save_point(vec[0], 0);
     if (rc) return rc;
@@ -645,6 +665,21 @@ int rydiff_forward_tangent(const RydProblem* p, const RydPlanInfo* info, const R
         if (rc) return rc;
     }
     return RYDIFF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rydiff_forward_tangent(const RydProblem* p, const RydPlanInfo* info, const RydTangent* tg, const void* psi0, double* expect_out,
+                           double* dexpect_out, void* workspace, size_t workspace_bytes, void* stream_) {
+    return tangent_sweep(p, info, tg, psi0, expect_out, dexpect_out, false, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream_));
+}
+
+// The same sweep with the Gram matrix of (psi, dpsi_0 .. dpsi_{n_dir - 1}) at every save point; the row tangents are optional here.
+int rydiff_forward_geometry(const RydProblem* p, const RydPlanInfo* info, const RydTangent* tg, const void* psi0, double* expect_out,
+                            double* dexpect_out, void* gram_out, void* workspace, size_t workspace_bytes, void* stream_) {
+    return tangent_sweep(p, info, tg, psi0, expect_out, dexpect_out, true, gram_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream_));
 }
 
 int rydiff_apply_factor(const RydProblem* p, const double* c_amp_reim, const double* c_det, const double* gamma_reim,

@@ -67,3 +67,11 @@ def deriv_param_all_times(sim, x: list, observables: list, **kw):
     (``basic_usage.ipynb``: ``for t in times: deriv_param(f=exp_val, x=diff_params, times=eval_times, t=t)``).  Returns
     ``Sensitivities``: ``values`` (n_obs, n_t), ``grads[i]`` (n_obs, n_t, *x[i].shape), ``route``."""
     return sim.run_sensitivities(x, observables, **kw)
+
+
+def quantum_fisher_information_all_times(sim, x: list, **kw):
+    """The quantum Fisher information matrix w.r.t. the scalar entries of ``x`` at EVERY evaluation time in one call:
+    ``sim.run_quantum_fisher(x, **kw)`` — the tangent sweep of ``deriv_param_all_times`` with the inner products of the tangent states
+    reduced at every save point.  Returns ``QuantumGeometry``: ``qfi`` (n_t, D, D), ``qgt``, ``berry``, ``gram``, ``times`` and the
+    ``values`` / ``grads`` of the optional ``observables``."""
+    return sim.run_quantum_fisher(x, **kw)

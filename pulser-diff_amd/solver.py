@@ -787,3 +787,111 @@ def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsav
         with torch.no_grad():
             expect = evolve(amp_c, det_c, u_c, tsave.detach(), psi_c, replace(spec, store_states=False), obs_c)[1]
     return expect, dexpect
+
+
+def _tangent_pick(t: Optional[Tensor], idx: list, shape: tuple, dtype: torch.dtype, name: str, dev) -> Optional[Tensor]:
+    """The directions ``idx`` of one tangent input as the contiguous device buffer the C ABI reads (None stays None)."""
+    if t is None:
+        return None
+    _require_cuda(t, name)
+    if tuple(t.shape[1:]) != tuple(shape):
+        raise ValueError(f"{name} must have shape (n_dir, {', '.join(str(s) for s in shape)}), got {tuple(t.shape)}")
+    return t[idx].detach().to(dev, dtype).contiguous()
+
+
+def evolve_geometry(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Tensor, spec: ProblemSpec,
+                    obs_diag: Optional[Tensor] = None, d_amp: Optional[Tensor] = None, d_det: Optional[Tensor] = None,
+                    d_u: Optional[Tensor] = None, d_psi0: Optional[Tensor] = None) -> tuple[Tensor, Tensor, Tensor]:
+    """``evolve_tangent`` that also returns the Gram matrix of the state and its tangents at EVERY evaluation time
+    (``rydiff_forward_geometry``): ``(expect, dexpect, gram)`` with ``gram`` complex128 of shape (n_t, B, 1 + n_dir, 1 + n_dir),
+    ``gram[k, b, i, j] = <v_i|v_j>``, ``v_0 = psi_b(t_k)``, ``v_{1+d} = d psi_b(t_k) / d theta_d`` — what
+    ``geometry.quantum_fisher_information`` and its neighbours take.  The sums are formed in a fixed order: two calls on the same
+    inputs return bit-identical matrices.  Same arguments as ``evolve_tangent``; tangents of inputs the problem does not have give
+    zero rows and columns.  More than 8 directions run one sweep per pair of groups of 4 (``geometry.geometry_sweeps``)."""
+    from .geometry import geometry_sweeps
+
+    if spec.rdms is not None:
+        raise NotImplementedError("evolve_geometry evaluates no reduced density matrices (rydiff_forward_geometry: RYDIFF_ENOTIMPL); "
+                                  "request them from evolve")
+    if spec.dm is not None:
+        raise NotImplementedError("evolve_geometry takes no density-matrix registers (rydiff_forward_geometry: RYDIFF_ENOTIMPL): the "
+                                  "pure-state quantum Fisher information is not the mixed-state one")
+    if spec.shots is not None:
+        raise NotImplementedError("evolve_geometry draws no measurement shots (rydiff_forward_geometry: RYDIFF_ENOTIMPL); request them from evolve")
+    L = _native.lib()
+    dev = psi0.device
+    for t, name in ((amp_tables, "amp_tables"), (det_tables, "det_tables"), (u_pairs, "u_pairs"), (psi0, "psi0")):
+        _require_cuda(t, name)
+    given = [t for t in (d_amp, d_det, d_u, d_psi0) if t is not None]
+    if not given:
+        raise ValueError("evolve_geometry needs at least one of d_amp, d_det, d_u, d_psi0")
+    n_dir = int(given[0].shape[0])
+    if n_dir < 1 or any(int(t.shape[0]) != n_dir for t in given):
+        raise ValueError("d_amp, d_det, d_u, d_psi0 must agree on the number of directions (their first axis), at least one")
+    amp_c = amp_tables.detach().to(torch.complex128).contiguous()
+    det_c = det_tables.detach().to(torch.float64).contiguous()
+    u_c = u_pairs.detach().to(torch.float64).contiguous()
+    psi_c = psi0.detach().to(torch.complex128).contiguous()
+    obs_c = None if obs_diag is None else obs_diag.detach().to(torch.float64).contiguous()
+    ts_host = tsave.detach().to("cpu", torch.float64).numpy()
+    if psi_c.ndim != 2:
+        raise ValueError(f"psi0 must be (batch, 2^N), got shape {tuple(psi_c.shape)}")
+    batch, dim = psi_c.shape
+    if dim != 2 ** spec.n_qubits:
+        raise ValueError(f"Incompatible shape of initial state.Expected {2 ** spec.n_qubits}, got {dim}.")
+    _check_shapes(spec, amp_c, det_c, u_c, obs_c, batch, dev)
+    n_t = len(ts_host)
+    call = _Call(spec, amp_c, det_c, u_c, ts_host, batch, obs_c)
+    call.problem.kernel_variant = 0  # the tangent sweep has one kernel family
+    p = call.problem
+    rows = p.n_obs + p.n_pauli_obs + 2 * p.n_overlaps
+    expect = torch.empty((rows, n_t, batch), dtype=torch.float64, device=dev)
+    dexpect = torch.empty((n_dir, rows, n_t, batch), dtype=torch.float64, device=dev)
+    gram = torch.empty((n_t, batch, 1 + n_dir, 1 + n_dir), dtype=torch.complex128, device=dev)
+    # tangents of inputs this problem does not have are zero: where nothing else is given the tangent states are identically zero,
+    # and ONE sweep with a single zero direction delivers <psi|psi> and the values; every other entry is an exact zero
+    live = ((d_amp is not None and amp_c.numel() > 0) or (d_det is not None and det_c.numel() > 0)
+            or (d_u is not None and u_c.numel() > 0) or d_psi0 is not None)
+    sweeps = geometry_sweeps(n_dir) if live else [[0]]
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        scratch = _new_workspace(_native.PLAN_SCRATCH_BYTES, dev)
+        info = _native.RydPlanInfo()
+        _native.check(L.rydiff_plan(ctypes.byref(p), 0, 0, _ptr(scratch), stream, ctypes.byref(info)))
+        workspace = None
+        done = torch.zeros(n_dir, dtype=torch.bool)
+        for s, idx in enumerate(sweeps):
+            if live:
+                bufs = (_tangent_pick(d_amp, idx, amp_c.shape, torch.complex128, "d_amp", dev) if amp_c.numel() else None,
+                        _tangent_pick(d_det, idx, det_c.shape, torch.float64, "d_det", dev) if det_c.numel() else None,
+                        _tangent_pick(d_u, idx, u_c.shape, torch.float64, "d_u", dev) if u_c.numel() else None,
+                        _tangent_pick(d_psi0, idx, psi_c.shape, torch.complex128, "d_psi0", dev))
+            else:
+                bufs = (None, None, None, torch.zeros((1,) + tuple(psi_c.shape), dtype=torch.complex128, device=dev))
+            tg = _native.RydTangent()
+            tg.n_dir = len(idx)
+            tg.d_amp, tg.d_det, tg.d_u, tg.d_psi0 = (None if b is None else b.data_ptr() for b in bufs)
+            g = torch.empty((n_t, batch, 1 + len(idx), 1 + len(idx)), dtype=torch.complex128, device=dev)
+            want_rows = rows > 0 and not bool(done[idx].all())  # a later sweep of directions whose row tangents are all there skips them
+            out = torch.empty((len(idx), rows, n_t, batch), dtype=torch.float64, device=dev) if want_rows else None
+            need = L.rydiff_geometry_workspace_bytes(ctypes.byref(p), ctypes.byref(info), tg.n_dir)
+            if need == 0:  # refused: the sweep's own (host-only) validation reports why, with its error code
+                _native.check(L.rydiff_forward_geometry(ctypes.byref(p), ctypes.byref(info), ctypes.byref(tg), _ptr(psi_c), None, None,
+                                                        _ptr(g), None, 0, stream))
+                raise RuntimeError("rydiff_geometry_workspace_bytes returned 0: " + _native.last_error())
+            if workspace is None or workspace.numel() < need:
+                workspace = _new_workspace(need, dev)
+            _native.check(L.rydiff_forward_geometry(ctypes.byref(p), ctypes.byref(info), ctypes.byref(tg), _ptr(psi_c),
+                                                    _ptr(expect) if (rows > 0 and s == 0) else None, None if out is None else _ptr(out),
+                                                    _ptr(g), _ptr(workspace), workspace.numel(), stream))
+            if not live:
+                gram.zero_()
+                gram[:, :, 0, 0] = g[:, :, 0, 0]
+                dexpect.zero_()
+                break
+            full = torch.tensor([0] + [1 + i for i in idx], device=dev)
+            gram[:, :, full[:, None], full[None, :]] = g
+            if out is not None:
+                dexpect[idx] = out
+            done[idx] = True
+    return expect, dexpect, gram
