@@ -345,3 +345,207 @@ def dense_from_structured_terms(n_qubits, u_pairs, amp_terms, det_terms, amp_con
             h[rows, rows ^ m] += c
             h[rows ^ m, rows] += complex(c).conjugate() if not isinstance(c, torch.Tensor) else torch.conj(c)
     return h
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Density-matrix observables (include/rydiff.h: RydProblem.dm_*): plain references on rho = v.reshape(2^n, 2^n).  Pauli strings act as
+# tensor operations on the atom axes (atom j = axis j of rho.reshape((2,) * n + ...)): X flips the axis, Z signs index 1, Y flips and
+# multiplies by (-i, +i) — no index masks, no dense 2^n x 2^n operator.  Every value comes with the sum of the absolute values of the
+# products it adds, which is what the tolerances of tests/test_gpu_dm_observables_wide.py are stated against.
+# ----------------------------------------------------------------------------------------------------------------------
+_AXIS_PHASE = {(0, 0): (1.0, 1.0), (1, 0): (1.0, 1.0), (0, 1): (1.0, -1.0), (1, 1): (-1j, 1j)}  # (x bit, z bit): I, X, Z, Y by result index
+
+
+def string_phase(x: int, z: int, n: int) -> np.ndarray:
+    """The phases of one string as a (2,) * n tensor over the RESULT index: the product over the atoms of (1, 1) for I and X,
+    (1, -1) for Z, (-i, i) for Y = [[0, -i], [i, 0]]  (masks: bit j = atom j, as PauliObservable.terms gives them)."""
+    ph = np.ones((2,) * n, dtype=np.complex128)
+    for j in range(n):
+        vec = np.asarray(_AXIS_PHASE[(x >> j & 1, z >> j & 1)], dtype=np.complex128)
+        ph = ph * vec.reshape((1,) * j + (2,) + (1,) * (n - 1 - j))
+    return ph
+
+
+def pauli_string_apply(t, x: int, z: int, n: int):
+    """P t for a numpy array or torch tensor t of shape (2,) * n + rest: the string acts on the first n axes."""
+    axes = [j for j in range(n) if x >> j & 1]
+    ph = string_phase(x, z, n)
+    ph = ph.reshape(ph.shape + (1,) * (t.ndim - n))
+    if isinstance(t, torch.Tensor):
+        return (torch.flip(t, axes) if axes else t) * torch.from_numpy(ph).to(t.device)
+    return (np.flip(t, axes) if axes else t) * ph
+
+
+def dm_pauli_row(rho: np.ndarray, terms, n: int) -> tuple[float, float]:
+    """(sum_s w_s Re Tr(P_s rho), sum_s |w_s| sum_x |rho[x ^ flips, x]|) for terms = [(w, x_mask, z_mask), ...].  The flip is a view
+    of rho.reshape((2,) * 2n) and the diagonal an einsum over that view, so a 4096 x 4096 matrix is never copied per string."""
+    t = rho.reshape((2,) * (2 * n))
+    idx = list(range(n))
+    val = tot = 0.0
+    for w, x, z in terms:
+        axes = [j for j in range(n) if x >> j & 1]
+        d = np.einsum(np.flip(t, axes) if axes else t, idx + idx, idx)  # d[x] = rho[x with the X / Y atoms flipped][x]
+        val += w * float((string_phase(x, z, n) * d).sum().real)
+        tot += abs(w) * float(np.abs(d).sum())
+    return val, tot
+
+
+def dm_pauli_row_torch(rho: torch.Tensor, terms, n: int) -> torch.Tensor:
+    """sum_s w_s Re Tr(P_s rho) in differentiable torch: P_s applied to rho.reshape((2,) * n + (2^n,)), then the trace."""
+    dim = 2 ** n
+    out = torch.zeros((), dtype=torch.float64, device=rho.device)
+    for w, x, z in terms:
+        out = out + w * pauli_string_apply(rho.reshape((2,) * n + (dim,)), x, z, n).reshape(dim, dim).diagonal().sum().real
+    return out
+
+
+def dm_rows_reference(v: np.ndarray, n: int, diag=(), paulis=(), targets=(), purity: bool = False):
+    """Every density-matrix row of one vector v = vec(rho) (4^n,), in the order of expect_out (diagonal tables, Pauli observables,
+    fidelities, purity): (values, sums of absolute terms), float64 arrays.  diag: (n_diag, 2^n) real; targets: (n_fid, 2^n) complex."""
+    dim = 2 ** n
+    rho = v.reshape(dim, dim)
+    val, tot = [], []
+    re_diag = np.diagonal(rho).real
+    for o in diag:
+        val.append(float((o * re_diag).sum()))
+        tot.append(float(np.abs(o * re_diag).sum()))
+    for p in paulis:
+        a, b = dm_pauli_row(rho, p.terms, n)
+        val.append(a)
+        tot.append(b)
+    if len(targets):
+        arho = np.abs(rho)
+        for phi in targets:
+            val.append(float((phi.conj() @ (rho @ phi)).real))
+            tot.append(float(np.abs(phi) @ (arho @ np.abs(phi))))
+    if purity:
+        s = float((np.abs(v) ** 2).sum())
+        val.append(s)
+        tot.append(s)
+    return np.asarray(val), np.asarray(tot)
+
+
+def dm_cotangent_reference(v: np.ndarray, n: int, g, diag=(), paulis=(), targets=(), purity: bool = False):
+    """The cotangent rydiff.h writes down for the density-matrix rows of one vector v (4^n,), row weights g in the order of
+    dm_rows_reference:  g o[x] on the diagonal;  g w_s conj(phase_s(x)) at the entries Re Tr(P_s rho) reads (torch.autograd through
+    dm_pauli_row_torch);  g phi[x] conj(phi[y]);  2 g v.  Returns (cotangent (4^n,) complex, sum of the absolute contributions per
+    entry (4^n,) real)."""
+    dim = 2 ** n
+    rho = v.reshape(dim, dim)
+    cot = np.zeros((dim, dim), dtype=np.complex128)
+    tot = np.zeros((dim, dim), dtype=np.float64)
+    g = [float(x) for x in g]
+    r = 0
+    at = np.arange(dim)
+    for o in diag:
+        cot[at, at] += g[r] * o
+        tot[at, at] += np.abs(g[r] * o)
+        r += 1
+    if len(paulis):
+        leaf = torch.from_numpy(rho.copy()).requires_grad_(True)
+        leaf_abs = torch.from_numpy(rho.copy()).requires_grad_(True)
+        loss = loss_abs = 0.0
+        for p in paulis:
+            loss = loss + g[r] * dm_pauli_row_torch(leaf, p.terms, n)
+            loss_abs = loss_abs + dm_pauli_row_torch(leaf_abs, [(abs(g[r] * w), x, 0) for w, x, _ in p.terms], n)  # moduli: X for Y, no Z
+            r += 1
+        loss.backward()
+        loss_abs.backward()
+        cot += leaf.grad.numpy()
+        tot += leaf_abs.grad.numpy().real
+    for phi in targets:
+        cot += g[r] * np.outer(phi, phi.conj())
+        tot += abs(g[r]) * np.outer(np.abs(phi), np.abs(phi))
+        r += 1
+    if purity:
+        cot += 2.0 * g[r] * rho
+        tot += 2.0 * abs(g[r]) * np.abs(rho)
+        r += 1
+    assert r == len(g)
+    return cot.reshape(-1), tot.reshape(-1)
+
+
+def ket_pauli_cotangent(v: np.ndarray, n_qubits: int, terms, g: float):
+    """2 g O v for a ket-style Pauli observable O = sum_s w_s P_s on the whole register (here: the doubled one), and the sum of the
+    absolute contributions per entry."""
+    t = v.reshape((2,) * n_qubits)
+    cot = np.zeros(t.shape, dtype=np.complex128)
+    tot = np.zeros(t.shape, dtype=np.float64)
+    for w, x, z in terms:
+        cot += 2.0 * g * w * pauli_string_apply(t, x, z, n_qubits)
+        tot += 2.0 * abs(g * w) * np.abs(pauli_string_apply(t, x, 0, n_qubits))
+    return cot.reshape(-1), tot.reshape(-1)
+
+
+def ket_pauli_row(t: np.ndarray, n_qubits: int, terms):
+    """(<v|O|v>.real, sum of the absolute products) for a ket-style Pauli observable on the whole register; t: the vector(s) with the
+    qubit axes first, shape (2,) * n_qubits + rest — the results have shape rest."""
+    axes = tuple(range(n_qubits))
+    val = tot = 0.0
+    for w, x, z in terms:
+        val = val + w * (t.conj() * pauli_string_apply(t, x, z, n_qubits)).sum(axis=axes).real
+        tot = tot + abs(w) * (np.abs(t) * np.abs(pauli_string_apply(t, x, 0, n_qubits))).sum(axis=axes)
+    return val, tot
+
+
+# ---- shots from the diagonal of rho: the shaped inputs of the wide cases and a second float64 prefix sum ------------------------------
+DM_SHOTS = 4096
+DM_SHOT_THREADS = 256  # k_dm_shots: one contiguous segment of ceil(2^n / 256) entries per thread
+
+
+def dm_shot_inputs(n: int, batch: int, seed: int):
+    """(v0 (B, 4^n) complex, uniforms (2, B, DM_SHOTS)) for the shot cases past one segment per thread.  The diagonal of v0 has a random
+    sign (about half is clamped); the first two and the last three whole thread segments and four consecutive segments in the middle
+    are zero or negative; every third remaining entry is an exact zero; the uniforms hold 0 and 1 - 2^-53."""
+    dim = 2 ** n
+    seg = (dim + DM_SHOT_THREADS - 1) // DM_SHOT_THREADS
+    n_seg = dim // seg
+    gen = torch.Generator().manual_seed(seed)
+    v0 = torch.randn(batch, dim * dim, generator=gen, dtype=torch.complex128)
+    d = torch.randn(batch, dim, generator=gen, dtype=torch.float64)
+    x = torch.arange(dim)
+    segment = x // seg
+    mid = n_seg // 2
+    dead = (segment < 2) | (segment >= n_seg - 3) | ((segment >= mid) & (segment < mid + 4))
+    d[:, dead] = -d[:, dead].abs()          # negative ...
+    d[:, dead & (x % 2 == 0)] = 0.0         # ... or exactly zero
+    live = torch.nonzero(~dead).squeeze(1)
+    d[:, live[::3]] = 0.0
+    v0[:, x * (dim + 1)] = torch.complex(d, torch.ones_like(d))  # (the imaginary part plays no part)
+    uniforms = torch.rand(2, batch, DM_SHOTS, generator=gen, dtype=torch.float64)
+    uniforms[:, :, 0] = 0.0
+    uniforms[:, :, 1] = 1.0 - 2.0 ** -53
+    return v0, uniforms
+
+
+def segmented_prefix(p: np.ndarray, threads: int = DM_SHOT_THREADS) -> np.ndarray:
+    """A float64 prefix sum of p (dim,) in another order than numpy.cumsum's: running sums inside `threads` contiguous segments, a
+    serial scan of the segment totals, then offset + running sum."""
+    dim = len(p)
+    seg = (dim + threads - 1) // threads
+    out = np.empty(dim, dtype=np.float64)
+    acc = 0.0
+    for lo in range(0, dim, seg):
+        local = np.cumsum(p[lo:lo + seg])
+        out[lo:lo + seg] = acc + local
+        acc = acc + float(local[-1])
+    return out
+
+
+def sample_with_prefix(p: np.ndarray, cum: np.ndarray, u: np.ndarray) -> np.ndarray:
+    """The shot rule on a given float64 prefix sum: the smallest x with cum[x] > u * cum[-1], u clamped into [0, 1); where there is
+    none, the last x with p[x] > 0."""
+    uc = np.where(u > 0, np.minimum(u, 1.0 - 2.0 ** -53), 0.0)
+    pos = np.searchsorted(cum, uc * cum[-1], side="right")
+    return np.where(pos < len(p), pos, np.flatnonzero(p > 0)[-1])
+
+
+def shot_band(p: np.ndarray, u: np.ndarray) -> np.ndarray:
+    """True for the shots left out of an equality check between two float64 prefix sums: |u S - C[x]| <= 4 D 2^-53 S for some x, C =
+    numpy.cumsum(p).  Either prefix sum is within (D - 1) 2^-53 S of the exact one; the band doubles their largest disagreement."""
+    cum = np.cumsum(p)
+    s, dim = cum[-1], len(p)
+    tau = np.where(u > 0, np.minimum(u, 1.0 - 2.0 ** -53), 0.0) * s
+    hi = np.minimum(np.searchsorted(cum, tau, side="left"), dim - 1)
+    lo = np.maximum(hi - 1, 0)
+    return np.minimum(np.abs(tau - cum[hi]), np.abs(tau - cum[lo])) <= 4.0 * dim * 2.0 ** -53 * s

@@ -235,7 +235,8 @@ def _route(n, dev, native, batch=2, seed=860):
 
 
 def test_gradients_at_seven_atoms_agree_with_the_stored_rho_route(cuda_device):
-    """14 doubled qubits on the direct kernels: the register is four tiles, the cotangent kernels run many blocks per trajectory."""
+    """14 doubled qubits on the direct kernels: the register is four tiles and k_dm_apply runs many blocks per trajectory (k_dm_scatter
+    still has one block per flip mask at 2^7 = 128 entries; tests/test_gpu_dm_observables_wide.py takes it past one block)."""
     got, want = _route(7, cuda_device, True), _route(7, cuda_device, False)
     for key in want:
         err = rel_err(got[key], want[key])
