@@ -242,6 +242,27 @@ typedef struct RydProblem {
     int32_t n_rdms;                 /* 0: none; at most RYDIFF_MAX_RDMS */
     const uint32_t* rdm_masks;      /* HOST [n_rdms] */
 
+    /* REDUCED DENSITY MATRICES OF A DENSITY-MATRIX REGISTER (dm_atoms = n > 0, below): the state of a subsystem A of m distinct ATOMS
+     * (1 <= m <= min(n, RYDIFF_MAX_RDM_QUBITS)), the other atoms E traced out, evaluated at every tsave and differentiated by
+     * rydiff_backward.  With v = vec(rho), v[x * 2^n + y] = rho[x][y], atom j <-> bit n-1-j of an atom index:
+     *   rho_o[a][a'] = sum_e v[idx(a, e) * 2^n + idx(a', e)]                                (= Tr_E rho)
+     * dm_rdm_masks[o]: the atoms of A (bit j = ATOM j, all below n); a enumerates their settings with the lowest-numbered atom most
+     * significant — the convention of the ket block above.  rho is assumed neither Hermitian nor normalised: all 4^m complex entries
+     * are computed independently, each a float64 sum of its 2^(n-m) terms in a fixed order (bit-reproducible, no atomics); the lower
+     * triangle is NOT filled by conjugation.  RDM o owns 2 * 4^{m_o} consecutive rows of expect_out / grad_expect BEHIND the dm_purity
+     * row (order: diag, Pauli, fidelity, purity, RDMs), entry (a, a') at offset 2 * (a * 2^m + a'), Re then Im.  rydiff_backward:
+     * with G = gRe + i gIm (the RDM's rows of grad_expect at (k, b)) the cotangent added to v is G[a][a'] at every entry
+     * (idx(a, e), idx(a', e)) — the map is linear in v, so there is no G + G^dagger as on kets — formed in the workspace buffer of
+     * the other density-matrix cotangents (after them) and injected through the grad_states route.  Honoured wherever the other
+     * dm_* rows are: every kernel family, every tape mode, states_out == NULL without a tape, next to ket-style rows on the doubled
+     * register.  Not together with shard_bits > 0 and not in rydiff_forward_tangent (RYDIFF_ENOTIMPL, as for dm_atoms > 0).
+     * RYDIFF_EINVAL, before anything touches a device: a count outside [0, RYDIFF_MAX_RDMS], NULL masks with a non-zero count, an
+     * empty mask, more than RYDIFF_MAX_RDM_QUBITS bits in a mask, a bit at or above n.  Traffic per RDM and state: 2^(n+m) * 16 B,
+     * never the 4^n matrix.  dm_atoms = 0: the fields are ignored, like the other dm_* fields.  n_dm_rdms = 0: nothing changes.  (The
+     * fields sit in front of dm_atoms: the 14 fields dm_atoms .. dm_shots stay contiguous and directly in front of tape_steps.) */
+    int32_t n_dm_rdms;              /* 0: none; at most RYDIFF_MAX_RDMS */
+    const uint32_t* dm_rdm_masks;   /* HOST [n_dm_rdms]: bit j = ATOM j, 1 .. min(n, RYDIFF_MAX_RDM_QUBITS) bits, all below n = dm_atoms */
+
     /* DENSITY-MATRIX observables: dm_atoms = n > 0 declares the register to be the DOUBLED register of a density matrix (the
      * master-equation path, see the pair terms above): n_qubits == 2n, row qubits 0..n-1, column qubits n..2n-1,
      *   vec(rho)[x * 2^n + y] = rho[x][y],
@@ -254,6 +275,7 @@ typedef struct RydProblem {
      *   n_dm_fid rows        Re sum_{x,y} conj(phi[x]) v[x 2^n + y] phi[y]                  (<phi|rho|phi>; targets are constants, not
      *                        normalised by the library; dm_fid_batch = 1: shared by the trajectories, B: one per trajectory)
      *   dm_purity row        sum_i |v_i|^2                                                  (Tr rho^2 for Hermitian rho)
+ *   n_dm_rdms blocks     2 * 4^{m_o} rows each: the reduced density matrices above
      * None of them assumes a Hermitian or normalised rho.  rydiff_backward differentiates every row: with g the row's entry of
      * grad_expect at (k, b), the cotangent added to v (torch's dL/dRe + i dL/dIm) is  g o[x] on the diagonal entries;
      * g w_s conj(phase_s(x)) at entry (x ^ xm, x);  g phi[x] conj(phi[y]);  2 g v — formed per save point in the workspace buffer of the
@@ -379,7 +401,7 @@ int rydiff_plan(const RydProblem* p, int need_tape, int need_backward, void* scr
  *               save points are copied out of it — stored states plus a later gradient without (or with less) recomputation.
  *   expect_out  DEVICE float64 [n_obs + n_pauli_obs + 2 * n_overlaps + 2 * sum_o 4^{m_o} + dm rows][n_tsave][B] (diagonal observables
  *               first, then the Pauli ones, then Re / Im of every overlap, then Re / Im of every reduced-density-matrix entry, then the
- *               density-matrix rows n_dm_diag + n_dm_pauli_obs + n_dm_fid + dm_purity), or NULL
+ *               density-matrix rows n_dm_diag + n_dm_pauli_obs + n_dm_fid + dm_purity + 2 * sum_o 4^{m_o} over dm_rdm_masks), or NULL
  * With RydProblem.n_shots > 0 the measurement shots of the save points in shot_times go to RydProblem.shots_out on the way. */
 int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi0, void* states_out, double* expect_out,
                    void* workspace, size_t workspace_bytes, int need_tape, void* stream);

@@ -79,6 +79,8 @@ class RydProblem(ctypes.Structure):
         ("shots_out", ctypes.c_void_p),
         ("n_rdms", ctypes.c_int32),
         ("rdm_masks", ctypes.c_void_p),
+        ("n_dm_rdms", ctypes.c_int32),
+        ("dm_rdm_masks", ctypes.c_void_p),
         ("dm_atoms", ctypes.c_int32),
         ("n_dm_diag", ctypes.c_int32),
         ("dm_diag", ctypes.c_void_p),

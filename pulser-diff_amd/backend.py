@@ -306,8 +306,8 @@ class TorchEmulator:
         ``observables`` (extension): diagonal observables (``DiagonalObservable`` or dense diagonal tensors) and sums of Pauli
         strings (``PauliObservable``, e.g. from ``build_observable``) and overlaps with target states (``StateOverlap``; read with
         ``results.overlap``) and states of subsystems (``ReducedDensityMatrix``, e.g. from ``build_reduced_density_matrix``; read
-        with ``results.reduced_density_matrix`` / ``results.entanglement_entropy``) to be evaluated natively at every evaluation
-        time; ``store_states=False`` keeps the trajectory out of the results.
+        with ``results.reduced_density_matrix`` / ``results.entanglement_entropy`` / ``results.negativity``; master-equation runs
+        serve them — ``Tr_E rho`` — with ``store_states=False``) to be evaluated natively at every evaluation time; ``store_states=False`` keeps the trajectory out of the results.
 
         ``shots`` (extension): measurement shots drawn natively while the state is on the device — an int (that many at the final
         evaluation time) or a ``ShotRequest`` (``times="all"``: every evaluation time).  ``results.sample_state`` /
@@ -392,9 +392,11 @@ class TorchEmulator:
                                           "state different from the ground.")
 
         def run_coherent() -> CoherentResults:
-            if rdm_objs and solver == SolverType.DP5_ME:
-                raise NotImplementedError("ReducedDensityMatrix observables stay refused in master-equation runs: partial traces of a "
-                                          "density matrix are not evaluated natively (diagonal, Pauli, StateOverlap and Purity are).")
+            if rdm_objs and solver == SolverType.DP5_ME and store_states:
+                raise NotImplementedError("ReducedDensityMatrix observables of master-equation runs are evaluated natively (the partial "
+                                          "trace Tr_E rho) with store_states=False only; with stored states "
+                                          "results.reduced_density_matrix(obs) computes it from the density matrices without the "
+                                          "observable being handed to run().")
             # A master-equation run that stores its density matrices already serves fidelities (results.fidelity) and samples
             # (sample_state) from them: the two requests that used to be refused there stay refused with stored states, and are
             # served natively where no trajectory is kept
@@ -407,17 +409,19 @@ class TorchEmulator:
                                           "store_states=False only; with stored states sample_state draws from the stored density "
                                           "matrices.")
             if solver == SolverType.DP5_ME:  # density matrices (backend.py:495-509); without collapse noise L = 0
-                # diagonal tables, Pauli strings (unrotated: this path runs in no rotating frame), fidelities, the purity and the
-                # shots are taken from rho while it is on the device; store_states=False keeps the (n_t, 4^N) trajectory out
+                # diagonal tables, Pauli strings (unrotated: this path runs in no rotating frame), fidelities, the purity, reduced
+                # density matrices and the shots are taken from rho while it is on the device; store_states=False keeps the (n_t, 4^N) trajectory out
                 res = mesolve(ham, psi0.to(dev), self._eval_times_array, ham.config, options,
-                              observables=obs_objs + pauli_objs + overlap_objs + purity_objs, shots=shots, store_states=store_states)
+                              observables=obs_objs + pauli_objs + overlap_objs + purity_objs + rdm_objs, shots=shots,
+                              store_states=store_states)
                 n_ex, n_ov = len(obs_objs) + len(pauli_objs), len(overlap_objs)
                 return CoherentResults(res.states, ham._size, ham.basis_name, self._eval_times_array, self._meas_basis, meas_errors,
                                        atom_order=tuple(ham._qdict), stats=res.stats, density=True,
                                        native_expect=torch.stack(res.expect[:n_ex]) if n_ex else None,
                                        native_observables=obs_objs + pauli_objs, overlap_observables=overlap_objs,
                                        native_fidelities=res.expect[n_ex:n_ex + n_ov] if n_ov else None,
-                                       native_purity=res.expect[n_ex + n_ov] if purity_objs else None, native_shots=res.shots)
+                                       native_purity=res.expect[n_ex + n_ov] if purity_objs else None, native_shots=res.shots,
+                                       native_rdms=res.rdms if rdm_objs else None, rdm_observables=rdm_objs)
             result = sesolve(ham, psi0.to(dev), self._eval_times_array, solver=solver, options=options, obs_diag=obs_diag,
                              store_states=store_states, pauli_obs=pauli_objs, overlap_obs=overlap_objs, shots=shots, rdm_obs=rdm_objs)
             states_tbd = result.states.permute(0, 2, 1) if result.states.numel() else result.states

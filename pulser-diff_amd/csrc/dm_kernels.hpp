@@ -11,7 +11,12 @@
 //   k_dm_apply      cotangent, dense parts:  out = base + sum_o g_o phi_o[x] conj(phi_o[y]) + 2 g_p v   (streaming, no atomics)
 //   k_dm_scatter    cotangent, sparse parts, in place behind k_dm_apply: one thread per (distinct flip mask, x) adds
 //                   sum_o g_o o[x] (xm = 0) + sum_s g w_s conj(phase_s(x)) at entry (x ^ xm, x) — one owner per entry, no atomics
-// The final sums follow the other observable kernels: wave shuffle, LDS, one atomic per block and row.
+//   k_dm_rdm        reduced density matrices  rho_o[a][a'] = sum_e v[idx(a, e) 2^n + idx(a', e)]: a block owns ONE row a of ONE RDM of
+//                   ONE state; thread <-> (a' = tid mod 2^m, e-slice = tid / 2^m), the slice sums in registers, added in a fixed order
+//                   through LDS — one owner per output, plain stores, no atomics: bit-reproducible.  2^(n+m) entries per RDM and state
+//   k_dm_rdm_scatter  cotangent of ONE RDM, in place behind k_dm_apply / k_dm_scatter (one launch per RDM, stream-ordered: two RDMs, or an
+//                   RDM and a Pauli row, may own the same entry): thread (a, y) adds G[a][ext_A(y)] at entry (dep_A(a) | (y & E), y)
+// The final sums of the first two follow the other observable kernels: wave shuffle, LDS, one atomic per block and row.
 #pragma once
 
 struct DmTables {
@@ -250,4 +255,95 @@ __global__ __launch_bounds__(256) void k_dm_scatter(DmScatterArgs a) {
     double2* dst = a.out + (size_t(blockIdx.z) * a.B + b) * (size_t(D) << a.n) + (size_t(xp) << a.n) + x;
     const double2 cur = *dst;
     *dst = make_double2(cur.x + sr, cur.y + si);
+}
+
+// the low bits of `val` deposited into the set bits of `mask`, lowest first (pdep) / the bits of `x` under `mask` gathered (pext)
+__device__ __forceinline__ uint32_t dm_deposit(uint32_t val, uint32_t mask) {
+    uint32_t r = 0u;
+    for (; mask; mask &= mask - 1u, val >>= 1) r |= (val & 1u) ? (mask & (0u - mask)) : 0u;
+    return r;
+}
+__device__ __forceinline__ uint32_t dm_extract(uint32_t x, uint32_t mask) {
+    uint32_t r = 0u, bit = 1u;
+    for (; mask; mask &= mask - 1u, bit <<= 1) r |= (x & mask & (0u - mask)) ? bit : 0u;
+    return r;
+}
+
+struct DmRdmArgs {
+    const double2* v;    // state at save point k0, trajectory 0
+    size_t kstride;
+    double* out;         // first RDM row of expect_out
+    int n_tsave, k0, B, b_first, b_count, n;
+    uint32_t am[RYDIFF_MAX_RDMS];  // atoms of A as bits of an atom index
+    int32_t m[RYDIFF_MAX_RDMS], row[RYDIFF_MAX_RDMS];  // atoms kept; first row (relative to `out`)
+};
+
+// grid (2^m_max, b_count * n_k, n_dm_rdms), 256 threads.  Consecutive lanes are consecutive a': the trailing atoms of A, the only
+// contiguous runs of the access set, fall on consecutive lanes.  Slice s of the settings of E = the settings whose lowest
+// log2(256 / 2^m) E-bits spell s; a thread walks the remaining E-bits with a masked increment.
+__global__ __launch_bounds__(256) void k_dm_rdm(DmRdmArgs a) {
+    __shared__ double2 part[256];
+    const int o = blockIdx.z, m = a.m[o];
+    if (blockIdx.x >= (1u << m)) return;  // (uniform)
+    const uint32_t D = 1u << a.n, am = a.am[o], em = (D - 1u) & ~am;
+    const int b = a.b_first + int(blockIdx.y) % a.b_count;
+    const int kk = int(blockIdx.y) / a.b_count;
+    const double2* __restrict__ v = a.v + size_t(kk) * a.kstride + (size_t(b) << (2 * a.n));
+    const uint32_t ap = threadIdx.x & ((1u << m) - 1u), s = threadIdx.x >> m;
+    const int sbits = min(8 - m, a.n - m);  // E-bits spelled by the slice number
+    uint32_t elo = 0u, rest = em;           // the lowest `sbits` bits of em / the others
+    for (int i = 0; i < sbits; ++i) {
+        elo |= rest & (0u - rest);
+        rest &= rest - 1u;
+    }
+    double2 acc = make_double2(0.0, 0.0);
+    if (s < (1u << sbits)) {
+        const size_t rowbase = size_t(dm_deposit(blockIdx.x, am) | dm_deposit(s, elo)) << a.n;
+        const uint32_t colbase = dm_deposit(ap, am) | dm_deposit(s, elo);
+        uint32_t e = 0u;
+        do {  // every subset of `rest`, ascending
+            const double2 q = v[rowbase + (size_t(e) << a.n) + (colbase | e)];
+            acc.x += q.x;
+            acc.y += q.y;
+            e = ((e | ~rest) + 1u) & rest;
+        } while (e != 0u);
+    }
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    if (threadIdx.x < (1u << m)) {
+        double2 sum = part[threadIdx.x];
+        for (uint32_t t = 1; t < (256u >> m); ++t) {  // fixed order
+            const double2 q = part[(t << m) + threadIdx.x];
+            sum.x += q.x;
+            sum.y += q.y;
+        }
+        const size_t rstride = size_t(a.n_tsave) * a.B;
+        double* dst = a.out + (size_t(a.row[o]) + 2u * ((size_t(blockIdx.x) << m) + threadIdx.x)) * rstride + size_t(a.k0 + kk) * a.B + b;
+        dst[0] = sum.x;
+        dst[rstride] = sum.y;
+    }
+}
+
+struct DmRdmScatterArgs {
+    double2* out;        // [n_k][B][4^n], already holding everything else
+    const double* gexp;  // first row of this RDM in grad_expect: [2 * 4^m][n_tsave][B]
+    int n_tsave, k0, B, n, m;
+    uint32_t am;
+};
+
+// grid (2^(n+m) / 256, B, n_k): thread (a, y) owns entry (dep_A(a) | (y & E), y) — distinct (a, y) give distinct entries
+__global__ __launch_bounds__(256) void k_dm_rdm_scatter(DmRdmScatterArgs a) {
+    const uint32_t D = 1u << a.n;
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= (D << a.m)) return;
+    const uint32_t y = t & (D - 1u), ar = t >> a.n;
+    const int b = blockIdx.y, k = a.k0 + int(blockIdx.z);
+    const size_t rstride = size_t(a.n_tsave) * a.B;
+    const double* g = a.gexp + 2u * ((size_t(ar) << a.m) + dm_extract(y, a.am)) * rstride + size_t(k) * a.B + b;
+    const double gr = g[0], gi = g[rstride];
+    if (gr == 0.0 && gi == 0.0) return;
+    const uint32_t x = dm_deposit(ar, a.am) | (y & ~a.am);
+    double2* dst = a.out + (size_t(blockIdx.z) * a.B + b) * (size_t(D) << a.n) + (size_t(x) << a.n) + y;
+    const double2 cur = *dst;
+    *dst = make_double2(cur.x + gr, cur.y + gi);
 }

@@ -92,6 +92,27 @@ int launch_dm_expect(const ForwardCtx& c, const double2* v, size_t kstride, int 
             else launch_dm_fidelity_n<RYDIFF_MAX_OVERLAPS>(a, grid, c.stream);
             LAUNCH_CHECK();
         }
+        if (pl.n_dm_rdm) {
+            DmRdmArgs a{};
+            a.v = v + size_t(k) * kstride;
+            a.kstride = kstride;
+            a.out = c.dm_out + size_t(n_trace + pl.n_dm_fid + pl.dm_purity) * row;
+            a.n_tsave = pl.T + 1;
+            a.k0 = k0 + k;
+            a.B = pl.B;
+            a.b_first = bs.first;
+            a.b_count = bs.count;
+            a.n = pl.dm_n;
+            int m_max = 0;
+            for (int o = 0; o < pl.n_dm_rdm; ++o) {
+                a.am[o] = pl.dm_rdm_am[o];
+                a.m[o] = pl.dm_rdm_m[o];
+                a.row[o] = pl.dm_rdm_row[o];
+                m_max = std::max(m_max, pl.dm_rdm_m[o]);
+            }
+            hipLaunchKernelGGL(k_dm_rdm, dim3(1u << m_max, gy, unsigned(pl.n_dm_rdm)), dim3(256), 0, c.stream, a);
+            LAUNCH_CHECK();
+        }
     }
     return RYDIFF_OK;
 }
@@ -151,6 +172,19 @@ void launch_dm_apply(const PauliInject& pi, const double2* psi, const int32_t* e
         a.xblocks = uint32_t((D + 255) / 256);
         hipLaunchKernelGGL(k_dm_scatter, dim3(a.xblocks * unsigned(pl.dm_agroups.size()), unsigned(pl.B), unsigned(nk)), dim3(256), 0,
                            pi.stream, a);
+    }
+    // one launch per RDM, in stream order: two RDMs (or an RDM and a row above) may own the same entry
+    for (int o = 0; o < pl.n_dm_rdm; ++o) {
+        DmRdmScatterArgs a{};
+        a.out = out;
+        a.gexp = pi.dm_gexp + size_t(n_trace + pl.n_dm_fid + pl.dm_purity + pl.dm_rdm_row[o]) * row;
+        a.n_tsave = pl.T + 1;
+        a.k0 = k0;
+        a.B = pl.B;
+        a.n = pl.dm_n;
+        a.m = pl.dm_rdm_m[o];
+        a.am = pl.dm_rdm_am[o];
+        hipLaunchKernelGGL(k_dm_rdm_scatter, dim3(unsigned(((D << a.m) + 255) / 256), unsigned(pl.B), unsigned(nk)), dim3(256), 0, pi.stream, a);
     }
 }
 

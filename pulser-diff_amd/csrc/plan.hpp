@@ -100,7 +100,11 @@ struct Plan {
     std::vector<PauliGroup> dm_groups, dm_agroups;
     std::vector<PauliString> dm_strings, dm_astrings;
     size_t off_dm = 0;
-    int dm_rows() const { return n_dm_diag + n_dm_pobs + n_dm_fid + dm_purity; }
+    // reduced density matrices of the density-matrix register: subsystem masks over atom-index bits, atoms, first row (behind the purity row)
+    int n_dm_rdm = 0, dm_rdm_rows = 0;
+    uint32_t dm_rdm_am[RYDIFF_MAX_RDMS] = {0};
+    int dm_rdm_m[RYDIFF_MAX_RDMS] = {0}, dm_rdm_row[RYDIFF_MAX_RDMS] = {0};
+    int dm_rows() const { return n_dm_diag + n_dm_pobs + n_dm_fid + dm_purity + dm_rdm_rows; }
     int ket_rows() const { return n_obs + n_pobs + 2 * n_ov + rdm_rows; }  // rows of expect_out in front of the density-matrix rows
     size_t dm_gfirst_bytes() const { return (dm_gfirst.size() * sizeof(int32_t) + 7) / 8 * 8; }
     size_t dm_bytes() const {
@@ -352,6 +356,7 @@ inline bool build_shots(const RydProblem* p, Plan& pl, std::string& err) {
 // RydProblem.dm_*: the doubled register, counts, masks, tables; the string groups of the evaluation and of the cotangent scatter
 inline bool build_dm(const RydProblem* p, Plan& pl, std::string& err) {
     pl.dm_n = pl.n_dm_diag = pl.n_dm_pobs = pl.n_dm_fid = pl.dm_purity = pl.dm_shots = 0;
+    pl.n_dm_rdm = pl.dm_rdm_rows = 0;
     pl.dm_fid_batch = 1;
     pl.dm_gfirst.clear();
     pl.dm_groups.clear();
@@ -432,11 +437,42 @@ inline bool build_dm(const RydProblem* p, Plan& pl, std::string& err) {
         err = "dm_shots needs n_shots > 0 (and the shot arrays)";
         return false;
     }
+    if (p->n_dm_rdms < 0 || p->n_dm_rdms > RYDIFF_MAX_RDMS) {
+        err = "n_dm_rdms must be in [0, " + std::to_string(RYDIFF_MAX_RDMS) + "]";
+        return false;
+    }
+    if (p->n_dm_rdms > 0 && !p->dm_rdm_masks) {
+        err = "missing dm_rdm_masks";
+        return false;
+    }
+    int rdm_rows = 0;
+    for (int o = 0; o < p->n_dm_rdms; ++o) {
+        const uint32_t qm = p->dm_rdm_masks[o];
+        if (n < 32 && (qm >> n) != 0) {
+            err = "dm_rdm_masks[" + std::to_string(o) + "] addresses an atom >= dm_atoms";
+            return false;
+        }
+        const int m = __builtin_popcount(qm);
+        if (m == 0) {
+            err = "dm_rdm_masks[" + std::to_string(o) + "] is empty";
+            return false;
+        }
+        if (m > RYDIFF_MAX_RDM_QUBITS) {
+            err = "dm_rdm_masks[" + std::to_string(o) + "] holds more than " + std::to_string(RYDIFF_MAX_RDM_QUBITS) + " atoms";
+            return false;
+        }
+        pl.dm_rdm_am[o] = to_index_mask(qm, n);
+        pl.dm_rdm_m[o] = m;
+        pl.dm_rdm_row[o] = rdm_rows;
+        rdm_rows += 2 << (2 * m);
+    }
     if (p->shard_bits > 0) {
         err = "density-matrix observables: not implemented together with state sharding";
         return false;
     }
     pl.dm_n = n;
+    pl.n_dm_rdm = p->n_dm_rdms;
+    pl.dm_rdm_rows = rdm_rows;
     pl.n_dm_diag = p->n_dm_diag;
     pl.n_dm_pobs = no;
     pl.n_dm_fid = p->n_dm_fid;

@@ -26,10 +26,10 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from .observables import DensityMatrixObservables, PauliObservable, Purity, StateOverlap, pack_overlaps
+from .observables import DensityMatrixObservables, PauliObservable, Purity, ReducedDensityMatrix, StateOverlap, pack_overlaps
 from .shots import ShotRequest
 from .simconfig import NoiseModel
-from .solver import ProblemSpec, SolverType, evolve, tolerance_from_options
+from .solver import ProblemSpec, SolverType, evolve, split_observables, tolerance_from_options
 from .utils import DiagonalObservable
 
 CD = torch.complex128
@@ -122,8 +122,9 @@ class MasterEquationResult:
 
     states: Tensor  # (n_t, dim, dim, B); empty (0, dim, dim, B) with store_states=False
     stats: dict
-    expect: list = field(default_factory=list)  # one real (n_t, B) tensor per entry of `observables`, evaluated natively (differentiable)
+    expect: list = field(default_factory=list)  # one real (n_t, B) tensor per non-RDM entry of `observables`, evaluated natively (differentiable)
     shots: Optional[ShotRequest] = None  # the request, holding the native shots (.indices: basis-state indices of the ATOMS)
+    rdms: list = field(default_factory=list)  # one complex (n_t, B, 2^m, 2^m) per ReducedDensityMatrix of `observables`, in order (native, differentiable)
 
     def __iter__(self):
         return iter((self.states, self.stats))
@@ -132,12 +133,18 @@ class MasterEquationResult:
 def pack_dm_observables(observables: Sequence, n: int, batch: int, device, shots: bool = False):
     """``observables`` of a master-equation run -> (``DensityMatrixObservables`` or None, the row of every observable).  Takes
     ``DiagonalObservable`` / diagonal ``(dim, dim)`` tensors / ``(dim,)`` diagonals, ``PauliObservable``, ``StateOverlap`` (the
-    fidelity ``<phi|rho|phi>``) and ``Purity``.  Strings go to the library as they are: the master equation runs in no rotating
-    frame (``mesolve`` hands ``ham.amp_tables`` over, never ``amp_tables_frame``)."""
+    fidelity ``<phi|rho|phi>``), ``Purity`` and ``ReducedDensityMatrix`` (``Tr_E rho``: its ``2 * 4^m`` rows sit behind all the real
+    rows; the row listed for it is the first of them, and ``DensityMatrixObservables.rdms`` keeps the objects in order).  Strings go
+    to the library as they are: the master equation runs in no rotating frame (``mesolve`` hands ``ham.amp_tables`` over, never
+    ``amp_tables_frame``)."""
     dim = 2 ** n
-    diags, paulis, overlaps, purity, kinds = [], [], [], False, []
+    diags, paulis, overlaps, purity, kinds, rdms = [], [], [], False, [], []
     for obs in observables:
-        if isinstance(obs, Purity):
+        if isinstance(obs, ReducedDensityMatrix):
+            obs.check(n)
+            kinds.append(("rdm", sum(2 * 4 ** o.n_sub for o in rdms)))
+            rdms.append(obs)
+        elif isinstance(obs, Purity):
             purity = True
             kinds.append(("purity", 0))
         elif isinstance(obs, StateOverlap):
@@ -160,7 +167,7 @@ def pack_dm_observables(observables: Sequence, n: int, batch: int, device, shots
                 d = obs.real if obs.is_complex() else obs
             else:
                 raise TypeError("observables of a master-equation run must be DiagonalObservable / PauliObservable / StateOverlap / "
-                                f"Purity objects or diagonal tensors, got {type(obs)}")
+                                f"Purity / ReducedDensityMatrix objects or diagonal tensors, got {type(obs)}")
             if d.shape[0] != dim:
                 raise ValueError(f"diagonal observable of dimension {d.shape[0]} handed to a register of dimension {dim}")
             kinds.append(("diag", len(diags)))
@@ -168,8 +175,10 @@ def pack_dm_observables(observables: Sequence, n: int, batch: int, device, shots
     if not kinds and not shots:
         return None, []
     dm = DensityMatrixObservables(n, diag=torch.stack(diags) if diags else None, pauli=paulis or None,
-                                  targets=pack_overlaps(overlaps, dim, batch, device) if overlaps else None, purity=purity, shots=shots)
-    first = {"diag": 0, "pauli": len(diags), "fid": len(diags) + len(paulis), "purity": len(diags) + len(paulis) + len(overlaps)}
+                                  targets=pack_overlaps(overlaps, dim, batch, device) if overlaps else None, purity=purity, shots=shots,
+                                  rdms=rdms or None)
+    n_real = len(diags) + len(paulis) + len(overlaps) + int(purity)
+    first = {"diag": 0, "pauli": len(diags), "fid": len(diags) + len(paulis), "purity": n_real - 1, "rdm": n_real}
     return dm, [first[kind] + i for kind, i in kinds]
 
 
@@ -181,7 +190,8 @@ def mesolve(ham, psi0: Tensor, tsave: Tensor, noise: NoiseModel, options: Option
 
     ``observables`` (see ``pack_dm_observables``) are evaluated natively at every evaluation time while rho is on the device
     (``MasterEquationResult.expect``, differentiable); ``shots``: an int (that many at the final time) or a ``ShotRequest``, drawn
-    natively from the diagonal of rho; ``store_states=False`` keeps the ``(n_t, 4^n)`` trajectory out of the result (``states``
+    natively from the diagonal of rho; ``ReducedDensityMatrix`` entries come back in ``MasterEquationResult.rdms`` (complex
+    ``(n_t, B, 2^m, 2^m)``, in the order of their ``qubits``) and take no slot of ``expect``; ``store_states=False`` keeps the ``(n_t, 4^n)`` trajectory out of the result (``states``
     is then empty) — gradients of the native values need no stored state."""
     n = ham._size
     if n > MAX_ME_QUBITS:
@@ -207,4 +217,7 @@ def mesolve(ham, psi0: Tensor, tsave: Tensor, noise: NoiseModel, options: Option
     rho0 = torch.einsum("xb,yb->bxy", psi, psi.conj()).reshape(psi.shape[1], dim * dim).contiguous()
     states, expect = evolve(amp2, det2, u2, tsave, rho0, spec, None)  # (n_t, B, dim^2), (rows, n_t, B)
     rho = states.reshape(states.shape[0], states.shape[1], dim, dim).permute(0, 2, 3, 1)
-    return MasterEquationResult(rho, dict(spec.options.get("_last_stats", {})), [expect[r] for r in rows], shots)
+    obs_list = list(observables or [])
+    expect, _, rdms = split_observables(expect, 0, dm.rdms if dm is not None else None)
+    real_rows = [r for r, o in zip(rows, obs_list) if not isinstance(o, ReducedDensityMatrix)]
+    return MasterEquationResult(rho, dict(spec.options.get("_last_stats", {})), [expect[r] for r in real_rows], shots, rdms or [])

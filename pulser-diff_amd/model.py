@@ -206,7 +206,8 @@ class QuantumModel(Module):
 
     def reduced_density_matrix(self, qubits) -> tuple[Tensor, Tensor]:
         """Evaluation times and the state of the subsystem ``qubits`` (indices in register order, or a ``ReducedDensityMatrix``),
-        complex ``(n_t, B, 2^m, 2^m)``, evaluated and differentiated natively: no trajectory is stored or handed to autograd."""
+        complex ``(n_t, B, 2^m, 2^m)``, evaluated and differentiated natively: no trajectory is stored or handed to autograd.  Noisy models (collapse-operator
+        noise: the master equation) return ``Tr_E rho(t)``, the partial trace of the register's density matrix."""
         obs = qubits if isinstance(qubits, ReducedDensityMatrix) else ReducedDensityMatrix(qubits)
         evaluation_times, results = self._run(observables=[obs], store_states=False)
         return evaluation_times, results.reduced_density_matrix(obs)

@@ -11,7 +11,7 @@ amplitude index): ``x`` = the qubits carrying X or Y, ``z`` = the qubits carryin
 from __future__ import annotations
 
 import math
-from typing import Iterable, Mapping, Sequence, Union
+from typing import Iterable, Mapping, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -297,7 +297,11 @@ class ReducedDensityMatrix:
 
     The matrix index ``a`` enumerates the settings of ``qubits`` with the FIRST listed qubit most significant, in the basis order of
     the register (r = 0, g = 1).  The library works in ascending qubit order; other orders are a permutation of the small matrix,
-    applied in torch.  Read the values with ``results.reduced_density_matrix`` / ``SolveResult.rdms``: complex ``(n_t, B, 2^m, 2^m)``."""
+    applied in torch.  Read the values with ``results.reduced_density_matrix`` / ``SolveResult.rdms``: complex ``(n_t, B, 2^m, 2^m)``.
+
+    In a master-equation run the same object asks for the partial trace of the register's density matrix,
+    ``rho_A[a][a'] = sum_e rho[idx(a, e)][idx(a', e)]`` (``RydProblem.n_dm_rdms / dm_rdm_masks``; ``csrc/dm_kernels.hpp``), with
+    ``store_states=False``; ``MasterEquationResult.rdms`` holds the values."""
 
     def __init__(self, qubits):
         qs = tuple(int(q) for q in qubits)
@@ -346,15 +350,16 @@ class ReducedDensityMatrix:
 
 
 def reduced_density_matrix(obs: ReducedDensityMatrix, states: Tensor) -> Tensor:
-    """The torch route on stored kets ``(n_t, dim, B)``: complex ``(n_t, B, 2^m, 2^m)``, differentiable."""
+    """The torch route on stored kets ``(n_t, dim, B)`` or stored density matrices ``(n_t, dim, dim, B)`` (the partial trace
+    ``Tr_E rho``; no Hermiticity assumed): complex ``(n_t, B, 2^m, 2^m)``, differentiable, in the order of ``obs.qubits``."""
     if not isinstance(obs, ReducedDensityMatrix):
         raise TypeError(f"expected a ReducedDensityMatrix, got {type(obs)}")
     if states.is_sparse:
         states = states.to_dense()
     if states.ndim == 4:
-        raise NotImplementedError("ReducedDensityMatrix is defined on kets; density matrices (master-equation runs) are not supported")
+        return _reduced_density_matrix_dm(obs, states)
     if states.ndim != 3:
-        raise ValueError(f"expected kets (n_t, dim, B), got {tuple(states.shape)}")
+        raise ValueError(f"expected kets (n_t, dim, B) or density matrices (n_t, dim, dim, B), got {tuple(states.shape)}")
     n_t, dim, batch = states.shape
     n = dim.bit_length() - 1
     if dim != 1 << n:
@@ -365,6 +370,22 @@ def reduced_density_matrix(obs: ReducedDensityMatrix, states: Tensor) -> Tensor:
     st = states.to(torch.complex128).reshape((n_t,) + (2,) * n + (batch,))
     st = st.permute([0] + [1 + q for q in obs.qubits] + [1 + q for q in rest] + [n + 1]).reshape(n_t, 2 ** m, 2 ** (n - m), batch)
     return torch.einsum("taeb,tceb->tbac", st, st.conj())
+
+
+def _reduced_density_matrix_dm(obs: ReducedDensityMatrix, states: Tensor) -> Tensor:
+    """``rho_A[a][a'] = sum_e rho[idx(a, e)][idx(a', e)]`` of stored density matrices ``(n_t, dim, dim, B)``."""
+    n_t, dim, dim2, batch = states.shape
+    n = dim.bit_length() - 1
+    if dim != 1 << n or dim2 != dim:
+        raise ValueError(f"ReducedDensityMatrix needs density matrices (n_t, 2^n, 2^n, B), got {tuple(states.shape)}")
+    obs.check(n)
+    m = obs.n_sub
+    rest = [q for q in range(n) if q not in obs.qubits]
+    order = list(obs.qubits) + rest
+    st = states.to(torch.complex128).reshape((n_t,) + (2,) * (2 * n) + (batch,))
+    st = st.permute([0] + [1 + q for q in order] + [1 + n + q for q in order] + [2 * n + 1])
+    st = st.reshape(n_t, 2 ** m, 2 ** (n - m), 2 ** m, 2 ** (n - m), batch)
+    return torch.einsum("taeceb->tbac", st)
 
 
 def pack_rdms(observables: Sequence[ReducedDensityMatrix], n_qubits: int) -> np.ndarray:
@@ -428,10 +449,13 @@ class DensityMatrixObservables:
     ``pauli``    list of ``PauliObservable`` on ``n_atoms`` qubits (or the four packed host arrays): ``Re Tr(O rho)``
     ``targets``  complex128 DEVICE tensor ``(n_fid, 1 | B, 2^n)`` (``pack_overlaps``): ``Re <phi|rho|phi>``; constants
     ``purity``   one row ``sum |rho_xy|^2``
+    ``rdms``     list of ``ReducedDensityMatrix`` over the ATOMS (or raw masks, bit j = atom j): ``2 * 4^m`` rows each, Re / Im of
+                 every entry of ``Tr_E rho`` in ascending atom order (``solver.split_observables`` takes them out)
     ``shots``    the shots of ``ProblemSpec.shots`` are drawn from ``max(Re rho[x][x], 0)`` (atom indices ``x < 2^n``)"""
 
-    def __init__(self, n_atoms: int, diag=None, pauli=None, targets=None, purity: bool = False, shots: bool = False):
+    def __init__(self, n_atoms: int, diag=None, pauli=None, targets=None, purity: bool = False, shots: bool = False, rdms=None):
         self.n_atoms = int(n_atoms)
+        self.rdms = None if rdms is None or len(rdms) == 0 else list(rdms)
         self.diag = diag
         self.pauli = pauli
         self.targets = targets
@@ -464,8 +488,34 @@ class DensityMatrixObservables:
         packed = self.packed_pauli()
         return 0 if packed is None else len(packed[0]) - 1
 
+    def packed_rdms(self) -> Optional[np.ndarray]:
+        """The host array of ``RydProblem.dm_rdm_masks`` (None: no reduced density matrices); validated like the library does."""
+        if self.rdms is None:
+            return None
+        if not 1 <= len(self.rdms) <= MAX_RDMS:
+            raise ValueError(f"DensityMatrixObservables.rdms: 1 to {MAX_RDMS} reduced density matrices per call, got {len(self.rdms)}")
+        masks = []
+        for o in self.rdms:
+            if isinstance(o, ReducedDensityMatrix):
+                o.check(self.n_atoms)
+                masks.append(o.mask)
+                continue
+            try:
+                v = int(o)
+            except (TypeError, ValueError):
+                raise TypeError(f"DensityMatrixObservables.rdms: ReducedDensityMatrix objects or integer masks, got {type(o)}") from None
+            if v <= 0 or v >> self.n_atoms or bin(v).count("1") > MAX_RDM_QUBITS:
+                raise ValueError(f"DensityMatrixObservables.rdms: mask {v:#x} must name 1 to {MAX_RDM_QUBITS} atoms below {self.n_atoms}")
+            masks.append(v)
+        return np.asarray(masks, dtype=np.uint32)
+
+    def rdm_rows(self) -> int:
+        """Rows the reduced density matrices take: 2 * sum_o 4^{m_o}."""
+        masks = self.packed_rdms()
+        return 0 if masks is None else sum(2 * 4 ** bin(int(v)).count("1") for v in masks)
+
     def rows(self) -> int:
-        return self.n_diag + self.n_pauli + self.n_fid + int(self.purity)
+        return self.n_diag + self.n_pauli + self.n_fid + int(self.purity) + self.rdm_rows()
 
     def check(self, n_qubits: int, batch: int, device=None) -> None:
         """Every buffer against the register (the C ABI sees raw pointers): ValueError, never a bad device read."""
@@ -485,6 +535,7 @@ class DensityMatrixObservables:
         if self.targets is not None and self.targets.shape[1] not in (1, batch):
             raise ValueError(f"DensityMatrixObservables.targets: the target batch must be 1 or the batch size {batch}, got {self.targets.shape[1]}")
         self.packed_pauli()
+        self.packed_rdms()
 
 
 def dm_trace_indices(obs: PauliObservable):

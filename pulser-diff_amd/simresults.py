@@ -22,7 +22,7 @@ from .result import SampledResult, TorchResult
 from .observables import (PauliObservable, ReducedDensityMatrix, StateOverlap, fidelity_states, overlap_states, purity_states,
                           reduced_density_matrix)
 from .shots import ShotRequest, bitstring_counts, indices_to_bitstrings
-from .utils import DiagonalObservable, expect, von_neumann_entropy
+from .utils import DiagonalObservable, expect, negativity, von_neumann_entropy
 
 
 class SimulationResults(ABC):
@@ -169,12 +169,11 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
         return purity_states(self.states)
 
     def reduced_density_matrix(self, obs: ReducedDensityMatrix) -> Tensor:
-        """``Tr_E |psi_b(t_k)><psi_b(t_k)|`` on the qubits of ``obs``, complex ``(n_t, B, 2^m, 2^m)``: the native values when ``obs``
-        was handed to ``run(observables=...)``, else computed from the stored states."""
+        """``Tr_E |psi_b(t_k)><psi_b(t_k)|`` on the qubits of ``obs`` — in a master-equation run ``Tr_E rho_b(t_k)`` — complex
+        ``(n_t, B, 2^m, 2^m)``: the native values when ``obs`` was handed to ``run(observables=...)``, else computed from the stored
+        states (kets or density matrices)."""
         if not isinstance(obs, ReducedDensityMatrix):
             raise TypeError(f"reduced_density_matrix takes a ReducedDensityMatrix, got {type(obs)}")
-        if self._density:
-            raise NotImplementedError("ReducedDensityMatrix is defined on kets; this is a master-equation run.")
         if self._basis_name == "all":
             raise NotImplementedError("ReducedDensityMatrix is not available in the three-level all-basis.")
         hit = [k for k, o in enumerate(self._rdm_observables) if o is obs]
@@ -184,8 +183,14 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
 
     def entanglement_entropy(self, obs: ReducedDensityMatrix, base: float = 2) -> Tensor:
         """Von Neumann entropy of the subsystem of ``obs`` at every evaluation time, real ``(n_t, B)`` (``base=2``: bits); for a pure
-        register state the entanglement entropy between the subsystem and the rest."""
+        register state the entanglement entropy between the subsystem and the rest.  For a MIXED register state (master-equation
+        runs) it is the entropy of the subsystem, not an entanglement measure: use ``negativity`` for that."""
         return von_neumann_entropy(self.reduced_density_matrix(obs), base)
+
+    def negativity(self, obs: ReducedDensityMatrix, n_first: int) -> Tensor:
+        """Negativity of the state of the subsystem of ``obs`` across the cut between its first ``n_first`` listed qubits and the
+        others, real ``(n_t, B)`` (``utils.negativity``); an entanglement measure for mixed states too."""
+        return negativity(self.reduced_density_matrix(obs), n_first)
 
     def sample_state(self, t: float, n_samples: int = 1000, t_tol: float = 1.0e-3) -> Counter:
         """simresults.py:497-540: ideal samples, then the detection errors of the SPAM model (a measured 0 flips with

@@ -80,7 +80,7 @@ class ProblemSpec:
     # indices (shots.ShotRequest.indices); a non-differentiable by-product, allowed next to a gradient
     shots: Optional[ShotRequest] = None
     # density-matrix observables (RydProblem.dm_*): the register is the doubled register of a density matrix and these functionals of
-    # rho — diagonal tables, Pauli strings over the atoms, fidelities with target states, the purity — are evaluated and differentiated
+    # rho — diagonal tables, Pauli strings over the atoms, fidelities with target states, the purity, reduced density matrices — are evaluated and differentiated
     # natively; their rows follow every other row of `expect` (observables.DensityMatrixObservables).  `dm.shots`: the shots of
     # `shots` are drawn from the diagonal of rho
     dm: Optional[DensityMatrixObservables] = None
@@ -231,8 +231,12 @@ class _Call:
             diag = None if dm.diag is None else dm.diag.contiguous()
             targets = None if dm.targets is None else dm.targets.contiguous()
             packed = dm.packed_pauli()
-            self.dm_buffers = (diag, targets, packed)
+            rdm_masks = dm.packed_rdms()
+            self.dm_buffers = (diag, targets, packed, rdm_masks)
             p.dm_atoms = dm.n_atoms
+            if rdm_masks is not None:
+                p.n_dm_rdms = len(rdm_masks)
+                p.dm_rdm_masks = rdm_masks.ctypes.data
             if diag is not None:
                 p.n_dm_diag = diag.shape[0]
                 p.dm_diag = diag.data_ptr()

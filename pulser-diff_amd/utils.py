@@ -185,3 +185,33 @@ def von_neumann_entropy(rho: Tensor, base: float = 2) -> Tensor:
     eigenvalues (pure states, product states); optimise ``purity`` instead."""
     ev = torch.linalg.eigvalsh(0.5 * (rho + rho.mH)).clamp_min(0.0)
     return -torch.special.xlogy(ev, ev).sum(dim=-1) / math.log(base)
+
+
+def partial_transpose(rho: Tensor, n_first: int) -> Tensor:
+    """Matrices ``(..., 2^m, 2^m)`` transposed on the first party: the ``n_first`` LEADING qubits of the matrix ordering
+    (``0 < n_first < m``), ``rho^{T_1}[(a1, a2), (b1, b2)] = rho[(b1, a2), (a1, b2)]``."""
+    d = rho.shape[-1]
+    m = d.bit_length() - 1
+    if rho.ndim < 2 or rho.shape[-2] != d or d != 1 << m:
+        raise ValueError(f"expected matrices (..., 2^m, 2^m), got {tuple(rho.shape)}")
+    if not 0 < int(n_first) < m:
+        raise ValueError(f"n_first must split the {m} qubits into two non-empty parties, got {n_first}")
+    d1, d2 = 2 ** int(n_first), 2 ** (m - int(n_first))
+    return rho.reshape(rho.shape[:-2] + (d1, d2, d1, d2)).transpose(-4, -2).reshape(rho.shape)
+
+
+def negativity(rho: Tensor, n_first: int) -> Tensor:
+    """``(||rho^{T_1}||_1 - tr rho) / 2`` = minus the sum of the negative eigenvalues of the partial transpose (``eigvalsh`` of its
+    Hermitian part) of density matrices ``(..., 2^m, 2^m)``; ``n_first`` as in ``partial_transpose``.  Zero for separable states,
+    1/2 for a Bell pair.  Differentiable; the gradient is undefined at degenerate spectra (``eigvalsh``)."""
+    pt = partial_transpose(rho, n_first)
+    ev = torch.linalg.eigvalsh(0.5 * (pt + pt.mH))
+    return (-ev).clamp_min(0.0).sum(dim=-1)
+
+
+def logarithmic_negativity(rho: Tensor, n_first: int, base: float = 2) -> Tensor:
+    """``log ||rho^{T_1}||_1`` from the same eigenvalues (``base=2``: 1 for a Bell pair); an upper bound on the distillable
+    entanglement.  Differentiable like ``negativity``."""
+    pt = partial_transpose(rho, n_first)
+    ev = torch.linalg.eigvalsh(0.5 * (pt + pt.mH))
+    return torch.log(ev.abs().sum(dim=-1)) / math.log(base)

@@ -9,7 +9,14 @@ synchronisation; median, min and max of the wall time and the peak device memory
 reset before every run after a garbage collection, minus what was allocated at that moment (the problem's tables, and whatever
 persistent workspace torch's BLAS took in an earlier stored-route run; printed as `held`).  Forward-only runs are repeated at half the evaluation times to show what grows with n_t.  `big` (0: skip):
 one forward-only run at that many atoms with half the evaluation times and no stored states — 4^12 amplitudes are 256 MiB per
-density matrix, which the stored-rho route cannot hold for a few hundred times."""
+density matrix, which the stored-rho route cannot hold for a few hundred times.
+
+    python tools/time_dm_observables.py rdm [atoms = 8,10,12] [evaluation times = 50] [repeats = 3] [times at 12 atoms = 8]
+
+The reduced-density-matrix leg: Tr_E rho on m = 2 and m = 6 atoms (the leading ones) at every evaluation time, natively with
+store_states=False against stored rho plus the torch partial trace (observables.reduced_density_matrix); forward only and, below 12
+atoms, forward + gradient of sum |rho_A(T)|^2.  Same measurement as above; 12 atoms runs forward only on few evaluation times (the
+stored route holds 256 MiB per time and torch's permuted copy of it)."""
 import gc
 import statistics
 import sys
@@ -23,7 +30,7 @@ import torch  # noqa: E402
 import pulser_diff_amd as P  # noqa: E402
 from pulser_diff_amd import pulses as pl  # noqa: E402
 from pulser_diff_amd.lindblad import mesolve  # noqa: E402
-from pulser_diff_amd.observables import StateOverlap  # noqa: E402
+from pulser_diff_amd.observables import ReducedDensityMatrix, StateOverlap, reduced_density_matrix  # noqa: E402
 from pulser_diff_amd.utils import DiagonalObservable, total_magnetization_diag  # noqa: E402
 
 DURATION_NS = 200
@@ -68,7 +75,21 @@ def run(route, ham, tsave, psi0, zsum, fid, grad):
     return float(z[-1, 0].detach()), float(f[-1, 0].detach())
 
 
-def measure(route, args, grad, repeats):
+def run_rdm(route, ham, tsave, psi0, obs, grad):
+    h = leaf_ham(ham, grad)
+    with torch.set_grad_enabled(grad):
+        if route == "native":
+            rho_a = mesolve(h, psi0, tsave, ham.config, observables=[obs], store_states=False).rdms[0]
+        else:  # the whole trajectory, the partial trace in torch
+            rho, _ = mesolve(h, psi0, tsave, ham.config)
+            rho_a = reduced_density_matrix(obs, rho)
+        pur = (rho_a[-1].real ** 2 + rho_a[-1].imag ** 2).sum()
+        if grad:
+            pur.backward()
+    return float(torch.einsum("baa->b", rho_a[-1].detach()).real[0]), float(pur.detach())
+
+
+def measure(route, args, grad, repeats, run=run):
     run(route, *args, grad)  # warm-up (allocator, plan cache, code objects)
     times, peak, held, vals = [], 0, 0, None
     for _ in range(repeats):
@@ -84,7 +105,34 @@ def measure(route, args, grad, repeats):
     return statistics.median(times), min(times), max(times), peak, held, vals
 
 
+def main_rdm(argv):
+    sizes = [int(s) for s in (argv[0] if len(argv) > 0 else "8,10,12").split(",")]
+    n_t = int(argv[1]) if len(argv) > 1 else 50
+    repeats = int(argv[2]) if len(argv) > 2 else 3
+    n_t_big = int(argv[3]) if len(argv) > 3 else 8
+    dev = "cuda"
+    print(f"device: {torch.cuda.get_device_name(0)}; {DURATION_NS} ns pulse, dephasing + relaxation; Tr_E rho on the m leading atoms at every "
+          f"evaluation time; 1 warm-up, {repeats} timed runs, median [min, max]")
+    print(f"{'atoms':>5} {'m':>2} {'n_t':>4} {'mode':>8} {'route':>7} {'median ms':>10} {'min ms':>9} {'max ms':>9} {'peak MiB':>10} {'held MiB':>9}   "
+          "Tr rho_A(T), sum |rho_A(T)|^2")
+    for n in sizes:
+        nt = n_t if n < 12 else n_t_big
+        ham, tsave, psi0, _, _ = problem(n, nt, dev)
+        for m in (2, 6):
+            obs = ReducedDensityMatrix(range(m))
+            for grad in ((False, True) if n < 12 else (False,)):
+                for route in ("native", "stored"):
+                    med, lo, hi, peak, held, vals = measure(route, (ham, tsave, psi0, obs), grad, repeats, run=run_rdm)
+                    print(f"{n:>5} {m:>2} {nt:>4} {'fwd+grad' if grad else 'fwd':>8} {route:>7} {1e3 * med:>10.1f} {1e3 * lo:>9.1f} {1e3 * hi:>9.1f} "
+                          f"{peak / 2**20:>10.1f} {held / 2**20:>9.1f}   {vals[0]:.9f} {vals[1]:.9f}", flush=True)
+        del ham, tsave, psi0
+        gc.collect()
+        torch.cuda.empty_cache()
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "rdm":
+        return main_rdm(sys.argv[2:])
     sizes = [int(s) for s in (sys.argv[1] if len(sys.argv) > 1 else "8,10").split(",")]
     n_t = int(sys.argv[2]) if len(sys.argv) > 2 else 200
     repeats = int(sys.argv[3]) if len(sys.argv) > 3 else 5
