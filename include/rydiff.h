@@ -255,7 +255,7 @@ typedef struct RydProblem {
      * (idx(a, e), idx(a', e)) — the map is linear in v, so there is no G + G^dagger as on kets — formed in the workspace buffer of
      * the other density-matrix cotangents (after them) and injected through the grad_states route.  Honoured wherever the other
      * dm_* rows are: every kernel family, every tape mode, states_out == NULL without a tape, next to ket-style rows on the doubled
-     * register.  Not together with shard_bits > 0 and not in rydiff_forward_tangent (RYDIFF_ENOTIMPL, as for dm_atoms > 0).
+     * register.  Not together with shard_bits > 0 and not in rydiff_forward_tangent (RYDIFF_ENOTIMPL: the other dm_* rows have tangents there).
      * RYDIFF_EINVAL, before anything touches a device: a count outside [0, RYDIFF_MAX_RDMS], NULL masks with a non-zero count, an
      * empty mask, more than RYDIFF_MAX_RDM_QUBITS bits in a mask, a bit at or above n.  Traffic per RDM and state: 2^(n+m) * 16 B,
      * never the 4^n matrix.  dm_atoms = 0: the fields are ignored, like the other dm_* fields.  n_dm_rdms = 0: nothing changes.  (The
@@ -285,7 +285,8 @@ typedef struct RydProblem {
      * smallest x with C[x] > u * S, the clamping of u, RYDIFF_SHOT_NONE when S == 0, never an x with p[x] == 0).
      * The ket-style fields keep their meaning on the doubled register.  Honoured by rydiff_forward in every kernel family and with
      * every tape mode (states_out == NULL without a tape included: rydiff_plan adds the trajectory the one-launch sweeps are
-     * evaluated from).  Not together with shard_bits > 0 and not in rydiff_forward_tangent (RYDIFF_ENOTIMPL).  RYDIFF_EINVAL:
+     * evaluated from).  Not together with shard_bits > 0 (RYDIFF_ENOTIMPL).  rydiff_forward_tangent evaluates the diag / Pauli /
+     * fidelity / purity rows and their tangents (not the RDMs, not the shots); rydiff_forward_geometry refuses dm_atoms > 0.  RYDIFF_EINVAL:
      * n_qubits != 2 * dm_atoms, dm_atoms outside [0, RYDIFF_MAX_DM_ATOMS], a count out of range (n_dm_diag <= RYDIFF_MAX_DM_DIAG,
      * strings <= RYDIFF_MAX_PAULI_STRINGS, n_dm_fid <= RYDIFF_MAX_OVERLAPS, dm_purity / dm_shots 0 or 1), a mask bit at or above n,
      * a NULL table with a non-zero count, dm_shots without n_shots.  Traffic per save point and trajectory: 2^n * 16 B per distinct
@@ -439,7 +440,11 @@ typedef struct RydTangent {
     const double* d_det;    /* DEVICE float64    [n_dir][coeff_batch][n_det_terms][n_samples] or NULL */
     const double* d_u;      /* DEVICE float64    [n_dir][N(N-1)/2] or NULL */
     const void*   d_psi0;   /* DEVICE complex128 [n_dir][B][2^N] or NULL */
+    int32_t flags;          /* 0, or RYDIFF_TANGENT_* ored: what the caller asks the sweep to take beyond plain Ising kets */
 } RydTangent;
+/* Without its flag a problem with dense pair terms / a density-matrix register is RYDIFF_ENOTIMPL, as before the sweep took them. */
+#define RYDIFF_TANGENT_PAIR_TERMS 1      /* n_pair_terms > 0: the pair terms ride in the pass as constants of every direction */
+#define RYDIFF_TANGENT_DENSITY_MATRIX 2  /* dm_atoms > 0: the vectors are vec(rho) and its tangents; the dm_* rows get tangents */
 
 /* sizeof(RydTangent) as this library was compiled (see rydiff_sizeof_problem). */
 size_t rydiff_sizeof_tangent(void);
@@ -447,18 +452,25 @@ size_t rydiff_sizeof_tangent(void);
 /* Device workspace of rydiff_forward_tangent for n_dir directions (sized as if every tangent pointer were given); 0 on an
  * error (rydiff_last_error).  `info`: from rydiff_plan(p, 0, 0, ...).  Host only. */
 size_t rydiff_tangent_workspace_bytes(const RydProblem* p, const RydPlanInfo* info, int n_dir);
+/* The same for a call with RydTangent.flags = flags (rydiff_tangent_workspace_bytes is flags = 0). */
+size_t rydiff_tangent_workspace_bytes_flags(const RydProblem* p, const RydPlanInfo* info, int n_dir, int flags);
 
 /* The tangent sweep.  Asynchronous like rydiff_forward with a plan: it only enqueues work on `stream`.
  *   info         HOST: result of rydiff_plan(p, 0, 0, ...) for the SAME table values (required)
- *   psi0         DEVICE complex128 [B][2^N]
+ *   psi0         DEVICE complex128 [B][2^N]  (dm_atoms > 0: vec(rho_0), and d_psi0 = vec(d rho_0))
  *   expect_out   DEVICE float64 [rows][n_tsave][B] or NULL: the values, rows = n_obs + n_pauli_obs + 2 * n_overlaps in the order
- *                of rydiff_forward
+ *                of rydiff_forward; with dm_atoms > 0 followed by n_dm_diag + n_dm_pauli_obs + n_dm_fid + dm_purity rows, as there
  *   dexpect_out  DEVICE float64 [n_dir][rows][n_tsave][B] (required): diagonal rows 2 sum_y o[y] Re(conj psi[y] dpsi_d[y]), Pauli
- *                rows 2 sum_s w_s Re<psi|P_s|dpsi_d>, overlap rows Re / Im <phi_o|dpsi_d>; every save point, k = 0 included
+ *                rows 2 sum_s w_s Re<psi|P_s|dpsi_d>, overlap rows Re / Im <phi_o|dpsi_d>; every save point, k = 0 included.
+ *                Density-matrix rows (dm_atoms > 0; v = vec(rho), dv_d its tangent): the diagonal, Pauli and fidelity rows are
+ *                linear in v — the row's functional of dv_d — and the purity row is 2 Re sum_i conj(v_i) dv_d,i
  *   workspace    DEVICE, >= rydiff_tangent_workspace_bytes(p, info, n_dir)
  * Both solvers, coeff_batch 1 or B, dp5_piece_refine honoured (same plan); kernel_variant is ignored: the sweep has one kernel
- * family (launch per factor, one amplitude per thread).  Not implemented (RYDIFF_ENOTIMPL): state-sharded runs, pair terms,
- * conditioned / ones-counting terms, density-matrix registers (dm_atoms > 0).  Every argument is validated before anything touches a device. */
+ * family (launch per factor, one amplitude per thread).  With RYDIFF_TANGENT_PAIR_TERMS in tangent->flags dense pair terms
+ * (n_pair_terms > 0: the XY exchange, the dissipator of a master-equation run on the doubled register) ride in the same pass as
+ * constants of every direction; with RYDIFF_TANGENT_DENSITY_MATRIX a register with dm_atoms > 0 is taken.  Not implemented
+ * (RYDIFF_ENOTIMPL): pair terms / dm_atoms > 0 without their flag, state-sharded runs, conditioned / ones-counting terms, shots,
+ * reduced density matrices (n_rdms > 0, n_dm_rdms > 0).  Every argument is validated before anything touches a device. */
 int rydiff_forward_tangent(const RydProblem* p, const RydPlanInfo* info, const RydTangent* tangent, const void* psi0,
                            double* expect_out, double* dexpect_out, void* workspace, size_t workspace_bytes, void* stream);
 
@@ -480,9 +492,12 @@ int rydiff_forward_tangent(const RydProblem* p, const RydPlanInfo* info, const R
  * order, the blocks in a fixed tree — so two calls on the same inputs return bit-identical matrices (F subtracts numbers of equal
  * size and is inverted in natural-gradient solves).  Traffic: one read of (1 + n_dir) * B * 2^N * 16 bytes per save point on top of
  * the sweep's; nothing of size 2^N is written.  Everything else — expect_out, the solvers, the validation before anything touches
- * a device, what is RYDIFF_ENOTIMPL (state-sharded runs, pair terms, conditioned / ones-counting terms, shots, reduced density
- * matrices, dm_atoms > 0) — is rydiff_forward_tangent's; RYDIFF_EINVAL also for a NULL gram_out. */
+ * a device, what is RYDIFF_ENOTIMPL (state-sharded runs, conditioned / ones-counting terms, shots, reduced density matrices) —
+ * is rydiff_forward_tangent's; pair terms on kets are taken with RYDIFF_TANGENT_PAIR_TERMS (the same sweep).  On top of that
+ * dm_atoms > 0 is RYDIFF_ENOTIMPL here whatever the flags (and the workspace functions return 0): the Gram matrix of vec(rho) and its
+ * tangents is not the mixed-state quantum Fisher information.  RYDIFF_EINVAL also for a NULL gram_out. */
 size_t rydiff_geometry_workspace_bytes(const RydProblem* p, const RydPlanInfo* info, int n_dir);
+size_t rydiff_geometry_workspace_bytes_flags(const RydProblem* p, const RydPlanInfo* info, int n_dir, int flags);
 int rydiff_forward_geometry(const RydProblem* p, const RydPlanInfo* info, const RydTangent* tangent, const void* psi0,
                             double* expect_out, double* dexpect_out /* may be NULL */,
                             void* gram_out /* DEVICE complex128 [n_tsave][B][1+n_dir][1+n_dir], required */,

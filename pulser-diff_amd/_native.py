@@ -32,6 +32,8 @@ MAX_OVERLAPS = 16
 MAX_RDMS = 8
 MAX_RDM_QUBITS = 6
 MAX_TANGENTS = 8
+TANGENT_PAIR_TERMS = 1      # RYDIFF_TANGENT_PAIR_TERMS (RydTangent.flags): take dense pair terms
+TANGENT_DENSITY_MATRIX = 2  # RYDIFF_TANGENT_DENSITY_MATRIX: take a density-matrix register (dm_atoms > 0)
 MAX_DM_ATOMS = 12  # atoms of a density-matrix register (RydProblem.dm_atoms)
 MAX_DM_DIAG = 64  # diagonal observables of a density-matrix register
 MAX_SHOTS = 1 << 20  # shots per (sampled save point, trajectory)
@@ -139,6 +141,7 @@ class RydTangent(ctypes.Structure):
         ("d_det", ctypes.c_void_p),
         ("d_u", ctypes.c_void_p),
         ("d_psi0", ctypes.c_void_p),
+        ("flags", ctypes.c_int32),
     ]
 
 
@@ -155,8 +158,10 @@ EXPORTS = (
     "rydiff_sizeof_plan_info",
     "rydiff_sizeof_tangent",
     "rydiff_tangent_workspace_bytes",
+    "rydiff_tangent_workspace_bytes_flags",
     "rydiff_forward_tangent",
     "rydiff_geometry_workspace_bytes",
+    "rydiff_geometry_workspace_bytes_flags",
     "rydiff_forward_geometry",
 )
 
@@ -203,11 +208,15 @@ def lib() -> ctypes.CDLL:
     L.rydiff_sizeof_tangent.restype = ctypes.c_size_t
     L.rydiff_tangent_workspace_bytes.argtypes = [ctypes.POINTER(RydProblem), ctypes.POINTER(RydPlanInfo), i32]
     L.rydiff_tangent_workspace_bytes.restype = ctypes.c_size_t
+    L.rydiff_tangent_workspace_bytes_flags.argtypes = [ctypes.POINTER(RydProblem), ctypes.POINTER(RydPlanInfo), i32, i32]
+    L.rydiff_tangent_workspace_bytes_flags.restype = ctypes.c_size_t
     L.rydiff_forward_tangent.argtypes = [ctypes.POINTER(RydProblem), ctypes.POINTER(RydPlanInfo), ctypes.POINTER(RydTangent), vp, vp, vp,
                                          vp, ctypes.c_size_t, vp]
     L.rydiff_forward_tangent.restype = i32
     L.rydiff_geometry_workspace_bytes.argtypes = [ctypes.POINTER(RydProblem), ctypes.POINTER(RydPlanInfo), i32]
     L.rydiff_geometry_workspace_bytes.restype = ctypes.c_size_t
+    L.rydiff_geometry_workspace_bytes_flags.argtypes = [ctypes.POINTER(RydProblem), ctypes.POINTER(RydPlanInfo), i32, i32]
+    L.rydiff_geometry_workspace_bytes_flags.restype = ctypes.c_size_t
     L.rydiff_forward_geometry.argtypes = [ctypes.POINTER(RydProblem), ctypes.POINTER(RydPlanInfo), ctypes.POINTER(RydTangent), vp, vp, vp,
                                           vp, vp, ctypes.c_size_t, vp]
     L.rydiff_forward_geometry.restype = i32

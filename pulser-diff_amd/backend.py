@@ -26,10 +26,10 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from . import pulser_adapter, pulses
+from . import _native, pulser_adapter, pulses
 from .hamiltonian import COLLAPSE_NOISES, Hamiltonian
 from .lindblad import (MAX_ME_QUBITS, ME_DEFAULT_TOL, dissipator_block, doubled_pair_terms, doubled_tables, local_collapse_operators,
-                       mesolve)
+                       mesolve, mesolve_tangent)
 from .result import SampledResult
 from .simconfig import SimConfig
 from .simresults import CoherentResults, NoisyResults, SimulationResults
@@ -488,16 +488,24 @@ class TorchEmulator:
         return tangents["amp"], tangents["det"], tangents["u"]
 
     def run_sensitivities(self, x: list, observables: list, solver: SolverType = SolverType.DP5_SE, dist_grad: bool = False,
-                          **options: Any) -> "Sensitivities":
+                          route: Optional[str] = None, **options: Any) -> "Sensitivities":
         """Values AND derivatives of observables at EVERY evaluation time w.r.t. the tensors in ``x`` — what a loop of
         ``deriv_param(f, x, times, t)`` over all ``t`` delivers, in one forward-mode sweep (``rydiff_forward_tangent``): the state
         and one tangent state per scalar entry of ``x`` advance together, ~(1 + D) forward passes instead of n_t reverse sweeps.
 
         ``x`` takes what ``deriv_param`` takes: leaf parameters of the pulses, register coordinates and — with ``dist_grad=True``,
         which has the side effects it has in ``run`` — distances from ``qq_distances``.  ``observables``: diagonal observables
-        (``DiagonalObservable`` or diagonal dense tensors) and ``PauliObservable`` objects.  Configurations the native tangent sweep
-        does not take (master equation, three-level basis, XY exchange) run the loop of one-hot reverse sweeps instead;
-        ``Sensitivities.route`` says which ran.  Derivatives w.r.t. the evaluation times come from ``deriv_time``."""
+        (``DiagonalObservable`` or diagonal dense tensors) and ``PauliObservable`` objects; master-equation runs (collapse-operator
+        noise, ``DP5_ME``) additionally take ``StateOverlap`` (the fidelity ``<phi|rho|phi>``) and ``Purity``.
+
+        ``route``: ``None`` — noiseless Ising runs take the tangent sweep; master-equation runs, the XY exchange and the three-level
+        basis run the loop of one-hot reverse sweeps, as they always have.  ``"tangent"`` asks for the sweep: master-equation runs
+        (``lindblad.mesolve_tangent``: vec(rho) and its tangents on the doubled register, the dissipator and the exchange as constant
+        pair terms) and XY runs take it too; the three-level basis, which the sweep does not take, raises.  ``"adjoint-loop"`` forces
+        the loop anywhere (the A/B partner of the sweep).  ``Sensitivities.route`` says which ran.  Derivatives w.r.t. the evaluation
+        times come from ``deriv_time``."""
+        if route not in (None, "tangent", "adjoint-loop"):
+            raise ValueError(f'route must be None, "tangent" or "adjoint-loop", got {route!r}')
         x = list(x)
         if not x or not all(isinstance(t, Tensor) for t in x):
             raise TypeError("x must be a non-empty list of tensors")
@@ -520,19 +528,31 @@ class TorchEmulator:
             if isinstance(obs, ReducedDensityMatrix):
                 raise NotImplementedError("run_sensitivities does not take ReducedDensityMatrix observables (the tangent sweep "
                                           "evaluates none); differentiate results.reduced_density_matrix through run().")
-            if not isinstance(obs, (DiagonalObservable, PauliObservable)) and not (isinstance(obs, Tensor) and obs.ndim == 2):
-                raise TypeError("observables must be DiagonalObservable / PauliObservable objects or diagonal (dim, dim) tensors")
+            if isinstance(obs, Purity) and solver == SolverType.DP5_ME:
+                continue
+            kinds = (DiagonalObservable, PauliObservable) + ((StateOverlap,) if solver == SolverType.DP5_ME else ())
+            if not isinstance(obs, kinds) and not (isinstance(obs, Tensor) and obs.ndim == 2):
+                raise TypeError("observables must be DiagonalObservable / PauliObservable objects or diagonal (dim, dim) tensors "
+                                "(master-equation runs: StateOverlap and Purity too)")
             if tuple(obs.shape) != (full, full):
                 raise ValueError(f"Incompatible shape of observable.Expected {(full, full)}, got {tuple(obs.shape)}.")
         if dist_grad:
             self._enable_dist_grad()
         times = self._eval_times_array.detach()
         n_t = int(times.shape[0])
-        native = solver != SolverType.DP5_ME and ham.basis_name != "all" and not getattr(ham, "pair_terms", ())
+        sweepable = ham.basis_name != "all"  # what the tangent sweep takes at all
+        if route == "tangent" and not sweepable:
+            raise NotImplementedError("run_sensitivities: the tangent sweep is not available in the three-level all-basis (no "
+                                      "conditioned flips / ones-counting terms); route=None runs the adjoint loop there.")
+        # route=None keeps the choice callers have relied on: master-equation and XY runs loop unless the sweep is asked for
+        native = sweepable and route != "adjoint-loop" and (
+            route == "tangent" or (solver != SolverType.DP5_ME and not getattr(ham, "pair_terms", ())))
         if not native:
             # the loop the tangent sweep replaces: one reverse sweep per evaluation time and observable
             results = self.run(dist_grad=False, solver=solver, **options)
-            fs = [f.real for f in results.expect(observables)]
+            plain = [o for o in observables if not isinstance(o, Purity)]
+            plain_fs = iter(results.expect(plain))
+            fs = [results.purity().sum(dim=-1) if isinstance(o, Purity) else next(plain_fs).real for o in observables]
             grads = [torch.zeros((len(fs), n_t) + tuple(t.shape), dtype=torch.float64, device=t.device) for t in x]
             for o, f in enumerate(fs):
                 for k in range(n_t):
@@ -542,6 +562,28 @@ class TorchEmulator:
                         if g is not None:
                             g_out[o, k] = g.detach().to(torch.float64)
             return Sensitivities(torch.stack([f.detach() for f in fs]).to(torch.float64), grads, "adjoint-loop", times)
+
+        n_dir = sum(int(t.numel()) for t in x)
+        if solver == SolverType.DP5_ME:
+            # vec(rho) and its tangents on the doubled register; the rows come back in the order of `observables`
+            d_amp, d_det, d_u = self._table_tangents(x)
+            psi0 = self.initial_state
+            psi_db = (psi0.unsqueeze(1) if psi0.ndim == 1 else psi0).to(dev)
+            if d_amp is None and d_det is None and d_u is None:  # nothing in x reaches the tables
+                with torch.no_grad():
+                    res = mesolve(ham, psi_db, times, ham.config, dict(options), observables=observables, store_states=False)
+                expect = torch.stack(res.expect)
+                dexpect = torch.zeros((n_dir,) + tuple(expect.shape), dtype=torch.float64, device=expect.device)
+            else:
+                expect, dexpect = mesolve_tangent(ham, psi_db, times, ham.config, dict(options), observables,
+                                                  d_amp=d_amp, d_det=d_det, d_u=d_u)
+            values, dvals = expect.sum(dim=-1), dexpect.sum(dim=-1)
+            grads, d0 = [], 0
+            for t in x:
+                m = int(t.numel())
+                grads.append(dvals[d0:d0 + m].permute(1, 2, 0).reshape(len(observables), n_t, *t.shape).to(t.device))
+                d0 += m
+            return Sensitivities(values, grads, "tangent", times)
 
         diag_rows, pauli_objs, order = [], [], []  # order: where observable i sits among the native rows
         for obs in observables:
@@ -576,7 +618,8 @@ class TorchEmulator:
         else:
             # the complex tables and the unrotated psi0: the rotating frame is a per-call device of sesolve, not of this path
             expect, dexpect = evolve_tangent(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, obs_diag,
-                                             d_amp=d_amp, d_det=d_det, d_u=d_u)
+                                             d_amp=d_amp, d_det=d_det, d_u=d_u,
+                                             flags=_native.TANGENT_PAIR_TERMS if spec.pair_terms else 0)  # (the XY exchange)
         values = expect.sum(dim=-1)[rows]            # (n_obs, n_t): summed over the columns of psi0 like results.expect
         dvals = dexpect.sum(dim=-1)[:, rows]         # (n_dir, n_obs, n_t)
         grads, d0 = [], 0
@@ -620,8 +663,8 @@ class TorchEmulator:
             raise NotImplementedError("run_quantum_fisher is not available in the three-level all-basis: the native tangent sweep takes "
                                       "no conditioned flips / ones-counting terms.")
         if getattr(ham, "pair_terms", ()):
-            raise NotImplementedError("run_quantum_fisher is not available with the XY exchange: the native tangent sweep takes no "
-                                      "dense pair terms.")
+            raise NotImplementedError("run_quantum_fisher is not available with the XY exchange: this route hands no dense pair terms "
+                                      "to the tangent sweep (solver.evolve_geometry takes them on request).")
         observables = list(observables)
         full = ham.dim ** ham._size
         for obs in observables:

@@ -86,6 +86,67 @@ __device__ __forceinline__ double2 pair_apply(const PairArgs& pa, int which, con
     return acc;
 }
 
+// relative flips of one pair term whose partner loads are in flight together in pair_apply_all: PF * NV loads of 16 bytes per thread —
+// the budget of the flip-bit chunks of the tangent sweep (tangent_kernels.hpp: TangentChunk), 15 / 14 / 18 loads at NV = 5 / 7 / 9
+template <int NV>
+struct PairFlips {
+    static constexpr int value = NV <= 5 ? 3 : 2;
+};
+
+// pair_apply on NV vectors at once (vector i of the caller's trajectory at v + i * vstride; its own values own[i] = v_i[x] are in
+// registers already):  acc_i += beta * sum_p sum_s T_p[4*own + s] * v_i[x with the pair's bits set to s].  The mask test per relative
+// flip is wave-uniform (flips absent from dl[t] cost nothing), the coefficient T[own][own ^ dlt] is read ONCE and serves all NV
+// vectors, dlt = 0 takes the own values, and the partner loads of a group of flips — of every vector — are issued together, before
+// any sum consumes one.
+template <int NV>
+__device__ __forceinline__ void pair_apply_all(const PairArgs& pa, const double2* __restrict__ v, size_t vstride, uint32_t x,
+                                               const double2 (&own)[NV], double br, double bi, double (&accr)[NV], double (&acci)[NV]) {
+    constexpr int PF = PairFlips<NV>::value;
+    for (int t = 0; t < pa.n; ++t) {  // uniform
+        const uint32_t ma = pa.ma[t], mb = pa.mb[t];
+        const unsigned dm = pa.dl[t];
+        const int o = ((x & ma) ? 2 : 0) | ((x & mb) ? 1 : 0);
+        const double2* __restrict__ row = pa.tab + size_t(t) * 32 + o * 4;  // the forward table
+        if (dm & 1u) {  // uniform: the diagonal of the block on the own values
+            const double2 c = row[o];
+            const double kr = br * c.x - bi * c.y, ki = br * c.y + bi * c.x;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                accr[i] += kr * own[i].x - ki * own[i].y;
+                acci[i] += kr * own[i].y + ki * own[i].x;
+            }
+        }
+#pragma unroll
+        for (int d0 = 1; d0 < 4; d0 += PF) {
+            if (!((dm >> d0) & ((1u << PF) - 1u))) continue;  // uniform: none of this group's flips in the block
+            double2 c[PF], part[PF][NV];
+#pragma unroll
+            for (int f = 0; f < PF; ++f) {
+                const int dlt = d0 + f;
+                if (dlt < 4 && (dm >> dlt & 1u)) {  // uniform
+                    c[f] = row[o ^ dlt];
+                    const uint32_t xp = x ^ ((dlt & 2) ? ma : 0u) ^ ((dlt & 1) ? mb : 0u);
+#pragma unroll
+                    for (int i = 0; i < NV; ++i) part[f][i] = v[size_t(i) * vstride + xp];
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);  // the scheduler may not sink a later flip's loads below the first flip's sums
+#pragma unroll
+            for (int f = 0; f < PF; ++f) {
+                const int dlt = d0 + f;
+                if (dlt < 4 && (dm >> dlt & 1u)) {  // uniform
+                    const double kr = br * c[f].x - bi * c[f].y, ki = br * c[f].y + bi * c[f].x;
+#pragma unroll
+                    for (int i = 0; i < NV; ++i) {
+                        accr[i] += kr * part[f][i].x - ki * part[f][i].y;
+                        acci[i] += kr * part[f][i].y + ki * part[f][i].x;
+                    }
+                }
+            }
+        }
+    }
+}
+
 struct FactorArgs {
     const double2* xin;
     double2* xout;

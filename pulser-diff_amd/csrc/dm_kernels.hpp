@@ -5,6 +5,8 @@
 //   k_dm_fidelity   <phi_o|rho|phi_o> for every target and the purity sum |v|^2 from ONE read of v: consecutive lanes on consecutive
 //                   y (rows of rho are contiguous: 16-byte loads), phi re-read from cache (2^n <= 4096 entries), the accumulators in
 //                   registers (NO = compile-time bound on the targets, as in k_overlap_expect)
+//   k_dm_purity_tangent  2 Re sum conj(v) dv_d: the tangent of the purity in the forward-mode sweep (the rows above are linear in v:
+//                   their tangents are the same kernels on dv_d)
 //   k_dm_shots      one workgroup per trajectory of a sampled save point: the clamped diagonal p[x] = max(Re v[x (2^n + 1)], 0)
 //                   into LDS, a fixed-order float64 prefix (segment sums, one serial scan of the 256 totals), one binary search per
 //                   shot — no float atomics: bit-reproducible
@@ -108,7 +110,31 @@ __global__ __launch_bounds__(256) void k_dm_fidelity(DmFidArgs a) {
     if (a.purity) block_atomic_add(pur, out + size_t(a.n_fid) * row, lds);
 }
 
-constexpr uint32_t kDmShotMax = 1u << RYDIFF_MAX_DM_ATOMS;  // probabilities of one density matrix: 32 KiB of LDS
+struct DmPurityTangentArgs {
+    const double2* v;    // vec(rho) at the save point, trajectory 0
+    const double2* dv;   // tangent 0 there
+    size_t vstride;      // amplitudes between consecutive tangents
+    double* out;         // &dexpect_out[0][purity row][0][0]
+    size_t out_dstride;  // doubles between directions
+    int k, B;
+    uint32_t total;      // 4^n
+};
+
+// grid (blocks, B, n_dir): out[d][k][b] += 2 Re sum_i conj(v_i) dv_d,i — the tangent of the purity sum |v|^2 (tangent sweep)
+__global__ __launch_bounds__(256) void k_dm_purity_tangent(DmPurityTangentArgs a) {
+    __shared__ double lds[8];
+    const int b = blockIdx.y, d = blockIdx.z;
+    const double2* __restrict__ v = a.v + size_t(b) * a.total;
+    const double2* __restrict__ w = a.dv + size_t(d) * a.vstride + size_t(b) * a.total;
+    double acc = 0.0;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < a.total; i += gridDim.x * 256u) {
+        const double2 q = v[i], t = w[i];
+        acc = fma(q.x, t.x, fma(q.y, t.y, acc));
+    }
+    block_atomic_add(2.0 * acc, a.out + size_t(d) * a.out_dstride + size_t(a.k) * a.B + b, lds);
+}
+
+constexpr uint32_t kDmShotMax =1u << RYDIFF_MAX_DM_ATOMS;  // probabilities of one density matrix: 32 KiB of LDS
 
 struct DmShotArgs {
     const double2* v;  // the sampled state, trajectory 0

@@ -42,8 +42,10 @@ void launch_dm_fidelity_n(const DmFidArgs& a, dim3 grid, hipStream_t stream) {
 }
 
 // every density-matrix row on the states of save points k0 .. k0 + nk - 1 (kstride amplitudes apart; `v` is the one at k0,
-// trajectory 0), trajectories of `bs`
-int launch_dm_expect(const ForwardCtx& c, const double2* v, size_t kstride, int k0, int nk, const BatchSlice& bs) {
+// trajectory 0), trajectories of `bs`.  `linear_only`: the rows that are linear in vec(rho) — diagonal, Pauli, fidelity — and nothing
+// else: what the tangent sweep runs on a tangent vector d rho_d, with c.dm_out redirected to direction d's rows of dexpect_out (the
+// purity row, quadratic, is k_dm_purity_tangent's)
+int launch_dm_expect(const ForwardCtx& c, const double2* v, size_t kstride, int k0, int nk, const BatchSlice& bs, bool linear_only = false) {
     const Plan& pl = c.rt.pl;
     if (!c.dm_out) return RYDIFF_OK;
     const size_t row = size_t(pl.T + 1) * pl.B;
@@ -69,7 +71,8 @@ int launch_dm_expect(const ForwardCtx& c, const double2* v, size_t kstride, int 
             hipLaunchKernelGGL(k_dm_trace, dim3(unsigned((D + 255) / 256), gy, unsigned(n_trace)), dim3(256), 0, c.stream, a);
             LAUNCH_CHECK();
         }
-        if (pl.n_dm_fid || pl.dm_purity) {
+        const int purity = linear_only ? 0 : pl.dm_purity;
+        if (pl.n_dm_fid || purity) {
             DmFidArgs a{};
             a.v = v + size_t(k) * kstride;
             a.kstride = kstride;
@@ -77,7 +80,7 @@ int launch_dm_expect(const ForwardCtx& c, const double2* v, size_t kstride, int 
             a.out = c.dm_out + size_t(n_trace) * row;
             a.n_fid = pl.n_dm_fid;
             a.fid_batch = pl.dm_fid_batch;
-            a.purity = pl.dm_purity;
+            a.purity = purity;
             a.n_tsave = pl.T + 1;
             a.k0 = k0 + k;
             a.B = pl.B;
@@ -92,7 +95,7 @@ int launch_dm_expect(const ForwardCtx& c, const double2* v, size_t kstride, int 
             else launch_dm_fidelity_n<RYDIFF_MAX_OVERLAPS>(a, grid, c.stream);
             LAUNCH_CHECK();
         }
-        if (pl.n_dm_rdm) {
+        if (pl.n_dm_rdm && !linear_only) {
             DmRdmArgs a{};
             a.v = v + size_t(k) * kstride;
             a.kstride = kstride;
@@ -114,6 +117,24 @@ int launch_dm_expect(const ForwardCtx& c, const double2* v, size_t kstride, int 
             LAUNCH_CHECK();
         }
     }
+    return RYDIFF_OK;
+}
+
+// tangent of the purity row at save point k: vec = [1 + D][B][4^n] with vec(rho) first; slot = &dexpect_out[0][purity row][0][0]
+int launch_dm_purity_tangent(const ForwardCtx& c, const double2* vec, int n_dir, int k, double* slot, size_t dstride) {
+    const Plan& pl = c.rt.pl;
+    DmPurityTangentArgs a{};
+    a.v = vec;
+    a.dv = vec + size_t(pl.B) * pl.dim;
+    a.vstride = size_t(pl.B) * pl.dim;
+    a.out = slot;
+    a.out_dstride = dstride;
+    a.k = k;
+    a.B = pl.B;
+    a.total = uint32_t(pl.dim);
+    const unsigned blocks = unsigned(std::min<size_t>((pl.dim + 255) / 256, 1024));
+    hipLaunchKernelGGL(k_dm_purity_tangent, dim3(blocks, unsigned(pl.B), unsigned(n_dir)), dim3(256), 0, c.stream, a);
+    LAUNCH_CHECK();
     return RYDIFF_OK;
 }
 

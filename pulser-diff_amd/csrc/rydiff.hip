@@ -565,16 +565,26 @@ int rydiff_backward(const RydProblem* p, const RydPlanInfo* info, const void* st
     return scatter_gradients(c, g_amp, g_det, g_u, g_tsave);
 }
 
-size_t rydiff_tangent_workspace_bytes(const RydProblem* p, const RydPlanInfo* info, int n_dir) {
+size_t rydiff_tangent_workspace_bytes_flags(const RydProblem* p, const RydPlanInfo* info, int n_dir, int flags) {
     Runtime rt;
     TangentLayout lay;
-    return tangent_plan(p, info, n_dir, rt, lay) ? 0 : lay.total;
+    return tangent_plan(p, info, n_dir, flags, rt, lay) ? 0 : lay.total;
+}
+
+size_t rydiff_tangent_workspace_bytes(const RydProblem* p, const RydPlanInfo* info, int n_dir) {
+    return rydiff_tangent_workspace_bytes_flags(p, info, n_dir, 0);
+}
+
+size_t rydiff_geometry_workspace_bytes_flags(const RydProblem* p, const RydPlanInfo* info, int n_dir, int flags) {
+    Runtime rt;
+    TangentLayout lay;
+    if (tangent_plan(p, info, n_dir, flags, rt, lay)) return 0;  // (the sweep's refusals first, as in rydiff_forward_geometry)
+    if (geometry_validate(p)) return 0;
+    return geometry_layout(rt.pl, lay, n_dir).total;
 }
 
 size_t rydiff_geometry_workspace_bytes(const RydProblem* p, const RydPlanInfo* info, int n_dir) {
-    Runtime rt;
-    TangentLayout lay;
-    return tangent_plan(p, info, n_dir, rt, lay) ? 0 : geometry_layout(rt.pl, lay, n_dir).total;
+    return rydiff_geometry_workspace_bytes_flags(p, info, n_dir, 0);
 }
 
 }  // extern "C"
@@ -584,14 +594,16 @@ namespace {
 // The forward-mode sweep behind rydiff_forward_tangent and rydiff_forward_geometry: the state and n_dir tangents through every
 // factor once (tangent_kernels.hpp); at every save point the observable values, their tangents (dexpect_out, skipped when NULL) and,
 // with `geometry`, the Gram matrix of the (1 + n_dir) vectors (gram_kernels.hpp).  One kernel family: launch per factor, one amplitude
-// per thread.
+// per thread; dense pair terms (the dissipator of a master-equation run, the XY exchange) ride in the same pass.  On the doubled
+// register of a density matrix (dm_atoms > 0) the vectors are vec(rho) and vec(d rho_d), and the density-matrix rows follow the ket rows.
 int tangent_sweep(const RydProblem* p, const RydPlanInfo* info, const RydTangent* tg, const void* psi0, double* expect_out,
                   double* dexpect_out, bool geometry, void* gram_out, void* workspace, size_t workspace_bytes, hipStream_t stream) {
     // ---- host-only validation: nothing below this block runs unless all of it passes ----
     if (!p) return fail(RYDIFF_EINVAL, "null problem");
     if (!tg) return fail(RYDIFF_EINVAL, "null tangent");
-    int rc = tangent_validate(p, info, tg->n_dir);  // n_dir, the plan, what the sweep does not implement
+    int rc = tangent_validate(p, info, tg->n_dir, tg->flags);  // n_dir, the plan, what the sweep does not implement
     if (rc) return rc;
+    if (geometry && (rc = geometry_validate(p))) return rc;
     if (!tg->d_amp && !tg->d_det && !tg->d_u && !tg->d_psi0)
         return fail(RYDIFF_EINVAL, "tangent: all of d_amp, d_det, d_u, d_psi0 are NULL (nothing to differentiate)");
     if (!geometry && !dexpect_out) return fail(RYDIFF_EINVAL, "null dexpect_out");
@@ -599,7 +611,7 @@ int tangent_sweep(const RydProblem* p, const RydPlanInfo* info, const RydTangent
     if (!psi0) return fail(RYDIFF_EINVAL, "null psi0");
     Runtime rt0;
     TangentLayout lay;
-    rc = tangent_plan(p, info, tg->n_dir, rt0, lay);
+    rc = tangent_plan(p, info, tg->n_dir, tg->flags, rt0, lay);
     if (rc) return rc;
     GeometryLayout glay;
     if (geometry) glay = geometry_layout(rt0.pl, lay, tg->n_dir);
@@ -629,7 +641,7 @@ int tangent_sweep(const RydProblem* p, const RydPlanInfo* info, const RydTangent
     } else {
         HIP_TRY(hipMemsetAsync(vec[0] + sv, 0, size_t(Dp) * pl.state_bytes, stream));
     }
-    const size_t rows = size_t(pl.n_obs + pl.n_pobs + 2 * pl.n_ov);
+    const size_t rows = size_t(pl.ket_rows() + pl.dm_rows());  // (no reduced density matrices: tangent_validate) ket rows, then the density-matrix rows
     const size_t row = size_t(pl.T + 1) * pl.B;
     if (rows && dexpect_out) HIP_TRY(hipMemsetAsync(dexpect_out, 0, size_t(D) * rows * row * sizeof(double), stream));
     ForwardCtx c{{rt, &q, ws, stream, sv}};
@@ -639,6 +651,7 @@ int tangent_sweep(const RydProblem* p, const RydPlanInfo* info, const RydTangent
     c.want_exp = expect_out && pl.n_obs > 0;
     c.pauli_out = (expect_out && pl.n_pobs) ? expect_out + size_t(pl.n_obs) * row : nullptr;
     c.overlap_out = (expect_out && pl.n_ov) ? expect_out + size_t(pl.n_obs + pl.n_pobs) * row : nullptr;
+    c.dm_out = (expect_out && pl.dm_rows()) ? expect_out + size_t(pl.ket_rows()) * row : nullptr;
     if (expect_out && rows) HIP_TRY(hipMemsetAsync(expect_out, 0, rows * row * sizeof(double), stream));
     auto save_point = [&](const double2* v, int k) -> int {  // values (the existing reductions on psi) and tangents of every row
         if (c.want_exp)

@@ -9,7 +9,11 @@
 //                         is NOT a chain of N dependent L2 latencies (DESIGN.md section 3 on the generic direct kernel).
 // k_expect_tangent        d<O> of the diagonal observables: 2 sum_y o[y] Re(conj psi[y] dpsi_d[y])
 // k_pauli_expect_tangent  d<O> of the Pauli observables: the direct Pauli reduction with bra = psi and ket = dpsi_d, times 2
-// (the overlap rows are k_overlap_expect on dpsi_d, as it is).  Complex coefficients throughout, no rotating frame, no pair terms,
+// k_factor_tangent<D, true>  the same pass with dense pair terms P (constants in every direction: M = H + P, dM_d has no pair part):
+//                         beta P on all 1 + D vectors by pair_apply_all (common.hpp) — the collapse operators of a master-equation run
+//                         on the doubled register, the XY exchange on kets.  <D, false> is the pass without them, unchanged.
+// (the overlap rows are k_overlap_expect on dpsi_d, as it is; the density-matrix rows of a doubled register are k_dm_trace /
+// k_dm_fidelity on dpsi_d and k_dm_purity_tangent, dm_kernels.hpp).  Complex coefficients throughout, no rotating frame,
 // no conditioned flips, no sharding (refused by the C ABI).
 #pragma once
 
@@ -29,6 +33,7 @@ struct TangentFactorArgs {
     uint32_t dmask[kMaxGroups];  // amplitude-index bit masks of the detuning groups
     int dcnt[kMaxGroups];
     uint32_t fbg[RYDIFF_MAX_QUBITS];  // the driven qubits, one word each: amplitude-index bit number | flip group << 8
+    PairArgs pair;         // dense pair terms (read by the PAIR instantiations only): constants in every tangent direction
 };
 
 // flip bits whose partner loads are in flight together: CH * (1 + D) loads of 16 bytes per thread
@@ -37,7 +42,7 @@ struct TangentChunk {
     static constexpr int value = D <= 1 ? 8 : (D <= 3 ? 4 : 2);
 };
 
-template <int D>
+template <int D, bool PAIR>
 __global__ __launch_bounds__(256) void k_factor_tangent(TangentFactorArgs a) {
     constexpr int CH = TangentChunk<D>::value;
     const uint32_t x = blockIdx.x * 256u + threadIdx.x;
@@ -76,6 +81,9 @@ __global__ __launch_bounds__(256) void k_factor_tangent(TangentFactorArgs a) {
             acci[1 + d] = dr * own[1 + d].y + di * own[1 + d].x + tr * own[0].y + ti * own[0].x;
         }
     }
+    // beta * (dense pair terms) on all 1 + D vectors, while the own values are still in registers: the pair part of M is the same
+    // in (gamma + beta M) dx_d, and dM_d has none
+    if constexpr (PAIR) pair_apply_all<1 + D>(a.pair, xin, a.vstride, x, own, a.br, a.bi, accr, acci);
 
     for (int i0 = 0; i0 < a.nflip; i0 += CH) {  // uniform
         // the chunk's flip bits, groups and coefficients first: wave-uniform words (scalar loads), nothing of them waits on the

@@ -6,18 +6,37 @@
 namespace {
 
 // Everything rydiff_forward_tangent refuses, checked on the host before anything touches a device.
-int tangent_validate(const RydProblem* p, const RydPlanInfo* info, int n_dir) {
+int tangent_validate(const RydProblem* p, const RydPlanInfo* info, int n_dir, int flags) {
     if (!p) return fail(RYDIFF_EINVAL, "null problem");
     if (n_dir < 1 || n_dir > RYDIFF_MAX_TANGENTS)
         return fail(RYDIFF_EINVAL, "n_dir must be in [1, " + std::to_string(RYDIFF_MAX_TANGENTS) + "], got " + std::to_string(n_dir));
     if (!info) return fail(RYDIFF_EINVAL, "the tangent sweep needs the plan of rydiff_plan(p, 0, 0, ...): null info");
     if (p->shard_bits > 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented for state-sharded runs (shard_bits > 0)");
-    if (p->n_pair_terms > 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented with dense pair terms (n_pair_terms > 0)");
+    if (flags & ~(RYDIFF_TANGENT_PAIR_TERMS | RYDIFF_TANGENT_DENSITY_MATRIX))
+        return fail(RYDIFF_EINVAL, "RydTangent.flags: unknown bits " + std::to_string(flags));
+    // dense pair terms and density-matrix registers run only where the caller asks for them (RydTangent.flags): a caller that does
+    // not know of them keeps the refusals it was written against
+    if (p->n_pair_terms > 0 && !(flags & RYDIFF_TANGENT_PAIR_TERMS))
+        return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented with dense pair terms (n_pair_terms > 0) unless RydTangent.flags "
+                                     "has RYDIFF_TANGENT_PAIR_TERMS");
     if (p->amp_conditioned_terms || p->det_ones_terms)
         return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented with conditioned flips / ones-counting terms (three-level registers)");
     if (p->n_shots > 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: measurement shots are not implemented (n_shots > 0): draw them in rydiff_forward");
     if (p->n_rdms > 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: reduced density matrices are not implemented (n_rdms > 0)");
-    if (p->dm_atoms != 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: density-matrix registers are not implemented (dm_atoms > 0)");
+    if (p->dm_atoms != 0 && !(flags & RYDIFF_TANGENT_DENSITY_MATRIX))
+        return fail(RYDIFF_ENOTIMPL, "tangent sweep: density-matrix registers are not implemented (dm_atoms > 0) unless RydTangent.flags "
+                                     "has RYDIFF_TANGENT_DENSITY_MATRIX");
+    if (p->dm_atoms != 0 && p->n_dm_rdms > 0)
+        return fail(RYDIFF_ENOTIMPL, "tangent sweep: reduced density matrices of density-matrix registers are not implemented (n_dm_rdms > 0)");
+    return RYDIFF_OK;
+}
+
+// What rydiff_forward_geometry refuses on top of that: the Gram matrix of vec(rho) and its tangents is not the mixed-state quantum
+// Fisher information
+int geometry_validate(const RydProblem* p) {
+    if (p && p->dm_atoms != 0)
+        return fail(RYDIFF_ENOTIMPL, "geometry sweep: density-matrix registers are not implemented (dm_atoms > 0): the Gram matrix of "
+                                     "vec(rho) is not the mixed-state quantum Fisher information");
     return RYDIFF_OK;
 }
 
@@ -54,8 +73,8 @@ TangentLayout tangent_layout(const Plan& pl, size_t base, int n_dir) {
 }
 
 // host-only planning of a tangent call: validation, the forward plan from `info`, the layout
-int tangent_plan(const RydProblem* p, const RydPlanInfo* info, int n_dir, Runtime& rt, TangentLayout& lay) {
-    int rc = tangent_validate(p, info, n_dir);
+int tangent_plan(const RydProblem* p, const RydPlanInfo* info, int n_dir, int flags, Runtime& rt, TangentLayout& lay) {
+    int rc = tangent_validate(p, info, n_dir, flags);
     if (rc) return rc;
     RydProblem q = *p;
     q.kernel_variant = 0;  // ignored: one kernel family
@@ -98,7 +117,8 @@ int tangent_tables(const Runtime& rt, const RydProblem* p, const RydTangent* tg,
 
 template <int D>
 void launch_factor_tangent_n(const TangentFactorArgs& a, dim3 grid, hipStream_t stream) {
-    hipLaunchKernelGGL((k_factor_tangent<D>), grid, dim3(256), 0, stream, a);
+    if (a.pair.n) hipLaunchKernelGGL((k_factor_tangent<D, true>), grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((k_factor_tangent<D, false>), grid, dim3(256), 0, stream, a);
 }
 
 // what every factor launch of one call shares
@@ -113,6 +133,7 @@ void fill_tangent_factor(TangentFactorArgs& a, const Runtime& rt, char* ws, cons
     a.ga = pl.ga.n;
     a.gd = pl.gd.n;
     fill_detuning(a.dmask, a.dcnt, pl);
+    a.pair = rt.parg;  // (tables uploaded by prepare)
     a.nflip = 0;
     for (int q = 0; q < pl.ga.n; ++q)
         for (uint32_t m = pl.ga.amp_index_mask[q]; m; m &= m - 1) {
@@ -150,7 +171,7 @@ int launch_expect_tangent(const ForwardCtx& c, const double2* vec, int n_dir, in
     const Plan& pl = c.rt.pl;
     const size_t vstride = size_t(pl.B) * pl.dim;
     const size_t row = size_t(pl.T + 1) * pl.B;
-    const size_t dstride = size_t(pl.n_obs + pl.n_pobs + 2 * pl.n_ov) * row;
+    const size_t dstride = size_t(pl.ket_rows() + pl.dm_rows()) * row;  // (no reduced density matrices here: tangent_validate)
     const unsigned red_blocks = unsigned(std::min<size_t>((pl.dim + 255) / 256, 1024));
     if (pl.n_obs > 0) {
         hipLaunchKernelGGL(k_expect_tangent, dim3(red_blocks, unsigned(pl.B), unsigned(n_dir)), dim3(256), 0, c.stream, vec, vec + vstride, vstride,
@@ -178,6 +199,20 @@ int launch_expect_tangent(const ForwardCtx& c, const double2* vec, int n_dir, in
             ForwardCtx t = c;
             t.overlap_out = dexp + size_t(d) * dstride + size_t(pl.n_obs + pl.n_pobs) * row;
             if (const int rc = launch_overlap_expect(t, vec + size_t(1 + d) * vstride, 0, k, 1, BatchSlice{0, pl.B, false})) return rc;
+        }
+    }
+    if (pl.dm_rows()) {
+        // diagonal, Pauli and fidelity rows are linear in vec(rho): k_dm_trace / k_dm_fidelity as they are, on d rho_d, into direction
+        // d's density-matrix rows; the purity |v|^2 has the tangent 2 Re <v|dv_d>
+        double* first = dexp + size_t(pl.ket_rows()) * row;
+        for (int d = 0; d < n_dir; ++d) {
+            ForwardCtx t = c;
+            t.dm_out = first + size_t(d) * dstride;
+            if (const int rc = launch_dm_expect(t, vec + size_t(1 + d) * vstride, 0, k, 1, BatchSlice{0, pl.B, false}, true)) return rc;
+        }
+        if (pl.dm_purity) {
+            double* slot = first + size_t(pl.n_dm_diag + pl.n_dm_pobs + pl.n_dm_fid) * row;
+            if (const int rc = launch_dm_purity_tangent(c, vec, n_dir, k, slot, dstride)) return rc;
         }
     }
     return RYDIFF_OK;

@@ -64,7 +64,11 @@ def deriv_param(f: Tensor, x: list, times: Optional[Tensor] = None, t=None):
 def deriv_param_all_times(sim, x: list, observables: list, **kw):
     """``deriv_param`` at EVERY evaluation time in one call: ``sim.run_sensitivities(x, observables, **kw)`` — one native
     forward-mode sweep that carries a tangent state per scalar entry of ``x`` instead of one reverse sweep per evaluation time
-    (``basic_usage.ipynb``: ``for t in times: deriv_param(f=exp_val, x=diff_params, times=eval_times, t=t)``).  Returns
+    (``basic_usage.ipynb``: ``for t in times: deriv_param(f=exp_val, x=diff_params, times=eval_times, t=t)``).  With
+    ``route="tangent"`` noisy runs with collapse operators (the master equation: vec(rho) and its tangents on the doubled register)
+    and the XY exchange take the sweep too (without it they run the loop of reverse sweeps, as does the three-level basis always);
+    master-equation runs also accept ``StateOverlap`` (the fidelity) and ``Purity`` observables.  ``route="adjoint-loop"`` forces the
+    loop (the A/B partner).  Returns
     ``Sensitivities``: ``values`` (n_obs, n_t), ``grads[i]`` (n_obs, n_t, *x[i].shape), ``route``."""
     return sim.run_sensitivities(x, observables, **kw)
 

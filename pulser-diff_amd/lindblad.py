@@ -221,3 +221,72 @@ def mesolve(ham, psi0: Tensor, tsave: Tensor, noise: NoiseModel, options: Option
     expect, _, rdms = split_observables(expect, 0, dm.rdms if dm is not None else None)
     real_rows = [r for r, o in zip(rows, obs_list) if not isinstance(o, ReducedDensityMatrix)]
     return MasterEquationResult(rho, dict(spec.options.get("_last_stats", {})), [expect[r] for r in real_rows], shots, rdms or [])
+
+
+def doubled_table_tangents(d_amp: Optional[Tensor], d_det: Optional[Tensor], d_u: Optional[Tensor], n: int) -> tuple:
+    """Tangents of ``doubled_tables`` in the directions ``d_amp`` / ``d_det`` / ``d_u`` (direction-major: one more leading axis than the
+    tables; None stays None).  The map is REAL-linear (the column half conjugates the drive coefficient), so its directional
+    derivative is the map itself applied per direction: ``cat[d_amp, -conj(d_amp)]``, ``cat[d_det, -d_det]``, and ``d_u`` through
+    the same index map (+ among row qubits, - among column qubits)."""
+    d_amp2 = None if d_amp is None else (torch.cat([d_amp, -d_amp.conj()], dim=2) if d_amp.shape[2] else d_amp)
+    d_det2 = None if d_det is None else (torch.cat([d_det, -d_det], dim=2) if d_det.shape[2] else d_det)
+    d_u2 = None
+    if d_u is not None:
+        n2 = 2 * n
+        d_u2 = torch.zeros((d_u.shape[0], n2 * (n2 - 1) // 2), dtype=torch.float64, device=d_u.device)
+        for k, (i, j) in enumerate(itertools.combinations(range(n), 2)):
+            d_u2[:, _pair_index(n2, i, j)] = d_u[:, k]
+            d_u2[:, _pair_index(n2, n + i, n + j)] = -d_u[:, k]
+    return d_amp2, d_det2, d_u2
+
+
+def mesolve_tangent(ham, psi0: Tensor, tsave: Tensor, noise: NoiseModel, options: Optional[dict] = None,
+                    observables: Optional[Sequence] = None, d_amp: Optional[Tensor] = None, d_det: Optional[Tensor] = None,
+                    d_u: Optional[Tensor] = None, d_psi0: Optional[Tensor] = None) -> tuple:
+    """Forward-mode twin of ``mesolve(..., store_states=False)``: ONE tangent sweep (``solver.evolve_tangent``) on the doubled
+    register carries vec(rho) and its tangents in up to 8 directions (more: chunks of 8) and returns ``(expect, dexpect)`` — the
+    values (n_obs, n_t, B) of ``observables`` and their directional derivatives (n_dir, n_obs, n_t, B) at EVERY evaluation time,
+    in the order of ``observables`` (diagonal / ``PauliObservable`` / ``StateOverlap`` = the fidelity ``<phi|rho|phi>`` /
+    ``Purity``; a ``ReducedDensityMatrix`` raises ``NotImplementedError``).
+
+    A direction d is a tangent of the UNDOUBLED inputs: ``d_amp[d]`` shaped like ``ham.amp_tables``, ``d_det[d]`` like
+    ``ham.det_tables``, ``d_u[d]`` like ``ham.u_pairs``, ``d_psi0[d]`` like ``psi0`` (dim, B) — the tangent of rho0 is then
+    ``|dpsi><psi| + |psi><dpsi|``.  The collapse rates of ``noise`` and the XY blocks of ``ham`` are constants in every direction.
+    Same tolerance default, time structure and pair terms as ``mesolve``."""
+    from . import _native
+    from .solver import evolve_tangent
+
+    n = ham._size
+    if n > MAX_ME_QUBITS:
+        raise ValueError(f"The master-equation solver keeps 4^N amplitudes; limited to {MAX_ME_QUBITS} qubits.")
+    obs_list = list(observables or [])
+    if any(isinstance(o, ReducedDensityMatrix) for o in obs_list):
+        raise NotImplementedError("mesolve_tangent evaluates no reduced density matrices (the tangent sweep has no tangents of them); "
+                                  "differentiate mesolve(..., store_states=False).rdms instead")
+    options = dict(options or {})
+    dev = ham.amp_tables.device
+    amp2, det2, u2, am2, dm2 = doubled_tables(ham.amp_tables.detach(), ham.det_tables.detach(), ham.u_pairs.detach(), ham.amp_masks,
+                                              ham.det_masks, n)
+    block = dissipator_block(local_collapse_operators(noise, getattr(ham, "basis_name", "ground-rydberg")))
+    pair_terms = doubled_pair_terms(getattr(ham, "pair_terms", ()), n, block)
+    psi = psi0.detach().to(dev, CD)
+    if psi.ndim == 1:
+        psi = psi.unsqueeze(1)
+    dim, batch = psi.shape
+    dm, rows = pack_dm_observables(obs_list, n, batch, dev)
+    spec = ProblemSpec(2 * n, ham.dt, ham.n_samples, am2, dm2, solver=SolverType.DP5_SE,
+                       tol=tolerance_from_options(options) or ME_DEFAULT_TOL, store_states=False, pair_terms=pair_terms,
+                       piece_refine=getattr(ham, "piece_refine", None), dm=dm)
+    rho0 = torch.einsum("xb,yb->bxy", psi, psi.conj()).reshape(batch, dim * dim).contiguous()
+    to_dev = lambda t, dt: None if t is None else t.detach().to(dev, dt)
+    d_amp2, d_det2, d_u2 = doubled_table_tangents(to_dev(d_amp, CD), to_dev(d_det, torch.float64), to_dev(d_u, torch.float64), n)
+    d_rho0 = None
+    if d_psi0 is not None:
+        dpsi = d_psi0.detach().to(dev, CD)
+        if dpsi.ndim == 2:
+            dpsi = dpsi.unsqueeze(2)
+        d_rho0 = (torch.einsum("dxb,yb->dbxy", dpsi, psi.conj()) + torch.einsum("xb,dyb->dbxy", psi, dpsi.conj()))
+        d_rho0 = d_rho0.reshape(dpsi.shape[0], batch, dim * dim).contiguous()
+    expect, dexpect = evolve_tangent(amp2, det2, u2, tsave, rho0, spec, None, d_amp=d_amp2, d_det=d_det2, d_u=d_u2, d_psi0=d_rho0,
+                                     flags=_native.TANGENT_PAIR_TERMS | _native.TANGENT_DENSITY_MATRIX)
+    return expect[rows], dexpect[:, rows]

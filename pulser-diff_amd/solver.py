@@ -711,20 +711,27 @@ def _tangent_chunk(t: Optional[Tensor], d0: int, d1: int, shape: tuple, dtype: t
 
 def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Tensor, spec: ProblemSpec,
                    obs_diag: Optional[Tensor] = None, d_amp: Optional[Tensor] = None, d_det: Optional[Tensor] = None,
-                   d_u: Optional[Tensor] = None, d_psi0: Optional[Tensor] = None) -> tuple[Tensor, Tensor]:
+                   d_u: Optional[Tensor] = None, d_psi0: Optional[Tensor] = None, flags: int = 0) -> tuple[Tensor, Tensor]:
     """Forward-mode twin of ``evolve`` (``rydiff_forward_tangent``): ONE sweep carries the state and the tangent states of up to 8
     directions through every factor and returns the observable values ``expect`` (rows, n_t, B) and their directional derivatives
     ``dexpect`` (n_dir, rows, n_t, B) at EVERY evaluation time — rows = diagonal observables, then the Pauli observables and Re / Im
     of the overlaps of ``spec``, as in ``evolve``.  A direction d is the tangent of the inputs: ``d_amp[d]`` shaped like
     ``amp_tables``, ``d_det[d]`` like ``det_tables``, ``d_u[d]`` like ``u_pairs``, ``d_psi0[d]`` like ``psi0`` (B, dim); an
-    input left out has tangent zero.  More than 8 directions run in chunks of 8.  No autograd graph hangs off the outputs."""
-    if spec.rdms is not None:
+    input left out has tangent zero.  More than 8 directions run in chunks of 8.  No autograd graph hangs off the outputs.
+
+    ``flags`` (``RydTangent.flags``) opts into what the sweep takes beyond plain Ising kets; without them such a problem is refused as
+    it always was.  ``_native.TANGENT_PAIR_TERMS``: ``spec.pair_terms`` (the XY exchange; the dissipator of a master-equation run)
+    ride in the same sweep, constants in every direction.  ``_native.TANGENT_DENSITY_MATRIX``: with ``spec.dm`` the register is the
+    doubled register of a density matrix (``lindblad.mesolve_tangent`` builds the doubled tables and their tangents): ``psi0`` /
+    ``d_psi0`` are ``vec(rho0)`` / ``vec(d rho0)``, and the density-matrix rows — diagonal, Pauli, fidelity, purity — and their
+    tangents follow the other rows, as in ``evolve``."""
+    if spec.rdms is not None or (spec.dm is not None and spec.dm.rdms is not None):
         raise NotImplementedError("evolve_tangent evaluates no reduced density matrices (rydiff_forward_tangent: RYDIFF_ENOTIMPL); "
                                   "request them from evolve")
-    if spec.dm is not None:
-        raise NotImplementedError("evolve_tangent takes no density-matrix registers (rydiff_forward_tangent: RYDIFF_ENOTIMPL); "
-                                  "differentiate evolve instead")
-    if spec.shots is not None:
+    if spec.dm is not None and not (int(flags) & _native.TANGENT_DENSITY_MATRIX):
+        raise NotImplementedError("evolve_tangent takes no density-matrix registers (rydiff_forward_tangent: RYDIFF_ENOTIMPL) unless "
+                                  "flags has _native.TANGENT_DENSITY_MATRIX (lindblad.mesolve_tangent); or differentiate evolve")
+    if spec.shots is not None or (spec.dm is not None and spec.dm.shots):
         raise NotImplementedError("evolve_tangent draws no measurement shots (rydiff_forward_tangent: RYDIFF_ENOTIMPL); request them from evolve")
     L = _native.lib()
     dev = psi0.device
@@ -752,7 +759,7 @@ def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsav
     call = _Call(spec, amp_c, det_c, u_c, ts_host, batch, obs_c)
     call.problem.kernel_variant = 0  # the tangent sweep has one kernel family
     p = call.problem
-    rows = p.n_obs + p.n_pauli_obs + 2 * p.n_overlaps
+    rows = p.n_obs + p.n_pauli_obs + 2 * p.n_overlaps + (spec.dm.rows() if spec.dm is not None else 0)
     expect = torch.empty((rows, n_t, batch), dtype=torch.float64, device=dev)
     dexpect = torch.empty((n_dir, rows, n_t, batch), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
@@ -775,7 +782,8 @@ def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsav
             tg = _native.RydTangent()
             tg.n_dir = d1 - d0
             tg.d_amp, tg.d_det, tg.d_u, tg.d_psi0 = (None if b is None else b.data_ptr() for b in bufs)
-            need = L.rydiff_tangent_workspace_bytes(ctypes.byref(p), ctypes.byref(info), tg.n_dir)
+            tg.flags = int(flags)
+            need = L.rydiff_tangent_workspace_bytes_flags(ctypes.byref(p), ctypes.byref(info), tg.n_dir, tg.flags)
             if need == 0:  # refused: the sweep's own (host-only) validation reports why, with its error code
                 _native.check(L.rydiff_forward_tangent(ctypes.byref(p), ctypes.byref(info), ctypes.byref(tg), _ptr(psi_c), None, _ptr(out),
                                                        None, 0, stream))
@@ -805,13 +813,14 @@ def _tangent_pick(t: Optional[Tensor], idx: list, shape: tuple, dtype: torch.dty
 
 def evolve_geometry(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Tensor, spec: ProblemSpec,
                     obs_diag: Optional[Tensor] = None, d_amp: Optional[Tensor] = None, d_det: Optional[Tensor] = None,
-                    d_u: Optional[Tensor] = None, d_psi0: Optional[Tensor] = None) -> tuple[Tensor, Tensor, Tensor]:
+                    d_u: Optional[Tensor] = None, d_psi0: Optional[Tensor] = None, flags: int = 0) -> tuple[Tensor, Tensor, Tensor]:
     """``evolve_tangent`` that also returns the Gram matrix of the state and its tangents at EVERY evaluation time
     (``rydiff_forward_geometry``): ``(expect, dexpect, gram)`` with ``gram`` complex128 of shape (n_t, B, 1 + n_dir, 1 + n_dir),
     ``gram[k, b, i, j] = <v_i|v_j>``, ``v_0 = psi_b(t_k)``, ``v_{1+d} = d psi_b(t_k) / d theta_d`` — what
     ``geometry.quantum_fisher_information`` and its neighbours take.  The sums are formed in a fixed order: two calls on the same
     inputs return bit-identical matrices.  Same arguments as ``evolve_tangent``; tangents of inputs the problem does not have give
-    zero rows and columns.  More than 8 directions run one sweep per pair of groups of 4 (``geometry.geometry_sweeps``)."""
+    zero rows and columns.  More than 8 directions run one sweep per pair of groups of 4 (``geometry.geometry_sweeps``).
+    ``flags=_native.TANGENT_PAIR_TERMS`` takes dense pair terms on kets; density-matrix registers stay refused."""
     from .geometry import geometry_sweeps
 
     if spec.rdms is not None:
@@ -875,10 +884,11 @@ def evolve_geometry(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsa
             tg = _native.RydTangent()
             tg.n_dir = len(idx)
             tg.d_amp, tg.d_det, tg.d_u, tg.d_psi0 = (None if b is None else b.data_ptr() for b in bufs)
+            tg.flags = int(flags)
             g = torch.empty((n_t, batch, 1 + len(idx), 1 + len(idx)), dtype=torch.complex128, device=dev)
             want_rows = rows > 0 and not bool(done[idx].all())  # a later sweep of directions whose row tangents are all there skips them
             out = torch.empty((len(idx), rows, n_t, batch), dtype=torch.float64, device=dev) if want_rows else None
-            need = L.rydiff_geometry_workspace_bytes(ctypes.byref(p), ctypes.byref(info), tg.n_dir)
+            need = L.rydiff_geometry_workspace_bytes_flags(ctypes.byref(p), ctypes.byref(info), tg.n_dir, tg.flags)
             if need == 0:  # refused: the sweep's own (host-only) validation reports why, with its error code
                 _native.check(L.rydiff_forward_geometry(ctypes.byref(p), ctypes.byref(info), ctypes.byref(tg), _ptr(psi_c), None, None,
                                                         _ptr(g), None, 0, stream))
