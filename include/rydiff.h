@@ -442,9 +442,11 @@ typedef struct RydTangent {
     const void*   d_psi0;   /* DEVICE complex128 [n_dir][B][2^N] or NULL */
     int32_t flags;          /* 0, or RYDIFF_TANGENT_* ored: what the caller asks the sweep to take beyond plain Ising kets */
 } RydTangent;
-/* Without its flag a problem with dense pair terms / a density-matrix register is RYDIFF_ENOTIMPL, as before the sweep took them. */
+/* Without its flag a problem with dense pair terms / a density-matrix register / reduced density matrices is RYDIFF_ENOTIMPL, as
+ * before the sweep took them. */
 #define RYDIFF_TANGENT_PAIR_TERMS 1      /* n_pair_terms > 0: the pair terms ride in the pass as constants of every direction */
 #define RYDIFF_TANGENT_DENSITY_MATRIX 2  /* dm_atoms > 0: the vectors are vec(rho) and its tangents; the dm_* rows get tangents */
+#define RYDIFF_TANGENT_RDMS 4            /* n_rdms > 0: the RDM block of rydiff_forward joins expect_out and dexpect_out */
 
 /* sizeof(RydTangent) as this library was compiled (see rydiff_sizeof_problem). */
 size_t rydiff_sizeof_tangent(void);
@@ -459,18 +461,24 @@ size_t rydiff_tangent_workspace_bytes_flags(const RydProblem* p, const RydPlanIn
  *   info         HOST: result of rydiff_plan(p, 0, 0, ...) for the SAME table values (required)
  *   psi0         DEVICE complex128 [B][2^N]  (dm_atoms > 0: vec(rho_0), and d_psi0 = vec(d rho_0))
  *   expect_out   DEVICE float64 [rows][n_tsave][B] or NULL: the values, rows = n_obs + n_pauli_obs + 2 * n_overlaps in the order
- *                of rydiff_forward; with dm_atoms > 0 followed by n_dm_diag + n_dm_pauli_obs + n_dm_fid + dm_purity rows, as there
+ *                of rydiff_forward; with RYDIFF_TANGENT_RDMS followed by the RDM block (2 * 4^{m_o} rows per reduced density matrix,
+ *                entry (a, a') at 2 (a 2^m + a'), Re then Im); with dm_atoms > 0 followed by n_dm_diag + n_dm_pauli_obs + n_dm_fid +
+ *                dm_purity rows, as there
  *   dexpect_out  DEVICE float64 [n_dir][rows][n_tsave][B] (required): diagonal rows 2 sum_y o[y] Re(conj psi[y] dpsi_d[y]), Pauli
- *                rows 2 sum_s w_s Re<psi|P_s|dpsi_d>, overlap rows Re / Im <phi_o|dpsi_d>; every save point, k = 0 included.
+ *                rows 2 sum_s w_s Re<psi|P_s|dpsi_d>, overlap rows Re / Im <phi_o|dpsi_d>, RDM rows the entries of
+ *                d rho_A = Tr_E(|dpsi_d><psi| + |psi><dpsi_d|) (the mirror entry is the exact conjugate, Im of the diagonal an exact
+ *                0; summed with atomics: not bit-reproducible); every save point, k = 0 included.  Need not be cleared.
  *                Density-matrix rows (dm_atoms > 0; v = vec(rho), dv_d its tangent): the diagonal, Pauli and fidelity rows are
  *                linear in v — the row's functional of dv_d — and the purity row is 2 Re sum_i conj(v_i) dv_d,i
  *   workspace    DEVICE, >= rydiff_tangent_workspace_bytes(p, info, n_dir)
  * Both solvers, coeff_batch 1 or B, dp5_piece_refine honoured (same plan); kernel_variant is ignored: the sweep has one kernel
  * family (launch per factor, one amplitude per thread).  With RYDIFF_TANGENT_PAIR_TERMS in tangent->flags dense pair terms
  * (n_pair_terms > 0: the XY exchange, the dissipator of a master-equation run on the doubled register) ride in the same pass as
- * constants of every direction; with RYDIFF_TANGENT_DENSITY_MATRIX a register with dm_atoms > 0 is taken.  Not implemented
- * (RYDIFF_ENOTIMPL): pair terms / dm_atoms > 0 without their flag, state-sharded runs, conditioned / ones-counting terms, shots,
- * reduced density matrices (n_rdms > 0, n_dm_rdms > 0).  Every argument is validated before anything touches a device. */
+ * constants of every direction; with RYDIFF_TANGENT_DENSITY_MATRIX a register with dm_atoms > 0 is taken; with RYDIFF_TANGENT_RDMS
+ * the reduced density matrices of a ket (n_rdms > 0) get values and tangents (one k_rdm_tangent launch per RDM and save point).
+ * Not implemented (RYDIFF_ENOTIMPL): pair terms / dm_atoms > 0 / n_rdms > 0 without their flag, state-sharded runs, conditioned /
+ * ones-counting terms, shots, partial traces of a density matrix (n_dm_rdms > 0) whatever the flags.  Every argument is validated
+ * before anything touches a device. */
 int rydiff_forward_tangent(const RydProblem* p, const RydPlanInfo* info, const RydTangent* tangent, const void* psi0,
                            double* expect_out, double* dexpect_out, void* workspace, size_t workspace_bytes, void* stream);
 
@@ -492,8 +500,9 @@ int rydiff_forward_tangent(const RydProblem* p, const RydPlanInfo* info, const R
  * order, the blocks in a fixed tree — so two calls on the same inputs return bit-identical matrices (F subtracts numbers of equal
  * size and is inverted in natural-gradient solves).  Traffic: one read of (1 + n_dir) * B * 2^N * 16 bytes per save point on top of
  * the sweep's; nothing of size 2^N is written.  Everything else — expect_out, the solvers, the validation before anything touches
- * a device, what is RYDIFF_ENOTIMPL (state-sharded runs, conditioned / ones-counting terms, shots, reduced density matrices) —
- * is rydiff_forward_tangent's; pair terms on kets are taken with RYDIFF_TANGENT_PAIR_TERMS (the same sweep).  On top of that
+ * a device, what is RYDIFF_ENOTIMPL (state-sharded runs, conditioned / ones-counting terms, shots, reduced density matrices
+ * without RYDIFF_TANGENT_RDMS) — is rydiff_forward_tangent's; pair terms on kets are taken with RYDIFF_TANGENT_PAIR_TERMS and
+ * reduced density matrices with RYDIFF_TANGENT_RDMS (the same sweep, the RDM rows are not part of the fixed-order guarantee).  On top of that
  * dm_atoms > 0 is RYDIFF_ENOTIMPL here whatever the flags (and the workspace functions return 0): the Gram matrix of vec(rho) and its
  * tangents is not the mixed-state quantum Fisher information.  RYDIFF_EINVAL also for a NULL gram_out. */
 size_t rydiff_geometry_workspace_bytes(const RydProblem* p, const RydPlanInfo* info, int n_dir);

@@ -26,14 +26,15 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from . import _native, pulser_adapter, pulses
+from . import _native, pulser_adapter, pulses, utils
 from .hamiltonian import COLLAPSE_NOISES, Hamiltonian
 from .lindblad import (MAX_ME_QUBITS, ME_DEFAULT_TOL, dissipator_block, doubled_pair_terms, doubled_tables, local_collapse_operators,
                        mesolve, mesolve_tangent)
 from .result import SampledResult
 from .simconfig import SimConfig
 from .simresults import CoherentResults, NoisyResults, SimulationResults
-from .solver import ProblemSpec, SolverType, evolve, evolve_geometry, evolve_tangent, sesolve, tolerance_from_options
+from .solver import (ProblemSpec, SolverType, evolve, evolve_geometry, evolve_tangent, sesolve, split_observables,
+                     tolerance_from_options)
 from .observables import PauliObservable, Purity, ReducedDensityMatrix, StateOverlap, pack_overlaps
 from .geometry import QuantumGeometry, quantum_geometric_tensor
 from .shots import MAX_SHOTS, ShotRequest, indices_to_bitstrings
@@ -56,6 +57,44 @@ class Sensitivities:
     grads: list
     route: str
     times: Tensor
+
+
+@dataclass
+class SubsystemSensitivities:
+    """What ``TorchEmulator.run_rdm_sensitivities`` returns: per subsystem ``o`` the reduced density matrix ``rho[o]`` complex
+    (n_t, B, 2^m, 2^m) at every evaluation time (B: the columns of the initial state) and, per tensor ``x_i`` of the request,
+    ``drho[o][i]`` complex (n_t, B, 2^m, 2^m, *x_i.shape) = d rho[o] / d x_i, on the device of ``x_i`` like the ``grads`` of
+    ``Sensitivities``; and the times.  The scalar functionals below are
+    formed from them in torch (``utils.purity_tangent``, ``utils.von_neumann_entropy_tangent``)."""
+
+    rho: list
+    drho: list
+    times: Tensor
+
+    def _along(self, o: int, tangent) -> list:
+        out = []
+        for dr in self.drho[o]:
+            lead, shape = tuple(dr.shape[:2]), tuple(dr.shape[4:])
+            flat = dr.reshape(dr.shape[:4] + (-1,)).permute(4, 0, 1, 2, 3)  # (numel, n_t, B, d, d)
+            out.append(tangent(self.rho[o].to(flat.device), flat).permute(1, 2, 0).reshape(lead + shape))  # (drho sits with x_i)
+        return out
+
+    def purity(self, o: int) -> Tensor:
+        """``tr rho[o]^2``, (n_t, B)."""
+        return utils.purity(self.rho[o])
+
+    def d_purity(self, o: int) -> list:
+        """Per tensor ``x_i``: d purity(o) / d x_i, (n_t, B, *x_i.shape)."""
+        return self._along(o, utils.purity_tangent)
+
+    def entropy(self, o: int, base: float = 2) -> Tensor:
+        """The von Neumann entropy of ``rho[o]``, (n_t, B)."""
+        return utils.von_neumann_entropy(self.rho[o], base)
+
+    def d_entropy(self, o: int, base: float = 2) -> list:
+        """Per tensor ``x_i``: d entropy(o) / d x_i, (n_t, B, *x_i.shape); defined where ``rho[o]`` has full rank only
+        (``utils.von_neumann_entropy_tangent``)."""
+        return self._along(o, lambda rho, drho: utils.von_neumann_entropy_tangent(rho, drho, base))
 
 
 class TorchEmulator:
@@ -526,6 +565,10 @@ class TorchEmulator:
         full = ham.dim ** ham._size
         for obs in observables:
             if isinstance(obs, ReducedDensityMatrix):
+                if solver != SolverType.DP5_ME:
+                    raise NotImplementedError("run_sensitivities does not take ReducedDensityMatrix observables (its rows are real "
+                                              "scalars); run_rdm_sensitivities returns the matrices and their derivatives at every "
+                                              "evaluation time from the same tangent sweep.")
                 raise NotImplementedError("run_sensitivities does not take ReducedDensityMatrix observables (the tangent sweep "
                                           "evaluates none); differentiate results.reduced_density_matrix through run().")
             if isinstance(obs, Purity) and solver == SolverType.DP5_ME:
@@ -628,6 +671,75 @@ class TorchEmulator:
             grads.append(dvals[d0:d0 + m].permute(1, 2, 0).reshape(len(rows), n_t, *t.shape).to(t.device))
             d0 += m
         return Sensitivities(values, grads, "tangent", times)
+
+    def run_rdm_sensitivities(self, x: list, subsystems: list, solver: SolverType = SolverType.DP5_SE, dist_grad: bool = False,
+                              **options: Any) -> "SubsystemSensitivities":
+        """Reduced density matrices of up to 8 subsystems AND their derivatives w.r.t. the tensors in ``x`` at EVERY evaluation time,
+        from one forward-mode sweep (``rydiff_forward_tangent`` with ``RYDIFF_TANGENT_RDMS``): at every save point the sweep holds the
+        state and one tangent state per scalar entry of ``x``, and ``d rho_A = Tr_E(|dpsi><psi| + |psi><dpsi|)`` is formed natively
+        beside ``rho_A``.  What the loop of one reverse sweep per evaluation time and per scalar functional of ``rho_A`` (purity,
+        entropy, mutual information ...) through ``run(observables=[ReducedDensityMatrix(...)])`` delivers.
+
+        ``x`` is what ``run_sensitivities`` takes.  ``subsystems``: ``ReducedDensityMatrix`` objects (e.g. from
+        ``build_reduced_density_matrix``) or tuples of qubit indices, 1 to 6 qubits each.  Noiseless Ising and XY runs (the exchange
+        rides in the sweep as constant pair terms).  Returns ``SubsystemSensitivities``."""
+        x = list(x)
+        if not x or not all(isinstance(t, Tensor) for t in x):
+            raise TypeError("x must be a non-empty list of tensors")
+        if any(t is self._eval_times_array for t in x):
+            raise ValueError("run_rdm_sensitivities differentiates w.r.t. parameters; the evaluation times are not one of them: "
+                             "run(time_grad=True) and deriv_time deliver d f(t_k) / d t_k for every k in one reverse sweep.")
+        noise = set(self.config.noise)
+        no_resampling = noise <= {"dephasing", "relaxation", "SPAM", "depolarizing", "eff_noise", "amplitude"} and (
+            "amplitude" not in noise or self.config.amp_sigma == 0.0)
+        if not no_resampling or ("SPAM" in noise and self.config.eta > 0):
+            raise NotImplementedError("run_rdm_sensitivities is not available in noisy runs that average over realisations.")
+        if noise & COLLAPSE_NOISES or solver == SolverType.DP5_ME:
+            raise NotImplementedError("run_rdm_sensitivities is not available for master-equation runs (collapse-operator noise, "
+                                      "DP5_ME): the tangent sweep forms no tangents of the partial trace of a density matrix; "
+                                      "differentiate results.reduced_density_matrix through run().")
+        if solver not in (SolverType.DP5_SE, SolverType.KRYLOV_SE):
+            raise ValueError(f"Solver {solver} not available.")
+        ham, dev = self._hamiltonian, self._compute_device
+        if ham.basis_name == "all":
+            raise NotImplementedError("run_rdm_sensitivities is not available in the three-level all-basis: the native tangent sweep "
+                                      "takes no conditioned flips / ones-counting terms, and ReducedDensityMatrix is a qubit observable.")
+        rdm_objs = [o if isinstance(o, ReducedDensityMatrix) else ReducedDensityMatrix(o) for o in subsystems]
+        if not 1 <= len(rdm_objs) <= _native.MAX_RDMS:
+            raise ValueError(f"run_rdm_sensitivities takes 1 to {_native.MAX_RDMS} subsystems per call, got {len(rdm_objs)}")
+        for obs in rdm_objs:
+            obs.check(ham._size)
+        if dist_grad:
+            self._enable_dist_grad()
+        times = self._eval_times_array.detach()
+        n_t = int(times.shape[0])
+        d_amp, d_det, d_u = self._table_tangents(x)
+        n_dir = sum(int(t.numel()) for t in x)
+        psi0 = self.initial_state
+        psi_bd = psi0.reshape(psi0.shape[0], -1).transpose(0, 1).to(dev)
+        spec = ham.problem_spec(solver=solver, tol=tolerance_from_options(dict(options)), store_states=False)
+        spec.rdms = rdm_objs
+        if d_amp is None and d_det is None and d_u is None:  # nothing in x reaches the tables: zero derivatives, values from a plain run
+            with torch.no_grad():
+                expect = evolve(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, None)[1]
+            dexpect = torch.zeros((n_dir,) + tuple(expect.shape), dtype=torch.float64, device=expect.device)
+        else:
+            # the complex tables and the unrotated psi0, as in run_sensitivities: the matrices are lab-frame ones
+            expect, dexpect = evolve_tangent(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, None,
+                                             d_amp=d_amp, d_det=d_det, d_u=d_u,
+                                             flags=_native.TANGENT_RDMS | (_native.TANGENT_PAIR_TERMS if spec.pair_terms else 0))
+        rho = split_observables(expect, 0, rdm_objs)[2]
+        per_dir = [split_observables(dexpect[d], 0, rdm_objs)[2] for d in range(n_dir)]
+        drho = []
+        for o in range(len(rdm_objs)):
+            stacked = torch.stack([per_dir[d][o] for d in range(n_dir)], dim=-1)  # (n_t, B, 2^m, 2^m, n_dir)
+            parts, d0 = [], 0
+            for t in x:
+                m = int(t.numel())
+                parts.append(stacked[..., d0:d0 + m].reshape(tuple(stacked.shape[:4]) + tuple(t.shape)).to(t.device))
+                d0 += m
+            drho.append(parts)
+        return SubsystemSensitivities(rho, drho, times)
 
     def run_quantum_fisher(self, x: list, observables: list = (), solver: SolverType = SolverType.DP5_SE, dist_grad: bool = False,
                            **options: Any) -> "QuantumGeometry":

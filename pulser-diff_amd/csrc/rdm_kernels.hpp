@@ -12,8 +12,17 @@
 // k_rdm_apply      the cotangent  out = base + (M_A (x) 1_E) psi,  M = G + G^dagger built in LDS from grad_expect on the device
 //                  (4^m amplitudes, 64 KiB at m = 6, where the tile shrinks to 2^11 so that both fit in 160 KiB); no atomics, may
 //                  run in place on `base`, skips a (k, b) whose G is identically zero (uniform over the workgroup).
+// k_rdm_tangent<M> the tangent of rho_A along one direction of the tangent sweep, d rho = dPsi Psi^dagger + Psi dPsi^dagger: the
+//                  staging, the M <= 3 / M >= 4 register split, the reduction and the atomics of k_rdm_expect, with a Psi tile and a
+//                  dPsi tile side by side in LDS (2 * 66 560 B at m = 6, 2 * 65 568 B at m = 1, of 160 KiB) and the sesquilinear form
+//                  in place of the quadratic one.  The direction is grid.z: a third tile (two directions per pass) does not fit in
+//                  LDS beside 2^12-amplitude tiles, and at M = 6 one direction already holds 32 accumulator doubles per thread
+//                  (138 VGPRs; a second direction's 64 more would pass the 256 of a 512-thread workgroup), so Psi is staged again
+//                  for every direction.  35 / 79 / 217 / 34 / 62 / 138 VGPRs at M = 1 .. 6, no scratch; k_rdm_expect<M> keeps its
+//                  34 / 62 / 182 / 26 / 52 / 114.
 // ONE PASS PER RDM: the staged bit set depends on A, so the RDMs of a call do not share a staging; each gets its own launch.
-// Cost per RDM and state (derived, not measured): one read of the state, 8 * 2^(N+m) flops.
+// Cost per RDM and state (derived, not measured): one read of the state, 8 * 2^(N+m) flops.  k_rdm_tangent, per RDM, save point,
+// trajectory and direction: two reads of 2^N amplitudes (Psi and dPsi_d: 2 D state reads for D directions), 16 * 2^(N+m) flops.
 #pragma once
 
 constexpr int kRdmThreads = 512;
@@ -78,39 +87,52 @@ __device__ __forceinline__ void rdm_emit(double* out, size_t row, uint32_t D, ui
     unsafeAtomicAdd(out + size_t(2 * (a2 * D + a) + 1) * row, -im);
 }
 
-// grid (min(tiles, kRdmMaxBlocks), b_count * n_k); dynamic LDS: the tile, or the reduction scratch where that is larger
-template <int M>
-__global__ __launch_bounds__(kRdmThreads) void k_rdm_expect(RdmExpectArgs a) {
+// one (a, a', e) term of entry (a, a'): p = Psi[a][e], q = Psi[a'][e]; tangent: dp, dq the same entries of dPsi
+//   value    p conj(q)                 tangent    dp conj(q) + p conj(dq)
+template <bool TAN>
+__device__ __forceinline__ void rdm_form(double& re, double& im, double2 p, double2 q, double2 dp, double2 dq) {
+    if constexpr (TAN) {
+        re = fma(dp.x, q.x, fma(dp.y, q.y, fma(p.x, dq.x, fma(p.y, dq.y, re))));
+        im = fma(dp.y, q.x, fma(-dp.x, q.y, fma(p.y, dq.x, fma(-p.x, dq.y, im))));
+    } else {
+        re = fma(p.x, q.x, fma(p.y, q.y, re));  // psi[a] conj(psi[a'])
+        im = fma(p.y, q.x, fma(-p.x, q.y, im));
+    }
+}
+
+// What k_rdm_expect<M> and k_rdm_tangent<M> share: the tiles of this workgroup staged one after the other, the upper triangle summed
+// in registers, one round of atomics into out[2 (a 2^M + a') (+ 1)][row].  TAN: dpsi is staged behind psi's tile and the form is the
+// sesquilinear one.  Dynamic LDS: the tile(s), or the reduction scratch where that is larger.
+template <int M, bool TAN>
+__device__ __forceinline__ void rdm_accumulate(const RdmTile& g, const double2* __restrict__ psi, const double2* __restrict__ dpsi,
+                                               uint32_t nblocks, double* out, size_t row) {
     extern __shared__ double2 rdm_lds[];
     constexpr uint32_t D = 1u << M;
-    const int b = a.b_first + int(blockIdx.y) % a.b_count;
-    const int kk = int(blockIdx.y) / a.b_count;
-    const double2* __restrict__ psi = a.psi + size_t(kk) * a.kstride + size_t(b) * a.dim;
-    const uint32_t E = 1u << (a.g.t - M), stride = a.g.stride;
-    double* out = a.out + size_t(a.k0 + kk) * a.B + b;
-    const size_t row = size_t(a.n_tsave) * a.B;
+    const uint32_t E = 1u << (g.t - M), stride = g.stride;
+    const double2* dtile = rdm_lds + D * stride;  // (TAN only)
     double* red = reinterpret_cast<double*>(rdm_lds);
     if constexpr (M <= 3) {
         constexpr int NE = int(D * (D + 1) / 2);
         double re[NE], im[NE];
 #pragma unroll
         for (int i = 0; i < NE; ++i) re[i] = im[i] = 0.0;
-        for (uint32_t blk = blockIdx.x; blk < a.nblocks; blk += gridDim.x) {
+        for (uint32_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
             __syncthreads();
-            rdm_stage(a.g, psi, blk, rdm_lds);
+            rdm_stage(g, psi, blk, rdm_lds);
+            if constexpr (TAN) rdm_stage(g, dpsi, blk, rdm_lds + D * stride);
             __syncthreads();
             for (uint32_t e = threadIdx.x; e < E; e += kRdmThreads) {
-                double2 v[D];
+                double2 v[D], w[D];
 #pragma unroll
-                for (uint32_t r = 0; r < D; ++r) v[r] = rdm_lds[r * stride + e];
+                for (uint32_t r = 0; r < D; ++r) {
+                    v[r] = rdm_lds[r * stride + e];
+                    w[r] = TAN ? dtile[r * stride + e] : v[r];
+                }
                 int i = 0;
 #pragma unroll
                 for (uint32_t r = 0; r < D; ++r)
 #pragma unroll
-                    for (uint32_t c = r; c < D; ++c, ++i) {
-                        re[i] = fma(v[r].x, v[c].x, fma(v[r].y, v[c].y, re[i]));  // psi[a] conj(psi[a'])
-                        im[i] = fma(v[r].y, v[c].x, fma(-v[r].x, v[c].y, im[i]));
-                    }
+                    for (uint32_t c = r; c < D; ++c, ++i) rdm_form<TAN>(re[i], im[i], v[r], v[c], w[r], w[c]);
             }
         }
         __syncthreads();  // the tile is done with: its LDS becomes red[wave][2 * NE]
@@ -146,24 +168,24 @@ __global__ __launch_bounds__(kRdmThreads) void k_rdm_expect(RdmExpectArgs a) {
 #pragma unroll
             for (int c = 0; c < RB; ++c) re[r][c] = im[r][c] = 0.0;
         const uint32_t e0 = part < PARTS ? E * part / PARTS : 0u, e1 = part < PARTS ? E * (part + 1) / PARTS : 0u;
-        for (uint32_t blk = blockIdx.x; blk < a.nblocks; blk += gridDim.x) {
+        for (uint32_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
             __syncthreads();
-            rdm_stage(a.g, psi, blk, rdm_lds);
+            rdm_stage(g, psi, blk, rdm_lds);
+            if constexpr (TAN) rdm_stage(g, dpsi, blk, rdm_lds + D * stride);
             __syncthreads();
             for (uint32_t e = e0; e < e1; ++e) {
-                double2 va[RB], vb[RB];
+                double2 va[RB], vb[RB], wa[RB], wb[RB];
 #pragma unroll
                 for (int r = 0; r < RB; ++r) {
                     va[r] = rdm_lds[(bi * RB + r) * stride + e];
                     vb[r] = rdm_lds[(bj * RB + r) * stride + e];
+                    wa[r] = TAN ? dtile[(bi * RB + r) * stride + e] : va[r];
+                    wb[r] = TAN ? dtile[(bj * RB + r) * stride + e] : vb[r];
                 }
 #pragma unroll
                 for (int r = 0; r < RB; ++r)
 #pragma unroll
-                    for (int c = 0; c < RB; ++c) {
-                        re[r][c] = fma(va[r].x, vb[c].x, fma(va[r].y, vb[c].y, re[r][c]));
-                        im[r][c] = fma(va[r].y, vb[c].x, fma(-va[r].x, vb[c].y, im[r][c]));
-                    }
+                    for (int c = 0; c < RB; ++c) rdm_form<TAN>(re[r][c], im[r][c], va[r], vb[c], wa[r], wb[c]);
             }
         }
         for (uint32_t q = 1; q < PARTS; ++q) {  // parts 1, 2 -> part 0 through red[p][RB * RB][2]
@@ -198,6 +220,35 @@ __global__ __launch_bounds__(kRdmThreads) void k_rdm_expect(RdmExpectArgs a) {
                 }
         }
     }
+}
+
+// grid (min(tiles, kRdmMaxBlocks), b_count * n_k); dynamic LDS: the tile, or the reduction scratch where that is larger
+template <int M>
+__global__ __launch_bounds__(kRdmThreads) void k_rdm_expect(RdmExpectArgs a) {
+    const int b = a.b_first + int(blockIdx.y) % a.b_count;
+    const int kk = int(blockIdx.y) / a.b_count;
+    rdm_accumulate<M, false>(a.g, a.psi + size_t(kk) * a.kstride + size_t(b) * a.dim, nullptr, a.nblocks,
+                             a.out + size_t(a.k0 + kk) * a.B + b, size_t(a.n_tsave) * a.B);
+}
+
+struct RdmTangentArgs {
+    const double2* vec;  // [1 + n_dir][B][dim] at one save point: the state, then the tangent of every direction
+    size_t vstride;      // B * dim
+    double* out;         // first row of this RDM in direction 0's block of dexpect_out: [2 * 4^m][n_tsave][B]
+    size_t out_dstride;  // doubles between the blocks of consecutive directions
+    RdmTile g;
+    int n_tsave, k, B;
+    uint32_t dim, nblocks;
+};
+
+// grid (min(tiles, kRdmMaxBlocks), B, n_dir); dynamic LDS: two tiles (rdm_launch.hpp: rdm_tangent_lds).  Adds into rows the
+// library has zeroed; Im of the diagonal is never touched.
+template <int M>
+__global__ __launch_bounds__(kRdmThreads) void k_rdm_tangent(RdmTangentArgs a) {
+    const int b = blockIdx.y, d = blockIdx.z;
+    const double2* psi = a.vec + size_t(b) * a.dim;
+    rdm_accumulate<M, true>(a.g, psi, psi + size_t(1 + d) * a.vstride, a.nblocks,
+                            a.out + size_t(d) * a.out_dstride + size_t(a.k) * a.B + b, size_t(a.n_tsave) * a.B);
 }
 
 struct RdmApplyArgs {

@@ -1,5 +1,6 @@
 // rdm_launch.hpp — reduced density matrices (rdm_kernels.hpp): the tile geometry of one RDM, the evaluation launches of the forward
-// sweeps and the RDM part of the observable cotangent (overlap_launch.hpp: launch_observable_cotangent).  One launch per RDM.
+// sweeps, the RDM tangents of the tangent sweep (tangent_launch.hpp: launch_expect_tangent) and the RDM part of the observable
+// cotangent (overlap_launch.hpp: launch_observable_cotangent).  One launch per RDM.
 #pragma once
 
 namespace {
@@ -82,6 +83,49 @@ int launch_rdm_expect(const ForwardCtx& c, const double2* psi, size_t kstride, i
             }
             if (rc) return rc;
         }
+    }
+    return RYDIFF_OK;
+}
+
+// dynamic LDS of k_rdm_tangent<M>: the Psi tile and the dPsi tile (the reduction scratch reuses their place)
+size_t rdm_tangent_lds(int m, int t) { return std::max(2 * rdm_tile_bytes(m, t), rdm_expect_lds(m, t)); }
+
+template <int M>
+int launch_rdm_tangent_m(const RdmTangentArgs& a, dim3 grid, hipStream_t stream) {
+    if (int rc = set_max_dynamic_lds_once<&k_rdm_tangent<M>>(rdm_tangent_lds(M, kRdmTileBits))) return rc;
+    hipLaunchKernelGGL((k_rdm_tangent<M>), grid, dim3(kRdmThreads), rdm_tangent_lds(M, a.g.t), stream, a);
+    LAUNCH_CHECK();
+    return RYDIFF_OK;
+}
+
+// d rho_A of every RDM and direction at save point k: vec = [1 + n_dir][B][dim] with the state first; `out`: the first RDM row of
+// direction 0 in dexpect_out (zeroed by the caller of the sweep's launches: the kernel adds), dstride doubles between directions
+int launch_rdm_tangent(const ForwardCtx& c, const double2* vec, int n_dir, int k, double* out, size_t dstride) {
+    const Plan& pl = c.rt.pl;
+    const size_t row = size_t(pl.T + 1) * pl.B;
+    for (int o = 0; o < pl.n_rdm; ++o) {
+        RdmTangentArgs a{};
+        a.g = rdm_tile(pl, o, kRdmTileBits);
+        a.vec = vec;
+        a.vstride = size_t(pl.B) * pl.dim;
+        a.out = out + size_t(pl.rdm_row[o]) * row;
+        a.out_dstride = dstride;
+        a.n_tsave = pl.T + 1;
+        a.k = k;
+        a.B = pl.B;
+        a.dim = uint32_t(pl.dim);
+        a.nblocks = uint32_t(pl.dim >> a.g.t);
+        const dim3 grid(std::min<unsigned>(a.nblocks, kRdmMaxBlocks), unsigned(pl.B), unsigned(n_dir));
+        int rc = RYDIFF_OK;
+        switch (a.g.m) {
+            case 1: rc = launch_rdm_tangent_m<1>(a, grid, c.stream); break;
+            case 2: rc = launch_rdm_tangent_m<2>(a, grid, c.stream); break;
+            case 3: rc = launch_rdm_tangent_m<3>(a, grid, c.stream); break;
+            case 4: rc = launch_rdm_tangent_m<4>(a, grid, c.stream); break;
+            case 5: rc = launch_rdm_tangent_m<5>(a, grid, c.stream); break;
+            default: rc = launch_rdm_tangent_m<6>(a, grid, c.stream); break;
+        }
+        if (rc) return rc;
     }
     return RYDIFF_OK;
 }

@@ -641,7 +641,7 @@ int tangent_sweep(const RydProblem* p, const RydPlanInfo* info, const RydTangent
     } else {
         HIP_TRY(hipMemsetAsync(vec[0] + sv, 0, size_t(Dp) * pl.state_bytes, stream));
     }
-    const size_t rows = size_t(pl.ket_rows() + pl.dm_rows());  // (no reduced density matrices: tangent_validate) ket rows, then the density-matrix rows
+    const size_t rows = size_t(pl.ket_rows() + pl.dm_rows());  // ket rows (the RDM block last), then the density-matrix rows
     const size_t row = size_t(pl.T + 1) * pl.B;
     if (rows && dexpect_out) HIP_TRY(hipMemsetAsync(dexpect_out, 0, size_t(D) * rows * row * sizeof(double), stream));
     ForwardCtx c{{rt, &q, ws, stream, sv}};
@@ -651,6 +651,7 @@ int tangent_sweep(const RydProblem* p, const RydPlanInfo* info, const RydTangent
     c.want_exp = expect_out && pl.n_obs > 0;
     c.pauli_out = (expect_out && pl.n_pobs) ? expect_out + size_t(pl.n_obs) * row : nullptr;
     c.overlap_out = (expect_out && pl.n_ov) ? expect_out + size_t(pl.n_obs + pl.n_pobs) * row : nullptr;
+    c.rdm_out = (expect_out && pl.n_rdm) ? expect_out + size_t(pl.n_obs + pl.n_pobs + 2 * pl.n_ov) * row : nullptr;
     c.dm_out = (expect_out && pl.dm_rows()) ? expect_out + size_t(pl.ket_rows()) * row : nullptr;
     if (expect_out && rows) HIP_TRY(hipMemsetAsync(expect_out, 0, rows * row * sizeof(double), stream));
     auto save_point = [&](const double2* v, int k) -> int {  // values (the existing reductions on psi) and tangents of every row

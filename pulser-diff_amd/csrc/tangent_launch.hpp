@@ -12,9 +12,9 @@ int tangent_validate(const RydProblem* p, const RydPlanInfo* info, int n_dir, in
         return fail(RYDIFF_EINVAL, "n_dir must be in [1, " + std::to_string(RYDIFF_MAX_TANGENTS) + "], got " + std::to_string(n_dir));
     if (!info) return fail(RYDIFF_EINVAL, "the tangent sweep needs the plan of rydiff_plan(p, 0, 0, ...): null info");
     if (p->shard_bits > 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented for state-sharded runs (shard_bits > 0)");
-    if (flags & ~(RYDIFF_TANGENT_PAIR_TERMS | RYDIFF_TANGENT_DENSITY_MATRIX))
+    if (flags & ~(RYDIFF_TANGENT_PAIR_TERMS | RYDIFF_TANGENT_DENSITY_MATRIX | RYDIFF_TANGENT_RDMS))
         return fail(RYDIFF_EINVAL, "RydTangent.flags: unknown bits " + std::to_string(flags));
-    // dense pair terms and density-matrix registers run only where the caller asks for them (RydTangent.flags): a caller that does
+    // dense pair terms, density-matrix registers and reduced density matrices run only where the caller asks for them (RydTangent.flags): a caller that does
     // not know of them keeps the refusals it was written against
     if (p->n_pair_terms > 0 && !(flags & RYDIFF_TANGENT_PAIR_TERMS))
         return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented with dense pair terms (n_pair_terms > 0) unless RydTangent.flags "
@@ -22,7 +22,9 @@ int tangent_validate(const RydProblem* p, const RydPlanInfo* info, int n_dir, in
     if (p->amp_conditioned_terms || p->det_ones_terms)
         return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented with conditioned flips / ones-counting terms (three-level registers)");
     if (p->n_shots > 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: measurement shots are not implemented (n_shots > 0): draw them in rydiff_forward");
-    if (p->n_rdms > 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: reduced density matrices are not implemented (n_rdms > 0)");
+    if (p->n_rdms > 0 && !(flags & RYDIFF_TANGENT_RDMS))
+        return fail(RYDIFF_ENOTIMPL, "tangent sweep: reduced density matrices are not implemented (n_rdms > 0) unless RydTangent.flags "
+                                     "has RYDIFF_TANGENT_RDMS");
     if (p->dm_atoms != 0 && !(flags & RYDIFF_TANGENT_DENSITY_MATRIX))
         return fail(RYDIFF_ENOTIMPL, "tangent sweep: density-matrix registers are not implemented (dm_atoms > 0) unless RydTangent.flags "
                                      "has RYDIFF_TANGENT_DENSITY_MATRIX");
@@ -171,7 +173,7 @@ int launch_expect_tangent(const ForwardCtx& c, const double2* vec, int n_dir, in
     const Plan& pl = c.rt.pl;
     const size_t vstride = size_t(pl.B) * pl.dim;
     const size_t row = size_t(pl.T + 1) * pl.B;
-    const size_t dstride = size_t(pl.ket_rows() + pl.dm_rows()) * row;  // (no reduced density matrices here: tangent_validate)
+    const size_t dstride = size_t(pl.ket_rows() + pl.dm_rows()) * row;  // (ket rows: the RDM block behind the overlap rows)
     const unsigned red_blocks = unsigned(std::min<size_t>((pl.dim + 255) / 256, 1024));
     if (pl.n_obs > 0) {
         hipLaunchKernelGGL(k_expect_tangent, dim3(red_blocks, unsigned(pl.B), unsigned(n_dir)), dim3(256), 0, c.stream, vec, vec + vstride, vstride,
@@ -201,6 +203,8 @@ int launch_expect_tangent(const ForwardCtx& c, const double2* vec, int n_dir, in
             if (const int rc = launch_overlap_expect(t, vec + size_t(1 + d) * vstride, 0, k, 1, BatchSlice{0, pl.B, false})) return rc;
         }
     }
+    if (pl.n_rdm > 0)  // d rho_A = Tr_E(|dpsi_d><psi| + |psi><dpsi_d|): k_rdm_tangent, one launch per RDM over all directions
+        if (const int rc = launch_rdm_tangent(c, vec, n_dir, k, dexp + size_t(pl.n_obs + pl.n_pobs + 2 * pl.n_ov) * row, dstride)) return rc;
     if (pl.dm_rows()) {
         // diagonal, Pauli and fidelity rows are linear in vec(rho): k_dm_trace / k_dm_fidelity as they are, on d rho_d, into direction
         // d's density-matrix rows; the purity |v|^2 has the tangent 2 Re <v|dv_d>

@@ -73,6 +73,15 @@ def deriv_param_all_times(sim, x: list, observables: list, **kw):
     return sim.run_sensitivities(x, observables, **kw)
 
 
+def deriv_rdm_all_times(sim, x: list, subsystems: list, **kw):
+    """Reduced density matrices of ``subsystems`` AND their derivatives w.r.t. the scalar entries of ``x`` at EVERY evaluation time
+    in one call: ``sim.run_rdm_sensitivities(x, subsystems, **kw)`` — the tangent sweep of ``deriv_param_all_times`` with
+    ``d rho_A = Tr_E(|dpsi><psi| + |psi><dpsi|)`` formed natively at every save point, instead of one reverse sweep per evaluation
+    time and scalar functional of ``rho_A``.  Returns ``SubsystemSensitivities``: ``rho[o]`` (n_t, B, 2^m, 2^m), ``drho[o][i]``
+    (n_t, B, 2^m, 2^m, *x[i].shape), ``times`` and ``purity`` / ``d_purity`` / ``entropy`` / ``d_entropy``."""
+    return sim.run_rdm_sensitivities(x, subsystems, **kw)
+
+
 def quantum_fisher_information_all_times(sim, x: list, **kw):
     """The quantum Fisher information matrix w.r.t. the scalar entries of ``x`` at EVERY evaluation time in one call:
     ``sim.run_quantum_fisher(x, **kw)`` — the tangent sweep of ``deriv_param_all_times`` with the inner products of the tangent states

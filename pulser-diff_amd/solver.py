@@ -724,10 +724,12 @@ def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsav
     ride in the same sweep, constants in every direction.  ``_native.TANGENT_DENSITY_MATRIX``: with ``spec.dm`` the register is the
     doubled register of a density matrix (``lindblad.mesolve_tangent`` builds the doubled tables and their tangents): ``psi0`` /
     ``d_psi0`` are ``vec(rho0)`` / ``vec(d rho0)``, and the density-matrix rows — diagonal, Pauli, fidelity, purity — and their
-    tangents follow the other rows, as in ``evolve``."""
-    if spec.rdms is not None or (spec.dm is not None and spec.dm.rdms is not None):
-        raise NotImplementedError("evolve_tangent evaluates no reduced density matrices (rydiff_forward_tangent: RYDIFF_ENOTIMPL); "
-                                  "request them from evolve")
+    tangents follow the other rows, as in ``evolve``.  ``_native.TANGENT_RDMS``: the reduced density matrices of ``spec.rdms`` (kets
+    only) join the rows behind the overlaps, values in ``expect`` and ``d rho_A = Tr_E(|dpsi><psi| + |psi><dpsi|)`` in ``dexpect``;
+    ``split_observables`` takes them out of ``expect`` and, direction by direction, out of ``dexpect[d]``."""
+    if (spec.rdms is not None and not (int(flags) & _native.TANGENT_RDMS)) or (spec.dm is not None and spec.dm.rdms is not None):
+        raise NotImplementedError("evolve_tangent evaluates no reduced density matrices (rydiff_forward_tangent: RYDIFF_ENOTIMPL) unless "
+                                  "flags has _native.TANGENT_RDMS (kets only); or request them from evolve")
     if spec.dm is not None and not (int(flags) & _native.TANGENT_DENSITY_MATRIX):
         raise NotImplementedError("evolve_tangent takes no density-matrix registers (rydiff_forward_tangent: RYDIFF_ENOTIMPL) unless "
                                   "flags has _native.TANGENT_DENSITY_MATRIX (lindblad.mesolve_tangent); or differentiate evolve")
@@ -759,7 +761,7 @@ def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsav
     call = _Call(spec, amp_c, det_c, u_c, ts_host, batch, obs_c)
     call.problem.kernel_variant = 0  # the tangent sweep has one kernel family
     p = call.problem
-    rows = p.n_obs + p.n_pauli_obs + 2 * p.n_overlaps + (spec.dm.rows() if spec.dm is not None else 0)
+    rows = p.n_obs + p.n_pauli_obs + 2 * p.n_overlaps + spec.rdm_rows() + (spec.dm.rows() if spec.dm is not None else 0)
     expect = torch.empty((rows, n_t, batch), dtype=torch.float64, device=dev)
     dexpect = torch.empty((n_dir, rows, n_t, batch), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
@@ -820,12 +822,14 @@ def evolve_geometry(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsa
     ``geometry.quantum_fisher_information`` and its neighbours take.  The sums are formed in a fixed order: two calls on the same
     inputs return bit-identical matrices.  Same arguments as ``evolve_tangent``; tangents of inputs the problem does not have give
     zero rows and columns.  More than 8 directions run one sweep per pair of groups of 4 (``geometry.geometry_sweeps``).
-    ``flags=_native.TANGENT_PAIR_TERMS`` takes dense pair terms on kets; density-matrix registers stay refused."""
+    ``flags=_native.TANGENT_PAIR_TERMS`` takes dense pair terms on kets, ``_native.TANGENT_RDMS`` the reduced density matrices of
+    ``spec.rdms`` (rows as in ``evolve_tangent``; their sums use atomics and are not part of the fixed order); density-matrix registers
+    stay refused."""
     from .geometry import geometry_sweeps
 
-    if spec.rdms is not None:
-        raise NotImplementedError("evolve_geometry evaluates no reduced density matrices (rydiff_forward_geometry: RYDIFF_ENOTIMPL); "
-                                  "request them from evolve")
+    if spec.rdms is not None and not (int(flags) & _native.TANGENT_RDMS):
+        raise NotImplementedError("evolve_geometry evaluates no reduced density matrices (rydiff_forward_geometry: RYDIFF_ENOTIMPL) unless "
+                                  "flags has _native.TANGENT_RDMS; or request them from evolve")
     if spec.dm is not None:
         raise NotImplementedError("evolve_geometry takes no density-matrix registers (rydiff_forward_geometry: RYDIFF_ENOTIMPL): the "
                                   "pure-state quantum Fisher information is not the mixed-state one")
@@ -857,7 +861,7 @@ def evolve_geometry(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsa
     call = _Call(spec, amp_c, det_c, u_c, ts_host, batch, obs_c)
     call.problem.kernel_variant = 0  # the tangent sweep has one kernel family
     p = call.problem
-    rows = p.n_obs + p.n_pauli_obs + 2 * p.n_overlaps
+    rows = p.n_obs + p.n_pauli_obs + 2 * p.n_overlaps + spec.rdm_rows()
     expect = torch.empty((rows, n_t, batch), dtype=torch.float64, device=dev)
     dexpect = torch.empty((n_dir, rows, n_t, batch), dtype=torch.float64, device=dev)
     gram = torch.empty((n_t, batch, 1 + n_dir, 1 + n_dir), dtype=torch.complex128, device=dev)

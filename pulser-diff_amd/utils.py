@@ -187,6 +187,22 @@ def von_neumann_entropy(rho: Tensor, base: float = 2) -> Tensor:
     return -torch.special.xlogy(ev, ev).sum(dim=-1) / math.log(base)
 
 
+def purity_tangent(rho: Tensor, drho: Tensor) -> Tensor:
+    """The directional derivative ``2 Re tr(rho drho)`` of ``purity`` at ``rho`` along ``drho`` (both ``(..., d, d)``, broadcast
+    against each other)."""
+    return 2.0 * torch.einsum("...ij,...ji->...", rho, drho).real
+
+
+def von_neumann_entropy_tangent(rho: Tensor, drho: Tensor, base: float = 2) -> Tensor:
+    """The directional derivative ``-tr(drho (log rho + 1)) / ln(base)`` of ``von_neumann_entropy`` at ``rho`` along the Hermitian
+    direction ``drho`` (both ``(..., d, d)``, broadcast against each other), ``log rho`` from ``eigh`` of the Hermitian part.  Defined
+    for FULL-RANK ``rho`` only: at a zero eigenvalue (pure states, product states) ``log rho`` does not exist and the result is
+    infinite or NaN.  Unlike autograd through ``eigvalsh`` it needs no distinct eigenvalues."""
+    ev, vec = torch.linalg.eigh(0.5 * (rho + rho.mH))
+    rotated = torch.einsum("...ji,...jk,...ki->...i", vec.conj(), drho.to(vec.dtype), vec).real  # diagonal of V^H drho V
+    return -(rotated * (torch.log(ev) + 1.0)).sum(dim=-1) / math.log(base)
+
+
 def partial_transpose(rho: Tensor, n_first: int) -> Tensor:
     """Matrices ``(..., 2^m, 2^m)`` transposed on the first party: the ``n_first`` LEADING qubits of the matrix ordering
     (``0 < n_first < m``), ``rho^{T_1}[(a1, a2), (b1, b2)] = rho[(b1, a2), (a1, b2)]``."""
