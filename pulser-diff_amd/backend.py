@@ -38,7 +38,7 @@ from .solver import (ProblemSpec, SolverType, evolve, evolve_geometry, evolve_ta
 from .observables import PauliObservable, Purity, ReducedDensityMatrix, StateOverlap, pack_overlaps
 from .geometry import QuantumGeometry, quantum_geometric_tensor
 from .shots import MAX_SHOTS, ShotRequest, indices_to_bitstrings
-from .utils import DiagonalObservable
+from .utils import DiagonalObservable, real_diagonal
 
 
 def _same_field(a, b) -> bool:
@@ -401,16 +401,10 @@ class TorchEmulator:
                     raise ValueError(f"PauliObservable on {obs.n_qubits} qubits handed to a register of {ham._size}")
                 pauli_objs.append(obs)
                 continue
-            if isinstance(obs, DiagonalObservable):
-                diag = obs.diag
-            elif isinstance(obs, Tensor) and obs.ndim == 2:
-                dense = obs.to_dense() if obs.is_sparse else obs
-                if not torch.equal(torch.diag(torch.diagonal(dense)), dense):
-                    raise ValueError("Only diagonal observables can be evaluated natively; use results.expect on the states.")
-                diag = torch.diagonal(dense).real
-            else:
+            if not isinstance(obs, DiagonalObservable) and not (isinstance(obs, Tensor) and obs.ndim == 2):
                 raise TypeError("observables must be DiagonalObservable / PauliObservable / StateOverlap / ReducedDensityMatrix / Purity "
                                 "objects or diagonal (dim, dim) tensors")
+            diag = real_diagonal(obs, "Only diagonal observables can be evaluated natively; use results.expect on the states.")
             obs_tensors.append(diag.to(dev, torch.float64))
             obs_objs.append(obs)
         obs_diag = torch.stack(obs_tensors) if obs_tensors else None
@@ -472,10 +466,8 @@ class TorchEmulator:
                                    native_rdms=result.rdms, rdm_observables=rdm_objs)
 
         # does the noise ask for averaging over several runs?  (backend.py:531-569)
-        no_resampling = noise <= {"dephasing", "relaxation", "SPAM", "depolarizing", "eff_noise", "amplitude"} and (
-            "amplitude" not in noise or self.config.amp_sigma == 0.0)
         bad_atom_configs = None
-        if no_resampling:
+        if self._no_resampling():
             if "SPAM" not in noise or self.config.eta == 0:
                 return run_coherent()
             # only the state preparation is random: one run per distinct configuration of badly prepared atoms
@@ -526,6 +518,83 @@ class TorchEmulator:
             tangents[k] = torch.view_as_complex(stacked.contiguous()) if k == "amp" else stacked
         return tangents["amp"], tangents["det"], tangents["u"]
 
+    def _no_resampling(self) -> bool:
+        """The noise asks for no averaging over several runs of resampled tables (backend.py:531-569; a random state preparation,
+        SPAM with eta > 0, still does)."""
+        noise = set(self.config.noise)
+        return noise <= {"dephasing", "relaxation", "SPAM", "depolarizing", "eff_noise", "amplitude"} and (
+            "amplitude" not in noise or self.config.amp_sigma == 0.0)
+
+    def _check_sensitivity_request(self, name: str, x: list, solver: SolverType, averaging: str = "",
+                                   master_equation: Optional[str] = None, all_basis: Optional[str] = None) -> tuple:
+        """What the all-times methods (`name`) ask of a request before they look at the observables -> (x as a list, the solver that
+        will run).  ``averaging``: the method's reason behind the refusal of averaging noise; ``master_equation`` / ``all_basis``: the
+        method's refusal of master-equation runs / of the three-level basis (None: it takes them)."""
+        x = list(x)
+        if not x or not all(isinstance(t, Tensor) for t in x):
+            raise TypeError("x must be a non-empty list of tensors")
+        if any(t is self._eval_times_array for t in x):
+            raise ValueError(f"{name} differentiates w.r.t. parameters; the evaluation times are not one of them: "
+                             "run(time_grad=True) and deriv_time deliver d f(t_k) / d t_k for every k in one reverse sweep.")
+        noise = set(self.config.noise)
+        if not self._no_resampling() or ("SPAM" in noise and self.config.eta > 0):
+            raise NotImplementedError(f"{name} is not available in noisy runs that average over realisations{averaging}.")
+        if noise & COLLAPSE_NOISES:
+            solver = SolverType.DP5_ME
+        if solver == SolverType.DP5_ME and master_equation is not None:
+            raise NotImplementedError(master_equation)
+        if solver not in (SolverType.DP5_SE, SolverType.KRYLOV_SE, SolverType.DP5_ME):
+            raise ValueError(f"Solver {solver} not available.")
+        if self._hamiltonian.basis_name == "all" and all_basis is not None:
+            raise NotImplementedError(all_basis)
+        return x, solver
+
+    def _pack_row_observables(self, observables: list, overlaps: bool = False) -> tuple:
+        """Diagonal observables, ``PauliObservable`` and (``overlaps``) ``StateOverlap`` objects -> (obs_diag or None, the Pauli
+        objects, the overlap objects, rows): ``rows`` lists the native rows of the observables in the order they were handed in —
+        diagonal rows, then the Pauli rows, then two rows (Re, Im) per overlap, the order ``solver._Call.expect_rows`` counts."""
+        ham, dev = self._hamiltonian, self._compute_device
+        diag_rows, pauli_objs, overlap_objs, order = [], [], [], []  # order: where observable i sits among the native rows
+        for obs in observables:
+            if isinstance(obs, PauliObservable):
+                if obs.n_qubits != ham._size:
+                    raise ValueError(f"PauliObservable on {obs.n_qubits} qubits handed to a register of {ham._size}")
+                order.append(("p", len(pauli_objs)))
+                pauli_objs.append(obs)
+                continue
+            if overlaps and isinstance(obs, StateOverlap):
+                order.append(("o", len(overlap_objs)))
+                overlap_objs.append(obs)
+                continue
+            diag = real_diagonal(obs, "Only diagonal observables can be evaluated natively; build off-diagonal ones with build_observable.")
+            order.append(("d", len(diag_rows)))
+            diag_rows.append(diag.to(dev, torch.float64))
+        n_real = len(diag_rows) + len(pauli_objs)
+        rows = []
+        for kind, r in order:
+            rows += [r] if kind == "d" else ([len(diag_rows) + r] if kind == "p" else [n_real + 2 * r, n_real + 2 * r + 1])
+        return torch.stack(diag_rows) if diag_rows else None, pauli_objs, overlap_objs, rows
+
+    @staticmethod
+    def _plain_run_with_zero_tangents(n_dir: int, run) -> tuple:
+        """Nothing in x reaches the tables: (expect, dexpect) with the values of the plain run ``run()`` (under no_grad) and zero
+        derivatives in every direction."""
+        with torch.no_grad():
+            expect = run()
+        return expect, torch.zeros((n_dir,) + tuple(expect.shape), dtype=torch.float64, device=expect.device)
+
+    @staticmethod
+    def _per_tensor(dvals: Tensor, x: list) -> list:
+        """Direction-major derivatives (n_dir, ...), one direction per scalar entry of the tensors in x -> one tensor per x_i on
+        x_i's device, of shape (..., *x_i.shape)."""
+        dvals = dvals.movedim(0, -1)
+        out, d0 = [], 0
+        for t in x:
+            m = int(t.numel())
+            out.append(dvals[..., d0:d0 + m].reshape(tuple(dvals.shape[:-1]) + tuple(t.shape)).to(t.device))
+            d0 += m
+        return out
+
     def run_sensitivities(self, x: list, observables: list, solver: SolverType = SolverType.DP5_SE, dist_grad: bool = False,
                           route: Optional[str] = None, **options: Any) -> "Sensitivities":
         """Values AND derivatives of observables at EVERY evaluation time w.r.t. the tensors in ``x`` — what a loop of
@@ -545,21 +614,7 @@ class TorchEmulator:
         times come from ``deriv_time``."""
         if route not in (None, "tangent", "adjoint-loop"):
             raise ValueError(f'route must be None, "tangent" or "adjoint-loop", got {route!r}')
-        x = list(x)
-        if not x or not all(isinstance(t, Tensor) for t in x):
-            raise TypeError("x must be a non-empty list of tensors")
-        if any(t is self._eval_times_array for t in x):
-            raise ValueError("run_sensitivities differentiates w.r.t. parameters; the evaluation times are not one of them: "
-                             "run(time_grad=True) and deriv_time deliver d f(t_k) / d t_k for every k in one reverse sweep.")
-        noise = set(self.config.noise)
-        no_resampling = noise <= {"dephasing", "relaxation", "SPAM", "depolarizing", "eff_noise", "amplitude"} and (
-            "amplitude" not in noise or self.config.amp_sigma == 0.0)
-        if not no_resampling or ("SPAM" in noise and self.config.eta > 0):
-            raise NotImplementedError("run_sensitivities is not available in noisy runs that average over realisations.")
-        if noise & COLLAPSE_NOISES:
-            solver = SolverType.DP5_ME
-        if solver not in (SolverType.DP5_SE, SolverType.KRYLOV_SE, SolverType.DP5_ME):
-            raise ValueError(f"Solver {solver} not available.")
+        x, solver = self._check_sensitivity_request("run_sensitivities", x, solver)
         ham, dev = self._hamiltonian, self._compute_device
         observables = list(observables)
         full = ham.dim ** ham._size
@@ -613,38 +668,14 @@ class TorchEmulator:
             psi0 = self.initial_state
             psi_db = (psi0.unsqueeze(1) if psi0.ndim == 1 else psi0).to(dev)
             if d_amp is None and d_det is None and d_u is None:  # nothing in x reaches the tables
-                with torch.no_grad():
-                    res = mesolve(ham, psi_db, times, ham.config, dict(options), observables=observables, store_states=False)
-                expect = torch.stack(res.expect)
-                dexpect = torch.zeros((n_dir,) + tuple(expect.shape), dtype=torch.float64, device=expect.device)
+                expect, dexpect = self._plain_run_with_zero_tangents(n_dir, lambda: torch.stack(
+                    mesolve(ham, psi_db, times, ham.config, dict(options), observables=observables, store_states=False).expect))
             else:
                 expect, dexpect = mesolve_tangent(ham, psi_db, times, ham.config, dict(options), observables,
                                                   d_amp=d_amp, d_det=d_det, d_u=d_u)
-            values, dvals = expect.sum(dim=-1), dexpect.sum(dim=-1)
-            grads, d0 = [], 0
-            for t in x:
-                m = int(t.numel())
-                grads.append(dvals[d0:d0 + m].permute(1, 2, 0).reshape(len(observables), n_t, *t.shape).to(t.device))
-                d0 += m
-            return Sensitivities(values, grads, "tangent", times)
+            return Sensitivities(expect.sum(dim=-1), self._per_tensor(dexpect.sum(dim=-1), x), "tangent", times)
 
-        diag_rows, pauli_objs, order = [], [], []  # order: where observable i sits among the native rows
-        for obs in observables:
-            if isinstance(obs, PauliObservable):
-                if obs.n_qubits != ham._size:
-                    raise ValueError(f"PauliObservable on {obs.n_qubits} qubits handed to a register of {ham._size}")
-                order.append(("p", len(pauli_objs)))
-                pauli_objs.append(obs)
-                continue
-            if isinstance(obs, DiagonalObservable):
-                diag = obs.diag
-            else:
-                dense = obs.to_dense() if obs.is_sparse else obs
-                if not torch.equal(torch.diag(torch.diagonal(dense)), dense):
-                    raise ValueError("Only diagonal observables can be evaluated natively; build off-diagonal ones with build_observable.")
-                diag = torch.diagonal(dense).real
-            order.append(("d", len(diag_rows)))
-            diag_rows.append(diag.to(dev, torch.float64))
+        obs_diag, pauli_objs, _, rows = self._pack_row_observables(observables)
         d_amp, d_det, d_u = self._table_tangents(x)
         n_dir = sum(int(t.numel()) for t in x)
         psi0 = self.initial_state
@@ -652,12 +683,9 @@ class TorchEmulator:
         spec = ham.problem_spec(solver=solver, tol=tolerance_from_options(dict(options)), store_states=False)
         if pauli_objs:
             spec.pauli = pauli_objs
-        obs_diag = torch.stack(diag_rows) if diag_rows else None
-        rows = [r if kind == "d" else len(diag_rows) + r for kind, r in order]
         if d_amp is None and d_det is None and d_u is None:  # nothing in x reaches the tables: zero derivatives, values from a plain run
-            with torch.no_grad():
-                expect = evolve(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, obs_diag)[1]
-            dexpect = torch.zeros((n_dir,) + tuple(expect.shape), dtype=torch.float64, device=expect.device)
+            expect, dexpect = self._plain_run_with_zero_tangents(
+                n_dir, lambda: evolve(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, obs_diag)[1])
         else:
             # the complex tables and the unrotated psi0: the rotating frame is a per-call device of sesolve, not of this path
             expect, dexpect = evolve_tangent(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, obs_diag,
@@ -665,12 +693,7 @@ class TorchEmulator:
                                              flags=_native.TANGENT_PAIR_TERMS if spec.pair_terms else 0)  # (the XY exchange)
         values = expect.sum(dim=-1)[rows]            # (n_obs, n_t): summed over the columns of psi0 like results.expect
         dvals = dexpect.sum(dim=-1)[:, rows]         # (n_dir, n_obs, n_t)
-        grads, d0 = [], 0
-        for t in x:
-            m = int(t.numel())
-            grads.append(dvals[d0:d0 + m].permute(1, 2, 0).reshape(len(rows), n_t, *t.shape).to(t.device))
-            d0 += m
-        return Sensitivities(values, grads, "tangent", times)
+        return Sensitivities(values, self._per_tensor(dvals, x), "tangent", times)
 
     def run_rdm_sensitivities(self, x: list, subsystems: list, solver: SolverType = SolverType.DP5_SE, dist_grad: bool = False,
                               **options: Any) -> "SubsystemSensitivities":
@@ -683,27 +706,14 @@ class TorchEmulator:
         ``x`` is what ``run_sensitivities`` takes.  ``subsystems``: ``ReducedDensityMatrix`` objects (e.g. from
         ``build_reduced_density_matrix``) or tuples of qubit indices, 1 to 6 qubits each.  Noiseless Ising and XY runs (the exchange
         rides in the sweep as constant pair terms).  Returns ``SubsystemSensitivities``."""
-        x = list(x)
-        if not x or not all(isinstance(t, Tensor) for t in x):
-            raise TypeError("x must be a non-empty list of tensors")
-        if any(t is self._eval_times_array for t in x):
-            raise ValueError("run_rdm_sensitivities differentiates w.r.t. parameters; the evaluation times are not one of them: "
-                             "run(time_grad=True) and deriv_time deliver d f(t_k) / d t_k for every k in one reverse sweep.")
-        noise = set(self.config.noise)
-        no_resampling = noise <= {"dephasing", "relaxation", "SPAM", "depolarizing", "eff_noise", "amplitude"} and (
-            "amplitude" not in noise or self.config.amp_sigma == 0.0)
-        if not no_resampling or ("SPAM" in noise and self.config.eta > 0):
-            raise NotImplementedError("run_rdm_sensitivities is not available in noisy runs that average over realisations.")
-        if noise & COLLAPSE_NOISES or solver == SolverType.DP5_ME:
-            raise NotImplementedError("run_rdm_sensitivities is not available for master-equation runs (collapse-operator noise, "
-                                      "DP5_ME): the tangent sweep forms no tangents of the partial trace of a density matrix; "
-                                      "differentiate results.reduced_density_matrix through run().")
-        if solver not in (SolverType.DP5_SE, SolverType.KRYLOV_SE):
-            raise ValueError(f"Solver {solver} not available.")
+        x, solver = self._check_sensitivity_request(
+            "run_rdm_sensitivities", x, solver,
+            master_equation="run_rdm_sensitivities is not available for master-equation runs (collapse-operator noise, "
+                            "DP5_ME): the tangent sweep forms no tangents of the partial trace of a density matrix; "
+                            "differentiate results.reduced_density_matrix through run().",
+            all_basis="run_rdm_sensitivities is not available in the three-level all-basis: the native tangent sweep "
+                      "takes no conditioned flips / ones-counting terms, and ReducedDensityMatrix is a qubit observable.")
         ham, dev = self._hamiltonian, self._compute_device
-        if ham.basis_name == "all":
-            raise NotImplementedError("run_rdm_sensitivities is not available in the three-level all-basis: the native tangent sweep "
-                                      "takes no conditioned flips / ones-counting terms, and ReducedDensityMatrix is a qubit observable.")
         rdm_objs = [o if isinstance(o, ReducedDensityMatrix) else ReducedDensityMatrix(o) for o in subsystems]
         if not 1 <= len(rdm_objs) <= _native.MAX_RDMS:
             raise ValueError(f"run_rdm_sensitivities takes 1 to {_native.MAX_RDMS} subsystems per call, got {len(rdm_objs)}")
@@ -712,7 +722,6 @@ class TorchEmulator:
         if dist_grad:
             self._enable_dist_grad()
         times = self._eval_times_array.detach()
-        n_t = int(times.shape[0])
         d_amp, d_det, d_u = self._table_tangents(x)
         n_dir = sum(int(t.numel()) for t in x)
         psi0 = self.initial_state
@@ -720,9 +729,8 @@ class TorchEmulator:
         spec = ham.problem_spec(solver=solver, tol=tolerance_from_options(dict(options)), store_states=False)
         spec.rdms = rdm_objs
         if d_amp is None and d_det is None and d_u is None:  # nothing in x reaches the tables: zero derivatives, values from a plain run
-            with torch.no_grad():
-                expect = evolve(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, None)[1]
-            dexpect = torch.zeros((n_dir,) + tuple(expect.shape), dtype=torch.float64, device=expect.device)
+            expect, dexpect = self._plain_run_with_zero_tangents(
+                n_dir, lambda: evolve(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, None)[1])
         else:
             # the complex tables and the unrotated psi0, as in run_sensitivities: the matrices are lab-frame ones
             expect, dexpect = evolve_tangent(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, None,
@@ -730,15 +738,8 @@ class TorchEmulator:
                                              flags=_native.TANGENT_RDMS | (_native.TANGENT_PAIR_TERMS if spec.pair_terms else 0))
         rho = split_observables(expect, 0, rdm_objs)[2]
         per_dir = [split_observables(dexpect[d], 0, rdm_objs)[2] for d in range(n_dir)]
-        drho = []
-        for o in range(len(rdm_objs)):
-            stacked = torch.stack([per_dir[d][o] for d in range(n_dir)], dim=-1)  # (n_t, B, 2^m, 2^m, n_dir)
-            parts, d0 = [], 0
-            for t in x:
-                m = int(t.numel())
-                parts.append(stacked[..., d0:d0 + m].reshape(tuple(stacked.shape[:4]) + tuple(t.shape)).to(t.device))
-                d0 += m
-            drho.append(parts)
+        # per subsystem: (n_dir, n_t, B, 2^m, 2^m) -> one (n_t, B, 2^m, 2^m, *x_i.shape) per x_i
+        drho = [self._per_tensor(torch.stack([per_dir[d][o] for d in range(n_dir)]), x) for o in range(len(rdm_objs))]
         return SubsystemSensitivities(rho, drho, times)
 
     def run_quantum_fisher(self, x: list, observables: list = (), solver: SolverType = SolverType.DP5_SE, dist_grad: bool = False,
@@ -752,28 +753,15 @@ class TorchEmulator:
         Gauss-Newton term ``2 Re(conj(dc_i) dc_j)`` of a fidelity loss can be formed from the same call.  One initial state gives
         (n_t, D, D) matrices, several columns of it (n_t, B, D, D): the geometry of a batch is per state.  This is the PURE-state
         quantity: runs whose state is a density matrix or an average are refused, there is no fallback loop."""
-        x = list(x)
-        if not x or not all(isinstance(t, Tensor) for t in x):
-            raise TypeError("x must be a non-empty list of tensors")
-        if any(t is self._eval_times_array for t in x):
-            raise ValueError("run_quantum_fisher differentiates w.r.t. parameters; the evaluation times are not one of them: "
-                             "run(time_grad=True) and deriv_time deliver d f(t_k) / d t_k for every k in one reverse sweep.")
-        noise = set(self.config.noise)
-        no_resampling = noise <= {"dephasing", "relaxation", "SPAM", "depolarizing", "eff_noise", "amplitude"} and (
-            "amplitude" not in noise or self.config.amp_sigma == 0.0)
-        if not no_resampling or ("SPAM" in noise and self.config.eta > 0):
-            raise NotImplementedError("run_quantum_fisher is not available in noisy runs that average over realisations: the average "
-                                      "of pure states is a mixed state, and this is the pure-state quantum Fisher information.")
-        if noise & COLLAPSE_NOISES or solver == SolverType.DP5_ME:
-            raise NotImplementedError("run_quantum_fisher is not available for master-equation runs (collapse-operator noise, DP5_ME): "
-                                      "the state is a density matrix, and the pure-state quantum Fisher information is not the "
-                                      "mixed-state one.")
-        if solver not in (SolverType.DP5_SE, SolverType.KRYLOV_SE):
-            raise ValueError(f"Solver {solver} not available.")
+        x, solver = self._check_sensitivity_request(
+            "run_quantum_fisher", x, solver,
+            averaging=": the average of pure states is a mixed state, and this is the pure-state quantum Fisher information",
+            master_equation="run_quantum_fisher is not available for master-equation runs (collapse-operator noise, DP5_ME): "
+                            "the state is a density matrix, and the pure-state quantum Fisher information is not the "
+                            "mixed-state one.",
+            all_basis="run_quantum_fisher is not available in the three-level all-basis: the native tangent sweep takes "
+                      "no conditioned flips / ones-counting terms.")
         ham, dev = self._hamiltonian, self._compute_device
-        if ham.basis_name == "all":
-            raise NotImplementedError("run_quantum_fisher is not available in the three-level all-basis: the native tangent sweep takes "
-                                      "no conditioned flips / ones-counting terms.")
         if getattr(ham, "pair_terms", ()):
             raise NotImplementedError("run_quantum_fisher is not available with the XY exchange: this route hands no dense pair terms "
                                       "to the tangent sweep (solver.evolve_geometry takes them on request).")
@@ -788,27 +776,7 @@ class TorchEmulator:
             self._enable_dist_grad()
         times = self._eval_times_array.detach()
         n_t = int(times.shape[0])
-        diag_rows, pauli_objs, overlap_objs, order = [], [], [], []  # order: where observable i sits among the native rows
-        for obs in observables:
-            if isinstance(obs, PauliObservable):
-                if obs.n_qubits != ham._size:
-                    raise ValueError(f"PauliObservable on {obs.n_qubits} qubits handed to a register of {ham._size}")
-                order.append(("p", len(pauli_objs)))
-                pauli_objs.append(obs)
-                continue
-            if isinstance(obs, StateOverlap):
-                order.append(("o", len(overlap_objs)))
-                overlap_objs.append(obs)
-                continue
-            if isinstance(obs, DiagonalObservable):
-                diag = obs.diag
-            else:
-                dense = obs.to_dense() if obs.is_sparse else obs
-                if not torch.equal(torch.diag(torch.diagonal(dense)), dense):
-                    raise ValueError("Only diagonal observables can be evaluated natively; build off-diagonal ones with build_observable.")
-                diag = torch.diagonal(dense).real
-            order.append(("d", len(diag_rows)))
-            diag_rows.append(diag.to(dev, torch.float64))
+        obs_diag, pauli_objs, overlap_objs, rows = self._pack_row_observables(observables, overlaps=True)
         d_amp, d_det, d_u = self._table_tangents(x)
         n_dir = sum(int(t.numel()) for t in x)
         psi0 = self.initial_state
@@ -819,11 +787,6 @@ class TorchEmulator:
             spec.pauli = pauli_objs
         if overlap_objs:  # the complex tables and the unrotated psi0 (as in run_sensitivities): the targets stay in the lab frame too
             spec.overlaps = pack_overlaps(overlap_objs, int(psi_bd.shape[1]), batch, dev)
-        obs_diag = torch.stack(diag_rows) if diag_rows else None
-        n_real = len(diag_rows) + len(pauli_objs)
-        rows = []
-        for kind, r in order:
-            rows += [r] if kind == "d" else ([len(diag_rows) + r] if kind == "p" else [n_real + 2 * r, n_real + 2 * r + 1])
         if d_amp is None and d_det is None and d_u is None:
             # nothing in x reaches the tables: every tangent state is zero — <psi|psi> and the values from one sweep with one zero direction
             expect, _, g1 = evolve_geometry(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, obs_diag,
@@ -838,13 +801,8 @@ class TorchEmulator:
             gram = gram[:, 0]
         values = expect.sum(dim=-1)[rows]            # (n_rows, n_t): summed over the columns of psi0 like results.expect
         dvals = dexpect.sum(dim=-1)[:, rows]         # (n_dir, n_rows, n_t)
-        grads, d0 = [], 0
-        for t in x:
-            m = int(t.numel())
-            grads.append(dvals[d0:d0 + m].permute(1, 2, 0).reshape(len(rows), n_t, *t.shape).to(t.device))
-            d0 += m
         qgt = quantum_geometric_tensor(gram)
-        return QuantumGeometry(gram, qgt, 4.0 * qgt.real, -2.0 * qgt.imag, values, grads, "tangent", times)
+        return QuantumGeometry(gram, qgt, 4.0 * qgt.real, -2.0 * qgt.imag, values, self._per_tensor(dvals, x), "tangent", times)
 
     def _run_noisy(self, psi0: Tensor, solver: SolverType, options: dict, reps: list, bad_atom_configs,
                    meas_errors, native_shots: bool = False) -> NoisyResults:

@@ -48,10 +48,10 @@ void launch_dm_fidelity_n(const DmFidArgs& a, dim3 grid, hipStream_t stream) {
 int launch_dm_expect(const ForwardCtx& c, const double2* v, size_t kstride, int k0, int nk, const BatchSlice& bs, bool linear_only = false) {
     const Plan& pl = c.rt.pl;
     if (!c.dm_out) return RYDIFF_OK;
-    const size_t row = size_t(pl.T + 1) * pl.B;
+    const ExpectRows rows(pl);  // (c.dm_out is the first density-matrix row: offsets from DmTrace)
     const size_t D = size_t(1) << pl.dm_n;
     const int kmax = std::max(1, 65535 / bs.count);  // grid.y
-    const int n_trace = pl.n_dm_diag + pl.n_dm_pobs;
+    const int n_trace = rows.count(ExpectRows::DmTrace);
     for (int k = 0; k < nk; k += kmax) {
         const unsigned gy = unsigned(bs.count * std::min(kmax, nk - k));
         if (n_trace) {
@@ -77,7 +77,7 @@ int launch_dm_expect(const ForwardCtx& c, const double2* v, size_t kstride, int 
             a.v = v + size_t(k) * kstride;
             a.kstride = kstride;
             a.phi = static_cast<const double2*>(c.p->dm_fid_targets);
-            a.out = c.dm_out + size_t(n_trace) * row;
+            a.out = c.dm_out + rows.offset(ExpectRows::DmFid, ExpectRows::DmTrace);
             a.n_fid = pl.n_dm_fid;
             a.fid_batch = pl.dm_fid_batch;
             a.purity = purity;
@@ -99,7 +99,7 @@ int launch_dm_expect(const ForwardCtx& c, const double2* v, size_t kstride, int 
             DmRdmArgs a{};
             a.v = v + size_t(k) * kstride;
             a.kstride = kstride;
-            a.out = c.dm_out + size_t(n_trace + pl.n_dm_fid + pl.dm_purity) * row;
+            a.out = c.dm_out + rows.offset(ExpectRows::DmRdm, ExpectRows::DmTrace);
             a.n_tsave = pl.T + 1;
             a.k0 = k0 + k;
             a.B = pl.B;
@@ -158,9 +158,8 @@ int launch_dm_shots(const ForwardCtx& c, const double2* v, size_t kstride, int k
 void launch_dm_apply(const PauliInject& pi, const double2* psi, const int32_t* entry, int kmul, int k0, int nk, const double2* base,
                      double2* out) {
     const Plan& pl = pi.rt->pl;
-    const size_t row = size_t(pl.T + 1) * pl.B;
+    const ExpectRows rows(pl);  // (pi.dm_gexp is the first density-matrix row: offsets from DmTrace)
     const size_t D = size_t(1) << pl.dm_n;
-    const int n_trace = pl.n_dm_diag + pl.n_dm_pobs;
     if (pl.n_dm_fid || pl.dm_purity || base != out) {  // the dense pass (also what copies or clears where nothing has written `out` yet)
         DmApplyArgs a{};
         a.psi = psi;
@@ -169,8 +168,8 @@ void launch_dm_apply(const PauliInject& pi, const double2* psi, const int32_t* e
         a.base = base;
         a.out = out;
         a.phi = pi.dm_phi;
-        a.g_fid = pi.dm_gexp + size_t(n_trace) * row;
-        a.g_pur = pl.dm_purity ? pi.dm_gexp + size_t(n_trace + pl.n_dm_fid) * row : nullptr;
+        a.g_fid = pi.dm_gexp + rows.offset(ExpectRows::DmFid, ExpectRows::DmTrace);
+        a.g_pur = pl.dm_purity ? pi.dm_gexp + rows.offset(ExpectRows::DmPurity, ExpectRows::DmTrace) : nullptr;
         a.n_fid = pl.n_dm_fid;
         a.fid_batch = pl.dm_fid_batch;
         a.n_tsave = pl.T + 1;
@@ -198,7 +197,7 @@ void launch_dm_apply(const PauliInject& pi, const double2* psi, const int32_t* e
     for (int o = 0; o < pl.n_dm_rdm; ++o) {
         DmRdmScatterArgs a{};
         a.out = out;
-        a.gexp = pi.dm_gexp + size_t(n_trace + pl.n_dm_fid + pl.dm_purity + pl.dm_rdm_row[o]) * row;
+        a.gexp = pi.dm_gexp + rows.offset(ExpectRows::DmRdm, ExpectRows::DmTrace) + size_t(pl.dm_rdm_row[o]) * rows.stride;
         a.n_tsave = pl.T + 1;
         a.k0 = k0;
         a.B = pl.B;

@@ -11,7 +11,7 @@ struct OverlapExpectArgs {
     const double2* psi;  // state at save point k0, trajectory 0
     size_t kstride;      // amplitudes between consecutive save points (grid.y covers b_count * n_k states)
     const double2* phi;  // targets
-    double* out;         // &expect_out[n_obs + n_pobs][0][0]: [2 * n_ov][n_tsave][B]
+    double* out;         // the Overlap block of expect_out (ExpectRows, plan.hpp): [2 * n_ov][n_tsave][B]
     int n_ov, ov_batch, n_tsave, k0, B, b_first, b_count;
     uint32_t dim;
 };
@@ -54,7 +54,7 @@ struct OverlapApplyArgs {
     const double2* base;  // [n_k][B][dim]: what the overlap cotangent is added to (the Pauli cotangent, grad_states from k0 on), or nullptr
     double2* out;         // [n_k][B][dim]; may be `base`
     const double2* phi;   // targets
-    const double* gexp;   // &grad_expect[n_obs + n_pobs][0][0]: [2 * n_ov][n_tsave][B]
+    const double* gexp;   // the Overlap block of grad_expect (ExpectRows, plan.hpp): [2 * n_ov][n_tsave][B]
     int n_ov, ov_batch, n_tsave, k0, B;
     uint32_t dim;
 };

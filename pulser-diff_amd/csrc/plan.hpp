@@ -105,7 +105,6 @@ struct Plan {
     uint32_t dm_rdm_am[RYDIFF_MAX_RDMS] = {0};
     int dm_rdm_m[RYDIFF_MAX_RDMS] = {0}, dm_rdm_row[RYDIFF_MAX_RDMS] = {0};
     int dm_rows() const { return n_dm_diag + n_dm_pobs + n_dm_fid + dm_purity + dm_rdm_rows; }
-    int ket_rows() const { return n_obs + n_pobs + 2 * n_ov + rdm_rows; }  // rows of expect_out in front of the density-matrix rows
     size_t dm_gfirst_bytes() const { return (dm_gfirst.size() * sizeof(int32_t) + 7) / 8 * 8; }
     size_t dm_bytes() const {
         return dm_gfirst_bytes() + (dm_groups.size() + dm_agroups.size()) * sizeof(PauliGroup) +
@@ -126,6 +125,34 @@ struct Plan {
     size_t total_fwd = 0;
     int chain_slots = 0;
     int tape_mode = 0;
+};
+
+// The row order of expect_out / grad_expect / dexpect_out ([rows][n_tsave][B] each, dexpect_out one such array per direction):
+// the blocks of the enumeration, in its order.  The only place that adds row counts up; every launch takes its pointers from at().
+struct ExpectRows {
+    // DmTrace (dm_diag rows, then the density-matrix Pauli rows) .. DmRdm: the density-matrix rows
+    enum Block { Diag, Pauli, Overlap, Rdm, DmTrace, DmFid, DmPurity, DmRdm, End };
+    size_t stride = 0;        // doubles per row: (T + 1) * B
+    int first[End + 1] = {};  // first row of each block; first[End]: all rows
+    explicit ExpectRows(const Plan& pl) : stride(size_t(pl.T + 1) * pl.B) {
+        const int count[End] = {pl.n_obs, pl.n_pobs, 2 * pl.n_ov, pl.rdm_rows, pl.n_dm_diag + pl.n_dm_pobs, pl.n_dm_fid, pl.dm_purity, pl.dm_rdm_rows};
+        for (int b = 0; b < End; ++b) first[b + 1] = first[b] + count[b];
+    }
+    int count(Block b) const { return first[b + 1] - first[b]; }
+    int total() const { return first[End]; }
+    size_t size() const { return size_t(total()) * stride; }  // doubles of one such array: the direction stride of dexpect_out
+    // doubles from the first row of block `from` to the first row of block b (a launch that is handed the density-matrix rows
+    // alone counts from DmTrace)
+    size_t offset(Block b, Block from = Diag) const { return size_t(first[b] - first[from]) * stride; }
+    // the first row of block b in the array that starts at `base`; nullptr: no such array, or no row in the blocks [b, end)
+    template <class T>
+    T* at(T* base, Block b, Block end) const {
+        return (base && first[end] > first[b]) ? base + offset(b) : nullptr;
+    }
+    template <class T>
+    T* at(T* base, Block b) const {
+        return at(base, b, Block(b + 1));
+    }
 };
 
 inline size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }

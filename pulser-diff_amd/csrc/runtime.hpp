@@ -543,11 +543,12 @@ struct PauliInject {
     char* ws = nullptr;
     hipStream_t stream = nullptr;
     const double2* gstate = nullptr;  // the caller's grad_states or nullptr
-    const double* gexp = nullptr;     // &grad_expect[n_obs][0][0], or nullptr: no Pauli observables
-    const double* ov_gexp = nullptr;  // &grad_expect[n_obs + n_pobs][0][0], or nullptr: no overlaps
+    // the blocks of grad_expect (ExpectRows::at, plan.hpp), or nullptr: no such rows
+    const double* gexp = nullptr;     // Pauli
+    const double* ov_gexp = nullptr;  // Overlap
     const double2* ov_targets = nullptr;
-    const double* rdm_gexp = nullptr; // &grad_expect[n_obs + n_pobs + 2 n_ov][0][0], or nullptr: no reduced density matrices
-    const double* dm_gexp = nullptr;  // the first density-matrix row of grad_expect, or nullptr: no density-matrix rows
+    const double* rdm_gexp = nullptr; // Rdm
+    const double* dm_gexp = nullptr;  // DmTrace .. End: the first density-matrix row
     const double* dm_diag = nullptr;  // RydProblem.dm_diag / dm_fid_targets
     const double2* dm_phi = nullptr;
     double2* buf = nullptr;           // one state (one-launch adjoints: n_tsave states)
@@ -631,10 +632,11 @@ struct ForwardCtx : SweepCtx {
     const double* obs = nullptr;
     double* expect_out = nullptr;
     bool want_exp = false;
-    double* pauli_out = nullptr;   // &expect_out[n_obs][0][0] where Pauli observables are evaluated
-    double* overlap_out = nullptr; // &expect_out[n_obs + n_pobs][0][0] where overlaps are evaluated
-    double* rdm_out = nullptr;     // &expect_out[n_obs + n_pobs + 2 n_ov][0][0] where reduced density matrices are evaluated
-    double* dm_out = nullptr;      // the first density-matrix row of expect_out where such rows are evaluated
+    // the blocks of expect_out (ExpectRows::at, plan.hpp) where such rows are evaluated
+    double* pauli_out = nullptr;   // Pauli
+    double* overlap_out = nullptr; // Overlap
+    double* rdm_out = nullptr;     // Rdm
+    double* dm_out = nullptr;      // DmTrace .. End: the first density-matrix row
     const double* shot_u = nullptr;  // RydProblem.shot_uniforms / shots_out where shots are drawn (rydiff_forward with n_shots > 0)
     uint32_t* shots_out = nullptr;
 };

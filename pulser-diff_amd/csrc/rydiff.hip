@@ -122,6 +122,21 @@ int launch_expect(const ForwardCtx& c, const double2* psi, int k) {
     return RYDIFF_OK;
 }
 
+// where the value rows of a sweep go (ExpectRows, plan.hpp), cleared: the reductions add into them
+int bind_expect_rows(ForwardCtx& c, double* expect_out) {
+    const Plan& pl = c.rt.pl;
+    const ExpectRows rows(pl);
+    c.obs = c.p->obs_diag;
+    c.expect_out = expect_out;
+    c.want_exp = expect_out && pl.n_obs > 0;
+    c.pauli_out = rows.at(expect_out, ExpectRows::Pauli);
+    c.overlap_out = rows.at(expect_out, ExpectRows::Overlap);
+    c.rdm_out = rows.at(expect_out, ExpectRows::Rdm);
+    c.dm_out = rows.at(expect_out, ExpectRows::DmTrace, ExpectRows::End);
+    if (expect_out && rows.total()) HIP_TRY(hipMemsetAsync(expect_out, 0, rows.size() * sizeof(double), c.stream));
+    return RYDIFF_OK;
+}
+
 // chained tile passes: one chain over the whole run: factor i of step k; complete outputs at step ends go to the tape
 int forward_chained(const ForwardCtx& c) {
     const Runtime& rt = c.rt;
@@ -470,19 +485,12 @@ int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi
         c.start = c.tape;
     }
     if (c.copy_out) HIP_TRY(hipMemcpyAsync(c.copy_out, psi0, pl.state_bytes, hipMemcpyDeviceToDevice, stream));
-    c.obs = p->obs_diag;
-    c.expect_out = expect_out;
-    c.want_exp = expect_out && pl.n_obs > 0;
-    c.pauli_out = (expect_out && pl.n_pobs) ? expect_out + size_t(pl.n_obs) * (pl.T + 1) * pl.B : nullptr;
-    c.overlap_out = (expect_out && pl.n_ov) ? expect_out + size_t(pl.n_obs + pl.n_pobs) * (pl.T + 1) * pl.B : nullptr;
-    c.rdm_out = (expect_out && pl.n_rdm) ? expect_out + size_t(pl.n_obs + pl.n_pobs + 2 * pl.n_ov) * (pl.T + 1) * pl.B : nullptr;
-    c.dm_out = (expect_out && pl.dm_rows()) ? expect_out + size_t(pl.ket_rows()) * (pl.T + 1) * pl.B : nullptr;
     if (pl.n_shots) {  // drawn wherever launch_observables_expect sees a sampled save point
         c.shot_u = p->shot_uniforms;
         c.shots_out = p->shots_out;
     }
-    if (c.want_exp || c.pauli_out || c.overlap_out || c.rdm_out || c.dm_out)
-        HIP_TRY(hipMemsetAsync(expect_out, 0, size_t(pl.ket_rows() + pl.dm_rows()) * (pl.T + 1) * pl.B * sizeof(double), stream));
+    rc = bind_expect_rows(c, expect_out);
+    if (rc) return rc;
     if (c.want_exp) {
         rc = launch_expect(c, c.start, 0);
         if (rc) return rc;
@@ -523,16 +531,17 @@ int rydiff_backward(const RydProblem* p, const RydPlanInfo* info, const void* st
     c.inj.gexp = have_gexp ? grad_expect : nullptr;
     c.inj.obs = p->obs_diag;
     c.inj.n_obs = have_gexp ? pl.n_obs : 0;
-    if (grad_expect && (pl.n_pobs || pl.n_ov || pl.n_rdm || pl.dm_rows())) {
+    const ExpectRows rows(pl);
+    if (grad_expect && rows.total() > rows.count(ExpectRows::Diag)) {  // some row that is not a diagonal observable's
         c.pauli.rt = &rt;
         c.pauli.ws = c.ws;
         c.pauli.stream = stream;
         c.pauli.gstate = c.inj.gstate;
-        c.pauli.gexp = pl.n_pobs ? grad_expect + size_t(pl.n_obs) * (pl.T + 1) * pl.B : nullptr;
-        c.pauli.ov_gexp = pl.n_ov ? grad_expect + size_t(pl.n_obs + pl.n_pobs) * (pl.T + 1) * pl.B : nullptr;
+        c.pauli.gexp = rows.at(grad_expect, ExpectRows::Pauli);
+        c.pauli.ov_gexp = rows.at(grad_expect, ExpectRows::Overlap);
         c.pauli.ov_targets = static_cast<const double2*>(p->overlap_targets);
-        c.pauli.rdm_gexp = pl.n_rdm ? grad_expect + size_t(pl.n_obs + pl.n_pobs + 2 * pl.n_ov) * (pl.T + 1) * pl.B : nullptr;
-        c.pauli.dm_gexp = pl.dm_rows() ? grad_expect + size_t(pl.ket_rows()) * (pl.T + 1) * pl.B : nullptr;
+        c.pauli.rdm_gexp = rows.at(grad_expect, ExpectRows::Rdm);
+        c.pauli.dm_gexp = rows.at(grad_expect, ExpectRows::DmTrace, ExpectRows::End);
         c.pauli.dm_diag = p->dm_diag;
         c.pauli.dm_phi = static_cast<const double2*>(p->dm_fid_targets);
         if (pl.n_rdm && (rc = rdm_apply_prepare())) return rc;
@@ -641,19 +650,12 @@ int tangent_sweep(const RydProblem* p, const RydPlanInfo* info, const RydTangent
     } else {
         HIP_TRY(hipMemsetAsync(vec[0] + sv, 0, size_t(Dp) * pl.state_bytes, stream));
     }
-    const size_t rows = size_t(pl.ket_rows() + pl.dm_rows());  // ket rows (the RDM block last), then the density-matrix rows
-    const size_t row = size_t(pl.T + 1) * pl.B;
-    if (rows && dexpect_out) HIP_TRY(hipMemsetAsync(dexpect_out, 0, size_t(D) * rows * row * sizeof(double), stream));
+    const ExpectRows rows(pl);
+    if (rows.total() && dexpect_out) HIP_TRY(hipMemsetAsync(dexpect_out, 0, size_t(D) * rows.size() * sizeof(double), stream));
     ForwardCtx c{{rt, &q, ws, stream, sv}};
     c.psi0 = c.start = vec[0];
-    c.obs = q.obs_diag;
-    c.expect_out = expect_out;
-    c.want_exp = expect_out && pl.n_obs > 0;
-    c.pauli_out = (expect_out && pl.n_pobs) ? expect_out + size_t(pl.n_obs) * row : nullptr;
-    c.overlap_out = (expect_out && pl.n_ov) ? expect_out + size_t(pl.n_obs + pl.n_pobs) * row : nullptr;
-    c.rdm_out = (expect_out && pl.n_rdm) ? expect_out + size_t(pl.n_obs + pl.n_pobs + 2 * pl.n_ov) * row : nullptr;
-    c.dm_out = (expect_out && pl.dm_rows()) ? expect_out + size_t(pl.ket_rows()) * row : nullptr;
-    if (expect_out && rows) HIP_TRY(hipMemsetAsync(expect_out, 0, rows * row * sizeof(double), stream));
+    rc = bind_expect_rows(c, expect_out);
+    if (rc) return rc;
     auto save_point = [&](const double2* v, int k) -> int {  // values (the existing reductions on psi) and tangents of every row
         if (c.want_exp)
             if (const int r = launch_expect(c, v, k)) return r;

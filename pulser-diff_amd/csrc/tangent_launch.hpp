@@ -172,8 +172,8 @@ int launch_factor_tangent(TangentFactorArgs& a, const Runtime& rt, char* ws, con
 int launch_expect_tangent(const ForwardCtx& c, const double2* vec, int n_dir, int k, double* dexp) {
     const Plan& pl = c.rt.pl;
     const size_t vstride = size_t(pl.B) * pl.dim;
-    const size_t row = size_t(pl.T + 1) * pl.B;
-    const size_t dstride = size_t(pl.ket_rows() + pl.dm_rows()) * row;  // (ket rows: the RDM block behind the overlap rows)
+    const ExpectRows rows(pl);
+    const size_t dstride = rows.size();
     const unsigned red_blocks = unsigned(std::min<size_t>((pl.dim + 255) / 256, 1024));
     if (pl.n_obs > 0) {
         hipLaunchKernelGGL(k_expect_tangent, dim3(red_blocks, unsigned(pl.B), unsigned(n_dir)), dim3(256), 0, c.stream, vec, vec + vstride, vstride,
@@ -186,7 +186,7 @@ int launch_expect_tangent(const ForwardCtx& c, const double2* vec, int n_dir, in
         a.dpsi = vec + vstride;
         a.vstride = vstride;
         a.t = pauli_tables(pl, c.ws);
-        a.out = dexp + size_t(pl.n_obs) * row;
+        a.out = rows.at(dexp, ExpectRows::Pauli);
         a.out_dstride = dstride;
         a.n_pobs = pl.n_pobs;
         a.n_tsave = pl.T + 1;
@@ -199,24 +199,23 @@ int launch_expect_tangent(const ForwardCtx& c, const double2* vec, int n_dir, in
     if (pl.n_ov > 0) {  // Re / Im <phi_o|dpsi_d>: k_overlap_expect as it is, on the tangent, into direction d's overlap rows
         for (int d = 0; d < n_dir; ++d) {
             ForwardCtx t = c;
-            t.overlap_out = dexp + size_t(d) * dstride + size_t(pl.n_obs + pl.n_pobs) * row;
+            t.overlap_out = rows.at(dexp + size_t(d) * dstride, ExpectRows::Overlap);
             if (const int rc = launch_overlap_expect(t, vec + size_t(1 + d) * vstride, 0, k, 1, BatchSlice{0, pl.B, false})) return rc;
         }
     }
     if (pl.n_rdm > 0)  // d rho_A = Tr_E(|dpsi_d><psi| + |psi><dpsi_d|): k_rdm_tangent, one launch per RDM over all directions
-        if (const int rc = launch_rdm_tangent(c, vec, n_dir, k, dexp + size_t(pl.n_obs + pl.n_pobs + 2 * pl.n_ov) * row, dstride)) return rc;
+        if (const int rc = launch_rdm_tangent(c, vec, n_dir, k, rows.at(dexp, ExpectRows::Rdm), dstride)) return rc;
     if (pl.dm_rows()) {
         // diagonal, Pauli and fidelity rows are linear in vec(rho): k_dm_trace / k_dm_fidelity as they are, on d rho_d, into direction
         // d's density-matrix rows; the purity |v|^2 has the tangent 2 Re <v|dv_d>
-        double* first = dexp + size_t(pl.ket_rows()) * row;
+        double* first = rows.at(dexp, ExpectRows::DmTrace, ExpectRows::End);
         for (int d = 0; d < n_dir; ++d) {
             ForwardCtx t = c;
             t.dm_out = first + size_t(d) * dstride;
             if (const int rc = launch_dm_expect(t, vec + size_t(1 + d) * vstride, 0, k, 1, BatchSlice{0, pl.B, false}, true)) return rc;
         }
         if (pl.dm_purity) {
-            double* slot = first + size_t(pl.n_dm_diag + pl.n_dm_pobs + pl.n_dm_fid) * row;
-            if (const int rc = launch_dm_purity_tangent(c, vec, n_dir, k, slot, dstride)) return rc;
+            if (const int rc = launch_dm_purity_tangent(c, vec, n_dir, k, rows.at(dexp, ExpectRows::DmPurity), dstride)) return rc;
         }
     }
     return RYDIFF_OK;

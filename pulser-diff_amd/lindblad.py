@@ -30,7 +30,7 @@ from .observables import DensityMatrixObservables, PauliObservable, Purity, Redu
 from .shots import ShotRequest
 from .simconfig import NoiseModel
 from .solver import ProblemSpec, SolverType, evolve, split_observables, tolerance_from_options
-from .utils import DiagonalObservable
+from .utils import DiagonalObservable, real_diagonal
 
 CD = torch.complex128
 MAX_ME_QUBITS = 12  # 4^12 amplitudes = 256 MiB per density matrix
@@ -156,13 +156,8 @@ def pack_dm_observables(observables: Sequence, n: int, batch: int, device, shots
             kinds.append(("pauli", len(paulis)))
             paulis.append(obs)
         else:
-            if isinstance(obs, DiagonalObservable):
-                d = obs.diag
-            elif isinstance(obs, Tensor) and obs.ndim == 2:
-                dense = obs.to_dense() if obs.is_sparse else obs
-                if not torch.equal(torch.diag(torch.diagonal(dense)), dense):
-                    raise ValueError("Only diagonal tensors can be evaluated natively; hand off-diagonal ones over as PauliObservable.")
-                d = torch.diagonal(dense).real
+            if isinstance(obs, DiagonalObservable) or (isinstance(obs, Tensor) and obs.ndim == 2):
+                d = real_diagonal(obs, "Only diagonal tensors can be evaluated natively; hand off-diagonal ones over as PauliObservable.")
             elif isinstance(obs, Tensor) and obs.ndim == 1:
                 d = obs.real if obs.is_complex() else obs
             else:

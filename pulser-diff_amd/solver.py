@@ -13,7 +13,7 @@ from __future__ import annotations
 import ctypes
 import enum
 from dataclasses import dataclass, field, replace
-from typing import Any, Optional, Sequence, Union
+from typing import Any, NamedTuple, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -257,6 +257,13 @@ class _Call:
         self.problem = p
         self.shot_buffers = None
 
+    def expect_rows(self) -> int:
+        """Rows of `expect` / `dexpect[d]`, in the order the library writes them (ExpectRows, csrc/plan.hpp): diagonal observables,
+        then the Pauli ones, then Re / Im of every overlap, then Re / Im of every RDM entry, then the density-matrix rows."""
+        p = self.problem
+        dm_rows = self.spec.dm.rows() if self.spec.dm is not None else 0
+        return p.n_obs + p.n_pauli_obs + 2 * p.n_overlaps + self.spec.rdm_rows() + dm_rows
+
     def set_shots(self, times: np.ndarray, uniforms: Tensor, out: Tensor) -> None:
         """RydProblem.n_shots / shot_*: sampled save points (host int32), uniforms (device float64) and the output (device, 32-bit),
         both (n_shot_times, batch, n_shots).  rydiff_backward is handed the same fields: the counts size the workspace."""
@@ -363,6 +370,43 @@ def _new_workspace(nbytes: int, dev) -> Tensor:
     return torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
 
 
+class _Prepared(NamedTuple):
+    """The inputs of one native call as the C ABI reads them (``_prepare``)."""
+
+    amp: Tensor
+    det: Tensor
+    u: Tensor
+    psi: Tensor
+    obs: Optional[Tensor]
+    ts_host: np.ndarray
+    batch: int
+    dim: int
+    n_t: int
+    call: _Call
+
+
+def _prepare(amp: Tensor, det: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Tensor, spec: ProblemSpec, obs: Optional[Tensor],
+             real_amp_grad: bool = False) -> _Prepared:
+    """What every entry point does first: the inputs must be on the GPU; detached, contiguous copies in the library's dtypes; their
+    shapes against the spec; the ctypes problem."""
+    for t, name in ((amp, "amp_tables"), (det, "det_tables"), (u_pairs, "u_pairs"), (psi0, "psi0")):
+        _require_cuda(t, name)
+    amp_c = amp.detach().to(torch.complex128).contiguous()
+    det_c = det.detach().to(torch.float64).contiguous()
+    u_c = u_pairs.detach().to(torch.float64).contiguous()
+    psi_c = psi0.detach().to(torch.complex128).contiguous()
+    obs_c = None if obs is None else obs.detach().to(torch.float64).contiguous()
+    ts_host = tsave.detach().to("cpu", torch.float64).numpy()
+    if psi_c.ndim != 2:
+        raise ValueError(f"psi0 must be (batch, 2^N), got shape {tuple(psi_c.shape)}")
+    batch, dim = psi_c.shape
+    if dim != 2 ** spec.n_qubits:
+        raise ValueError(f"Incompatible shape of initial state.Expected {2 ** spec.n_qubits}, got {dim}.")
+    _check_shapes(spec, amp_c, det_c, u_c, obs_c, batch, psi0.device)
+    call = _Call(spec, amp_c, det_c, u_c, ts_host, batch, obs_c, real_amp_grad=real_amp_grad)
+    return _Prepared(amp_c, det_c, u_c, psi_c, obs_c, ts_host, batch, dim, len(ts_host), call)
+
+
 class _RydbergEvolve(torch.autograd.Function):
     """states, expect = evolve(amp_tables, det_tables, u_pairs, tsave, psi0; obs_diag, spec)."""
 
@@ -371,23 +415,9 @@ class _RydbergEvolve(torch.autograd.Function):
                 obs: Optional[Tensor], spec: ProblemSpec):
         L = _native.lib()
         dev = psi0.device
-        for t, name in ((amp, "amp_tables"), (det, "det_tables"), (u_pairs, "u_pairs"), (psi0, "psi0")):
-            _require_cuda(t, name)
-        amp_c = amp.detach().to(torch.complex128).contiguous()
-        det_c = det.detach().to(torch.float64).contiguous()
-        u_c = u_pairs.detach().to(torch.float64).contiguous()
-        psi_c = psi0.detach().to(torch.complex128).contiguous()
-        obs_c = None if obs is None else obs.detach().to(torch.float64).contiguous()
-        ts_host = tsave.detach().to("cpu", torch.float64).numpy()
-        if psi_c.ndim != 2:
-            raise ValueError(f"psi0 must be (batch, 2^N), got shape {tuple(psi_c.shape)}")
-        batch, dim = psi_c.shape
-        if dim != 2 ** spec.n_qubits:
-            raise ValueError(f"Incompatible shape of initial state.Expected {2 ** spec.n_qubits}, got {dim}.")
-        _check_shapes(spec, amp_c, det_c, u_c, obs_c, batch, dev)
-        n_t = len(ts_host)
         # (real_amp_grad only matters to the adjoint launches; set here as well so that the plan's kernel_bwd names what will run)
-        call = _Call(spec, amp_c, det_c, u_c, ts_host, batch, obs_c, real_amp_grad=not amp.is_complex())
+        amp_c, det_c, u_c, psi_c, obs_c, ts_host, batch, dim, n_t, call = _prepare(amp, det, u_pairs, tsave, psi0, spec, obs,
+                                                                                   real_amp_grad=not amp.is_complex())
         # the kernel variant this call resolved to (spec field, else the CALLING thread's default): the backward pass runs on the
         # autograd engine's device thread, where that thread-local default is not visible
         ctx.kernel_variant = int(call.problem.kernel_variant)
@@ -459,10 +489,7 @@ class _RydbergEvolve(torch.autograd.Function):
                         raise
             states = (torch.empty((n_t, batch, dim), dtype=torch.complex128, device=dev) if spec.store_states
                       else torch.empty((0, batch, dim), dtype=torch.complex128, device=dev))
-            # diagonal observables first, then the Pauli ones, then Re / Im of every overlap, then Re / Im of every RDM entry
-            # then the density-matrix rows
-            n_obs = (call.problem.n_obs + call.problem.n_pauli_obs + 2 * call.problem.n_overlaps + spec.rdm_rows()
-                     + (spec.dm.rows() if spec.dm is not None else 0))
+            n_obs = call.expect_rows()
             expect = torch.empty((n_obs, n_t, batch), dtype=torch.float64, device=dev)
             _native.check(L.rydiff_forward(ctypes.byref(call.problem), ctypes.byref(info), _ptr(psi_c),
                                            _ptr(states) if spec.store_states else None,
@@ -699,14 +726,66 @@ def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverTyp
                        dict(spec.options.get("_last_stats", {})), overlaps, spec.shots, rdms)
 
 
-def _tangent_chunk(t: Optional[Tensor], d0: int, d1: int, shape: tuple, dtype: torch.dtype, name: str, dev) -> Optional[Tensor]:
-    """Directions d0:d1 of one tangent input as the contiguous device buffer the C ABI reads (None stays None)."""
+def _tangent_take(t: Optional[Tensor], sel, shape: tuple, dtype: torch.dtype, name: str, dev) -> Optional[Tensor]:
+    """The directions ``sel`` (a slice or a list of indices) of one tangent input as the contiguous device buffer the C ABI reads
+    (None stays None)."""
     if t is None:
         return None
     _require_cuda(t, name)
     if tuple(t.shape[1:]) != tuple(shape):
         raise ValueError(f"{name} must have shape (n_dir, {', '.join(str(s) for s in shape)}), got {tuple(t.shape)}")
-    return t[d0:d1].detach().to(dev, dtype).contiguous()
+    return t[sel].detach().to(dev, dtype).contiguous()
+
+
+def _tangent_buffers(sel, pre: _Prepared, d_amp, d_det, d_u, d_psi0, dev) -> tuple:
+    """(d_amp, d_det, d_u, d_psi0)[sel] for RydTangent; None: not given, or the tangent of an input this problem does not have."""
+    return (_tangent_take(d_amp, sel, pre.amp.shape, torch.complex128, "d_amp", dev) if pre.amp.numel() else None,
+            _tangent_take(d_det, sel, pre.det.shape, torch.float64, "d_det", dev) if pre.det.numel() else None,
+            _tangent_take(d_u, sel, pre.u.shape, torch.float64, "d_u", dev) if pre.u.numel() else None,
+            _tangent_take(d_psi0, sel, pre.psi.shape, torch.complex128, "d_psi0", dev))
+
+
+def _sweep_prepare(name: str, amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag, d_amp, d_det, d_u, d_psi0):
+    """What ``evolve_tangent`` and ``evolve_geometry`` (`name`) share behind their refusals: the number of directions, the inputs of
+    the call, its row count."""
+    given = [t for t in (d_amp, d_det, d_u, d_psi0) if t is not None]
+    if not given:
+        raise ValueError(f"{name} needs at least one of d_amp, d_det, d_u, d_psi0")
+    n_dir = int(given[0].shape[0])
+    if n_dir < 1 or any(int(t.shape[0]) != n_dir for t in given):
+        raise ValueError("d_amp, d_det, d_u, d_psi0 must agree on the number of directions (their first axis), at least one")
+    pre = _prepare(amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag)
+    pre.call.problem.kernel_variant = 0  # the tangent sweep has one kernel family
+    return n_dir, pre, pre.call.expect_rows()
+
+
+def _sweep_plan(L, p, dev) -> tuple:
+    """(stream, plan, plan scratch) of the sweeps of one call; inside ``torch.cuda.device(dev)``."""
+    stream = _stream_ptr(dev)
+    scratch = _new_workspace(_native.PLAN_SCRATCH_BYTES, dev)
+    info = _native.RydPlanInfo()
+    _native.check(L.rydiff_plan(ctypes.byref(p), 0, 0, _ptr(scratch), stream, ctypes.byref(info)))
+    return stream, info, scratch
+
+
+def _sweep_tangent(n_dir: int, bufs: tuple, flags: int) -> "_native.RydTangent":
+    tg = _native.RydTangent()
+    tg.n_dir = n_dir
+    tg.d_amp, tg.d_det, tg.d_u, tg.d_psi0 = (None if b is None else b.data_ptr() for b in bufs)
+    tg.flags = int(flags)
+    return tg
+
+
+def _sweep_workspace(size_fn, size_name: str, sweep, p, info, tg, workspace: Optional[Tensor], dev) -> Tensor:
+    """The workspace of one sweep: `workspace` where it is large enough for what ``size_fn`` asks, else a new one.  ``sweep(ws)``
+    makes the call on the workspace `ws`."""
+    need = size_fn(ctypes.byref(p), ctypes.byref(info), tg.n_dir, tg.flags)
+    if need == 0:  # refused: the sweep's own (host-only) validation reports why, with its error code
+        _native.check(sweep(None))
+        raise RuntimeError(f"{size_name} returned 0: " + _native.last_error())
+    if workspace is None or workspace.numel() < need:
+        workspace = _new_workspace(need, dev)
+    return workspace
 
 
 def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Tensor, spec: ProblemSpec,
@@ -737,80 +816,38 @@ def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsav
         raise NotImplementedError("evolve_tangent draws no measurement shots (rydiff_forward_tangent: RYDIFF_ENOTIMPL); request them from evolve")
     L = _native.lib()
     dev = psi0.device
-    for t, name in ((amp_tables, "amp_tables"), (det_tables, "det_tables"), (u_pairs, "u_pairs"), (psi0, "psi0")):
-        _require_cuda(t, name)
-    given = [t for t in (d_amp, d_det, d_u, d_psi0) if t is not None]
-    if not given:
-        raise ValueError("evolve_tangent needs at least one of d_amp, d_det, d_u, d_psi0")
-    n_dir = int(given[0].shape[0])
-    if n_dir < 1 or any(int(t.shape[0]) != n_dir for t in given):
-        raise ValueError("d_amp, d_det, d_u, d_psi0 must agree on the number of directions (their first axis), at least one")
-    amp_c = amp_tables.detach().to(torch.complex128).contiguous()
-    det_c = det_tables.detach().to(torch.float64).contiguous()
-    u_c = u_pairs.detach().to(torch.float64).contiguous()
-    psi_c = psi0.detach().to(torch.complex128).contiguous()
-    obs_c = None if obs_diag is None else obs_diag.detach().to(torch.float64).contiguous()
-    ts_host = tsave.detach().to("cpu", torch.float64).numpy()
-    if psi_c.ndim != 2:
-        raise ValueError(f"psi0 must be (batch, 2^N), got shape {tuple(psi_c.shape)}")
-    batch, dim = psi_c.shape
-    if dim != 2 ** spec.n_qubits:
-        raise ValueError(f"Incompatible shape of initial state.Expected {2 ** spec.n_qubits}, got {dim}.")
-    _check_shapes(spec, amp_c, det_c, u_c, obs_c, batch, dev)
-    n_t = len(ts_host)
-    call = _Call(spec, amp_c, det_c, u_c, ts_host, batch, obs_c)
-    call.problem.kernel_variant = 0  # the tangent sweep has one kernel family
-    p = call.problem
-    rows = p.n_obs + p.n_pauli_obs + 2 * p.n_overlaps + spec.rdm_rows() + (spec.dm.rows() if spec.dm is not None else 0)
+    n_dir, pre, rows = _sweep_prepare("evolve_tangent", amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag,
+                                      d_amp, d_det, d_u, d_psi0)
+    p, n_t, batch = pre.call.problem, pre.n_t, pre.batch
     expect = torch.empty((rows, n_t, batch), dtype=torch.float64, device=dev)
     dexpect = torch.empty((n_dir, rows, n_t, batch), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        scratch = _new_workspace(_native.PLAN_SCRATCH_BYTES, dev)
-        info = _native.RydPlanInfo()
-        _native.check(L.rydiff_plan(ctypes.byref(p), 0, 0, _ptr(scratch), stream, ctypes.byref(info)))
+        stream, info, _scratch = _sweep_plan(L, p, dev)
         workspace = None
         values_done = False
         for d0 in range(0, n_dir, _native.MAX_TANGENTS):
             d1 = min(n_dir, d0 + _native.MAX_TANGENTS)
-            bufs = (_tangent_chunk(d_amp, d0, d1, amp_c.shape, torch.complex128, "d_amp", dev) if amp_c.numel() else None,
-                    _tangent_chunk(d_det, d0, d1, det_c.shape, torch.float64, "d_det", dev) if det_c.numel() else None,
-                    _tangent_chunk(d_u, d0, d1, u_c.shape, torch.float64, "d_u", dev) if u_c.numel() else None,
-                    _tangent_chunk(d_psi0, d0, d1, psi_c.shape, torch.complex128, "d_psi0", dev))
+            bufs = _tangent_buffers(slice(d0, d1), pre, d_amp, d_det, d_u, d_psi0, dev)
             out = dexpect[d0:d1]
             if all(b is None for b in bufs):  # tangents of inputs this problem does not have: the derivative is zero
                 out.zero_()
                 continue
-            tg = _native.RydTangent()
-            tg.n_dir = d1 - d0
-            tg.d_amp, tg.d_det, tg.d_u, tg.d_psi0 = (None if b is None else b.data_ptr() for b in bufs)
-            tg.flags = int(flags)
-            need = L.rydiff_tangent_workspace_bytes_flags(ctypes.byref(p), ctypes.byref(info), tg.n_dir, tg.flags)
-            if need == 0:  # refused: the sweep's own (host-only) validation reports why, with its error code
-                _native.check(L.rydiff_forward_tangent(ctypes.byref(p), ctypes.byref(info), ctypes.byref(tg), _ptr(psi_c), None, _ptr(out),
-                                                       None, 0, stream))
-                raise RuntimeError("rydiff_tangent_workspace_bytes returned 0: " + _native.last_error())
-            if workspace is None or workspace.numel() < need:
-                workspace = _new_workspace(need, dev)
+            tg = _sweep_tangent(d1 - d0, bufs, flags)
             want_values = rows > 0 and not values_done
+
+            def sweep(ws):
+                return L.rydiff_forward_tangent(ctypes.byref(p), ctypes.byref(info), ctypes.byref(tg), _ptr(pre.psi),
+                                                _ptr(expect) if want_values else None, _ptr(out), _ptr(ws),
+                                                0 if ws is None else ws.numel(), stream)
+
+            workspace = _sweep_workspace(L.rydiff_tangent_workspace_bytes_flags, "rydiff_tangent_workspace_bytes", sweep, p, info, tg,
+                                         workspace, dev)
             values_done = True
-            _native.check(L.rydiff_forward_tangent(ctypes.byref(p), ctypes.byref(info), ctypes.byref(tg), _ptr(psi_c),
-                                                   _ptr(expect) if want_values else None, _ptr(out), _ptr(workspace),
-                                                   workspace.numel(), stream))
+            _native.check(sweep(workspace))
     if rows and not values_done:  # no chunk reached the library (tangents of inputs the problem does not have)
         with torch.no_grad():
-            expect = evolve(amp_c, det_c, u_c, tsave.detach(), psi_c, replace(spec, store_states=False), obs_c)[1]
+            expect = evolve(pre.amp, pre.det, pre.u, tsave.detach(), pre.psi, replace(spec, store_states=False), pre.obs)[1]
     return expect, dexpect
-
-
-def _tangent_pick(t: Optional[Tensor], idx: list, shape: tuple, dtype: torch.dtype, name: str, dev) -> Optional[Tensor]:
-    """The directions ``idx`` of one tangent input as the contiguous device buffer the C ABI reads (None stays None)."""
-    if t is None:
-        return None
-    _require_cuda(t, name)
-    if tuple(t.shape[1:]) != tuple(shape):
-        raise ValueError(f"{name} must have shape (n_dir, {', '.join(str(s) for s in shape)}), got {tuple(t.shape)}")
-    return t[idx].detach().to(dev, dtype).contiguous()
 
 
 def evolve_geometry(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Tensor, spec: ProblemSpec,
@@ -837,71 +874,39 @@ def evolve_geometry(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsa
         raise NotImplementedError("evolve_geometry draws no measurement shots (rydiff_forward_geometry: RYDIFF_ENOTIMPL); request them from evolve")
     L = _native.lib()
     dev = psi0.device
-    for t, name in ((amp_tables, "amp_tables"), (det_tables, "det_tables"), (u_pairs, "u_pairs"), (psi0, "psi0")):
-        _require_cuda(t, name)
-    given = [t for t in (d_amp, d_det, d_u, d_psi0) if t is not None]
-    if not given:
-        raise ValueError("evolve_geometry needs at least one of d_amp, d_det, d_u, d_psi0")
-    n_dir = int(given[0].shape[0])
-    if n_dir < 1 or any(int(t.shape[0]) != n_dir for t in given):
-        raise ValueError("d_amp, d_det, d_u, d_psi0 must agree on the number of directions (their first axis), at least one")
-    amp_c = amp_tables.detach().to(torch.complex128).contiguous()
-    det_c = det_tables.detach().to(torch.float64).contiguous()
-    u_c = u_pairs.detach().to(torch.float64).contiguous()
-    psi_c = psi0.detach().to(torch.complex128).contiguous()
-    obs_c = None if obs_diag is None else obs_diag.detach().to(torch.float64).contiguous()
-    ts_host = tsave.detach().to("cpu", torch.float64).numpy()
-    if psi_c.ndim != 2:
-        raise ValueError(f"psi0 must be (batch, 2^N), got shape {tuple(psi_c.shape)}")
-    batch, dim = psi_c.shape
-    if dim != 2 ** spec.n_qubits:
-        raise ValueError(f"Incompatible shape of initial state.Expected {2 ** spec.n_qubits}, got {dim}.")
-    _check_shapes(spec, amp_c, det_c, u_c, obs_c, batch, dev)
-    n_t = len(ts_host)
-    call = _Call(spec, amp_c, det_c, u_c, ts_host, batch, obs_c)
-    call.problem.kernel_variant = 0  # the tangent sweep has one kernel family
-    p = call.problem
-    rows = p.n_obs + p.n_pauli_obs + 2 * p.n_overlaps + spec.rdm_rows()
+    n_dir, pre, rows = _sweep_prepare("evolve_geometry", amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag,
+                                      d_amp, d_det, d_u, d_psi0)
+    p, n_t, batch = pre.call.problem, pre.n_t, pre.batch
     expect = torch.empty((rows, n_t, batch), dtype=torch.float64, device=dev)
     dexpect = torch.empty((n_dir, rows, n_t, batch), dtype=torch.float64, device=dev)
     gram = torch.empty((n_t, batch, 1 + n_dir, 1 + n_dir), dtype=torch.complex128, device=dev)
     # tangents of inputs this problem does not have are zero: where nothing else is given the tangent states are identically zero,
     # and ONE sweep with a single zero direction delivers <psi|psi> and the values; every other entry is an exact zero
-    live = ((d_amp is not None and amp_c.numel() > 0) or (d_det is not None and det_c.numel() > 0)
-            or (d_u is not None and u_c.numel() > 0) or d_psi0 is not None)
+    live = ((d_amp is not None and pre.amp.numel() > 0) or (d_det is not None and pre.det.numel() > 0)
+            or (d_u is not None and pre.u.numel() > 0) or d_psi0 is not None)
     sweeps = geometry_sweeps(n_dir) if live else [[0]]
     with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        scratch = _new_workspace(_native.PLAN_SCRATCH_BYTES, dev)
-        info = _native.RydPlanInfo()
-        _native.check(L.rydiff_plan(ctypes.byref(p), 0, 0, _ptr(scratch), stream, ctypes.byref(info)))
+        stream, info, _scratch = _sweep_plan(L, p, dev)
         workspace = None
         done = torch.zeros(n_dir, dtype=torch.bool)
         for s, idx in enumerate(sweeps):
             if live:
-                bufs = (_tangent_pick(d_amp, idx, amp_c.shape, torch.complex128, "d_amp", dev) if amp_c.numel() else None,
-                        _tangent_pick(d_det, idx, det_c.shape, torch.float64, "d_det", dev) if det_c.numel() else None,
-                        _tangent_pick(d_u, idx, u_c.shape, torch.float64, "d_u", dev) if u_c.numel() else None,
-                        _tangent_pick(d_psi0, idx, psi_c.shape, torch.complex128, "d_psi0", dev))
+                bufs = _tangent_buffers(idx, pre, d_amp, d_det, d_u, d_psi0, dev)
             else:
-                bufs = (None, None, None, torch.zeros((1,) + tuple(psi_c.shape), dtype=torch.complex128, device=dev))
-            tg = _native.RydTangent()
-            tg.n_dir = len(idx)
-            tg.d_amp, tg.d_det, tg.d_u, tg.d_psi0 = (None if b is None else b.data_ptr() for b in bufs)
-            tg.flags = int(flags)
+                bufs = (None, None, None, torch.zeros((1,) + tuple(pre.psi.shape), dtype=torch.complex128, device=dev))
+            tg = _sweep_tangent(len(idx), bufs, flags)
             g = torch.empty((n_t, batch, 1 + len(idx), 1 + len(idx)), dtype=torch.complex128, device=dev)
             want_rows = rows > 0 and not bool(done[idx].all())  # a later sweep of directions whose row tangents are all there skips them
             out = torch.empty((len(idx), rows, n_t, batch), dtype=torch.float64, device=dev) if want_rows else None
-            need = L.rydiff_geometry_workspace_bytes_flags(ctypes.byref(p), ctypes.byref(info), tg.n_dir, tg.flags)
-            if need == 0:  # refused: the sweep's own (host-only) validation reports why, with its error code
-                _native.check(L.rydiff_forward_geometry(ctypes.byref(p), ctypes.byref(info), ctypes.byref(tg), _ptr(psi_c), None, None,
-                                                        _ptr(g), None, 0, stream))
-                raise RuntimeError("rydiff_geometry_workspace_bytes returned 0: " + _native.last_error())
-            if workspace is None or workspace.numel() < need:
-                workspace = _new_workspace(need, dev)
-            _native.check(L.rydiff_forward_geometry(ctypes.byref(p), ctypes.byref(info), ctypes.byref(tg), _ptr(psi_c),
-                                                    _ptr(expect) if (rows > 0 and s == 0) else None, None if out is None else _ptr(out),
-                                                    _ptr(g), _ptr(workspace), workspace.numel(), stream))
+
+            def sweep(ws):
+                return L.rydiff_forward_geometry(ctypes.byref(p), ctypes.byref(info), ctypes.byref(tg), _ptr(pre.psi),
+                                                 _ptr(expect) if (rows > 0 and s == 0) else None, _ptr(out), _ptr(g), _ptr(ws),
+                                                 0 if ws is None else ws.numel(), stream)
+
+            workspace = _sweep_workspace(L.rydiff_geometry_workspace_bytes_flags, "rydiff_geometry_workspace_bytes", sweep, p, info, tg,
+                                         workspace, dev)
+            _native.check(sweep(workspace))
             if not live:
                 gram.zero_()
                 gram[:, :, 0, 0] = g[:, :, 0, 0]

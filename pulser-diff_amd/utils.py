@@ -42,6 +42,17 @@ class DiagonalObservable:
         return torch.diag(self.diag.to(torch.complex128))
 
 
+def real_diagonal(obs, message: str) -> Tensor:
+    """The real diagonal of a ``DiagonalObservable`` or of a diagonal (dim, dim) tensor, dense or sparse; ``ValueError(message)``
+    where the tensor has an off-diagonal entry."""
+    if isinstance(obs, DiagonalObservable):
+        return obs.diag
+    dense = obs.to_dense() if obs.is_sparse else obs
+    if not torch.equal(torch.diag(torch.diagonal(dense)), dense):
+        raise ValueError(message)
+    return torch.diagonal(dense).real
+
+
 def kron(*args: Tensor) -> Tensor:
     """utils.py:12-44: Kronecker product; sparse in -> sparse COO out (index arithmetic, no Python loops)."""
     if not all(t.is_sparse for t in args):
