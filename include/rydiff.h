@@ -223,6 +223,23 @@ typedef struct RydProblem {
     const double* shot_uniforms;  /* DEVICE float64 [n_shot_times][B][n_shots], in any order */
     uint32_t* shots_out;          /* DEVICE [n_shot_times][B][n_shots]: amplitude indices */
 
+    /* OCCUPATION CORRELATIONS (bit moments): with p[y] = |psi_b(t_k)[y]|^2 and y_q the index bit of qubit q (qubit q <-> index bit
+     * N-1-q), evaluated at every tsave from ONE read of the state and differentiated by rydiff_backward:
+     *   S = sum_y p[y],   B_q = sum_y p[y] y_q  (q = 0..N-1),   B_qr = sum_y p[y] y_q y_r  (0 <= q < r < N)
+     * bit_moments = 1 adds 1 + N + N(N-1)/2 rows to expect_out / grad_expect BEHIND the reduced-density-matrix rows (the last
+     * block of a ket's rows): S, then B_q in ascending q, then B_qr in lexicographic (q, r) — pair (q, r) at offset
+     * 1 + N + q(2N-q-1)/2 + (r-q-1).  S is a row of its own because the state need not be normalised.  Every sum is formed in
+     * float64 in one fixed order (no atomics): two calls on the same input give bit-identical rows.  rydiff_backward: with g the
+     * rows of grad_expect at (k, b), the cotangent added to psi_b(t_k) is 2 q(y) psi[y], q(y) = g_S + sum_q g_q y_q +
+     * sum_{q<r} g_qr y_q y_r, formed per save point in the workspace buffer of the Pauli / overlap / RDM cotangents (after them)
+     * and injected through the grad_states route.  Honoured by rydiff_forward in every kernel family and with every tape mode
+     * next to every other ket row, shots, pair terms, conditioned and ones-counting terms (plain bits at this level).  Beyond 12
+     * qubits rydiff_plan adds 79 doubles per 2^12 amplitudes and trajectory to workspace_bytes.  RYDIFF_EINVAL: a value other
+     * than 0 or 1.  RYDIFF_ENOTIMPL: together with shard_bits > 0, with dm_atoms > 0, and in rydiff_forward_tangent /
+     * rydiff_forward_geometry.  Traffic per state: one read; nothing of size 2^N is written.  bit_moments = 0: nothing changes.
+     * (The field sits in front of n_rdms, so every later block keeps its place relative to its neighbours.) */
+    int32_t bit_moments;          /* 0: off; 1: all qubits */
+
     /* REDUCED DENSITY MATRICES: the state of a subsystem A of m distinct qubits (1 <= m <= RYDIFF_MAX_RDM_QUBITS), the rest E traced out,
      * evaluated at every tsave behind the overlap rows and differentiated by rydiff_backward:
      *   rho_o[a][a'] = sum_e psi[idx(a, e)] conj(psi[idx(a', e)])          (= Tr_E |psi><psi|, not normalised by the library)
@@ -400,8 +417,9 @@ int rydiff_plan(const RydProblem* p, int need_tape, int need_backward, void* scr
  *   states_out  DEVICE complex128 [n_tsave][B][2^N], or NULL (trajectory kept in the workspace tape if need_tape).
  *               With need_tape = 2 / 3 AND states_out the factor outputs go to the (granted) workspace tape and the states at the
  *               save points are copied out of it — stored states plus a later gradient without (or with less) recomputation.
- *   expect_out  DEVICE float64 [n_obs + n_pauli_obs + 2 * n_overlaps + 2 * sum_o 4^{m_o} + dm rows][n_tsave][B] (diagonal observables
- *               first, then the Pauli ones, then Re / Im of every overlap, then Re / Im of every reduced-density-matrix entry, then the
+ *   expect_out  DEVICE float64 [n_obs + n_pauli_obs + 2 * n_overlaps + 2 * sum_o 4^{m_o} + moment rows + dm rows][n_tsave][B] (diagonal observables
+ *               first, then the Pauli ones, then Re / Im of every overlap, then Re / Im of every reduced-density-matrix entry, then with
+ *               bit_moments the 1 + N + N(N-1)/2 moment rows S, B_q, B_qr, then the
  *               density-matrix rows n_dm_diag + n_dm_pauli_obs + n_dm_fid + dm_purity + 2 * sum_o 4^{m_o} over dm_rdm_masks), or NULL
  * With RydProblem.n_shots > 0 the measurement shots of the save points in shot_times go to RydProblem.shots_out on the way. */
 int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi0, void* states_out, double* expect_out,
@@ -414,7 +432,7 @@ int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi
  *   states       DEVICE: the states_out of the forward call, or NULL to use the workspace tape (with need_tape = 2 / 3 the
  *                granted workspace tape is used even when states is given)
  *   grad_states  DEVICE complex128 [n_tsave][B][2^N] or NULL
- *   grad_expect  DEVICE float64 [n_obs + n_pauli_obs + 2 * n_overlaps + 2 * sum_o 4^{m_o} + dm rows][n_tsave][B] or NULL
+ *   grad_expect  DEVICE float64 [n_obs + n_pauli_obs + 2 * n_overlaps + 2 * sum_o 4^{m_o} + moment rows + dm rows][n_tsave][B] or NULL
  *   g_amp        DEVICE complex128 [coeff_batch][n_amp_terms][n_samples] or NULL   (overwritten)
  *   g_det        DEVICE float64    [coeff_batch][n_det_terms][n_samples] or NULL   (overwritten)
  *   g_u          DEVICE float64 [N(N-1)/2] or NULL  (dist_grad, backend.py:456-460 / hamiltonian.py:341-344)

@@ -10,10 +10,10 @@ from pulser_diff_amd.model import QuantumModel  # noqa: F401
 from pulser_diff_amd.simconfig import SimConfig  # noqa: F401
 from pulser_diff_amd.solver import SolverType  # noqa: F401
 from pulser_diff_amd.utils import DiagonalObservable, logarithmic_negativity, negativity, partial_transpose  # noqa: F401
-from pulser_diff_amd.observables import PauliObservable, Purity, ReducedDensityMatrix, StateOverlap  # noqa: F401
+from pulser_diff_amd.observables import OccupationCorrelations, PauliObservable, Purity, ReducedDensityMatrix, StateOverlap  # noqa: F401
 from pulser_diff_amd.geometry import (QuantumGeometry, berry_curvature, quantum_fisher_information,  # noqa: F401
                                       quantum_geometric_tensor)
 
-__all__ = ["TorchEmulator", "SimConfig", "SolverType", "DiagonalObservable", "PauliObservable", "StateOverlap", "ReducedDensityMatrix", "Purity", "QuantumModel",
+__all__ = ["TorchEmulator", "SimConfig", "SolverType", "DiagonalObservable", "PauliObservable", "StateOverlap", "ReducedDensityMatrix", "Purity", "OccupationCorrelations", "QuantumModel",
            "QuantumGeometry", "quantum_geometric_tensor", "quantum_fisher_information", "berry_curvature",
            "partial_transpose", "negativity", "logarithmic_negativity"]

@@ -80,6 +80,7 @@ class RydProblem(ctypes.Structure):
         ("shot_times", ctypes.c_void_p),
         ("shot_uniforms", ctypes.c_void_p),
         ("shots_out", ctypes.c_void_p),
+        ("bit_moments", ctypes.c_int32),
         ("n_rdms", ctypes.c_int32),
         ("rdm_masks", ctypes.c_void_p),
         ("n_dm_rdms", ctypes.c_int32),

@@ -35,7 +35,7 @@ from .simconfig import SimConfig
 from .simresults import CoherentResults, NoisyResults, SimulationResults
 from .solver import (ProblemSpec, SolverType, evolve, evolve_geometry, evolve_tangent, sesolve, split_observables,
                      tolerance_from_options)
-from .observables import PauliObservable, Purity, ReducedDensityMatrix, StateOverlap, pack_overlaps
+from .observables import OccupationCorrelations, PauliObservable, Purity, ReducedDensityMatrix, StateOverlap, pack_overlaps
 from .geometry import QuantumGeometry, quantum_geometric_tensor
 from .shots import MAX_SHOTS, ShotRequest, indices_to_bitstrings
 from .utils import DiagonalObservable, real_diagonal
@@ -374,7 +374,17 @@ class TorchEmulator:
         dev = self._compute_device
         ham = self._hamiltonian
         obs_tensors, obs_objs, pauli_objs, overlap_objs, rdm_objs, purity_objs = [], [], [], [], [], []
+        moments = False
         for obs in observables or []:
+            if isinstance(obs, OccupationCorrelations):
+                if solver == SolverType.DP5_ME:
+                    raise NotImplementedError("OccupationCorrelations is evaluated natively on kets only: in a master-equation run "
+                                              "the moments of diag(rho) are a follow-up; hand run() DiagonalObservable projectors.")
+                if ham.basis_name == "all":
+                    raise NotImplementedError("OccupationCorrelations is not available in the three-level all-basis (an atom is "
+                                              "two qubits there); reduce the stored states instead.")
+                moments = True
+                continue
             if isinstance(obs, Purity):
                 if solver != SolverType.DP5_ME:
                     raise NotImplementedError("Purity is evaluated natively in master-equation runs only (a ket has purity "
@@ -402,8 +412,8 @@ class TorchEmulator:
                 pauli_objs.append(obs)
                 continue
             if not isinstance(obs, DiagonalObservable) and not (isinstance(obs, Tensor) and obs.ndim == 2):
-                raise TypeError("observables must be DiagonalObservable / PauliObservable / StateOverlap / ReducedDensityMatrix / Purity "
-                                "objects or diagonal (dim, dim) tensors")
+                raise TypeError("observables must be DiagonalObservable / PauliObservable / StateOverlap / ReducedDensityMatrix / Purity / "
+                                "OccupationCorrelations objects or diagonal (dim, dim) tensors")
             diag = real_diagonal(obs, "Only diagonal observables can be evaluated natively; use results.expect on the states.")
             obs_tensors.append(diag.to(dev, torch.float64))
             obs_objs.append(obs)
@@ -456,14 +466,15 @@ class TorchEmulator:
                                        native_purity=res.expect[n_ex + n_ov] if purity_objs else None, native_shots=res.shots,
                                        native_rdms=res.rdms if rdm_objs else None, rdm_observables=rdm_objs)
             result = sesolve(ham, psi0.to(dev), self._eval_times_array, solver=solver, options=options, obs_diag=obs_diag,
-                             store_states=store_states, pauli_obs=pauli_objs, overlap_obs=overlap_objs, shots=shots, rdm_obs=rdm_objs)
+                             store_states=store_states, pauli_obs=pauli_objs, overlap_obs=overlap_objs, shots=shots, rdm_obs=rdm_objs,
+                             moments=moments)
             states_tbd = result.states.permute(0, 2, 1) if result.states.numel() else result.states
             return CoherentResults(states_tbd, ham._size, ham.basis_name, self._eval_times_array, self._meas_basis,
                                    meas_errors, atom_order=tuple(ham._qdict),
                                    native_expect=result.expect if (obs_diag is not None or pauli_objs) else None,
                                    native_observables=obs_objs + pauli_objs, stats=result.stats,
                                    native_overlaps=result.overlaps, overlap_observables=overlap_objs, native_shots=result.shots,
-                                   native_rdms=result.rdms, rdm_observables=rdm_objs)
+                                   native_rdms=result.rdms, rdm_observables=rdm_objs, native_moments=result.moments)
 
         # does the noise ask for averaging over several runs?  (backend.py:531-569)
         bad_atom_configs = None
@@ -484,6 +495,8 @@ class TorchEmulator:
             raise NotImplementedError("ReducedDensityMatrix observables stay refused in noisy runs that average over realisations.")
         if purity_objs:
             raise NotImplementedError("Purity observables stay refused in noisy runs that average over realisations.")
+        if moments:
+            raise NotImplementedError("OccupationCorrelations stays refused in noisy runs that average over realisations.")
         if shots is not None:
             raise NotImplementedError("A ShotRequest belongs to one coherent run; noisy runs that average over realisations return "
                                       "their measurements as NoisyResults (native_shots=True draws them natively).")
@@ -619,6 +632,9 @@ class TorchEmulator:
         observables = list(observables)
         full = ham.dim ** ham._size
         for obs in observables:
+            if isinstance(obs, OccupationCorrelations):
+                raise NotImplementedError("run_sensitivities does not take OccupationCorrelations (the tangent sweep evaluates no "
+                                          "occupation correlations); differentiate results.occupation_correlations through run().")
             if isinstance(obs, ReducedDensityMatrix):
                 if solver != SolverType.DP5_ME:
                     raise NotImplementedError("run_sensitivities does not take ReducedDensityMatrix observables (its rows are real "
@@ -714,6 +730,9 @@ class TorchEmulator:
             all_basis="run_rdm_sensitivities is not available in the three-level all-basis: the native tangent sweep "
                       "takes no conditioned flips / ones-counting terms, and ReducedDensityMatrix is a qubit observable.")
         ham, dev = self._hamiltonian, self._compute_device
+        if any(isinstance(o, OccupationCorrelations) for o in subsystems):
+            raise NotImplementedError("run_rdm_sensitivities does not take OccupationCorrelations (the tangent sweep evaluates no "
+                                      "occupation correlations); differentiate results.occupation_correlations through run().")
         rdm_objs = [o if isinstance(o, ReducedDensityMatrix) else ReducedDensityMatrix(o) for o in subsystems]
         if not 1 <= len(rdm_objs) <= _native.MAX_RDMS:
             raise ValueError(f"run_rdm_sensitivities takes 1 to {_native.MAX_RDMS} subsystems per call, got {len(rdm_objs)}")
@@ -768,6 +787,9 @@ class TorchEmulator:
         observables = list(observables)
         full = ham.dim ** ham._size
         for obs in observables:
+            if isinstance(obs, OccupationCorrelations):
+                raise NotImplementedError("run_quantum_fisher does not take OccupationCorrelations (the geometry sweep evaluates no "
+                                          "occupation correlations); request them from run().")
             if not isinstance(obs, (DiagonalObservable, PauliObservable, StateOverlap)) and not (isinstance(obs, Tensor) and obs.ndim == 2):
                 raise TypeError("observables must be DiagonalObservable / PauliObservable / StateOverlap objects or diagonal (dim, dim) tensors")
             if tuple(obs.shape) != (full, full):

@@ -89,6 +89,12 @@ struct Plan {
     int n_rdm = 0, rdm_rows = 0;
     uint32_t rdm_am[RYDIFF_MAX_RDMS] = {0};
     int rdm_m[RYDIFF_MAX_RDMS] = {0}, rdm_row[RYDIFF_MAX_RDMS] = {0};
+    // occupation correlations (moments_kernels.hpp): S, B_q, B_qr of |psi|^2 over the index bits, 1 + N + N(N-1)/2 rows behind the RDM
+    // rows; past one tile of 2^12 amplitudes the tile records of one save point go through the workspace: [B][79][tiles] doubles
+    int moments = 0;
+    int moment_rows() const { return moments ? 1 + N + N * (N - 1) / 2 : 0; }
+    size_t moment_tiles() const { return dim >> 12; }  // (kMomTileBits)
+    size_t off_moments = 0;
     // measurement shots (shots_kernels.hpp): the sampled save points; scratch = chunk sums and their prefix, [B][shot_chunks()] doubles each
     int n_shots = 0;
     std::vector<int32_t> shot_times;
@@ -130,12 +136,13 @@ struct Plan {
 // The row order of expect_out / grad_expect / dexpect_out ([rows][n_tsave][B] each, dexpect_out one such array per direction):
 // the blocks of the enumeration, in its order.  The only place that adds row counts up; every launch takes its pointers from at().
 struct ExpectRows {
+    // Moments: S, B_q, B_qr of the occupation correlations (empty unless bit_moments), the last block of a ket's rows;
     // DmTrace (dm_diag rows, then the density-matrix Pauli rows) .. DmRdm: the density-matrix rows
-    enum Block { Diag, Pauli, Overlap, Rdm, DmTrace, DmFid, DmPurity, DmRdm, End };
+    enum Block { Diag, Pauli, Overlap, Rdm, Moments, DmTrace, DmFid, DmPurity, DmRdm, End };
     size_t stride = 0;        // doubles per row: (T + 1) * B
     int first[End + 1] = {};  // first row of each block; first[End]: all rows
     explicit ExpectRows(const Plan& pl) : stride(size_t(pl.T + 1) * pl.B) {
-        const int count[End] = {pl.n_obs, pl.n_pobs, 2 * pl.n_ov, pl.rdm_rows, pl.n_dm_diag + pl.n_dm_pobs, pl.n_dm_fid, pl.dm_purity, pl.dm_rdm_rows};
+        const int count[End] = {pl.n_obs, pl.n_pobs, 2 * pl.n_ov, pl.rdm_rows, pl.moment_rows(), pl.n_dm_diag + pl.n_dm_pobs, pl.n_dm_fid, pl.dm_purity, pl.dm_rdm_rows};
         for (int b = 0; b < End; ++b) first[b + 1] = first[b] + count[b];
     }
     int count(Block b) const { return first[b + 1] - first[b]; }
@@ -634,6 +641,20 @@ inline bool build_plan(const RydProblem* p, Plan& pl, std::string& err, double w
     if (!build_rdms(p, pl, err)) return false;
     if (!build_shots(p, pl, err)) return false;
     if (!build_dm(p, pl, err)) return false;
+    pl.moments = 0;
+    if (p->bit_moments != 0 && p->bit_moments != 1) {
+        err = "bit_moments must be 0 or 1";
+        return false;
+    }
+    if (p->bit_moments && p->shard_bits > 0) {
+        err = "bit moments (occupation correlations): not implemented together with state sharding";
+        return false;
+    }
+    if (p->bit_moments && p->dm_atoms != 0) {
+        err = "bit moments (occupation correlations): not implemented for density-matrix registers (dm_atoms > 0)";
+        return false;
+    }
+    pl.moments = p->bit_moments;
     pl.shard_bits = p->shard_bits;
     if (pl.shard_bits < 0 || pl.shard_bits > 6 || pl.shard_bits >= pl.N) {
         err = "shard_bits must be in [0, min(6, n_qubits - 1)]";
@@ -849,10 +870,11 @@ inline size_t carve(Plan& pl, int tape_mode, bool need_backward, int chain_slots
     pl.off_pauli = take(pl.pauli_bytes());
     // one-launch sweeps: the trajectory the Pauli and overlap observables are evaluated on (and the shots drawn from) where the
     // caller keeps none
-    pl.off_pauli_traj = take(((pl.n_pobs || pl.n_ov || pl.n_rdm || pl.n_shots || pl.dm_rows()) && pl.N <= 12) ? size_t(pl.T + 1) * pl.state_bytes : 0);
+    pl.off_pauli_traj = take(((pl.n_pobs || pl.n_ov || pl.n_rdm || pl.moments || pl.n_shots || pl.dm_rows()) && pl.N <= 12) ? size_t(pl.T + 1) * pl.state_bytes : 0);
     pl.off_dm = take(pl.dm_n ? pl.dm_bytes() : 0);  // string tables of the density-matrix observables
     pl.off_shot_sums = take(pl.n_shots ? size_t(pl.B) * pl.shot_chunks() * sizeof(double) : 0);
     pl.off_shot_prefix = take(pl.n_shots ? size_t(pl.B) * pl.shot_chunks() * sizeof(double) : 0);
+    pl.off_moments = take((pl.moments && pl.moment_tiles() > 1) ? size_t(pl.B) * 79 * pl.moment_tiles() * sizeof(double) : 0);  // kMomEntries per tile
     pl.total_fwd = off;
     pl.tape_mode = tape_mode;
     if (tape_mode == 2) pl.off_tape = take(size_t(total_factors + 1) * pl.state_bytes);
@@ -865,7 +887,7 @@ inline size_t carve(Plan& pl, int tape_mode, bool need_backward, int chain_slots
         pl.off_wtot = take(pl.dim * (pl.shard_bits ? size_t(pl.B) : 1) * sizeof(double));  // sharded: one weight slab per rank of the call
         // observable cotangent grad_states[k] + 2 sum_o g_o O_o psi_k + sum_o (gRe + i gIm)_o phi_o: one state, reused in stream order
         // (one-launch adjoints: every k)
-        pl.off_pauli_cot = take((pl.n_pobs || pl.n_ov || pl.n_rdm || pl.dm_rows()) ? size_t(pl.N <= 12 ? pl.T + 1 : 1) * pl.state_bytes : 0);
+        pl.off_pauli_cot = take((pl.n_pobs || pl.n_ov || pl.n_rdm || pl.moments || pl.dm_rows()) ? size_t(pl.N <= 12 ? pl.T + 1 : 1) * pl.state_bytes : 0);
         pl.off_meta2 = take(std::max(E * 40, size_t(pl.T + 1) * sizeof(int32_t)));  // StageBwdDev records, or the save-point flags of the one-launch adjoint
     }
     return off;

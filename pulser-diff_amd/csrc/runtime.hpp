@@ -537,7 +537,8 @@ void shard_groups(const Plan& pl, int (&grp)[kShardMaxBits]) {
 // writes grad_states[k] + 2 sum_o g_o O_o psi_k into a workspace buffer, k_overlap_apply (overlap_launch.hpp) adds
 // sum_o (gRe + i gIm)_o phi_o to it (or to grad_states[k] where no Pauli observable has a cotangent), and the injecting launch reads
 // that buffer instead of grad_states[k]; k_rdm_apply (rdm_launch.hpp) adds sum_o ((G + G^dagger)_{A_o} (x) 1) psi_k the same way, and
-// k_dm_apply / k_dm_scatter (dm_launch.hpp) the cotangents of the density-matrix rows
+// k_moments_apply (moments_launch.hpp) 2 q_k psi_k of the occupation-correlation rows, k_dm_apply / k_dm_scatter (dm_launch.hpp) the
+// cotangents of the density-matrix rows
 struct PauliInject {
     const Runtime* rt = nullptr;
     char* ws = nullptr;
@@ -548,6 +549,7 @@ struct PauliInject {
     const double* ov_gexp = nullptr;  // Overlap
     const double2* ov_targets = nullptr;
     const double* rdm_gexp = nullptr; // Rdm
+    const double* moments_gexp = nullptr;  // Moments
     const double* dm_gexp = nullptr;  // DmTrace .. End: the first density-matrix row
     const double* dm_diag = nullptr;  // RydProblem.dm_diag / dm_fid_targets
     const double2* dm_phi = nullptr;
@@ -636,6 +638,7 @@ struct ForwardCtx : SweepCtx {
     double* pauli_out = nullptr;   // Pauli
     double* overlap_out = nullptr; // Overlap
     double* rdm_out = nullptr;     // Rdm
+    double* moments_out = nullptr; // Moments
     double* dm_out = nullptr;      // DmTrace .. End: the first density-matrix row
     const double* shot_u = nullptr;  // RydProblem.shot_uniforms / shots_out where shots are drawn (rydiff_forward with n_shots > 0)
     uint32_t* shots_out = nullptr;

@@ -44,6 +44,7 @@ using namespace rydiff;
 #include "pauli_kernels.hpp"
 #include "overlap_kernels.hpp"
 #include "rdm_kernels.hpp"
+#include "moments_kernels.hpp"
 #include "shots_kernels.hpp"
 #include "dm_kernels.hpp"
 #include "tangent_kernels.hpp"
@@ -57,6 +58,7 @@ static_assert(sizeof(PersistFactor) == 48, "plan.hpp sizes the factor table with
 #include "pair_launch.hpp"
 #include "shots_launch.hpp"
 #include "rdm_launch.hpp"
+#include "moments_launch.hpp"
 #include "dm_launch.hpp"
 #include "overlap_launch.hpp"
 #include "tangent_launch.hpp"
@@ -132,6 +134,7 @@ int bind_expect_rows(ForwardCtx& c, double* expect_out) {
     c.pauli_out = rows.at(expect_out, ExpectRows::Pauli);
     c.overlap_out = rows.at(expect_out, ExpectRows::Overlap);
     c.rdm_out = rows.at(expect_out, ExpectRows::Rdm);
+    c.moments_out = rows.at(expect_out, ExpectRows::Moments);
     c.dm_out = rows.at(expect_out, ExpectRows::DmTrace, ExpectRows::End);
     if (expect_out && rows.total()) HIP_TRY(hipMemsetAsync(expect_out, 0, rows.size() * sizeof(double), c.stream));
     return RYDIFF_OK;
@@ -541,6 +544,7 @@ int rydiff_backward(const RydProblem* p, const RydPlanInfo* info, const void* st
         c.pauli.ov_gexp = rows.at(grad_expect, ExpectRows::Overlap);
         c.pauli.ov_targets = static_cast<const double2*>(p->overlap_targets);
         c.pauli.rdm_gexp = rows.at(grad_expect, ExpectRows::Rdm);
+        c.pauli.moments_gexp = rows.at(grad_expect, ExpectRows::Moments);
         c.pauli.dm_gexp = rows.at(grad_expect, ExpectRows::DmTrace, ExpectRows::End);
         c.pauli.dm_diag = p->dm_diag;
         c.pauli.dm_phi = static_cast<const double2*>(p->dm_fid_targets);

@@ -22,6 +22,7 @@ int tangent_validate(const RydProblem* p, const RydPlanInfo* info, int n_dir, in
     if (p->amp_conditioned_terms || p->det_ones_terms)
         return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented with conditioned flips / ones-counting terms (three-level registers)");
     if (p->n_shots > 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: measurement shots are not implemented (n_shots > 0): draw them in rydiff_forward");
+    if (p->bit_moments != 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: bit moments are not implemented (bit_moments != 0): request them from rydiff_forward");
     if (p->n_rdms > 0 && !(flags & RYDIFF_TANGENT_RDMS))
         return fail(RYDIFF_ENOTIMPL, "tangent sweep: reduced density matrices are not implemented (n_rdms > 0) unless RydTangent.flags "
                                      "has RYDIFF_TANGENT_RDMS");

@@ -21,7 +21,7 @@ from .backend import TorchEmulator
 from .simconfig import SimConfig
 from .simresults import SimulationResults
 from .solver import SolverType
-from .observables import PauliObservable, ReducedDensityMatrix, StateOverlap
+from .observables import OccupationCorrelations, PauliObservable, ReducedDensityMatrix, StateOverlap
 from .utils import DiagonalObservable, total_magnetization, total_magnetization_diag
 from .waveform_funcs import constant_waveform
 
@@ -211,3 +211,10 @@ class QuantumModel(Module):
         obs = qubits if isinstance(qubits, ReducedDensityMatrix) else ReducedDensityMatrix(qubits)
         evaluation_times, results = self._run(observables=[obs], store_states=False)
         return evaluation_times, results.reduced_density_matrix(obs)
+
+    def occupation_correlations(self, connected: bool = False) -> tuple[Tensor, Tensor]:
+        """Evaluation times and ``<n_i n_j>`` (``connected=True``: ``g_ij = <n_i n_j> - <n_i><n_j>``), real ``(n_t, N, N)`` with
+        ``<n_i>`` on the diagonal, evaluated and differentiated natively from one read of the state per evaluation time: no
+        trajectory is stored or handed to autograd.  Ket models only."""
+        evaluation_times, results = self._run(observables=[OccupationCorrelations()], store_states=False)
+        return evaluation_times, results.occupation_correlations(connected=connected)

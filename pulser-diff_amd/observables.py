@@ -408,6 +408,52 @@ class Purity:
     with ``results.purity()``.  Not an operator: ``results.expect`` does not take it."""
 
 
+class OccupationCorrelations:
+    """Every ``<n_i>`` and every ``<n_i n_j>`` of the register at every evaluation time, from one read of the state — handed to
+    ``run(observables=[...])`` of a ket run it is evaluated and differentiated natively (``include/rydiff.h``:
+    ``RydProblem.bit_moments``; ``csrc/moments_kernels.hpp``), no stored trajectory and no ``2^N`` table.  Read it with
+    ``results.occupations()``, ``results.occupation_correlations(connected=...)`` and ``results.structure_factor(signs)``.  Not an
+    operator: ``results.expect`` does not take it.  All qubits, or off: there is no subset."""
+
+
+def moment_rows(n_qubits: int) -> int:
+    """Rows of the moments block: ``1 + N + N(N-1)/2``."""
+    return 1 + n_qubits + n_qubits * (n_qubits - 1) // 2
+
+
+def moment_pair_row(n_qubits: int, q: int, r: int) -> int:
+    """The row of ``B_qr`` (``q < r``) in the moments block: ``S``, the ``B_q``, then the pairs in lexicographic order."""
+    if not 0 <= q < r < n_qubits:
+        raise ValueError(f"a pair row needs 0 <= q < r < {n_qubits}, got ({q}, {r})")
+    return 1 + n_qubits + q * (2 * n_qubits - q - 1) // 2 + (r - q - 1)
+
+
+def occupation_moments(states: Tensor) -> Tensor:
+    """The rows of ``RydProblem.bit_moments`` in torch on stored kets ``(n_t, dim, B)``: real ``(1 + N + N(N-1)/2, n_t, B)``,
+    differentiable.  With ``p[y] = |psi[y]|^2`` and ``y_q`` the index bit of qubit ``q`` (index bit ``N-1-q``): ``S = sum p``, then
+    ``B_q = sum p y_q`` in ascending ``q``, then ``B_qr = sum p y_q y_r`` in lexicographic ``(q, r)``."""
+    if states.is_sparse:
+        states = states.to_dense()
+    if states.ndim == 4:
+        raise NotImplementedError("OccupationCorrelations is defined on kets; density matrices (master-equation runs) are not supported")
+    if states.ndim != 3:
+        raise ValueError(f"expected kets (n_t, dim, B), got {tuple(states.shape)}")
+    n_t, dim, batch = states.shape
+    n = dim.bit_length() - 1
+    if dim != 1 << n:
+        raise ValueError(f"OccupationCorrelations needs a register of qubits (dim a power of two), got dim {dim}")
+    p = states.real.to(torch.float64) ** 2 + states.imag.to(torch.float64) ** 2 if states.is_complex() else states.to(torch.float64) ** 2
+    y = torch.arange(dim, device=states.device)
+    bits = torch.stack([((y >> (n - 1 - q)) & 1).to(torch.float64) for q in range(n)]) if n else torch.zeros(0, dim, dtype=torch.float64)
+    rows = [p.sum(dim=1)[None]]
+    if n:
+        rows.append(torch.einsum("qy,tyb->qtb", bits, p))
+    if n > 1:
+        iq, ir = torch.triu_indices(n, n, offset=1, device=states.device)  # lexicographic (q, r), q < r
+        rows.append(torch.einsum("ey,tyb->etb", bits[iq] * bits[ir], p))
+    return torch.cat(rows, dim=0)
+
+
 def fidelity_states(obs: StateOverlap, states: Tensor) -> Tensor:
     """``<phi_b| rho_b(t_k) |phi_b>`` in torch, real ``(n_t, B)``: stored density matrices ``(n_t, dim, dim, B)``, or kets
     ``(n_t, dim, B)`` (``|<phi|psi>|^2``).  The real part of the bilinear form, as the library takes it (no Hermiticity assumed)."""

@@ -19,10 +19,11 @@ import torch
 from torch import Tensor
 
 from .result import SampledResult, TorchResult
-from .observables import (PauliObservable, ReducedDensityMatrix, StateOverlap, fidelity_states, overlap_states, purity_states,
-                          reduced_density_matrix)
+from .observables import (PauliObservable, ReducedDensityMatrix, StateOverlap, fidelity_states, occupation_moments, overlap_states,
+                          purity_states, reduced_density_matrix)
 from .shots import ShotRequest, bitstring_counts, indices_to_bitstrings
-from .utils import DiagonalObservable, expect, negativity, von_neumann_entropy
+from .utils import (DiagonalObservable, connected_correlations, expect, negativity, occupation_correlations_from_moments,
+                    occupations_from_moments, structure_factor, von_neumann_entropy)
 
 
 class SimulationResults(ABC):
@@ -60,7 +61,8 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
                  stats: Optional[dict] = None, density: bool = False, native_overlaps: Optional[Tensor] = None,
                  overlap_observables: Optional[list] = None, native_shots: Optional[ShotRequest] = None,
                  native_rdms: Optional[list] = None, rdm_observables: Optional[list] = None,
-                 native_fidelities: Optional[list] = None, native_purity: Optional[Tensor] = None) -> None:
+                 native_fidelities: Optional[list] = None, native_purity: Optional[Tensor] = None,
+                 native_moments: Optional[Tensor] = None) -> None:
         super().__init__(size, basis_name, sim_times)
         if self._basis_name == "all":  # simresults.py:381-383
             if meas_basis not in {"ground-rydberg", "digital"}:
@@ -82,6 +84,7 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
         self._rdm_observables = list(rdm_observables or [])
         self._native_fidelities = native_fidelities  # master-equation runs, per StateOverlap: real (n_t, B) = <phi|rho|phi>
         self._native_purity = native_purity  # master-equation runs with a Purity observable: real (n_t, B)
+        self._native_moments = native_moments  # run with OccupationCorrelations: real (1 + N + N(N-1)/2, n_t, B): S, B_q, B_qr
         self._native_shots = native_shots  # filled by the solver: amplitude indices (n_shot_times, B, n_shots)
         self.solver_stats = dict(stats or {})
 
@@ -191,6 +194,35 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
         """Negativity of the state of the subsystem of ``obs`` across the cut between its first ``n_first`` listed qubits and the
         others, real ``(n_t, B)`` (``utils.negativity``); an entanglement measure for mixed states too."""
         return negativity(self.reduced_density_matrix(obs), n_first)
+
+    def _occupation_moments(self) -> tuple[Tensor, int]:
+        """(the moments S, B_q, B_qr summed over the columns of the initial state like ``expect``: (rows, n_t); the index value of
+        the level ``sample_state`` reports as "1": r = 0 in the ground-rydberg basis, 1 in the digital and XY bases)."""
+        if self._density:
+            raise NotImplementedError("Occupation correlations are defined on kets; this is a master-equation run: hand run() "
+                                      "DiagonalObservable projectors instead.")
+        if self._basis_name == "all":
+            raise NotImplementedError("Occupation correlations are not available in the three-level all-basis.")
+        rows = self._native_moments if self._native_moments is not None else occupation_moments(self.states)
+        return rows.sum(dim=-1), 0 if self._basis_name == "ground-rydberg" else 1
+
+    def occupations(self) -> Tensor:
+        """``<n_i>`` of every atom (in ``atom_order``) at every evaluation time, real ``(n_t, N)``; "occupied" is the level
+        ``sample_state`` reports as "1".  The native values when the run was handed ``OccupationCorrelations()``, else computed
+        from the stored states.  Not normalised by the library (``S = <psi|psi>`` enters as it is)."""
+        rows, bit = self._occupation_moments()
+        return occupations_from_moments(rows, self._size, bit)
+
+    def occupation_correlations(self, connected: bool = False) -> Tensor:
+        """``<n_i n_j>``, real symmetric ``(n_t, N, N)`` with ``<n_i>`` on the diagonal (``n^2 = n``); ``connected=True``:
+        ``g_ij = <n_i n_j> - <n_i><n_j>``.  Native when the run was handed ``OccupationCorrelations()``, else from the stored states."""
+        rows, bit = self._occupation_moments()
+        return connected_correlations(rows, self._size, bit) if connected else occupation_correlations_from_moments(rows, self._size, bit)
+
+    def structure_factor(self, signs) -> Tensor:
+        """``sum_ij s_i s_j g_ij / N`` at every evaluation time, real ``(n_t,)``, for a pattern ``signs`` of +-1 over the atoms in
+        ``atom_order``; the Neel pattern gives the antiferromagnetic order parameter."""
+        return structure_factor(self.occupation_correlations(connected=True), signs)
 
     def sample_state(self, t: float, n_samples: int = 1000, t_tol: float = 1.0e-3) -> Counter:
         """simresults.py:497-540: ideal samples, then the detection errors of the SPAM model (a measured 0 flips with

@@ -20,8 +20,8 @@ import torch
 from torch import Tensor
 
 from . import _native
-from .observables import (DensityMatrixObservables, PauliObservable, ReducedDensityMatrix, StateOverlap, check_pauli, pack_overlaps,
-                          pack_pauli, pack_rdms)
+from .observables import (DensityMatrixObservables, PauliObservable, ReducedDensityMatrix, StateOverlap, check_pauli, moment_rows,
+                          pack_overlaps, pack_pauli, pack_rdms)
 from .shots import ShotRequest
 
 
@@ -84,6 +84,13 @@ class ProblemSpec:
     # natively; their rows follow every other row of `expect` (observables.DensityMatrixObservables).  `dm.shots`: the shots of
     # `shots` are drawn from the diagonal of rho
     dm: Optional[DensityMatrixObservables] = None
+    # occupation correlations (RydProblem.bit_moments): the moments S, B_q, B_qr of |psi|^2 over the index bits, 1 + N + N(N-1)/2 rows
+    # behind the reduced-density-matrix rows of `expect` (split_moments takes them off the end); kets only
+    moments: bool = False
+
+    def moment_rows(self) -> int:
+        """Rows of `expect` the occupation correlations take: 1 + N + N(N-1)/2, or 0."""
+        return moment_rows(self.n_qubits) if self.moments else 0
 
     @property
     def n_overlaps(self) -> int:
@@ -224,6 +231,7 @@ class _Call:
         if self.rdm_masks is not None:
             p.n_rdms = len(self.rdm_masks)
             p.rdm_masks = self.rdm_masks.ctypes.data
+        p.bit_moments = int(spec.moments)
         self.dm_buffers = None
         if spec.dm is not None:
             dm = spec.dm
@@ -259,10 +267,10 @@ class _Call:
 
     def expect_rows(self) -> int:
         """Rows of `expect` / `dexpect[d]`, in the order the library writes them (ExpectRows, csrc/plan.hpp): diagonal observables,
-        then the Pauli ones, then Re / Im of every overlap, then Re / Im of every RDM entry, then the density-matrix rows."""
+        then the Pauli ones, then Re / Im of every overlap, then Re / Im of every RDM entry, then the moments S, B_q, B_qr of the occupation correlations, then the density-matrix rows."""
         p = self.problem
         dm_rows = self.spec.dm.rows() if self.spec.dm is not None else 0
-        return p.n_obs + p.n_pauli_obs + 2 * p.n_overlaps + self.spec.rdm_rows() + dm_rows
+        return p.n_obs + p.n_pauli_obs + 2 * p.n_overlaps + self.spec.rdm_rows() + self.spec.moment_rows() + dm_rows
 
     def set_shots(self, times: np.ndarray, uniforms: Tensor, out: Tensor) -> None:
         """RydProblem.n_shots / shot_*: sampled save points (host int32), uniforms (device float64) and the output (device, 32-bit),
@@ -588,6 +596,7 @@ class SolveResult:
     overlaps: Optional[Tensor] = None  # complex (n_ov, n_t, B): <phi_o,b | psi_b(t_k)> evaluated natively (differentiable), or None
     shots: Optional[ShotRequest] = None  # the request handed to sesolve(shots=...), holding the native shots (.indices)
     rdms: Optional[list] = None  # per ReducedDensityMatrix: complex (n_t, B, 2^m, 2^m), evaluated natively (differentiable), or None
+    moments: Optional[Tensor] = None  # (1 + N + N(N-1)/2, n_t, B): S, B_q, B_qr evaluated natively (differentiable), or None
 
 
 def split_expect(expect: Tensor, n_overlaps: int) -> tuple[Tensor, Optional[Tensor]]:
@@ -623,6 +632,15 @@ def split_observables(expect: Tensor, n_overlaps: int, rdms=None) -> tuple[Tenso
     return real, ov, out
 
 
+def split_moments(expect: Tensor, n_qubits: int) -> tuple[Tensor, Tensor]:
+    """Takes the moments block of the occupation correlations (``ProblemSpec.moments``) off the END of a ket's `expect`:
+    -> (the other rows, as ``split_observables`` takes them; the moments (1 + N + N(N-1)/2, n_t, B): S, B_q, B_qr)."""
+    n = moment_rows(n_qubits)
+    if expect.shape[0] < n:
+        raise ValueError(f"expect holds {expect.shape[0]} rows: fewer than the {n} moment rows of {n_qubits} qubits")
+    return expect[:expect.shape[0] - n], expect[expect.shape[0] - n:]
+
+
 def frame_factor(n_sub: int, phi: float) -> Tensor:
     """``exp(-i phi (ones(a) - ones(a')))``, ``(2^m, 2^m)``: takes a reduced density matrix of the state ``V psi`` in the frame that
     rotates with a constant drive phase ``phi`` (``V = exp(i phi * number of ones)``) back to the lab frame."""
@@ -642,7 +660,7 @@ def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverTyp
             options: Optional[dict] = None, obs_diag: Optional[Tensor] = None, store_states: bool = True,
             pauli_obs: Optional[Sequence[PauliObservable]] = None,
             overlap_obs: Optional[Sequence[StateOverlap]] = None, shots: Union[None, int, ShotRequest] = None,
-            rdm_obs: Optional[Sequence[ReducedDensityMatrix]] = None) -> SolveResult:
+            rdm_obs: Optional[Sequence[ReducedDensityMatrix]] = None, moments: bool = False) -> SolveResult:
     """Drop-in for ``pyqtorch.sesolve(H=..., psi0, tsave, solver, options)`` at ``backend.py:488-494``.
 
     ``problem`` is the structured Hamiltonian (``pulser_diff_amd.hamiltonian.Hamiltonian``) instead of the opaque
@@ -651,7 +669,9 @@ def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverTyp
     into ``SolveResult.overlaps``.  ``shots``: a ``ShotRequest`` (or an int: that many shots at the final time) filled natively and
     returned as ``SolveResult.shots``; its indices are in the basis order of the native register (three-level registers: two qubits
     per atom, see ``shots.indices_to_bitstrings``).  ``rdm_obs``: ``ReducedDensityMatrix`` observables evaluated natively into
-    ``SolveResult.rdms`` (lab frame, the order of their ``qubits``).
+    ``SolveResult.rdms`` (lab frame, the order of their ``qubits``).  ``moments``: the occupation correlations — the moments
+    ``S, B_q, B_qr`` of ``|psi|^2`` over the index bits — evaluated natively into ``SolveResult.moments`` (diagonal: they do not see
+    the rotating frame).
     """
     options = dict(options or {})
     spec = problem.problem_spec(solver=solver, tol=tolerance_from_options(options), store_states=store_states)
@@ -683,6 +703,11 @@ def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverTyp
             raise NotImplementedError("ReducedDensityMatrix is not available in the three-level all-basis (an atom is two qubits "
                                       "there); trace the stored states instead.")
         spec.rdms = rdm_obs
+    if moments:
+        if embed is not None:
+            raise NotImplementedError("OccupationCorrelations is not available in the three-level all-basis (an atom is two qubits "
+                                      "there); reduce the stored states instead.")
+        spec.moments = True
     pauli_obs = list(pauli_obs or [])
     if pauli_obs and embed is not None:
         raise NotImplementedError("Pauli observables are not available in the three-level all-basis; use results.expect on stored states.")
@@ -718,12 +743,15 @@ def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverTyp
         states = states * rot.conj()[None, None, :]
     if embed is not None and states.numel():
         states = states.index_select(2, embed)
+    mom = None
+    if spec.moments:
+        expect, mom = split_moments(expect, spec.n_qubits)
     expect, overlaps, rdms = split_observables(expect, len(overlap_obs), rdm_obs)
     if rdms is not None and rot is not None:
         # the library saw V psi: rho_lab[a][a'] = rho[a][a'] exp(-i phi (ones(a) - ones(a'))), on the small matrix (differentiable)
         rdms = [r * frame_factor(o.n_sub, float(phi)).to(r.device) for o, r in zip(rdm_obs, rdms)]
     return SolveResult(states.permute(0, 2, 1) if states.numel() else states, expect,
-                       dict(spec.options.get("_last_stats", {})), overlaps, spec.shots, rdms)
+                       dict(spec.options.get("_last_stats", {})), overlaps, spec.shots, rdms, mom)
 
 
 def _tangent_take(t: Optional[Tensor], sel, shape: tuple, dtype: torch.dtype, name: str, dev) -> Optional[Tensor]:
@@ -812,6 +840,8 @@ def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsav
     if spec.dm is not None and not (int(flags) & _native.TANGENT_DENSITY_MATRIX):
         raise NotImplementedError("evolve_tangent takes no density-matrix registers (rydiff_forward_tangent: RYDIFF_ENOTIMPL) unless "
                                   "flags has _native.TANGENT_DENSITY_MATRIX (lindblad.mesolve_tangent); or differentiate evolve")
+    if spec.moments:
+        raise NotImplementedError("evolve_tangent evaluates no occupation correlations (rydiff_forward_tangent: RYDIFF_ENOTIMPL); request them from evolve")
     if spec.shots is not None or (spec.dm is not None and spec.dm.shots):
         raise NotImplementedError("evolve_tangent draws no measurement shots (rydiff_forward_tangent: RYDIFF_ENOTIMPL); request them from evolve")
     L = _native.lib()
@@ -870,6 +900,8 @@ def evolve_geometry(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsa
     if spec.dm is not None:
         raise NotImplementedError("evolve_geometry takes no density-matrix registers (rydiff_forward_geometry: RYDIFF_ENOTIMPL): the "
                                   "pure-state quantum Fisher information is not the mixed-state one")
+    if spec.moments:
+        raise NotImplementedError("evolve_geometry evaluates no occupation correlations (rydiff_forward_geometry: RYDIFF_ENOTIMPL); request them from evolve")
     if spec.shots is not None:
         raise NotImplementedError("evolve_geometry draws no measurement shots (rydiff_forward_geometry: RYDIFF_ENOTIMPL); request them from evolve")
     L = _native.lib()

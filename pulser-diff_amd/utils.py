@@ -242,3 +242,53 @@ def logarithmic_negativity(rho: Tensor, n_first: int, base: float = 2) -> Tensor
     pt = partial_transpose(rho, n_first)
     ev = torch.linalg.eigvalsh(0.5 * (pt + pt.mH))
     return torch.log(ev.abs().sum(dim=-1)) / math.log(base)
+
+
+# ---- occupation correlations from the moments block (observables.occupation_moments / RydProblem.bit_moments) --------------------
+def _moment_parts(moments: Tensor, n_qubits: int) -> tuple[Tensor, Tensor, Tensor]:
+    """(S (...), B_q (N, ...), B_qr as a symmetric (N, N, ...) with zeros on the diagonal) of rows ``(1 + N + N(N-1)/2, ...)``."""
+    n = int(n_qubits)
+    if moments.shape[0] != 1 + n + n * (n - 1) // 2:
+        raise ValueError(f"the moments of {n} qubits are 1 + N + N(N-1)/2 = {1 + n + n * (n - 1) // 2} rows, got {moments.shape[0]}")
+    pairs = torch.zeros((n, n) + tuple(moments.shape[1:]), dtype=moments.dtype, device=moments.device)
+    if n > 1:
+        iq, ir = torch.triu_indices(n, n, offset=1, device=moments.device)  # lexicographic (q, r): the order of the rows
+        pairs = pairs.index_put((iq, ir), moments[1 + n:]).index_put((ir, iq), moments[1 + n:])
+    return moments[0], moments[1:1 + n], pairs
+
+
+def occupations_from_moments(moments: Tensor, n_qubits: int, occupied_bit: int = 0) -> Tensor:
+    """``<n_i>`` from the rows ``S, B_q, B_qr`` (``(rows, ...)`` -> ``(..., N)``).  ``occupied_bit``: the index value of the occupied
+    level — 0 in the ground-rydberg basis (r is index value 0: ``<n_i> = S - B_i``), 1 in the digital and XY bases (``B_i``)."""
+    s, b1, _ = _moment_parts(moments, n_qubits)
+    occ = b1 if occupied_bit else s[None] - b1
+    return torch.movedim(occ, 0, -1)
+
+
+def occupation_correlations_from_moments(moments: Tensor, n_qubits: int, occupied_bit: int = 0) -> Tensor:
+    """``<n_i n_j>`` from the rows (``(rows, ...)`` -> ``(..., N, N)``): symmetric, diagonal ``<n_i>`` (``n^2 = n``).  With r as index
+    value 0, ``<n_i n_j> = S - B_i - B_j + B_ij``."""
+    s, b1, b2 = _moment_parts(moments, n_qubits)
+    n = int(n_qubits)
+    occ = b1 if occupied_bit else s[None] - b1
+    nn = b2 if occupied_bit else (s[None, None] + b2) - (b1[:, None] + b1[None, :])  # (a + b == b + a: symmetric bit for bit)
+    eye = torch.eye(n, dtype=torch.bool, device=moments.device).reshape((n, n) + (1,) * (moments.ndim - 1))
+    nn = torch.where(eye, occ[:, None].expand_as(nn), nn)
+    return torch.movedim(torch.movedim(nn, 0, -1), 0, -1)
+
+
+def connected_correlations(moments: Tensor, n_qubits: int, occupied_bit: int = 0) -> Tensor:
+    """``g_ij = <n_i n_j> - <n_i><n_j>`` from the rows (``(rows, ...)`` -> ``(..., N, N)``); diagonal ``<n_i> - <n_i>^2``."""
+    occ = occupations_from_moments(moments, n_qubits, occupied_bit)
+    return occupation_correlations_from_moments(moments, n_qubits, occupied_bit) - occ[..., :, None] * occ[..., None, :]
+
+
+def structure_factor(g: Tensor, signs) -> Tensor:
+    """``sum_ij s_i s_j g_ij / N`` of connected correlations ``(..., N, N)`` for a pattern of +-1 (the Neel pattern +1, -1, +1, ...
+    gives the antiferromagnetic order parameter)."""
+    s = torch.as_tensor(signs, dtype=g.dtype, device=g.device)
+    if s.ndim != 1 or s.shape[0] != g.shape[-1] or g.shape[-2] != g.shape[-1]:
+        raise ValueError(f"signs must hold one entry per atom ({g.shape[-1]}), got {tuple(s.shape)}")
+    if not bool(torch.all(s.abs() == 1)):
+        raise ValueError("signs must be a pattern of +1 and -1")
+    return torch.einsum("i,...ij,j->...", s, g, s) / g.shape[-1]
