@@ -236,7 +236,8 @@ typedef struct RydProblem {
      * next to every other ket row, shots, pair terms, conditioned and ones-counting terms (plain bits at this level).  Beyond 12
      * qubits rydiff_plan adds 79 doubles per 2^12 amplitudes and trajectory to workspace_bytes.  RYDIFF_EINVAL: a value other
      * than 0 or 1.  RYDIFF_ENOTIMPL: together with shard_bits > 0, with dm_atoms > 0, and in rydiff_forward_tangent /
-     * rydiff_forward_geometry.  Traffic per state: one read; nothing of size 2^N is written.  bit_moments = 0: nothing changes.
+     * rydiff_forward_geometry without RYDIFF_TANGENT_MOMENTS in RydTangent.flags (with it: values and tangents at every save
+     * point).  Traffic per state: one read; nothing of size 2^N is written.  bit_moments = 0: nothing changes.
      * (The field sits in front of n_rdms, so every later block keeps its place relative to its neighbours.) */
     int32_t bit_moments;          /* 0: off; 1: all qubits */
 
@@ -460,17 +461,23 @@ typedef struct RydTangent {
     const void*   d_psi0;   /* DEVICE complex128 [n_dir][B][2^N] or NULL */
     int32_t flags;          /* 0, or RYDIFF_TANGENT_* ored: what the caller asks the sweep to take beyond plain Ising kets */
 } RydTangent;
-/* Without its flag a problem with dense pair terms / a density-matrix register / reduced density matrices is RYDIFF_ENOTIMPL, as
- * before the sweep took them. */
+/* Without its flag a problem with dense pair terms / a density-matrix register / reduced density matrices / bit moments is
+ * RYDIFF_ENOTIMPL, as before the sweep took them. */
 #define RYDIFF_TANGENT_PAIR_TERMS 1      /* n_pair_terms > 0: the pair terms ride in the pass as constants of every direction */
 #define RYDIFF_TANGENT_DENSITY_MATRIX 2  /* dm_atoms > 0: the vectors are vec(rho) and its tangents; the dm_* rows get tangents */
 #define RYDIFF_TANGENT_RDMS 4            /* n_rdms > 0: the RDM block of rydiff_forward joins expect_out and dexpect_out */
+#define RYDIFF_TANGENT_MOMENTS 8         /* bit_moments = 1 (kets): the Moments block of rydiff_forward joins expect_out and dexpect_out;
+                                          * RYDIFF_EINVAL with bit_moments = 0 */
 
 /* sizeof(RydTangent) as this library was compiled (see rydiff_sizeof_problem). */
 size_t rydiff_sizeof_tangent(void);
 
 /* Device workspace of rydiff_forward_tangent for n_dir directions (sized as if every tangent pointer were given); 0 on an
- * error (rydiff_last_error).  `info`: from rydiff_plan(p, 0, 0, ...).  Host only. */
+ * error (rydiff_last_error).  `info`: from rydiff_plan(p, 0, 0, ...).  Host only.  The regions, each rounded up to 256 bytes: the
+ * forward plan's (info->workspace_bytes; with bit_moments beyond 12 qubits that holds B * 79 * 2^(N-12) doubles for the values' tile
+ * records), two vector sets of (1 + D') * B * 2^N * 16 bytes (D' = n_dir, 5 -> 6, 7 -> 8), D' coefficient-record sets, D' * 2^N
+ * doubles of tangent interaction diagonals and, with RYDIFF_TANGENT_MOMENTS and bit_moments beyond 12 qubits, n_dir * B * 79 * 2^(N-12)
+ * doubles for the tile records of the moment tangents (nothing up to 12 qubits). */
 size_t rydiff_tangent_workspace_bytes(const RydProblem* p, const RydPlanInfo* info, int n_dir);
 /* The same for a call with RydTangent.flags = flags (rydiff_tangent_workspace_bytes is flags = 0). */
 size_t rydiff_tangent_workspace_bytes_flags(const RydProblem* p, const RydPlanInfo* info, int n_dir, int flags);
@@ -480,12 +487,17 @@ size_t rydiff_tangent_workspace_bytes_flags(const RydProblem* p, const RydPlanIn
  *   psi0         DEVICE complex128 [B][2^N]  (dm_atoms > 0: vec(rho_0), and d_psi0 = vec(d rho_0))
  *   expect_out   DEVICE float64 [rows][n_tsave][B] or NULL: the values, rows = n_obs + n_pauli_obs + 2 * n_overlaps in the order
  *                of rydiff_forward; with RYDIFF_TANGENT_RDMS followed by the RDM block (2 * 4^{m_o} rows per reduced density matrix,
- *                entry (a, a') at 2 (a 2^m + a'), Re then Im); with dm_atoms > 0 followed by n_dm_diag + n_dm_pauli_obs + n_dm_fid +
- *                dm_purity rows, as there
+ *                entry (a, a') at 2 (a 2^m + a'), Re then Im); with RYDIFF_TANGENT_MOMENTS and bit_moments = 1 followed by the
+ *                Moments block behind the RDM block, as in rydiff_forward (1 + N + N(N-1)/2 rows: S, B_q in ascending q, B_qr at
+ *                1 + N + q(2N-q-1)/2 + (r-q-1)); with dm_atoms > 0 followed by n_dm_diag + n_dm_pauli_obs + n_dm_fid + dm_purity
+ *                rows, as there
  *   dexpect_out  DEVICE float64 [n_dir][rows][n_tsave][B] (required): diagonal rows 2 sum_y o[y] Re(conj psi[y] dpsi_d[y]), Pauli
  *                rows 2 sum_s w_s Re<psi|P_s|dpsi_d>, overlap rows Re / Im <phi_o|dpsi_d>, RDM rows the entries of
  *                d rho_A = Tr_E(|dpsi_d><psi| + |psi><dpsi_d|) (the mirror entry is the exact conjugate, Im of the diagonal an exact
- *                0; summed with atomics: not bit-reproducible); every save point, k = 0 included.  Need not be cleared.
+ *                0; summed with atomics: not bit-reproducible), Moments rows the same moments of the signed weight
+ *                dp_d[y] = 2 Re(conj psi[y] dpsi_d[y]): dS_d = sum_y dp_d[y], dB_q = sum_y dp_d[y] y_q, dB_qr = sum_y dp_d[y] y_q y_r
+ *                (no atomics, one fixed order: two calls give the same bits; only the n_dir real directions are evaluated); every
+ *                save point, k = 0 included.  Need not be cleared.
  *                Density-matrix rows (dm_atoms > 0; v = vec(rho), dv_d its tangent): the diagonal, Pauli and fidelity rows are
  *                linear in v — the row's functional of dv_d — and the purity row is 2 Re sum_i conj(v_i) dv_d,i
  *   workspace    DEVICE, >= rydiff_tangent_workspace_bytes(p, info, n_dir)
@@ -493,9 +505,13 @@ size_t rydiff_tangent_workspace_bytes_flags(const RydProblem* p, const RydPlanIn
  * family (launch per factor, one amplitude per thread).  With RYDIFF_TANGENT_PAIR_TERMS in tangent->flags dense pair terms
  * (n_pair_terms > 0: the XY exchange, the dissipator of a master-equation run on the doubled register) ride in the same pass as
  * constants of every direction; with RYDIFF_TANGENT_DENSITY_MATRIX a register with dm_atoms > 0 is taken; with RYDIFF_TANGENT_RDMS
- * the reduced density matrices of a ket (n_rdms > 0) get values and tangents (one k_rdm_tangent launch per RDM and save point).
- * Not implemented (RYDIFF_ENOTIMPL): pair terms / dm_atoms > 0 / n_rdms > 0 without their flag, state-sharded runs, conditioned /
- * ones-counting terms, shots, partial traces of a density matrix (n_dm_rdms > 0) whatever the flags.  Every argument is validated
+ * the reduced density matrices of a ket (n_rdms > 0) get values and tangents (one k_rdm_tangent launch per RDM and save point); with
+ * RYDIFF_TANGENT_MOMENTS the bit moments of a ket (bit_moments = 1) get values and tangents (one k_moments_tangent launch per save
+ * point over all directions, beyond 12 qubits followed by k_moments_finish).  The flags combine.
+ * Not implemented (RYDIFF_ENOTIMPL): pair terms / dm_atoms > 0 / n_rdms > 0 / bit_moments without their flag, state-sharded runs,
+ * conditioned / ones-counting terms, shots, partial traces of a density matrix (n_dm_rdms > 0), bit_moments with dm_atoms > 0 whatever
+ * the flags.  RYDIFF_EINVAL: flag bits from 16 up, and RYDIFF_TANGENT_MOMENTS on a problem with bit_moments = 0 (the flag asks for a
+ * block the problem does not have; callers that predate it and probe bit 8 as an unknown one keep their answer).  Every argument is validated
  * before anything touches a device. */
 int rydiff_forward_tangent(const RydProblem* p, const RydPlanInfo* info, const RydTangent* tangent, const void* psi0,
                            double* expect_out, double* dexpect_out, void* workspace, size_t workspace_bytes, void* stream);
@@ -519,8 +535,9 @@ int rydiff_forward_tangent(const RydProblem* p, const RydPlanInfo* info, const R
  * size and is inverted in natural-gradient solves).  Traffic: one read of (1 + n_dir) * B * 2^N * 16 bytes per save point on top of
  * the sweep's; nothing of size 2^N is written.  Everything else — expect_out, the solvers, the validation before anything touches
  * a device, what is RYDIFF_ENOTIMPL (state-sharded runs, conditioned / ones-counting terms, shots, reduced density matrices
- * without RYDIFF_TANGENT_RDMS) — is rydiff_forward_tangent's; pair terms on kets are taken with RYDIFF_TANGENT_PAIR_TERMS and
- * reduced density matrices with RYDIFF_TANGENT_RDMS (the same sweep, the RDM rows are not part of the fixed-order guarantee).  On top of that
+ * without RYDIFF_TANGENT_RDMS, bit moments without RYDIFF_TANGENT_MOMENTS) — is rydiff_forward_tangent's; pair terms on kets are taken
+ * with RYDIFF_TANGENT_PAIR_TERMS, reduced density matrices with RYDIFF_TANGENT_RDMS (the same sweep, the RDM rows are not part of the
+ * fixed-order guarantee) and bit moments with RYDIFF_TANGENT_MOMENTS (fixed order; the Gram matrix does not change).  On top of that
  * dm_atoms > 0 is RYDIFF_ENOTIMPL here whatever the flags (and the workspace functions return 0): the Gram matrix of vec(rho) and its
  * tangents is not the mixed-state quantum Fisher information.  RYDIFF_EINVAL also for a NULL gram_out. */
 size_t rydiff_geometry_workspace_bytes(const RydProblem* p, const RydPlanInfo* info, int n_dir);

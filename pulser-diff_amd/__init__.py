@@ -5,7 +5,7 @@ Drop-in for the hot path of ``pulser_diff`` (``pulser_diff/__init__.py:17-18`` e
 matrix-exponential-on-vector, expectation values and the adjoint gradient sweep run as hand-written HIP kernels
 behind the C ABI in ``include/rydiff.h``.
 """
-from pulser_diff_amd.backend import TorchEmulator  # noqa: F401
+from pulser_diff_amd.backend import OccupationSensitivities, TorchEmulator  # noqa: F401
 from pulser_diff_amd.model import QuantumModel  # noqa: F401
 from pulser_diff_amd.simconfig import SimConfig  # noqa: F401
 from pulser_diff_amd.solver import SolverType  # noqa: F401
@@ -14,6 +14,6 @@ from pulser_diff_amd.observables import OccupationCorrelations, PauliObservable,
 from pulser_diff_amd.geometry import (QuantumGeometry, berry_curvature, quantum_fisher_information,  # noqa: F401
                                       quantum_geometric_tensor)
 
-__all__ = ["TorchEmulator", "SimConfig", "SolverType", "DiagonalObservable", "PauliObservable", "StateOverlap", "ReducedDensityMatrix", "Purity", "OccupationCorrelations", "QuantumModel",
+__all__ = ["TorchEmulator", "SimConfig", "SolverType", "DiagonalObservable", "PauliObservable", "StateOverlap", "ReducedDensityMatrix", "Purity", "OccupationCorrelations", "OccupationSensitivities", "QuantumModel",
            "QuantumGeometry", "quantum_geometric_tensor", "quantum_fisher_information", "berry_curvature",
            "partial_transpose", "negativity", "logarithmic_negativity"]

@@ -35,6 +35,8 @@ MAX_TANGENTS = 8
 TANGENT_PAIR_TERMS = 1      # RYDIFF_TANGENT_PAIR_TERMS (RydTangent.flags): take dense pair terms
 TANGENT_DENSITY_MATRIX = 2  # RYDIFF_TANGENT_DENSITY_MATRIX: take a density-matrix register (dm_atoms > 0)
 TANGENT_RDMS = 4            # RYDIFF_TANGENT_RDMS: take the reduced density matrices of a ket (n_rdms > 0), values and tangents
+TANGENT_MOMENTS = 8         # RYDIFF_TANGENT_MOMENTS: take the occupation correlations of a ket (bit_moments = 1), values and tangents;
+                            # RYDIFF_EINVAL on a problem without them
 MAX_DM_ATOMS = 12  # atoms of a density-matrix register (RydProblem.dm_atoms)
 MAX_DM_DIAG = 64  # diagonal observables of a density-matrix register
 MAX_SHOTS = 1 << 20  # shots per (sampled save point, trajectory)

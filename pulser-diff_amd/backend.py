@@ -33,8 +33,8 @@ from .lindblad import (MAX_ME_QUBITS, ME_DEFAULT_TOL, dissipator_block, doubled_
 from .result import SampledResult
 from .simconfig import SimConfig
 from .simresults import CoherentResults, NoisyResults, SimulationResults
-from .solver import (ProblemSpec, SolverType, evolve, evolve_geometry, evolve_tangent, sesolve, split_observables,
-                     tolerance_from_options)
+from .solver import (ProblemSpec, SolverType, evolve, evolve_geometry, evolve_tangent, sesolve, split_moments,
+                     split_observables, tolerance_from_options)
 from .observables import OccupationCorrelations, PauliObservable, Purity, ReducedDensityMatrix, StateOverlap, pack_overlaps
 from .geometry import QuantumGeometry, quantum_geometric_tensor
 from .shots import MAX_SHOTS, ShotRequest, indices_to_bitstrings
@@ -95,6 +95,66 @@ class SubsystemSensitivities:
         """Per tensor ``x_i``: d entropy(o) / d x_i, (n_t, B, *x_i.shape); defined where ``rho[o]`` has full rank only
         (``utils.von_neumann_entropy_tangent``)."""
         return self._along(o, lambda rho, drho: utils.von_neumann_entropy_tangent(rho, drho, base))
+
+
+@dataclass
+class OccupationSensitivities:
+    """What ``TorchEmulator.run_occupation_sensitivities`` returns: the moments ``S, B_q, B_qr`` of ``|psi|^2`` over the index bits
+    (``RydProblem.bit_moments``) at every evaluation time, ``moments`` (1 + N + N(N-1)/2, n_t, B) (B: the columns of the initial
+    state), per tensor ``x_i`` of the request ``dmoments[i]`` (rows, n_t, B, *x_i.shape) = d moments / d x_i on the device of
+    ``x_i``, the times, and ``occupied_bit``: the index value of the level ``sample_state`` reports as "1" (r = 0 in the
+    ground-rydberg basis, 1 in the digital and XY bases).  The accessors below convert them in torch (``utils``): values
+    ``(n_t, B, ...)``, derivatives one ``(n_t, B, ..., *x_i.shape)`` per ``x_i``.  Nothing is normalised (``S`` enters as it is)."""
+
+    moments: Tensor
+    dmoments: list
+    times: Tensor
+    occupied_bit: int
+
+    @property
+    def n_qubits(self) -> int:
+        rows = int(self.moments.shape[0])
+        return next(n for n in range(1, _native.MAX_QUBITS + 1) if 1 + n + n * (n - 1) // 2 == rows)
+
+    def _along(self, tangent, tail: int) -> list:
+        """``tangent(rows (rows, P, n_t, B)) -> (P, n_t, B, <tail axes>)`` per ``x_i`` -> ``(n_t, B, <tail axes>, *x_i.shape)``."""
+        out = []
+        for dm in self.dmoments:
+            shape = tuple(dm.shape[3:])
+            flat = dm.reshape(tuple(dm.shape[:3]) + (-1,)).movedim(-1, 1)  # (rows, P, n_t, B)
+            res = tangent(flat).movedim(0, -1)
+            out.append(res.reshape(tuple(res.shape[:2 + tail]) + shape))
+        return out
+
+    def occupations(self) -> Tensor:
+        """``<n_i>``, (n_t, B, N)."""
+        return utils.occupations_from_moments(self.moments, self.n_qubits, self.occupied_bit)
+
+    def d_occupations(self) -> list:
+        """Per tensor ``x_i``: d<n_j> / d x_i, (n_t, B, N, *x_i.shape)."""
+        return self._along(lambda dm: utils.occupations_from_moments(dm, self.n_qubits, self.occupied_bit), 1)
+
+    def correlations(self, connected: bool = False) -> Tensor:
+        """``<n_i n_j>`` (diagonal ``<n_i>``), (n_t, B, N, N); ``connected=True``: ``g_ij = <n_i n_j> - <n_i><n_j>``."""
+        fn = utils.connected_correlations if connected else utils.occupation_correlations_from_moments
+        return fn(self.moments, self.n_qubits, self.occupied_bit)
+
+    def d_correlations(self, connected: bool = False) -> list:
+        """Per tensor ``x_i``: d<n_j n_k> / d x_i (``connected=True``: d g_jk / d x_i, the product rule), (n_t, B, N, N, *x_i.shape)."""
+        if connected:
+            return self._along(lambda dm: utils.connected_correlations_tangent(self.moments.to(dm.device), dm, self.n_qubits,
+                                                                              self.occupied_bit), 2)
+        return self._along(lambda dm: utils.occupation_correlations_from_moments(dm, self.n_qubits, self.occupied_bit), 2)
+
+    def structure_factor(self, signs) -> Tensor:
+        """``sum_ij s_i s_j g_ij / N`` for a pattern ``signs`` of +-1 over the atoms (the Neel pattern: the antiferromagnetic
+        order parameter), (n_t, B)."""
+        return utils.structure_factor(self.correlations(connected=True), signs)
+
+    def d_structure_factor(self, signs) -> list:
+        """Per tensor ``x_i``: d structure_factor / d x_i, (n_t, B, *x_i.shape)."""
+        return self._along(lambda dm: utils.structure_factor_tangent(self.moments.to(dm.device), dm, self.n_qubits, signs,
+                                                                     self.occupied_bit), 0)
 
 
 class TorchEmulator:
@@ -633,8 +693,9 @@ class TorchEmulator:
         full = ham.dim ** ham._size
         for obs in observables:
             if isinstance(obs, OccupationCorrelations):
-                raise NotImplementedError("run_sensitivities does not take OccupationCorrelations (the tangent sweep evaluates no "
-                                          "occupation correlations); differentiate results.occupation_correlations through run().")
+                raise NotImplementedError("run_sensitivities does not take OccupationCorrelations (its rows are one scalar per "
+                                          "observable); run_occupation_sensitivities returns every <n_i>, <n_i n_j> and their "
+                                          "derivatives at every evaluation time from the same tangent sweep.")
             if isinstance(obs, ReducedDensityMatrix):
                 if solver != SolverType.DP5_ME:
                     raise NotImplementedError("run_sensitivities does not take ReducedDensityMatrix observables (its rows are real "
@@ -731,8 +792,8 @@ class TorchEmulator:
                       "takes no conditioned flips / ones-counting terms, and ReducedDensityMatrix is a qubit observable.")
         ham, dev = self._hamiltonian, self._compute_device
         if any(isinstance(o, OccupationCorrelations) for o in subsystems):
-            raise NotImplementedError("run_rdm_sensitivities does not take OccupationCorrelations (the tangent sweep evaluates no "
-                                      "occupation correlations); differentiate results.occupation_correlations through run().")
+            raise NotImplementedError("run_rdm_sensitivities does not take OccupationCorrelations (they are no subsystem); "
+                                      "run_occupation_sensitivities returns them and their derivatives at every evaluation time.")
         rdm_objs = [o if isinstance(o, ReducedDensityMatrix) else ReducedDensityMatrix(o) for o in subsystems]
         if not 1 <= len(rdm_objs) <= _native.MAX_RDMS:
             raise ValueError(f"run_rdm_sensitivities takes 1 to {_native.MAX_RDMS} subsystems per call, got {len(rdm_objs)}")
@@ -761,6 +822,47 @@ class TorchEmulator:
         drho = [self._per_tensor(torch.stack([per_dir[d][o] for d in range(n_dir)]), x) for o in range(len(rdm_objs))]
         return SubsystemSensitivities(rho, drho, times)
 
+    def run_occupation_sensitivities(self, x: list, solver: SolverType = SolverType.DP5_SE, dist_grad: bool = False,
+                                     **options: Any) -> "OccupationSensitivities":
+        """The occupation correlations — the moments behind every ``<n_i>`` and ``<n_i n_j>`` — AND their derivatives w.r.t. the
+        tensors in ``x`` at EVERY evaluation time, from one forward-mode sweep (``rydiff_forward_tangent`` with
+        ``RYDIFF_TANGENT_MOMENTS``): at every save point the sweep holds the state and one tangent state per scalar entry of ``x``,
+        and the moments of ``2 Re(conj psi . dpsi)`` are formed natively beside those of ``|psi|^2``, one read of each vector.
+        What the loop of one reverse sweep per evaluation time and per scalar functional (a structure factor, one ``g_ij``)
+        through ``run(observables=[OccupationCorrelations()])`` delivers.
+
+        ``x`` is what ``run_sensitivities`` takes.  Noiseless Ising and XY runs (the exchange rides in the sweep as constant pair
+        terms).  Returns ``OccupationSensitivities``."""
+        x, solver = self._check_sensitivity_request(
+            "run_occupation_sensitivities", x, solver,
+            averaging=": OccupationCorrelations stays refused there",
+            master_equation="run_occupation_sensitivities is not available for master-equation runs (collapse-operator noise, "
+                            "DP5_ME): occupation correlations are evaluated natively on kets only; hand run_sensitivities "
+                            "DiagonalObservable projectors instead.",
+            all_basis="run_occupation_sensitivities is not available in the three-level all-basis: an atom is two qubits "
+                      "there, and the native tangent sweep takes no conditioned flips / ones-counting terms.")
+        ham, dev = self._hamiltonian, self._compute_device
+        if dist_grad:
+            self._enable_dist_grad()
+        times = self._eval_times_array.detach()
+        d_amp, d_det, d_u = self._table_tangents(x)
+        n_dir = sum(int(t.numel()) for t in x)
+        psi0 = self.initial_state
+        psi_bd = psi0.reshape(psi0.shape[0], -1).transpose(0, 1).to(dev)
+        spec = ham.problem_spec(solver=solver, tol=tolerance_from_options(dict(options)), store_states=False)
+        spec.moments = True
+        if d_amp is None and d_det is None and d_u is None:  # nothing in x reaches the tables: zero derivatives, values from a plain run
+            expect, dexpect = self._plain_run_with_zero_tangents(
+                n_dir, lambda: evolve(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, None)[1])
+        else:
+            # the complex tables and the unrotated psi0, as in run_sensitivities (the moments are diagonal: they see no frame)
+            expect, dexpect = evolve_tangent(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, None,
+                                             d_amp=d_amp, d_det=d_det, d_u=d_u,
+                                             flags=_native.TANGENT_MOMENTS | (_native.TANGENT_PAIR_TERMS if spec.pair_terms else 0))
+        moments = split_moments(expect, ham._size)[1]
+        dmom = torch.stack([split_moments(dexpect[d], ham._size)[1] for d in range(n_dir)])  # (n_dir, rows, n_t, B)
+        return OccupationSensitivities(moments, self._per_tensor(dmom, x), times, 0 if ham.basis_name == "ground-rydberg" else 1)
+
     def run_quantum_fisher(self, x: list, observables: list = (), solver: SolverType = SolverType.DP5_SE, dist_grad: bool = False,
                            **options: Any) -> "QuantumGeometry":
         """The quantum Fisher information matrix of the state w.r.t. the scalar entries of the tensors in ``x`` at EVERY evaluation
@@ -788,8 +890,9 @@ class TorchEmulator:
         full = ham.dim ** ham._size
         for obs in observables:
             if isinstance(obs, OccupationCorrelations):
-                raise NotImplementedError("run_quantum_fisher does not take OccupationCorrelations (the geometry sweep evaluates no "
-                                          "occupation correlations); request them from run().")
+                raise NotImplementedError("run_quantum_fisher does not take OccupationCorrelations (its rows are one scalar per "
+                                          "observable); run_occupation_sensitivities returns them and their derivatives at every "
+                                          "evaluation time (solver.evolve_geometry takes them with _native.TANGENT_MOMENTS).")
             if not isinstance(obs, (DiagonalObservable, PauliObservable, StateOverlap)) and not (isinstance(obs, Tensor) and obs.ndim == 2):
                 raise TypeError("observables must be DiagonalObservable / PauliObservable / StateOverlap objects or diagonal (dim, dim) tensors")
             if tuple(obs.shape) != (full, full):

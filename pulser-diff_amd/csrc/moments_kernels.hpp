@@ -9,6 +9,9 @@
 //                    (registers), across the 6 lane bits by exchanges with the partner lane (every lane leaves a step with the merged
 //                    record), across the 4 waves through LDS.  Up to 12 qubits the tile is the state and the rows go straight to
 //                    expect_out; beyond, the tile's 79 doubles go to the workspace ([state][entry][tile], plan.hpp: off_moments).
+// k_moments_tangent  the same body (moments_tile<TAN>) on the signed weight dp[y] = 2 Re(conj psi[y] dpsi_d[y]): the tangent of a moment
+//                    of p is that moment of dp.  One direction per grid.z; rows into direction d's Moments block of dexpect_out, or
+//                    the tile records into the tangent sweep's region ([D][B][79][tiles], tangent_launch.hpp: off_dmoments).
 // k_moments_finish   the rows from the tile records, one wave per row: the tile index is the high bits, so low singles / low-low pairs
 //                    are plain sums over the tiles, high singles / high-high pairs bit moments of the tile sums S_tau, high-low pairs
 //                    bit moments of f_tau[j].  Lane l takes tiles l, l + 64, ... ascending, then the wave tree.
@@ -112,13 +115,17 @@ struct MomentsTileArgs {
     uint32_t dim, tiles;
 };
 
-// grid (tiles, b_count * n_k), 256 threads
-__global__ __launch_bounds__(256) void k_moments_tile(MomentsTileArgs a) {
+// The tile reduction, one body for the moments of p = |psi|^2 (TAN = false: k_moments_tile) and for their tangents, the same moments
+// of the signed weight dp = 2 Re(conj psi . dpsi) (TAN = true: k_moments_tangent).  `dvec`: the tangent vector laid out like a.psi
+// (TAN only); `out` / `rec`: where this launch's rows / tile records go.
+template <bool TAN>
+__device__ __forceinline__ void moments_tile(const MomentsTileArgs& a, const double2* dvec, double* out, double* rec) {
     __shared__ double wrec[4][kMomWaveEntries];
     const int b = a.b_first + int(blockIdx.y) % a.b_count;
     const int kk = int(blockIdx.y) / a.b_count;
     const uint32_t tau = blockIdx.x;
-    const double2* __restrict__ psi = a.psi + size_t(kk) * a.kstride + size_t(b) * a.dim + (size_t(tau) << kMomTileBits);
+    const size_t first = size_t(kk) * a.kstride + size_t(b) * a.dim + (size_t(tau) << kMomTileBits);
+    const double2* __restrict__ psi = a.psi + first;
     const uint32_t left = a.dim - (tau << kMomTileBits);  // amplitudes from the tile's first one on (a tile past the state: none)
     double2 v[1 << kMomLocalBits];
 #pragma unroll
@@ -127,8 +134,20 @@ __global__ __launch_bounds__(256) void k_moments_tile(MomentsTileArgs a) {
         v[r] = t < left ? psi[t] : make_double2(0.0, 0.0);
     }
     double p[1 << kMomLocalBits];
+    if constexpr (TAN) {
+        const double2* __restrict__ dpsi = dvec + first;
+        double2 w[1 << kMomLocalBits];
 #pragma unroll
-    for (uint32_t r = 0; r < (1u << kMomLocalBits); ++r) p[r] = v[r].x * v[r].x + v[r].y * v[r].y;
+        for (uint32_t r = 0; r < (1u << kMomLocalBits); ++r) {
+            const uint32_t t = r * 256u + threadIdx.x;
+            w[r] = t < left ? dpsi[t] : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (uint32_t r = 0; r < (1u << kMomLocalBits); ++r) p[r] = 2.0 * (v[r].x * w[r].x + v[r].y * w[r].y);
+    } else {
+#pragma unroll
+        for (uint32_t r = 0; r < (1u << kMomLocalBits); ++r) p[r] = v[r].x * v[r].x + v[r].y * v[r].y;
+    }
     const MomRec<4> r4 = mom_local<4>(p);
     const MomRec<5> r5 = mom_lane_merge<4>(r4, 0);
     const MomRec<6> r6 = mom_lane_merge<5>(r5, 1);
@@ -164,14 +183,30 @@ __global__ __launch_bounds__(256) void k_moments_tile(MomentsTileArgs a) {
     }
     const size_t state = size_t(kk) * a.B + b;
     if (a.tiles > 1u) {
-        a.rec[(state * kMomEntries + e) * a.tiles + tau] = val;
+        rec[(state * kMomEntries + e) * a.tiles + tau] = val;
         return;
     }
     int ba, bb;
     const int nb = mom_entry_bits(e, ba, bb);
     if (ba >= a.N || bb >= a.N) return;  // a bit the register does not have
     const int row = nb == 0 ? 0 : (nb == 1 ? mom_row1(a.N, ba) : mom_row2(a.N, ba, bb));
-    a.out[(size_t(row) * a.n_tsave + a.k0 + kk) * a.B + b] = val;
+    out[(size_t(row) * a.n_tsave + a.k0 + kk) * a.B + b] = val;
+}
+
+// grid (tiles, b_count * n_k), 256 threads
+__global__ __launch_bounds__(256) void k_moments_tile(MomentsTileArgs a) { moments_tile<false>(a, nullptr, a.out, a.rec); }
+
+struct MomentsTangentArgs {
+    MomentsTileArgs t;   // psi: the state of vec = [1 + D][B][dim] (one save point: kstride 0); out / rec: those of direction 0
+    size_t vstride;      // amplitudes between the vectors of vec: B * dim
+    size_t out_dstride;  // doubles between the directions of dexpect_out: ExpectRows::size()
+    size_t rec_dstride;  // doubles between the directions' tile records: B * 79 * tiles
+};
+
+// grid (tiles, B, n_dir), 256 threads: direction d = blockIdx.z reads psi and dpsi_d
+__global__ __launch_bounds__(256) void k_moments_tangent(MomentsTangentArgs a) {
+    const size_t d = blockIdx.z;
+    moments_tile<true>(a.t, a.t.psi + (1 + d) * a.vstride, a.t.out + d * a.out_dstride, a.t.rec + d * a.rec_dstride);
 }
 
 struct MomentsFinishArgs {
@@ -179,9 +214,10 @@ struct MomentsFinishArgs {
     double* out;        // the Moments block of expect_out
     int N, n_tsave, k0, B, b_first, b_count;
     uint32_t tiles;     // 2^(N - 12), at least 2
+    size_t rec_dstride, out_dstride;  // tangent records: doubles between the directions (grid.z) of rec / of out; else 0
 };
 
-// grid (79 + H + 12 H + H (H - 1) / 2, b_count * n_k), H = N - 12 high bits; one wave per row
+// grid (79 + H + 12 H + H (H - 1) / 2, b_count * n_k, directions or 1), H = N - 12 high bits; one wave per row
 __global__ __launch_bounds__(64) void k_moments_finish(MomentsFinishArgs a) {
     const int b = a.b_first + int(blockIdx.y) % a.b_count;
     const int kk = int(blockIdx.y) / a.b_count;
@@ -212,12 +248,12 @@ __global__ __launch_bounds__(64) void k_moments_finish(MomentsFinishArgs a) {
         mask = (1u << h1) | (1u << h2);
         row = mom_row2(a.N, kMomTileBits + h1, kMomTileBits + h2);
     }
-    const double* __restrict__ src = a.rec + ((size_t(kk) * a.B + b) * kMomEntries + col) * a.tiles;
+    const double* __restrict__ src = a.rec + size_t(blockIdx.z) * a.rec_dstride + ((size_t(kk) * a.B + b) * kMomEntries + col) * a.tiles;
     double s = 0.0;
     for (uint32_t tau = threadIdx.x; tau < a.tiles; tau += 64u)  // ascending, the same trip for every row
         if ((tau & mask) == mask) s += src[tau];
     s = wave_sum(s);
-    if (threadIdx.x == 0) a.out[(size_t(row) * a.n_tsave + a.k0 + kk) * a.B + b] = s;
+    if (threadIdx.x == 0) a.out[size_t(blockIdx.z) * a.out_dstride + (size_t(row) * a.n_tsave + a.k0 + kk) * a.B + b] = s;
 }
 
 struct MomentsApplyArgs {

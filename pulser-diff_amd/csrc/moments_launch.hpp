@@ -1,8 +1,30 @@
-// moments_launch.hpp — occupation correlations (moments_kernels.hpp): the evaluation launches of the forward sweeps and the moments
-// part of the observable cotangent (overlap_launch.hpp: launch_observable_cotangent).
+// moments_launch.hpp — occupation correlations (moments_kernels.hpp): the evaluation launches of the forward sweeps, the moment
+// tangents of the tangent sweep (tangent_launch.hpp: launch_expect_tangent) and the moments part of the observable cotangent
+// (overlap_launch.hpp: launch_observable_cotangent).
 #pragma once
 
 namespace {
+
+// the rows of save points k0 .. k0 + nk - 1 from the tile records `rec` ([n_dir][nk][B][79][tiles], n_dir = 1: the values)
+void launch_moments_finish(const ForwardCtx& c, const double* rec, double* out, int k0, int nk, const BatchSlice& bs, int n_dir,
+                           size_t rec_dstride, size_t out_dstride) {
+    const Plan& pl = c.rt.pl;
+    MomentsFinishArgs f{};
+    f.rec = rec;
+    f.out = out;
+    f.N = pl.N;
+    f.n_tsave = pl.T + 1;
+    f.k0 = k0;
+    f.B = pl.B;
+    f.b_first = bs.first;
+    f.b_count = bs.count;
+    f.tiles = uint32_t(pl.dim >> kMomTileBits);
+    f.rec_dstride = rec_dstride;
+    f.out_dstride = out_dstride;
+    const int H = pl.N - kMomTileBits;
+    hipLaunchKernelGGL(k_moments_finish, dim3(unsigned(kMomEntries + H + kMomTileBits * H + H * (H - 1) / 2), unsigned(bs.count * nk), unsigned(n_dir)),
+                       dim3(64), 0, c.stream, f);
+}
 
 // S, B_q, B_qr of the states of save points k0 .. k0 + nk - 1 (kstride amplitudes apart; `psi` is the one at k0, trajectory 0),
 // trajectories of `bs`.  Up to 12 qubits one launch covers every state; beyond, the tile records of one save point at a time go
@@ -29,22 +51,42 @@ int launch_moments_expect(const ForwardCtx& c, const double2* psi, size_t kstrid
         a.tiles = tiles;
         hipLaunchKernelGGL(k_moments_tile, dim3(tiles, unsigned(bs.count * n)), dim3(256), 0, c.stream, a);
         LAUNCH_CHECK();
-        if (tiles == 1u) continue;
-        MomentsFinishArgs f{};
-        f.rec = a.rec;
-        f.out = c.moments_out;
-        f.N = pl.N;
-        f.n_tsave = pl.T + 1;
-        f.k0 = k0 + k;
-        f.B = pl.B;
-        f.b_first = bs.first;
-        f.b_count = bs.count;
-        f.tiles = tiles;
-        const int H = pl.N - kMomTileBits;
-        hipLaunchKernelGGL(k_moments_finish, dim3(unsigned(kMomEntries + H + kMomTileBits * H + H * (H - 1) / 2), unsigned(bs.count * n)),
-                           dim3(64), 0, c.stream, f);
+        if (tiles > 1u) launch_moments_finish(c, a.rec, c.moments_out, k0 + k, n, bs, 1, 0, 0);
         LAUNCH_CHECK();
     }
+    return RYDIFF_OK;
+}
+
+// The tangents of S, B_q, B_qr in every direction at save point k: vec = [1 + n_dir][B][dim] with the state first; `out`: the first
+// Moments row of direction 0 in dexpect_out, dstride doubles between directions.  One launch over all directions (grid.z); past 12
+// qubits their tile records go to the tangent sweep's own region (c.moments_drec: [n_dir][B][79][tiles]) and a second launch turns
+// them into the rows.  Every entry is written.
+int launch_moments_tangent(const ForwardCtx& c, const double2* vec, int n_dir, int k, double* out, size_t dstride) {
+    const Plan& pl = c.rt.pl;
+    if (!out) return RYDIFF_OK;
+    const uint32_t tiles = uint32_t(std::max<size_t>(pl.dim >> kMomTileBits, 1));
+    if (tiles > 1u && !c.moments_drec) return fail(RYDIFF_EINVAL, "internal: no workspace region for the moment tangents' tile records");
+    const BatchSlice bs{0, pl.B, false};
+    MomentsTangentArgs a{};
+    a.t.psi = vec;
+    a.t.kstride = 0;
+    a.t.out = out;
+    a.t.rec = tiles > 1u ? c.moments_drec : nullptr;
+    a.t.N = pl.N;
+    a.t.n_tsave = pl.T + 1;
+    a.t.k0 = k;
+    a.t.B = pl.B;
+    a.t.b_first = 0;
+    a.t.b_count = pl.B;
+    a.t.dim = uint32_t(pl.dim);
+    a.t.tiles = tiles;
+    a.vstride = size_t(pl.B) * pl.dim;
+    a.out_dstride = dstride;
+    a.rec_dstride = tiles > 1u ? size_t(pl.B) * kMomEntries * tiles : 0;
+    hipLaunchKernelGGL(k_moments_tangent, dim3(tiles, unsigned(pl.B), unsigned(n_dir)), dim3(256), 0, c.stream, a);
+    LAUNCH_CHECK();
+    if (tiles > 1u) launch_moments_finish(c, a.t.rec, out, k, 1, bs, n_dir, a.rec_dstride, dstride);
+    LAUNCH_CHECK();
     return RYDIFF_OK;
 }
 

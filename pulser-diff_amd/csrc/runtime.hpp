@@ -639,6 +639,7 @@ struct ForwardCtx : SweepCtx {
     double* overlap_out = nullptr; // Overlap
     double* rdm_out = nullptr;     // Rdm
     double* moments_out = nullptr; // Moments
+    double* moments_drec = nullptr;  // tangent sweep past 12 qubits: the tile records of the moment tangents (TangentLayout::off_dmoments)
     double* dm_out = nullptr;      // DmTrace .. End: the first density-matrix row
     const double* shot_u = nullptr;  // RydProblem.shot_uniforms / shots_out where shots are drawn (rydiff_forward with n_shots > 0)
     uint32_t* shots_out = nullptr;

@@ -660,6 +660,7 @@ int tangent_sweep(const RydProblem* p, const RydPlanInfo* info, const RydTangent
     c.psi0 = c.start = vec[0];
     rc = bind_expect_rows(c, expect_out);
     if (rc) return rc;
+    if (pl.moments && pl.moment_tiles() > 1) c.moments_drec = reinterpret_cast<double*>(ws + lay.off_dmoments);
     auto save_point = [&](const double2* v, int k) -> int {  // values (the existing reductions on psi) and tangents of every row
         if (c.want_exp)
             if (const int r = launch_expect(c, v, k)) return r;

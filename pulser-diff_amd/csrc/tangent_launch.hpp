@@ -12,9 +12,14 @@ int tangent_validate(const RydProblem* p, const RydPlanInfo* info, int n_dir, in
         return fail(RYDIFF_EINVAL, "n_dir must be in [1, " + std::to_string(RYDIFF_MAX_TANGENTS) + "], got " + std::to_string(n_dir));
     if (!info) return fail(RYDIFF_EINVAL, "the tangent sweep needs the plan of rydiff_plan(p, 0, 0, ...): null info");
     if (p->shard_bits > 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented for state-sharded runs (shard_bits > 0)");
-    if (flags & ~(RYDIFF_TANGENT_PAIR_TERMS | RYDIFF_TANGENT_DENSITY_MATRIX | RYDIFF_TANGENT_RDMS))
+    if (flags & ~(RYDIFF_TANGENT_PAIR_TERMS | RYDIFF_TANGENT_DENSITY_MATRIX | RYDIFF_TANGENT_RDMS | RYDIFF_TANGENT_MOMENTS))
         return fail(RYDIFF_EINVAL, "RydTangent.flags: unknown bits " + std::to_string(flags));
-    // dense pair terms, density-matrix registers and reduced density matrices run only where the caller asks for them (RydTangent.flags): a caller that does
+    // the moments flag is valid only on a problem that has the block: callers written before it existed probe bit 8 as an unknown one on
+    // problems without bit moments and keep their RYDIFF_EINVAL
+    if ((flags & RYDIFF_TANGENT_MOMENTS) && p->bit_moments == 0)
+        return fail(RYDIFF_EINVAL, "RydTangent.flags: RYDIFF_TANGENT_MOMENTS (8) asks for the Moments block of a problem that has none "
+                                   "(bit_moments = 0)");
+    // dense pair terms, density-matrix registers, reduced density matrices and bit moments run only where the caller asks for them (RydTangent.flags): a caller that does
     // not know of them keeps the refusals it was written against
     if (p->n_pair_terms > 0 && !(flags & RYDIFF_TANGENT_PAIR_TERMS))
         return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented with dense pair terms (n_pair_terms > 0) unless RydTangent.flags "
@@ -22,7 +27,9 @@ int tangent_validate(const RydProblem* p, const RydPlanInfo* info, int n_dir, in
     if (p->amp_conditioned_terms || p->det_ones_terms)
         return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented with conditioned flips / ones-counting terms (three-level registers)");
     if (p->n_shots > 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: measurement shots are not implemented (n_shots > 0): draw them in rydiff_forward");
-    if (p->bit_moments != 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: bit moments are not implemented (bit_moments != 0): request them from rydiff_forward");
+    if (p->bit_moments != 0 && (!(flags & RYDIFF_TANGENT_MOMENTS) || p->dm_atoms != 0))  // (moments of diag rho: no kernel, whatever the flags)
+        return fail(RYDIFF_ENOTIMPL, "tangent sweep: bit moments are not implemented (bit_moments != 0) unless RydTangent.flags has "
+                                     "RYDIFF_TANGENT_MOMENTS (kets only, dm_atoms = 0): request them from rydiff_forward");
     if (p->n_rdms > 0 && !(flags & RYDIFF_TANGENT_RDMS))
         return fail(RYDIFF_ENOTIMPL, "tangent sweep: reduced density matrices are not implemented (n_rdms > 0) unless RydTangent.flags "
                                      "has RYDIFF_TANGENT_RDMS");
@@ -48,6 +55,7 @@ struct TangentLayout {
     size_t off_vec[2] = {0, 0};  // ping-pong: [1 + D][B][dim] amplitudes each
     size_t off_dcoef = 0;        // [D][Bc][E][NC] doubles
     size_t off_dudiag = 0;       // [D][dim] doubles
+    size_t off_dmoments = 0;     // bit moments past 12 qubits: the tile records of the moment tangents, [n_dir][B][79][dim >> 12] doubles
     size_t total = 0;
     long dcoef_dstride = 0;      // doubles
 };
@@ -56,8 +64,8 @@ struct TangentLayout {
 // vector, zero records: it stays zero and nothing reads it)
 int tangent_padded(int n_dir) { return n_dir == 5 ? 6 : (n_dir == 7 ? 8 : n_dir); }
 
-TangentLayout tangent_layout(const Plan& pl, size_t base, int n_dir) {
-    n_dir = tangent_padded(n_dir);
+TangentLayout tangent_layout(const Plan& pl, size_t base, int n_real) {
+    const int n_dir = tangent_padded(n_real);
     TangentLayout t;
     size_t off = align_up(base);
     auto take = [&](size_t bytes) {
@@ -71,6 +79,8 @@ TangentLayout tangent_layout(const Plan& pl, size_t base, int n_dir) {
     t.dcoef_dstride = long(pl.Bc) * long(pl.stages.size()) * pl.NC;
     t.off_dcoef = take(size_t(n_dir) * size_t(std::max<long>(t.dcoef_dstride, 1)) * sizeof(double));
     t.off_dudiag = take(size_t(n_dir) * pl.dim * sizeof(double));
+    // (only the real directions' moments are evaluated; the values' records go through the plan's own region, off_moments)
+    t.off_dmoments = take((pl.moments && pl.moment_tiles() > 1) ? size_t(n_real) * pl.B * kMomEntries * pl.moment_tiles() * sizeof(double) : 0);
     t.total = off;
     return t;
 }
@@ -206,6 +216,8 @@ int launch_expect_tangent(const ForwardCtx& c, const double2* vec, int n_dir, in
     }
     if (pl.n_rdm > 0)  // d rho_A = Tr_E(|dpsi_d><psi| + |psi><dpsi_d|): k_rdm_tangent, one launch per RDM over all directions
         if (const int rc = launch_rdm_tangent(c, vec, n_dir, k, rows.at(dexp, ExpectRows::Rdm), dstride)) return rc;
+    if (pl.moments)  // d S, d B_q, d B_qr: the moments of 2 Re(conj psi . dpsi_d), k_moments_tangent over all directions
+        if (const int rc = launch_moments_tangent(c, vec, n_dir, k, rows.at(dexp, ExpectRows::Moments), dstride)) return rc;
     if (pl.dm_rows()) {
         // diagonal, Pauli and fidelity rows are linear in vec(rho): k_dm_trace / k_dm_fidelity as they are, on d rho_d, into direction
         // d's density-matrix rows; the purity |v|^2 has the tangent 2 Re <v|dv_d>

@@ -82,6 +82,16 @@ def deriv_rdm_all_times(sim, x: list, subsystems: list, **kw):
     return sim.run_rdm_sensitivities(x, subsystems, **kw)
 
 
+def deriv_occupations_all_times(sim, x: list, **kw):
+    """The occupation correlations — every ``<n_i>`` and ``<n_i n_j>`` — AND their derivatives w.r.t. the scalar entries of ``x`` at
+    EVERY evaluation time in one call: ``sim.run_occupation_sensitivities(x, **kw)`` — the tangent sweep of
+    ``deriv_param_all_times`` with the moments of ``2 Re(conj psi . dpsi)`` formed natively at every save point, instead of one
+    reverse sweep per evaluation time and scalar functional through ``run(observables=[OccupationCorrelations()])``.  Returns
+    ``OccupationSensitivities``: ``moments`` (rows, n_t, B), ``dmoments[i]`` (rows, n_t, B, *x[i].shape), ``times`` and
+    ``occupations`` / ``correlations`` / ``structure_factor`` with their ``d_`` twins."""
+    return sim.run_occupation_sensitivities(x, **kw)
+
+
 def quantum_fisher_information_all_times(sim, x: list, **kw):
     """The quantum Fisher information matrix w.r.t. the scalar entries of ``x`` at EVERY evaluation time in one call:
     ``sim.run_quantum_fisher(x, **kw)`` — the tangent sweep of ``deriv_param_all_times`` with the inner products of the tangent states

@@ -833,15 +833,20 @@ def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsav
     ``d_psi0`` are ``vec(rho0)`` / ``vec(d rho0)``, and the density-matrix rows — diagonal, Pauli, fidelity, purity — and their
     tangents follow the other rows, as in ``evolve``.  ``_native.TANGENT_RDMS``: the reduced density matrices of ``spec.rdms`` (kets
     only) join the rows behind the overlaps, values in ``expect`` and ``d rho_A = Tr_E(|dpsi><psi| + |psi><dpsi|)`` in ``dexpect``;
-    ``split_observables`` takes them out of ``expect`` and, direction by direction, out of ``dexpect[d]``."""
+    ``split_observables`` takes them out of ``expect`` and, direction by direction, out of ``dexpect[d]``.
+    ``_native.TANGENT_MOMENTS``: the occupation correlations of ``spec.moments`` (kets only) join the rows behind the RDM block — the
+    moments ``S, B_q, B_qr`` in ``expect``, the same moments of ``2 Re(conj psi . dpsi_d)`` in ``dexpect[d]``, formed in a fixed order
+    (two calls return the same bits); ``split_moments`` takes the block off ``expect`` and off each ``dexpect[d]``.  The flag without
+    ``spec.moments`` is a ``ValueError`` (``RYDIFF_EINVAL``: it asks for a block the problem does not have)."""
     if (spec.rdms is not None and not (int(flags) & _native.TANGENT_RDMS)) or (spec.dm is not None and spec.dm.rdms is not None):
         raise NotImplementedError("evolve_tangent evaluates no reduced density matrices (rydiff_forward_tangent: RYDIFF_ENOTIMPL) unless "
                                   "flags has _native.TANGENT_RDMS (kets only); or request them from evolve")
     if spec.dm is not None and not (int(flags) & _native.TANGENT_DENSITY_MATRIX):
         raise NotImplementedError("evolve_tangent takes no density-matrix registers (rydiff_forward_tangent: RYDIFF_ENOTIMPL) unless "
                                   "flags has _native.TANGENT_DENSITY_MATRIX (lindblad.mesolve_tangent); or differentiate evolve")
-    if spec.moments:
-        raise NotImplementedError("evolve_tangent evaluates no occupation correlations (rydiff_forward_tangent: RYDIFF_ENOTIMPL); request them from evolve")
+    if spec.moments and (spec.dm is not None or not (int(flags) & _native.TANGENT_MOMENTS)):
+        raise NotImplementedError("evolve_tangent evaluates no occupation correlations (rydiff_forward_tangent: RYDIFF_ENOTIMPL) unless "
+                                  "flags has _native.TANGENT_MOMENTS (kets only); or request them from evolve")
     if spec.shots is not None or (spec.dm is not None and spec.dm.shots):
         raise NotImplementedError("evolve_tangent draws no measurement shots (rydiff_forward_tangent: RYDIFF_ENOTIMPL); request them from evolve")
     L = _native.lib()
@@ -890,8 +895,9 @@ def evolve_geometry(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsa
     inputs return bit-identical matrices.  Same arguments as ``evolve_tangent``; tangents of inputs the problem does not have give
     zero rows and columns.  More than 8 directions run one sweep per pair of groups of 4 (``geometry.geometry_sweeps``).
     ``flags=_native.TANGENT_PAIR_TERMS`` takes dense pair terms on kets, ``_native.TANGENT_RDMS`` the reduced density matrices of
-    ``spec.rdms`` (rows as in ``evolve_tangent``; their sums use atomics and are not part of the fixed order); density-matrix registers
-    stay refused."""
+    ``spec.rdms`` (rows as in ``evolve_tangent``; their sums use atomics and are not part of the fixed order),
+    ``_native.TANGENT_MOMENTS`` the occupation correlations of ``spec.moments`` (fixed order, like the Gram matrix, which they leave
+    as it is); density-matrix registers stay refused."""
     from .geometry import geometry_sweeps
 
     if spec.rdms is not None and not (int(flags) & _native.TANGENT_RDMS):
@@ -900,8 +906,9 @@ def evolve_geometry(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsa
     if spec.dm is not None:
         raise NotImplementedError("evolve_geometry takes no density-matrix registers (rydiff_forward_geometry: RYDIFF_ENOTIMPL): the "
                                   "pure-state quantum Fisher information is not the mixed-state one")
-    if spec.moments:
-        raise NotImplementedError("evolve_geometry evaluates no occupation correlations (rydiff_forward_geometry: RYDIFF_ENOTIMPL); request them from evolve")
+    if spec.moments and not (int(flags) & _native.TANGENT_MOMENTS):
+        raise NotImplementedError("evolve_geometry evaluates no occupation correlations (rydiff_forward_geometry: RYDIFF_ENOTIMPL) unless "
+                                  "flags has _native.TANGENT_MOMENTS; or request them from evolve")
     if spec.shots is not None:
         raise NotImplementedError("evolve_geometry draws no measurement shots (rydiff_forward_geometry: RYDIFF_ENOTIMPL); request them from evolve")
     L = _native.lib()

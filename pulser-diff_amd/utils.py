@@ -292,3 +292,22 @@ def structure_factor(g: Tensor, signs) -> Tensor:
     if not bool(torch.all(s.abs() == 1)):
         raise ValueError("signs must be a pattern of +1 and -1")
     return torch.einsum("i,...ij,j->...", s, g, s) / g.shape[-1]
+
+
+# ---- their tangents (the Moments block of the tangent sweep: solver.evolve_tangent with _native.TANGENT_MOMENTS) ----------------
+# ``occupations_from_moments`` and ``occupation_correlations_from_moments`` are linear in the rows, and ``structure_factor`` is
+# linear in g: applied to tangent rows ``dmoments`` as they are they return the tangents.  The connected correlations are not:
+def connected_correlations_tangent(moments: Tensor, dmoments: Tensor, n_qubits: int, occupied_bit: int = 0) -> Tensor:
+    """``d g_ij = d<n_i n_j> - d<n_i> <n_j> - <n_i> d<n_j>`` (the product rule on ``connected_correlations``) from the rows
+    ``moments`` ``(rows, *shape)`` and their tangents ``dmoments`` ``(rows, *lead, *shape)`` — any number of leading direction axes
+    in front of the shape of the values — -> ``(*lead, *shape, N, N)``."""
+    occ = occupations_from_moments(moments, n_qubits, occupied_bit)
+    docc = occupations_from_moments(dmoments, n_qubits, occupied_bit)
+    dnn = occupation_correlations_from_moments(dmoments, n_qubits, occupied_bit)
+    return dnn - (docc[..., :, None] * occ[..., None, :] + occ[..., :, None] * docc[..., None, :])
+
+
+def structure_factor_tangent(moments: Tensor, dmoments: Tensor, n_qubits: int, signs, occupied_bit: int = 0) -> Tensor:
+    """The tangent of ``structure_factor(connected_correlations(moments, ...), signs)`` along ``dmoments`` (shapes as in
+    ``connected_correlations_tangent``) -> ``(*lead, *shape)``."""
+    return structure_factor(connected_correlations_tangent(moments, dmoments, n_qubits, occupied_bit), signs)
