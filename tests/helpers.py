@@ -549,3 +549,167 @@ def shot_band(p: np.ndarray, u: np.ndarray) -> np.ndarray:
     hi = np.minimum(np.searchsorted(cum, tau, side="left"), dim - 1)
     lo = np.maximum(hi - 1, 0)
     return np.minimum(np.abs(tau - cum[hi]), np.abs(tau - cum[lo])) <= 4.0 * dim * 2.0 ** -53 * s
+
+
+# ---- per-atom addressing: one single-qubit amplitude term and one single-qubit detuning term per atom --------------------------------
+def per_atom_terms(n, n_samples, dt, seed, phase=True, undriven=(), undetuned=(), global_drive=False) -> R.HamTerms:
+    """What the stochastic-noise runs, SLM masks and local channels hand over: amp_coeff = det_coeff = None, one extra_amp entry ([q])
+    per driven atom and one extra_det entry ([q]) per detuned atom, on a jittered chain.  With t = linspace(0, 1, n_samples):
+        amplitude of atom q  0.5 * 6 * (s_q sin^2(pi t) + 0.2 cos((q + 1) t)) * exp(-i (0.7 t + phi_q)),  s_q in [1, 1.3], phi_q in [0, 1)
+                             (phase=False: no phase factor at all, a real profile stored as complex)
+        detuning of atom q   -2.5 (2 t - 1) + 0.7 xi_q + 0.3 sin((q + 2) t),  xi_q standard normal
+    No two rows are proportional (every atom has its own frequency), so swapping two groups changes values and gradients.
+    global_drive=True: ONE amplitude term (the profile of "atom 0") on all atoms next to the per-atom detunings — the doppler / SLM
+    shape.  The seeded draws do not depend on undriven / undetuned / global_drive."""
+    g = torch.Generator().manual_seed(seed)
+    coords = torch.stack([torch.arange(n, dtype=torch.float64) * 8.0, torch.rand(n, generator=g, dtype=torch.float64) * 2.0], dim=1)
+    s = 1.0 + 0.3 * torch.rand(n, generator=g, dtype=torch.float64)
+    phi = torch.rand(n, generator=g, dtype=torch.float64)
+    xi = torch.randn(n, generator=g, dtype=torch.float64)
+    t = torch.linspace(0, 1, n_samples, dtype=torch.float64)
+
+    def amp_row(q):
+        a = 0.5 * 6.0 * (s[q] * torch.sin(np.pi * t) ** 2 + 0.2 * torch.cos((q + 1) * t))
+        return (a * torch.exp(-1j * (0.7 * t + phi[q]).to(torch.complex128))) if phase else a.to(torch.complex128)
+
+    terms = R.HamTerms(n, R.interaction_strengths(coords), None, None, dt, n_samples)
+    if global_drive:
+        terms.extra_amp = [(amp_row(0), list(range(n)))]
+    else:
+        terms.extra_amp = [(amp_row(q), [q]) for q in range(n) if q not in undriven]
+    terms.extra_det = [(-2.5 * (2 * t - 1) + 0.7 * xi[q] + 0.3 * torch.sin((q + 2) * t), [q]) for q in range(n) if q not in undetuned]
+    return terms
+
+
+def per_atom_terms_batch(n, n_samples, dt, seeds, **kw) -> list:
+    """Per-trajectory tables: one per_atom_terms per seed, all on the register (u_pairs) of the first."""
+    sets = [per_atom_terms(n, n_samples, dt, seed, **kw) for seed in seeds]
+    for tr in sets[1:]:
+        tr.u_pairs = sets[0].u_pairs
+    return sets
+
+
+def stack_tables(sets, device="cpu", real_amp: bool = False):
+    """A list of B HamTerms with the same term structure -> (amp [B, Ka, n], det [B, Kd, n]) for evolve (to_native only repeats one
+    table set).  real_amp: the amplitude tables as a REAL tensor (they must be phase-free)."""
+    masks = [[tuple(tg) for _, tg in tr.amp_terms()] + [None] + [tuple(tg) for _, tg in tr.det_terms()] for tr in sets]
+    assert all(m == masks[0] for m in masks), "the table sets must share one term structure"
+    amp = torch.stack([torch.stack([c.detach().to(torch.complex128) for c, _ in tr.amp_terms()]) for tr in sets])
+    det = torch.stack([torch.stack([c.detach().to(torch.float64) for c, _ in tr.det_terms()]) for tr in sets])
+    if real_amp:
+        assert float(amp.imag.abs().max()) == 0.0
+        amp = amp.real.contiguous()
+    return amp.to(device), det.to(device)
+
+
+def product_state(n, gen) -> torch.Tensor:
+    """The Kronecker product of n random normalised single-qubit states, (2^n,) complex128 (qubit 0 = the most significant index bit).
+    A Haar-random register state makes every gradient tiny; a product state keeps them at their natural size.  The single-qubit states
+    are (cos(th/2), e^{i phi} sin(th/2)) with cos(th) uniform in [-0.8, 0.8] and phi uniform: both populations at least 0.1.  The
+    detuning of atom q acts through its occupation n_q and its drive through <X_q>, <Y_q>, so an atom that starts at a pole of its
+    Bloch sphere has a gradient row close to zero — with twenty atoms or sixteen trajectories there would always be one."""
+    psi = torch.ones(1, dtype=torch.complex128)
+    for _ in range(n):
+        r = torch.rand(2, generator=gen, dtype=torch.float64)
+        p1 = 0.5 * (1.0 - 0.8 * (2.0 * float(r[0]) - 1.0))
+        v = torch.tensor([np.sqrt(1.0 - p1), np.sqrt(p1) * np.exp(2j * np.pi * float(r[1]))], dtype=torch.complex128)
+        psi = torch.kron(psi, v)
+    return psi
+
+
+ROW_FLOOR = 1e-2  # assert_rows_close: a row is measured against max(its own largest entry, ROW_FLOOR * the tensor's largest entry)
+
+
+def row_errors(got, ref):
+    """Per row r of a [..., K, n_samples] tensor (rows = everything but the last axis): max|got_r - ref_r| / max(max|ref_r|,
+    ROW_FLOOR * max|ref|), and max|ref_r| / max|ref|.  float64 numpy arrays of shape [..., K]."""
+    got, ref = np.asarray(got), np.asarray(ref)
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    scale = np.abs(ref).max(axis=-1)
+    top = float(scale.max())
+    err = np.abs(got - ref).max(axis=-1) / np.maximum(np.maximum(scale, ROW_FLOOR * top), 1e-300)
+    return err, scale / max(top, 1e-300)
+
+
+def assert_rows_close(got, ref, rtol, name="") -> float:
+    """Every row of a gradient [..., K, n_samples] on its own:  max|got_r - ref_r| <= rtol * max(max|ref_r|, 1e-2 * max|ref|).  So that
+    the floor never hides a row, first asserts — on the reference alone — that every row reaches 1e-2 of the largest.  Returns the
+    worst per-row error (for the measurement tables)."""
+    err, ratio = row_errors(got, ref)
+    assert np.isfinite(np.asarray(got)).all(), f"{name}: non-finite entries"
+    assert float(ratio.min()) >= ROW_FLOOR, f"{name}: reference row {np.unravel_index(ratio.argmin(), ratio.shape)} is {ratio.min():.2e} of the largest row"
+    worst = float(err.max())
+    assert worst <= rtol, f"{name}: row {np.unravel_index(err.argmax(), err.shape)} off by {worst:.3e} of its scale (bar {rtol:.0e})"
+    return worst
+
+
+PER_ATOM_TSAVE = (0.0, 0.0041, 0.0102, 0.0163, 0.024)  # four unequal save intervals, off the sample grid
+
+
+def per_atom_loss(states, expect, w, cot):
+    """The loss of the per-atom parity cases, torch on either side: states (n_t, B, dim), expect (n_obs >= 2, n_t, B), w (n_t,), cot
+    (n_t, B, dim).  Every save point is weighted through <O_0>, one through <O_1>, and the states themselves through cot."""
+    return (w[:, None] * expect[0]).sum() - 0.4 * expect[1, expect.shape[1] // 2].sum() + (cot.conj() * states).real.sum()
+
+
+def per_atom_problem(n, batch, seed, n_t=len(PER_ATOM_TSAVE), device="cpu"):
+    """The seeded non-table inputs of a per-atom case on the CPU: psi0 (B, dim) product states, two random diagonal observables (2, dim),
+    the weights linspace(0.5, 1.5, n_t) and state cotangents (n_t, B, dim) at every save point after the first:
+        cot_k = c_k psi0 + sum_q (e_kq Z_q + f_kq X_q) psi0 / sqrt(2 n) + a random part of norm 0.3,   c, e, f seeded complex normals.
+    Z_q psi0 and X_q psi0 are the directions in which a change of atom q's detuning / drive moves the state at first order.  With psi0
+    alone (a random vector would weigh 2^(-n/2)) the gradient row of atom q scales with <Z_q> or <X_q>, <Y_q> of its random single-qubit
+    state, and among many atoms one of those is always close to zero; with its own weight at every save point each row keeps a part
+    of the common size, whatever the atom's state.  device: where the tensors are formed and returned (the seeded draws are the
+    CPU generator's either way; the large registers form their cotangents on the GPU)."""
+    gen = torch.Generator().manual_seed(seed)
+    dim = 2**n
+    psi0 = torch.stack([product_state(n, gen) for _ in range(batch)]).to(device)
+    obs = torch.rand(2, dim, generator=gen, dtype=torch.float64).to(device)
+    w = torch.linspace(0.5, 1.5, n_t, dtype=torch.float64).to(device)
+    c = torch.randn(n_t, generator=gen, dtype=torch.complex128).to(device)
+    ef = (torch.randn(2, n_t, n, generator=gen, dtype=torch.complex128) / np.sqrt(2.0 * n)).to(device)
+    cot = c[:, None, None] * psi0[None] + (0.3 * torch.randn(n_t, batch, dim, generator=gen, dtype=torch.complex128) / np.sqrt(dim)).to(device)
+    sign = torch.tensor([1.0, -1.0], dtype=torch.float64, device=device)
+    for q in range(n):
+        v = psi0.reshape(batch, 2**q, 2, 2 ** (n - 1 - q))  # axis 2: the bit of atom q (qubit 0 = the most significant index bit)
+        zq = (v * sign[None, None, :, None]).reshape(batch, dim)
+        xq = torch.flip(v, dims=(2,)).reshape(batch, dim)
+        cot += ef[0, :, q, None, None] * zq[None] + ef[1, :, q, None, None] * xq[None]
+    cot[0] = 0.0
+    return psi0, obs, w, cot
+
+
+def oracle_value_and_grads(terms, psi0, tsave, obs, w, cot, method="matrix_free"):
+    """States, <O>(t_k), the loss per_atom_loss and its five gradients from torch autograd through one of the CPU references:
+    "matrix_free" (R.krylov_map_matrix_free_torch), "dense" (R.krylov_map_dense) or "magnus" (magnus_cf4_dense at the native default
+    sub-step, the model of DP5_SE).  terms: one HamTerms shared by the B trajectories, or a list of B (per-trajectory tables on one
+    register: run one by one; the U and tsave gradients are summed).  psi0 (B, dim), cot (n_t, B, dim).  Returns numpy arrays: states
+    (n_t, B, dim), expect (n_obs, n_t, B), amp ([B,] Ka, n) complex, det ([B,] Kd, n), u, tsave, psi0 (B, dim)."""
+    if isinstance(terms, (list, tuple)):
+        parts = [oracle_value_and_grads(tr, psi0[b:b + 1], tsave, obs, w, cot[:, b:b + 1], method) for b, tr in enumerate(terms)]
+        out = {k: np.concatenate([p[k] for p in parts], axis=1) for k in ("states", "expect")}
+        out["expect"] = np.concatenate([p["expect"] for p in parts], axis=2)
+        out.update({k: np.stack([p[k] for p in parts]) for k in ("amp", "det")})
+        out.update({k: sum(p[k] for p in parts) for k in ("u", "tsave", "loss")})
+        out["psi0"] = np.concatenate([p["psi0"] for p in parts], axis=0)
+        return out
+    o = R.HamTerms(terms.n_qubits, terms.u_pairs.clone().requires_grad_(True), None, None, terms.dt, terms.n_samples)
+    o.extra_amp = [(c.clone().requires_grad_(True), tg) for c, tg in terms.amp_terms()]
+    o.extra_det = [(c.clone().requires_grad_(True), tg) for c, tg in terms.det_terms()]
+    ts = torch.as_tensor(tsave, dtype=torch.float64).clone().requires_grad_(True)
+    p0 = psi0.T.contiguous().clone().requires_grad_(True)  # (dim, B)
+    if method == "matrix_free":
+        st = R.krylov_map_matrix_free_torch(o, p0, ts)
+    elif method == "dense":
+        st = R.krylov_map_dense(o, p0, ts)
+    elif method == "magnus":
+        st = magnus_cf4_dense(o, p0, ts, h_max=DP5_DEFAULT_H_MAX)
+    else:
+        raise ValueError(method)
+    st = st.permute(0, 2, 1)  # (n_t, B, dim)
+    expect = torch.stack([(st.abs() ** 2 * d[None, None, :]).sum(2) for d in obs])
+    loss = per_atom_loss(st, expect, w, cot)
+    loss.backward()
+    return {"states": st.detach().numpy(), "expect": expect.detach().numpy(), "loss": float(loss),
+            "amp": torch.stack([c.grad for c, _ in o.extra_amp]).numpy(), "det": torch.stack([c.grad for c, _ in o.extra_det]).numpy(),
+            "u": o.u_pairs.grad.numpy(), "tsave": ts.grad.numpy(), "psi0": p0.grad.T.contiguous().numpy()}
