@@ -547,6 +547,37 @@ int rydiff_forward_geometry(const RydProblem* p, const RydPlanInfo* info, const 
                             void* gram_out /* DEVICE complex128 [n_tsave][B][1+n_dir][1+n_dir], required */,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* Classical Fisher information of the occupation-basis measurement (bitstrings) from the tangent sweep: the same sweep as
+ * rydiff_forward_geometry, which at every save point also forms the "classical Gram matrix" of the vectors it carries.  With
+ * u[y] = psi[y] / |psi[y]| the phase of the amplitude, the REAL vectors
+ *   w_0[y] = |psi[y]|  (= sqrt p[y]),     w_{1+d}[y] = 2 Re(conj(u[y]) dpsi_d[y])  (= dp_d[y] / sqrt p[y])
+ * and C_ij(t_k) = sum_y w_i[y] w_j[y], real symmetric.  C_00 = S = <psi|psi>, C_{0,1+d} = dS / d theta_d, and the caller forms
+ *   classical Fisher information   F_C,de = C_{1+d,1+e} / S - C_{0,1+d} C_{0,1+e} / S^2      (valid for unnormalised states)
+ * of p(y) = |psi[y]|^2 / S, to hold against the quantum one of gram_out (F_C <= F_Q as matrices).  An amplitude that is exactly zero
+ * contributes nothing (w_i[y] = 0 for every i: the sum over the support).  The phase is formed without |psi[y]|^2: amplitudes whose
+ * square would overflow or underflow (1e-170, denormals) are legitimate input.
+ *   cgram_out    DEVICE float64 [n_tsave][B][1 + n_dir][1 + n_dir] (required): the FULL symmetric matrix per save point and
+ *                trajectory, the lower triangle an exact copy of the upper one.  Every entry is written, k = 0 included (there C is
+ *                the matrix of psi0 and d_psi0 as given); neither cgram_out nor the workspace needs to be cleared.  A direction
+ *                padded to the kernel's width (n_dir 5, 7) leaves no trace in the output.
+ *   gram_out     as in rydiff_forward_geometry (the same launches, the same bits), or NULL: the Gram matrix is skipped
+ *   dexpect_out  as in rydiff_forward_tangent, or NULL: the row tangents are skipped
+ *   workspace    DEVICE, >= rydiff_fisher_workspace_bytes_flags(p, info, n_dir, flags): the geometry sweep's regions and, behind
+ *                them, gram_blocks * B * (1 + n_pad)(2 + n_pad) / 2 doubles rounded up to 256 bytes — one upper triangle per block
+ *                and trajectory, gram_blocks = min(ceil(2^N / 256), 1024), n_pad = n_dir padded (5 -> 6, 7 -> 8).  Sized as if every
+ *                pointer were given.
+ * Fixed order, like the Gram matrix: no atomics, two calls on the same inputs return bit-identical matrices.  Traffic: one more read
+ * of (1 + n_dir) * B * 2^N * 16 bytes per save point; nothing of size 2^N is written.  Validation happens before anything touches a
+ * device; everything rydiff_forward_geometry refuses is refused here with the same codes (dm_atoms > 0 included: RYDIFF_ENOTIMPL
+ * whatever the flags, and the workspace function returns 0), and the flags mean what they mean there.  RYDIFF_EINVAL also for a NULL
+ * cgram_out; RYDIFF_EWORKSPACE: "fisher workspace too small: need ...". */
+size_t rydiff_fisher_workspace_bytes_flags(const RydProblem* p, const RydPlanInfo* info, int n_dir, int flags);
+int rydiff_forward_fisher(const RydProblem* p, const RydPlanInfo* info, const RydTangent* tangent, const void* psi0,
+                          double* expect_out, double* dexpect_out /* may be NULL */,
+                          void* gram_out /* DEVICE complex128 [n_tsave][B][1+n_dir][1+n_dir], may be NULL */,
+                          double* cgram_out /* DEVICE float64 [n_tsave][B][1+n_dir][1+n_dir], required */,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* One matrix-free application y = H(coefficients) x on DEVICE buffers, for get_hamiltonian-style
  * checks (backend.py:401-427) and micro-benchmarks.  c_amp: HOST complex (re,im) per amp term,
  * c_det: HOST value per det term (already interpolated, reference units as above). */

@@ -167,6 +167,8 @@ EXPORTS = (
     "rydiff_geometry_workspace_bytes",
     "rydiff_geometry_workspace_bytes_flags",
     "rydiff_forward_geometry",
+    "rydiff_fisher_workspace_bytes_flags",
+    "rydiff_forward_fisher",
 )
 
 _lib = None
@@ -224,6 +226,11 @@ def lib() -> ctypes.CDLL:
     L.rydiff_forward_geometry.argtypes = [ctypes.POINTER(RydProblem), ctypes.POINTER(RydPlanInfo), ctypes.POINTER(RydTangent), vp, vp, vp,
                                           vp, vp, ctypes.c_size_t, vp]
     L.rydiff_forward_geometry.restype = i32
+    L.rydiff_fisher_workspace_bytes_flags.argtypes = [ctypes.POINTER(RydProblem), ctypes.POINTER(RydPlanInfo), i32, i32]
+    L.rydiff_fisher_workspace_bytes_flags.restype = ctypes.c_size_t
+    L.rydiff_forward_fisher.argtypes = [ctypes.POINTER(RydProblem), ctypes.POINTER(RydPlanInfo), ctypes.POINTER(RydTangent), vp, vp, vp,
+                                        vp, vp, vp, ctypes.c_size_t, vp]
+    L.rydiff_forward_fisher.restype = i32
     if (L.rydiff_sizeof_problem(), L.rydiff_sizeof_plan_info(), L.rydiff_sizeof_tangent()) != (
             ctypes.sizeof(RydProblem), ctypes.sizeof(RydPlanInfo), ctypes.sizeof(RydTangent)):
         raise RuntimeError(f"{_LIB_PATH} was built from another include/rydiff.h than this binding mirrors (struct sizes differ): rebuild it")

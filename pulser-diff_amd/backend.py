@@ -33,10 +33,11 @@ from .lindblad import (MAX_ME_QUBITS, ME_DEFAULT_TOL, dissipator_block, doubled_
 from .result import SampledResult
 from .simconfig import SimConfig
 from .simresults import CoherentResults, NoisyResults, SimulationResults
-from .solver import (ProblemSpec, SolverType, evolve, evolve_geometry, evolve_tangent, sesolve, split_moments,
+from .solver import (ProblemSpec, SolverType, evolve, evolve_fisher, evolve_geometry, evolve_tangent, sesolve, split_moments,
                      split_observables, tolerance_from_options)
 from .observables import OccupationCorrelations, PauliObservable, Purity, ReducedDensityMatrix, StateOverlap, pack_overlaps
-from .geometry import QuantumGeometry, quantum_geometric_tensor
+from .geometry import (MeasurementFisher, QuantumGeometry, classical_fisher_information, quantum_fisher_information,
+                       quantum_geometric_tensor)
 from .shots import MAX_SHOTS, ShotRequest, indices_to_bitstrings
 from .utils import DiagonalObservable, real_diagonal
 
@@ -882,15 +883,46 @@ class TorchEmulator:
                             "mixed-state one.",
             all_basis="run_quantum_fisher is not available in the three-level all-basis: the native tangent sweep takes "
                       "no conditioned flips / ones-counting terms.")
+        gram, _, values, grads, times = self._run_gram_sweep("run_quantum_fisher", False, x, observables, solver, dist_grad, options)
+        qgt = quantum_geometric_tensor(gram)
+        return QuantumGeometry(gram, qgt, 4.0 * qgt.real, -2.0 * qgt.imag, values, grads, "tangent", times)
+
+    def run_classical_fisher(self, x: list, observables: list = (), solver: SolverType = SolverType.DP5_SE, dist_grad: bool = False,
+                             **options: Any) -> "MeasurementFisher":
+        """The classical Fisher information matrix of the device's one measurement — bitstrings in the occupation basis,
+        ``p(y) = |psi[y]|^2`` — w.r.t. the scalar entries of the tensors in ``x`` at EVERY evaluation time, next to the quantum
+        Fisher information of the same sweep: ``F_C <= F_Q`` as matrices, with equality where the native measurement saturates the
+        quantum Cramer-Rao bound (``geometry.fisher_efficiency``).  One native forward-mode sweep as in ``run_quantum_fisher``,
+        which at every save point also reduces the classical Gram matrix of the state and its tangents
+        (``rydiff_forward_fisher``); no state is stored.  ``x`` and ``observables`` are what ``run_quantum_fisher`` takes.  One
+        initial state gives (n_t, D, D) matrices, several columns of it (n_t, B, D, D).  Pure states only: runs whose state is a
+        density matrix or an average are refused, there is no fallback loop.  Returns ``MeasurementFisher``."""
+        x, solver = self._check_sensitivity_request(
+            "run_classical_fisher", x, solver,
+            averaging=": the bitstring distribution of an average of runs is that of a mixed state, and run_classical_fisher forms "
+                      "the classical Fisher information of a pure state's distribution",
+            master_equation="run_classical_fisher is not available for master-equation runs (collapse-operator noise, DP5_ME): "
+                            "the state is a density matrix, and the classical Fisher information of diag rho is not formed "
+                            "by the tangent sweep.",
+            all_basis="run_classical_fisher is not available in the three-level all-basis: the native tangent sweep takes "
+                      "no conditioned flips / ones-counting terms, and a bitstring there is not one index bit per atom.")
+        gram, cgram, values, grads, times = self._run_gram_sweep("run_classical_fisher", True, x, observables, solver, dist_grad, options)
+        return MeasurementFisher(cgram, classical_fisher_information(cgram), gram, quantum_fisher_information(gram), values, grads,
+                                 "tangent", times)
+
+    def _run_gram_sweep(self, name: str, fisher: bool, x: list, observables: list, solver: SolverType, dist_grad: bool, options: dict):
+        """What ``run_quantum_fisher`` and ``run_classical_fisher`` (`name`) share behind their request checks: the observables, the
+        table tangents, the sweep.  ``(gram, cgram or None, values, grads, times)``."""
         ham, dev = self._hamiltonian, self._compute_device
+        sweep = evolve_fisher if fisher else (lambda *a, **k: evolve_geometry(*a, **k) + (None,))
         if getattr(ham, "pair_terms", ()):
-            raise NotImplementedError("run_quantum_fisher is not available with the XY exchange: this route hands no dense pair terms "
+            raise NotImplementedError(f"{name} is not available with the XY exchange: this route hands no dense pair terms "
                                       "to the tangent sweep (solver.evolve_geometry takes them on request).")
         observables = list(observables)
         full = ham.dim ** ham._size
         for obs in observables:
             if isinstance(obs, OccupationCorrelations):
-                raise NotImplementedError("run_quantum_fisher does not take OccupationCorrelations (its rows are one scalar per "
+                raise NotImplementedError(f"{name} does not take OccupationCorrelations (its rows are one scalar per "
                                           "observable); run_occupation_sensitivities returns them and their derivatives at every "
                                           "evaluation time (solver.evolve_geometry takes them with _native.TANGENT_MOMENTS).")
             if not isinstance(obs, (DiagonalObservable, PauliObservable, StateOverlap)) and not (isinstance(obs, Tensor) and obs.ndim == 2):
@@ -914,20 +946,24 @@ class TorchEmulator:
             spec.overlaps = pack_overlaps(overlap_objs, int(psi_bd.shape[1]), batch, dev)
         if d_amp is None and d_det is None and d_u is None:
             # nothing in x reaches the tables: every tangent state is zero — <psi|psi> and the values from one sweep with one zero direction
-            expect, _, g1 = evolve_geometry(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, obs_diag,
-                                            d_psi0=torch.zeros((1,) + tuple(psi_bd.shape), dtype=torch.complex128, device=dev))
+            expect, _, g1, c1 = sweep(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, obs_diag,
+                                      d_psi0=torch.zeros((1,) + tuple(psi_bd.shape), dtype=torch.complex128, device=dev))
             dexpect = torch.zeros((n_dir,) + tuple(expect.shape), dtype=torch.float64, device=expect.device)
             gram = torch.zeros((n_t, batch, 1 + n_dir, 1 + n_dir), dtype=torch.complex128, device=g1.device)
             gram[:, :, 0, 0] = g1[:, :, 0, 0]
+            cgram = None
+            if fisher:
+                cgram = torch.zeros((n_t, batch, 1 + n_dir, 1 + n_dir), dtype=torch.float64, device=c1.device)
+                cgram[:, :, 0, 0] = c1[:, :, 0, 0]
         else:
-            expect, dexpect, gram = evolve_geometry(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, obs_diag,
-                                                    d_amp=d_amp, d_det=d_det, d_u=d_u)
+            expect, dexpect, gram, cgram = sweep(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, obs_diag,
+                                                 d_amp=d_amp, d_det=d_det, d_u=d_u)
         if batch == 1:
             gram = gram[:, 0]
+            cgram = cgram[:, 0] if fisher else None
         values = expect.sum(dim=-1)[rows]            # (n_rows, n_t): summed over the columns of psi0 like results.expect
         dvals = dexpect.sum(dim=-1)[:, rows]         # (n_dir, n_rows, n_t)
-        qgt = quantum_geometric_tensor(gram)
-        return QuantumGeometry(gram, qgt, 4.0 * qgt.real, -2.0 * qgt.imag, values, self._per_tensor(dvals, x), "tangent", times)
+        return gram, cgram, values, self._per_tensor(dvals, x), times
 
     def _run_noisy(self, psi0: Tensor, solver: SolverType, options: dict, reps: list, bad_atom_configs,
                    meas_errors, native_shots: bool = False) -> NoisyResults:

@@ -49,6 +49,7 @@ using namespace rydiff;
 #include "dm_kernels.hpp"
 #include "tangent_kernels.hpp"
 #include "gram_kernels.hpp"
+#include "fisher_kernels.hpp"
 static_assert(sizeof(PersistFactor) == 48, "plan.hpp sizes the factor table with 48 bytes per entry");
 
 #include "runtime.hpp"
@@ -63,6 +64,7 @@ static_assert(sizeof(PersistFactor) == 48, "plan.hpp sizes the factor table with
 #include "overlap_launch.hpp"
 #include "tangent_launch.hpp"
 #include "gram_launch.hpp"
+#include "fisher_launch.hpp"
 #include "persist_launch.hpp"
 
 namespace {
@@ -600,17 +602,27 @@ size_t rydiff_geometry_workspace_bytes(const RydProblem* p, const RydPlanInfo* i
     return rydiff_geometry_workspace_bytes_flags(p, info, n_dir, 0);
 }
 
+size_t rydiff_fisher_workspace_bytes_flags(const RydProblem* p, const RydPlanInfo* info, int n_dir, int flags) {
+    Runtime rt;
+    TangentLayout lay;
+    if (tangent_plan(p, info, n_dir, flags, rt, lay)) return 0;  // (the refusals of rydiff_forward_geometry, in its order)
+    if (geometry_validate(p)) return 0;
+    return fisher_layout(rt.pl, geometry_layout(rt.pl, lay, n_dir), n_dir).total;
+}
+
 }  // extern "C"
 
 namespace {
 
-// The forward-mode sweep behind rydiff_forward_tangent and rydiff_forward_geometry: the state and n_dir tangents through every
-// factor once (tangent_kernels.hpp); at every save point the observable values, their tangents (dexpect_out, skipped when NULL) and,
-// with `geometry`, the Gram matrix of the (1 + n_dir) vectors (gram_kernels.hpp).  One kernel family: launch per factor, one amplitude
+// The forward-mode sweep behind rydiff_forward_tangent, rydiff_forward_geometry and rydiff_forward_fisher: the state and n_dir tangents
+// through every factor once (tangent_kernels.hpp); at every save point the observable values, their tangents (dexpect_out, skipped when
+// NULL), with `geometry` the Gram matrix of the (1 + n_dir) vectors (gram_kernels.hpp) and with `fisher` (which implies `geometry`: its
+// refusals and its workspace; gram_out is optional then) their classical Gram matrix (fisher_kernels.hpp).  One kernel family: launch per factor, one amplitude
 // per thread; dense pair terms (the dissipator of a master-equation run, the XY exchange) ride in the same pass.  On the doubled
 // register of a density matrix (dm_atoms > 0) the vectors are vec(rho) and vec(d rho_d), and the density-matrix rows follow the ket rows.
 int tangent_sweep(const RydProblem* p, const RydPlanInfo* info, const RydTangent* tg, const void* psi0, double* expect_out,
-                  double* dexpect_out, bool geometry, void* gram_out, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+                  double* dexpect_out, bool geometry, void* gram_out, bool fisher, double* cgram_out, void* workspace, size_t workspace_bytes,
+                  hipStream_t stream) {
     // ---- host-only validation: nothing below this block runs unless all of it passes ----
     if (!p) return fail(RYDIFF_EINVAL, "null problem");
     if (!tg) return fail(RYDIFF_EINVAL, "null tangent");
@@ -620,7 +632,8 @@ int tangent_sweep(const RydProblem* p, const RydPlanInfo* info, const RydTangent
     if (!tg->d_amp && !tg->d_det && !tg->d_u && !tg->d_psi0)
         return fail(RYDIFF_EINVAL, "tangent: all of d_amp, d_det, d_u, d_psi0 are NULL (nothing to differentiate)");
     if (!geometry && !dexpect_out) return fail(RYDIFF_EINVAL, "null dexpect_out");
-    if (geometry && !gram_out) return fail(RYDIFF_EINVAL, "null gram_out");
+    if (geometry && !fisher && !gram_out) return fail(RYDIFF_EINVAL, "null gram_out");
+    if (fisher && !cgram_out) return fail(RYDIFF_EINVAL, "null cgram_out");
     if (!psi0) return fail(RYDIFF_EINVAL, "null psi0");
     Runtime rt0;
     TangentLayout lay;
@@ -628,10 +641,12 @@ int tangent_sweep(const RydProblem* p, const RydPlanInfo* info, const RydTangent
     if (rc) return rc;
     GeometryLayout glay;
     if (geometry) glay = geometry_layout(rt0.pl, lay, tg->n_dir);
-    const size_t need = geometry ? glay.total : lay.total;
+    FisherLayout flay;
+    if (fisher) flay = fisher_layout(rt0.pl, glay, tg->n_dir);
+    const size_t need = fisher ? flay.total : (geometry ? glay.total : lay.total);
     if (!workspace) return fail(RYDIFF_EINVAL, "null workspace");
     if (workspace_bytes < need)
-        return fail(RYDIFF_EWORKSPACE, std::string(geometry ? "geometry" : "tangent") + " workspace too small: need " + std::to_string(need) +
+        return fail(RYDIFF_EWORKSPACE, std::string(fisher ? "fisher" : (geometry ? "geometry" : "tangent")) + " workspace too small: need " + std::to_string(need) +
                                            " bytes, got " + std::to_string(workspace_bytes));
     // ---- device work ----
     RydProblem q = *p;
@@ -667,7 +682,9 @@ int tangent_sweep(const RydProblem* p, const RydPlanInfo* info, const RydTangent
         if (const int r = launch_observables_expect(c, v, 0, k, 1, BatchSlice{0, pl.B, false})) return r;
         if (dexpect_out)
             if (const int r = launch_expect_tangent(c, v, D, k, dexpect_out)) return r;
-        return geometry ? launch_gram(rt, ws, glay, v, D, k, static_cast<double2*>(gram_out), stream) : RYDIFF_OK;
+        if (geometry && gram_out)
+            if (const int r = launch_gram(rt, ws, glay, v, D, k, static_cast<double2*>(gram_out), stream)) return r;
+        return fisher ? launch_cfi(rt, ws, flay, v, D, k, cgram_out, stream) : RYDIFF_OK;
     };
     rc = save_point(vec[0], 0);
     if (rc) return rc;
@@ -694,13 +711,23 @@ extern "C" {
 
 int rydiff_forward_tangent(const RydProblem* p, const RydPlanInfo* info, const RydTangent* tg, const void* psi0, double* expect_out,
                            double* dexpect_out, void* workspace, size_t workspace_bytes, void* stream_) {
-    return tangent_sweep(p, info, tg, psi0, expect_out, dexpect_out, false, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream_));
+    return tangent_sweep(p, info, tg, psi0, expect_out, dexpect_out, false, nullptr, false, nullptr, workspace, workspace_bytes,
+                         static_cast<hipStream_t>(stream_));
 }
 
 // The same sweep with the Gram matrix of (psi, dpsi_0 .. dpsi_{n_dir - 1}) at every save point; the row tangents are optional here.
 int rydiff_forward_geometry(const RydProblem* p, const RydPlanInfo* info, const RydTangent* tg, const void* psi0, double* expect_out,
                             double* dexpect_out, void* gram_out, void* workspace, size_t workspace_bytes, void* stream_) {
-    return tangent_sweep(p, info, tg, psi0, expect_out, dexpect_out, true, gram_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream_));
+    return tangent_sweep(p, info, tg, psi0, expect_out, dexpect_out, true, gram_out, false, nullptr, workspace, workspace_bytes,
+                         static_cast<hipStream_t>(stream_));
+}
+
+// The geometry sweep with the classical Gram matrix of the same vectors (the occupation-basis measurement) at every save point; the
+// Gram matrix itself is optional here.
+int rydiff_forward_fisher(const RydProblem* p, const RydPlanInfo* info, const RydTangent* tg, const void* psi0, double* expect_out,
+                          double* dexpect_out, void* gram_out, double* cgram_out, void* workspace, size_t workspace_bytes, void* stream_) {
+    return tangent_sweep(p, info, tg, psi0, expect_out, dexpect_out, true, gram_out, true, cgram_out, workspace, workspace_bytes,
+                         static_cast<hipStream_t>(stream_));
 }
 
 int rydiff_apply_factor(const RydProblem* p, const double* c_amp_reim, const double* c_det, const double* gamma_reim,

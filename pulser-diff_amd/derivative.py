@@ -98,3 +98,12 @@ def quantum_fisher_information_all_times(sim, x: list, **kw):
     reduced at every save point.  Returns ``QuantumGeometry``: ``qfi`` (n_t, D, D), ``qgt``, ``berry``, ``gram``, ``times`` and the
     ``values`` / ``grads`` of the optional ``observables``."""
     return sim.run_quantum_fisher(x, **kw)
+
+
+def classical_fisher_information_all_times(sim, x: list, **kw):
+    """The classical Fisher information matrix of the occupation-basis measurement (bitstrings) w.r.t. the scalar entries of ``x`` at
+    EVERY evaluation time in one call: ``sim.run_classical_fisher(x, **kw)`` — the tangent sweep of
+    ``quantum_fisher_information_all_times`` with the classical Gram matrix reduced beside the Gram matrix at every save point.
+    Returns ``MeasurementFisher``: ``cfi`` and ``qfi`` (n_t, D, D), ``cgram``, ``gram``, ``times`` and the ``values`` / ``grads`` of
+    the optional ``observables``."""
+    return sim.run_classical_fisher(x, **kw)

@@ -11,7 +11,9 @@ states (``N = <psi|psi> = gram[..., 0, 0]``):
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import Optional
 
+import torch
 from torch import Tensor
 
 SWEEP_DIRECTIONS = 8  # directions of one native sweep (RYDIFF_MAX_TANGENTS)
@@ -29,6 +31,14 @@ def geometry_sweeps(n_dir: int) -> list[list[int]]:
         return [list(range(n_dir))]
     groups = [list(range(d0, min(n_dir, d0 + GROUP_DIRECTIONS))) for d0 in range(0, n_dir, GROUP_DIRECTIONS)]
     return [groups[a] + groups[b] for a in range(len(groups)) for b in range(a + 1, len(groups))]
+
+
+def place_sweep_block(full: Tensor, idx: list, block: Tensor) -> None:
+    """Write the (..., 1 + len(idx), 1 + len(idx)) matrix `block` of the sweep over the directions `idx` into the
+    (..., 1 + n_dir, 1 + n_dir) matrix `full`: row / column 0 is the state, 1 + d direction d.  The assembly of ``evolve_geometry``
+    and ``evolve_fisher`` for more than one sweep (``geometry_sweeps``)."""
+    sel = torch.tensor([0] + [1 + i for i in idx], device=full.device)
+    full[..., sel[:, None], sel[None, :]] = block
 
 
 def quantum_geometric_tensor(gram: Tensor) -> Tensor:
@@ -49,6 +59,33 @@ def berry_curvature(gram: Tensor) -> Tensor:
     return -2.0 * quantum_geometric_tensor(gram).imag
 
 
+def classical_fisher_information(cgram: Tensor) -> Tensor:
+    """``(..., 1 + D, 1 + D)`` classical Gram matrices (``solver.evolve_fisher``, ``observables.classical_gram``) -> the real
+    ``(..., D, D)`` classical Fisher information of the occupation-basis measurement, ``F_C,de = sum_y d_d p(y) d_e p(y) / p(y)`` with
+    ``p(y) = |psi[y]|^2 / S``:  ``F_C = C[1:, 1:] / S - C[1:, 0] C[0, 1:] / S^2``, ``S = C_00`` (valid for unnormalised states)."""
+    if cgram.ndim < 2 or cgram.shape[-1] != cgram.shape[-2] or cgram.shape[-1] < 2:
+        raise ValueError(f"cgram must be (..., 1 + D, 1 + D) with D >= 1, got {tuple(cgram.shape)}")
+    if cgram.is_complex():
+        raise TypeError("cgram is the real classical Gram matrix; the complex Gram matrix goes to quantum_fisher_information")
+    norm = cgram[..., 0, 0][..., None, None]
+    return cgram[..., 1:, 1:] / norm - cgram[..., 1:, :1] * cgram[..., :1, 1:] / norm ** 2
+
+
+def fisher_efficiency(cgram: Tensor, gram: Tensor, direction: Optional[Tensor] = None) -> Tensor:
+    """``F_C / F_Q``, the share of the quantum Cramer-Rao bound the occupation-basis measurement reaches: per diagonal entry
+    ``(..., D)``, or with ``direction`` (a real vector of D entries) along it, ``n.F_C.n / n.F_Q.n`` of shape ``(...)``.  Where both
+    are zero (the state does not depend on the parameter) the ratio is NaN."""
+    fc, fq = classical_fisher_information(cgram), quantum_fisher_information(gram)
+    if direction is None:
+        num, den = torch.diagonal(fc, dim1=-2, dim2=-1), torch.diagonal(fq, dim1=-2, dim2=-1)
+    else:
+        n = torch.as_tensor(direction, dtype=fc.dtype, device=fc.device)
+        if n.ndim != 1 or n.shape[0] != fc.shape[-1]:
+            raise ValueError(f"direction must be a vector of {fc.shape[-1]} entries, got {tuple(n.shape)}")
+        num, den = torch.einsum("d,...de,e->...", n, fc, n), torch.einsum("d,...de,e->...", n, fq, n)
+    return num / den  # 0 / 0 = NaN
+
+
 @dataclass
 class QuantumGeometry:
     """What ``TorchEmulator.run_quantum_fisher`` returns.  With D scalar entries in the request ``x`` (in the order of ``x``, each
@@ -61,6 +98,24 @@ class QuantumGeometry:
     qgt: Tensor
     qfi: Tensor
     berry: Tensor
+    values: Tensor
+    grads: list
+    route: str
+    times: Tensor
+
+
+@dataclass
+class MeasurementFisher:
+    """What ``TorchEmulator.run_classical_fisher`` returns.  With D scalar entries in the request ``x`` (in the order of ``x``, each
+    tensor flattened): ``cgram`` (n_t, 1 + D, 1 + D) real, the classical Gram matrix of the occupation-basis measurement, ``cfi``
+    (n_t, D, D) its classical Fisher information, ``gram`` (n_t, 1 + D, 1 + D) complex and ``qfi`` (n_t, D, D) the quantum ones of
+    the same sweep (``cfi <= qfi`` as matrices) — with several columns in the initial state every one of them carries a batch axis
+    behind the time axis, (n_t, B, ...).  ``values``, ``grads``, ``route`` and ``times`` as in ``QuantumGeometry``."""
+
+    cgram: Tensor
+    cfi: Tensor
+    gram: Tensor
+    qfi: Tensor
     values: Tensor
     grads: list
     route: str

@@ -454,6 +454,24 @@ def occupation_moments(states: Tensor) -> Tensor:
     return torch.cat(rows, dim=0)
 
 
+def classical_gram(states: Tensor, tangents: Tensor) -> Tensor:
+    """The "classical Gram matrix" of ``rydiff_forward_fisher`` in plain torch on stored vectors: ``states`` complex ``(..., dim)``,
+    ``tangents`` complex ``(..., D, dim)`` (the same leading axes) -> real ``(..., 1 + D, 1 + D)``.  With ``u = psi / |psi|`` the
+    phase of every amplitude, ``w_0 = |psi|`` and ``w_{1+d} = 2 Re(conj(u) dpsi_d)``, ``C_ij = sum_y w_i[y] w_j[y]`` — what
+    ``geometry.classical_fisher_information`` takes.  The modulus is ``torch.abs`` on the complex amplitude (no ``|psi|^2`` that
+    could underflow); an amplitude that is exactly zero contributes nothing (``w_i[y] = 0`` for every ``i``: the sum over the
+    support).  The reference of the native route, and the route for users who hold states on the CPU."""
+    if not states.is_complex() or not tangents.is_complex():
+        raise TypeError("classical_gram takes complex states and tangents")
+    if tangents.ndim != states.ndim + 1 or tangents.shape[:-2] != states.shape[:-1] or tangents.shape[-1] != states.shape[-1]:
+        raise ValueError(f"expected states (..., dim) and tangents (..., D, dim), got {tuple(states.shape)} and {tuple(tangents.shape)}")
+    mod = torch.abs(states)
+    support = mod > 0
+    phase = torch.where(support, states / torch.where(support, mod, torch.ones_like(mod)), torch.zeros_like(states))
+    w = torch.cat([mod[..., None, :], 2.0 * (phase.conj()[..., None, :] * tangents).real], dim=-2)  # (..., 1 + D, dim)
+    return torch.einsum("...iy,...jy->...ij", w, w)
+
+
 def fidelity_states(obs: StateOverlap, states: Tensor) -> Tensor:
     """``<phi_b| rho_b(t_k) |phi_b>`` in torch, real ``(n_t, B)``: stored density matrices ``(n_t, dim, dim, B)``, or kets
     ``(n_t, dim, B)`` (``|<phi|psi>|^2``).  The real part of the bilinear form, as the library takes it (no Hermiticity assumed)."""

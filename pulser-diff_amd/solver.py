@@ -898,32 +898,55 @@ def evolve_geometry(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsa
     ``spec.rdms`` (rows as in ``evolve_tangent``; their sums use atomics and are not part of the fixed order),
     ``_native.TANGENT_MOMENTS`` the occupation correlations of ``spec.moments`` (fixed order, like the Gram matrix, which they leave
     as it is); density-matrix registers stay refused."""
-    from .geometry import geometry_sweeps
+    return _evolve_gram(False, amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag, d_amp, d_det, d_u, d_psi0, flags)[:3]
 
+
+def evolve_fisher(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Tensor, spec: ProblemSpec,
+                  obs_diag: Optional[Tensor] = None, d_amp: Optional[Tensor] = None, d_det: Optional[Tensor] = None,
+                  d_u: Optional[Tensor] = None, d_psi0: Optional[Tensor] = None, flags: int = 0) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``evolve_geometry`` that also returns the classical Gram matrix of the occupation-basis measurement at EVERY evaluation time
+    (``rydiff_forward_fisher``): ``(expect, dexpect, gram, cgram)`` with ``cgram`` float64 of shape (n_t, B, 1 + n_dir, 1 + n_dir),
+    ``cgram[k, b, i, j] = sum_y w_i[y] w_j[y]``, ``w_0 = |psi_b(t_k)|``, ``w_{1+d} = 2 Re(conj(psi / |psi|) d psi_b(t_k) / d theta_d)``
+    — what ``geometry.classical_fisher_information`` and ``geometry.fisher_efficiency`` take; ``observables.classical_gram`` is the
+    same matrix in torch on stored vectors.  ``gram`` is ``evolve_geometry``'s, bit for bit: one sweep serves the quantum and the
+    classical Fisher information.  Fixed order: two calls on the same inputs return bit-identical matrices.  Same arguments, flags and
+    refusals as ``evolve_geometry``; tangents of inputs the problem does not have give zero rows and columns (``cgram[..., 0, 0]``
+    stays ``<psi|psi>``).  More than 8 directions run one sweep per pair of groups of 4 (``geometry.geometry_sweeps``)."""
+    return _evolve_gram(True, amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag, d_amp, d_det, d_u, d_psi0, flags)
+
+
+def _evolve_gram(fisher: bool, amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag, d_amp, d_det, d_u, d_psi0, flags):
+    """``evolve_geometry`` (``cgram`` None) and ``evolve_fisher``: the refusals, the sweeps over groups of directions, the assembly."""
+    from .geometry import geometry_sweeps, place_sweep_block
+
+    name, native = ("evolve_fisher", "rydiff_forward_fisher") if fisher else ("evolve_geometry", "rydiff_forward_geometry")
     if spec.rdms is not None and not (int(flags) & _native.TANGENT_RDMS):
-        raise NotImplementedError("evolve_geometry evaluates no reduced density matrices (rydiff_forward_geometry: RYDIFF_ENOTIMPL) unless "
+        raise NotImplementedError(f"{name} evaluates no reduced density matrices ({native}: RYDIFF_ENOTIMPL) unless "
                                   "flags has _native.TANGENT_RDMS; or request them from evolve")
     if spec.dm is not None:
-        raise NotImplementedError("evolve_geometry takes no density-matrix registers (rydiff_forward_geometry: RYDIFF_ENOTIMPL): the "
+        raise NotImplementedError(f"{name} takes no density-matrix registers ({native}: RYDIFF_ENOTIMPL): the "
                                   "pure-state quantum Fisher information is not the mixed-state one")
     if spec.moments and not (int(flags) & _native.TANGENT_MOMENTS):
-        raise NotImplementedError("evolve_geometry evaluates no occupation correlations (rydiff_forward_geometry: RYDIFF_ENOTIMPL) unless "
+        raise NotImplementedError(f"{name} evaluates no occupation correlations ({native}: RYDIFF_ENOTIMPL) unless "
                                   "flags has _native.TANGENT_MOMENTS; or request them from evolve")
     if spec.shots is not None:
-        raise NotImplementedError("evolve_geometry draws no measurement shots (rydiff_forward_geometry: RYDIFF_ENOTIMPL); request them from evolve")
+        raise NotImplementedError(f"{name} draws no measurement shots ({native}: RYDIFF_ENOTIMPL); request them from evolve")
     L = _native.lib()
     dev = psi0.device
-    n_dir, pre, rows = _sweep_prepare("evolve_geometry", amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag,
+    n_dir, pre, rows = _sweep_prepare(name, amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag,
                                       d_amp, d_det, d_u, d_psi0)
     p, n_t, batch = pre.call.problem, pre.n_t, pre.batch
     expect = torch.empty((rows, n_t, batch), dtype=torch.float64, device=dev)
     dexpect = torch.empty((n_dir, rows, n_t, batch), dtype=torch.float64, device=dev)
     gram = torch.empty((n_t, batch, 1 + n_dir, 1 + n_dir), dtype=torch.complex128, device=dev)
+    cgram = torch.empty((n_t, batch, 1 + n_dir, 1 + n_dir), dtype=torch.float64, device=dev) if fisher else None
     # tangents of inputs this problem does not have are zero: where nothing else is given the tangent states are identically zero,
     # and ONE sweep with a single zero direction delivers <psi|psi> and the values; every other entry is an exact zero
     live = ((d_amp is not None and pre.amp.numel() > 0) or (d_det is not None and pre.det.numel() > 0)
             or (d_u is not None and pre.u.numel() > 0) or d_psi0 is not None)
     sweeps = geometry_sweeps(n_dir) if live else [[0]]
+    size_fn = L.rydiff_fisher_workspace_bytes_flags if fisher else L.rydiff_geometry_workspace_bytes_flags
+    size_name = "rydiff_fisher_workspace_bytes_flags" if fisher else "rydiff_geometry_workspace_bytes"
     with torch.cuda.device(dev):
         stream, info, _scratch = _sweep_plan(L, p, dev)
         workspace = None
@@ -935,25 +958,30 @@ def evolve_geometry(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsa
                 bufs = (None, None, None, torch.zeros((1,) + tuple(pre.psi.shape), dtype=torch.complex128, device=dev))
             tg = _sweep_tangent(len(idx), bufs, flags)
             g = torch.empty((n_t, batch, 1 + len(idx), 1 + len(idx)), dtype=torch.complex128, device=dev)
+            c = torch.empty((n_t, batch, 1 + len(idx), 1 + len(idx)), dtype=torch.float64, device=dev) if fisher else None
             want_rows = rows > 0 and not bool(done[idx].all())  # a later sweep of directions whose row tangents are all there skips them
             out = torch.empty((len(idx), rows, n_t, batch), dtype=torch.float64, device=dev) if want_rows else None
 
             def sweep(ws):
-                return L.rydiff_forward_geometry(ctypes.byref(p), ctypes.byref(info), ctypes.byref(tg), _ptr(pre.psi),
-                                                 _ptr(expect) if (rows > 0 and s == 0) else None, _ptr(out), _ptr(g), _ptr(ws),
-                                                 0 if ws is None else ws.numel(), stream)
+                head = (ctypes.byref(p), ctypes.byref(info), ctypes.byref(tg), _ptr(pre.psi),
+                        _ptr(expect) if (rows > 0 and s == 0) else None, _ptr(out), _ptr(g))
+                tail = (_ptr(ws), 0 if ws is None else ws.numel(), stream)
+                return L.rydiff_forward_fisher(*head, _ptr(c), *tail) if fisher else L.rydiff_forward_geometry(*head, *tail)
 
-            workspace = _sweep_workspace(L.rydiff_geometry_workspace_bytes_flags, "rydiff_geometry_workspace_bytes", sweep, p, info, tg,
-                                         workspace, dev)
+            workspace = _sweep_workspace(size_fn, size_name, sweep, p, info, tg, workspace, dev)
             _native.check(sweep(workspace))
             if not live:
                 gram.zero_()
                 gram[:, :, 0, 0] = g[:, :, 0, 0]
+                if fisher:
+                    cgram.zero_()
+                    cgram[:, :, 0, 0] = c[:, :, 0, 0]
                 dexpect.zero_()
                 break
-            full = torch.tensor([0] + [1 + i for i in idx], device=dev)
-            gram[:, :, full[:, None], full[None, :]] = g
+            place_sweep_block(gram, idx, g)
+            if fisher:
+                place_sweep_block(cgram, idx, c)
             if out is not None:
                 dexpect[idx] = out
             done[idx] = True
-    return expect, dexpect, gram
+    return expect, dexpect, gram, cgram
