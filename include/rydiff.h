@@ -136,6 +136,11 @@ typedef struct RydProblem {
      *  19 automatic, but one factor per adjoint launch (forward blocks as automatic)
      *  20 / 21 as 17, with the adjoint block kernel's tape vectors staged through registers / by LDS-DMA (DESIGN.md section 3;
      *     17 and automatic take the one that measured faster)
+     *  22..30 as 20, with a request order and a store policy of the block kernels' own: inputs requested vector-major (v of every wave,
+     *     then w, then t / the tape) and / or some outputs stored write-through (level 1: v_mid and y, adjoint mu_out; 2: also w';
+     *     3: all).  22 vector-major | 23 / 24 / 25 write-through level 1 / 2 / 3 | 26 / 27 / 28 both | 29 vector-major with LDS-DMA
+     *     staging and streaming stores | 30 neither (wave-major requests, streaming stores).  DESIGN.md section 3; automatic, 17, 20
+     *     and 21 take the combination that measured fastest (that of 28)
      * "automatic" takes the one-launch sweeps up to 12 qubits, the direct kernels while few tiles are in flight
      * (B * 2^N <= 2^18, with gradients 2^19) and the chained passes beyond.  Results do not depend on the variant beyond rounding. */
     int32_t kernel_variant;

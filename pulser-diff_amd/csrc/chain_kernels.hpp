@@ -37,6 +37,22 @@ __device__ __forceinline__ void stream_store(double2* p, const double2& v) {
 #endif
 }
 
+// Write-through store of 16 bytes (buffer_store_dwordx4 ... sc1) to element i of the n-element vector at `base` (wave-uniform;
+// n * 16 bytes below 2^31): the line leaves for memory as it is written, where stream_store keeps it dirty in this XCD's L2 until
+// the write-back at the end of the kernel.  For outputs that still have compute behind them in the same launch (the block passes,
+// pair_kernels.hpp).  A store the compiler counts, like stream_store; out-of-range elements are dropped by the range check.
+__device__ __forceinline__ void through_store(double2* base, uint32_t n, unsigned i, const double2& v) {
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    const __amdgpu_buffer_rsrc_t dst = __builtin_amdgcn_make_buffer_rsrc(base, 0, int(n * uint32_t(sizeof(double2))), 0x00020000);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), dst, int(i * unsigned(sizeof(double2))), 0, /* sc1 */ 16);
+}
+
+template <bool THROUGH>
+__device__ __forceinline__ void out_store(double2* base, uint32_t n, unsigned i, const double2& v) {
+    if constexpr (THROUGH) through_store(base, n, i, v);
+    else stream_store(base + i, v);
+}
+
 // Streaming load: every vector element is read exactly once per pass, so there is no point allocating it in the
 // vector L1 (global_load_dwordx4 ... nt; measured 14.8 -> 14.3 us per pass on the 20-qubit workload)
 __device__ __forceinline__ double2 stream_load(const double2* p) {
@@ -276,10 +292,12 @@ __device__ __forceinline__ void partner_sums_lanes(const double2& own, uint32_t 
 }
 
 #ifdef RYDIFF_TIMELINE
-__device__ unsigned long long g_timeline[4096 * 8];  // tuning builds: per-workgroup phase timestamps of the last launch
+// tuning builds: per-workgroup phase timestamps of the last launch, [4096][8]; a ninth stamp (slot 8) lives behind them, [4096]
+__device__ unsigned long long g_timeline[4096 * 9];
 #define RYDIFF_TL(slot)                                                                                   \
     do {                                                                                                  \
-        if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.x < 4096 && a.has_p && a.has_q) g_timeline[blockIdx.x * 8 + (slot)] = __builtin_readcyclecounter(); \
+        if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.x < 4096 && a.has_p && a.has_q)               \
+            g_timeline[(slot) < 8 ? blockIdx.x * 8 + (slot) : 4096 * 8 + blockIdx.x] = __builtin_readcyclecounter(); \
     } while (0)
 #else
 #define RYDIFF_TL(slot)

@@ -44,9 +44,17 @@ struct Chain2Args {
     long exp_ostride;
 };
 
-template <int LT, int LGT>
+// ORD: the workgroup requests its inputs vector-major.  A CU's vector-memory path serves requests roughly in issue order, and each
+// wave issues v, w, t back to back, so wave-major the last wave's v is requested behind almost all of w and t and round A's barrier
+// waits for about the whole load phase.  With ORD every wave issues v, a bare execution barrier (s_barrier: no fence, no wait on
+// the counter) lets the other waves issue theirs, and only then follow w and, behind another barrier, t.  Speed only: each wave
+// still awaits each input where it uses it.  (The early return above the loads is workgroup-uniform.)
+// WT: which outputs are stored write-through (through_store) instead of streaming (stream_store, dirty in L2 until the end of the
+// kernel): 0 none | 1 v_mid and y, which have the whole start stage behind them | 2 also w' | 3 all, t' included.
+template <int LT, int LGT, bool ORD = false, int WT = 0>
 __global__ __launch_bounds__(1 << LGT) void k_chain2(Chain2Args a) {
     constexpr int NT = 1 << LGT, R = 1 << (LT - LGT);
+    static_assert(WT >= 0 && WT <= 3);
     extern __shared__ __attribute__((aligned(16))) double2 tiles[];
     double* red = reinterpret_cast<double*>(tiles + 2 * (size_t(1) << LT));
     const unsigned tid = threadIdx.x;
@@ -58,6 +66,24 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2(Chain2Args a) {
     const unsigned lomask = (1u << a.lo) - 1u;
     const int midlow = a.hs - a.lo;
     const unsigned xbase = ((t & ((1u << midlow) - 1u)) << a.lo) | ((t >> midlow) << (a.hs + a.hb));
+    RYDIFF_TL(0);
+    // ORD: the diagonal's table entries and the coefficients of both stages (L2 hits, at most one detuning group where the blocks
+    // are legal) are requested ahead of the streamed vectors, as in k_chain2_bwd.  Behind them, the wait for the table would retire
+    // v, w and t together, and the start stage's coefficient reads would wait for the acknowledgement of the y stores.
+    const double* __restrict__ vrow = a.vr + size_t(t) * 16;
+    [[maybe_unused]] double ut[R], vtop[LT + 1], c_fin = 0.0, c_sta = 0.0, cdet_fin = 0.0, cdet_sta = 0.0;
+    if constexpr (ORD) {
+#pragma unroll
+        for (int b2 = 0; b2 <= LT; ++b2) vtop[b2] = vrow[b2];  // (workgroup-uniform: scalar loads, as long as nothing is in their way)
+#pragma unroll
+        for (int r = 0; r < R; ++r) ut[r] = a.utt[unsigned(r) * NT + tid];
+        c_fin = a.coef_fin[bt * a.coef_bstride];
+        c_sta = a.coef_sta[bt * a.coef_bstride];
+        if (a.gd) {  // (uniform)
+            cdet_fin = a.coef_fin[bt * a.coef_bstride + 2];
+            cdet_sta = a.coef_sta[bt * a.coef_bstride + 2];
+        }
+    }
     double2 uu[R], ww[R], tt[R];
     unsigned xg[R];
 #pragma unroll
@@ -66,34 +92,56 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2(Chain2Args a) {
         xg[r] = xbase | (i & lomask) | ((i >> a.lo) << a.hs);
         uu[r] = stream_load(a.v + boff + xg[r]);
     }
+    if constexpr (ORD) __builtin_amdgcn_s_barrier();  // every wave's v is requested before any wave's w
     // w and t requested with v, outside of control flow (the host passes valid pointers for the first launch too): each is awaited
     // where it is first used — w after the first round, t after the second
 #pragma unroll
     for (int r = 0; r < R; ++r) ww[r] = stream_load(a.w + boff + xg[r]);
+    if constexpr (ORD) __builtin_amdgcn_s_barrier();  // ... and every wave's w before any wave's t
 #pragma unroll
     for (int r = 0; r < R; ++r) tt[r] = stream_load(a.t + boff + xg[r]);
+    // ORD: the amplitude indices are taken afresh for each stage's stores, from a copy of tid the compiler cannot see through (as in
+    // k_chain2_bwd): otherwise the 64-bit addresses of the loads stay live up to the stores and spill
+    auto reindex = [&]() {
+        if constexpr (ORD) {
+            unsigned tid_o = tid;
+            asm volatile("" : "+v"(tid_o));
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const unsigned i = unsigned(r) * NT + tid_o;
+                xg[r] = xbase | (i & lomask) | ((i >> a.lo) << a.hs);
+            }
+        }
+    };
+    reindex();
     double du[R];  // interaction diagonal (as k_chain)
     {
-        const double* __restrict__ vrow = a.vr + size_t(t) * 16;
         double vloc[LT];
 #pragma unroll
-        for (int b2 = 0; b2 < LT; ++b2) vloc[b2] = vrow[b2];
-        double dlane = vrow[LT];
+        for (int b2 = 0; b2 < LT; ++b2) vloc[b2] = ORD ? vtop[b2] : vrow[b2];
+        double dlane = ORD ? vtop[LT] : vrow[LT];
 #pragma unroll
         for (int b2 = 0; b2 < LGT; ++b2)
             if (!(tid >> b2 & 1u)) dlane += vloc[b2];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            double d = a.utt[unsigned(r) * NT + tid] + dlane;
+            double d;
+            if constexpr (ORD) d = ut[r] + dlane;
+            else d = a.utt[unsigned(r) * NT + tid] + dlane;
 #pragma unroll
             for (int b2 = LGT; b2 < LT; ++b2)
                 if (!(r >> (b2 - LGT) & 1)) d += vloc[b2];
             du[r] = d;
         }
     }
-    auto diag = [&](const double* cf, int r) -> double {  // D(x) of one exponential: interaction + detuning groups
+    // D(x) of one exponential: interaction + detuning groups (ORD: the one group's coefficient was fetched at the top, cdet)
+    auto diag = [&](const double* cf, [[maybe_unused]] double cdet, int r) -> double {
         double d = du[r];
-        for (int g = 0; g < a.gd; ++g) d += cf[2 + g] * double(a.dcnt[g] - popc_i(xg[r] & a.dmask[g]));
+        if constexpr (ORD) {  // (the same loop, so that the compiler forms the same fused multiply-adds around it: bit-identical states)
+            for (int g = 0; g < a.gd; ++g) d += cdet * double(a.dcnt[g] - popc_i(xg[r] & a.dmask[g]));
+        } else {
+            for (int g = 0; g < a.gd; ++g) d += cf[2 + g] * double(a.dcnt[g] - popc_i(xg[r] & a.dmask[g]));
+        }
         return d;
     };
     int buf = 0;  // LDS buffer the next round writes
@@ -110,23 +158,28 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2(Chain2Args a) {
     double2 y[R];
     if (a.has_p) {
         const double* __restrict__ cf = a.coef_fin + bt * a.coef_bstride;
-        const double c = cf[0];
+        double c;
+        if constexpr (ORD) c = c_fin;
+        else c = cf[0];
         double2 s[R], h1[R], ds[R];
-        partner_sums<LT, LGT, false>(put(uu), uu, a.fin_mask, tid, s, ds);
+        const double2* vtile = put(uu);
+        RYDIFF_TL(1);
+        partner_sums<LT, LGT, false>(vtile, uu, a.fin_mask, tid, s, ds);
         double d[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            d[r] = diag(cf, r);
+            d[r] = diag(cf, cdet_fin, r);
             h1[r].x = d[r] * uu[r].x + c * (ww[r].x + s[r].x);
             h1[r].y = d[r] * uu[r].y + c * (ww[r].y + s[r].y);
             const double2 p = cmul(a.a_r, a.a_i, uu[r]), q = cmul(a.b_r, a.b_i, h1[r]);
             y[r] = make_double2(p.x + q.x, p.y + q.y);
         }
+        RYDIFF_TL(2);
         if (a.vmid_out) {
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const double2 p = cmul(a.g1_r, a.g1_i, uu[r]), q = cmul(a.b1_r, a.b1_i, h1[r]);
-                stream_store(a.vmid_out + boff + xg[r], make_double2(p.x + q.x, p.y + q.y));
+                out_store<(WT >= 1)>(a.vmid_out + boff, a.dim, xg[r], make_double2(p.x + q.x, p.y + q.y));
             }
         }
         if (a.k_r != 0.0 || a.k_i != 0.0) {  // (uniform) second finishing round: P_Y' e
@@ -142,8 +195,10 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2(Chain2Args a) {
                 y[r].y += k.y;
             }
         }
+        RYDIFF_TL(3);
 #pragma unroll
-        for (int r = 0; r < R; ++r) stream_store(a.y_out + boff + xg[r], y[r]);
+        for (int r = 0; r < R; ++r) out_store<(WT >= 1)>(a.y_out + boff, a.dim, xg[r], y[r]);
+        RYDIFF_TL(4);
         if (a.obs) {  // <y|O|y> for diagonal observables, straight from the registers that hold y
             for (int o = 0; o < a.n_obs; ++o) {
                 double ex = 0.0;
@@ -153,28 +208,40 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2(Chain2Args a) {
             }
         }
     } else {
+        // A chain's first launch has no block to finish, and the host passes v for w and t as well.  ORD: y is taken from the LAST of
+        // the three requests, which retires all of them on this path.  Left pending, they would make the start stage of the OTHER
+        // path wait for the acknowledgement of its y stores: the compiler places its waits after the join of the two paths.
 #pragma unroll
-        for (int r = 0; r < R; ++r) y[r] = uu[r];
+        for (int r = 0; r < R; ++r) y[r] = ORD ? tt[r] : uu[r];
     }
     if (!a.has_q) return;
 
     // start the next block in this layout: w' = P_Y y, t' = P_Y (D' y + c' w')
+    reindex();
     const double* __restrict__ cf = a.coef_sta + bt * a.coef_bstride;
-    const double c = cf[0];
+    double c;
+    if constexpr (ORD) c = c_sta;
+    else c = cf[0];
     double2 w2[R], ds[R];
     partner_sums<LT, LGT, false, true>(put(y), y, ~0u, tid, w2, ds);
 #pragma unroll
-    for (int r = 0; r < R; ++r) stream_store(a.w_out + boff + xg[r], w2[r]);
+    for (int r = 0; r < R; ++r) out_store<(WT >= 2)>(a.w_out + boff, a.dim, xg[r], w2[r]);
+    RYDIFF_TL(5);
     double2 z[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const double d = diag(cf, r);
+        const double d = diag(cf, cdet_sta, r);
         z[r] = make_double2(d * y[r].x + c * w2[r].x, d * y[r].y + c * w2[r].y);
     }
     double2 t2[R];
     partner_sums<LT, LGT, false, true>(put(z), z, ~0u, tid, t2, ds);
 #pragma unroll
-    for (int r = 0; r < R; ++r) stream_store(a.t_out + boff + xg[r], t2[r]);
+    for (int r = 0; r < R; ++r) out_store<(WT >= 3)>(a.t_out + boff, a.dim, xg[r], t2[r]);
+    RYDIFF_TL(6);
+#ifdef RYDIFF_TIMELINE
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (tuning builds: the last stamp is taken once this wave's stores are acknowledged)
+    RYDIFF_TL(7);
+#endif
 }
 
 // ---- adjoint of a block (k_chain2_bwd) -------------------------------------------------------------------------------------
@@ -257,9 +324,12 @@ constexpr size_t chain2_bwd_lds_bytes() {
 // register instantiation parks it) and kChain2BwdXbLds elements of x_b into a staging area behind the parked partials, which no
 // put() touches: it lives until the mu_out store.  The other elements of x_b wait in registers.  Every DMA is retired (vmcnt(0))
 // before round A's barrier and read after it, by the wave that issued it.  !DMA: the register-staged kernel described above.
-template <int LT, int LGT, bool DMA>
+// ORD, WT: as in k_chain2.  ORD: every wave requests mu, then (behind a bare execution barrier) w, then (behind another) the tape
+// vectors.  WT: 1 mu_out, which has the whole start stage behind it | 2 also w' | 3 all.
+template <int LT, int LGT, bool ORD, int WT, bool DMA>
 __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
     constexpr int NT = 1 << LGT, R = 1 << (LT - LGT), NW = NT / 64;
+    static_assert(WT >= 0 && WT <= 3);
     constexpr int XBL = DMA ? kChain2BwdXbLds : 0;
     static_assert(XBL <= R && (2 * NW * sizeof(double)) % sizeof(double2) == 0);
     extern __shared__ __attribute__((aligned(16))) double2 tiles[];
@@ -312,9 +382,11 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
         xg[r] = xbase | (i & lomask) | ((i >> a.lo) << a.hs);
         uu[r] = stream_load(a.mu + boff + xg[r]);
     }
+    if constexpr (ORD) __builtin_amdgcn_s_barrier();  // every wave's mu is requested before any wave's w
     // w and x_a requested with mu, outside of control flow (the host passes valid pointers for the first launch too)
 #pragma unroll
     for (int r = 0; r < R; ++r) ww[r] = stream_load(a.w + boff + xg[r]);
+    if constexpr (ORD) __builtin_amdgcn_s_barrier();  // ... and every wave's w before any wave's tape vector
     [[maybe_unused]] double2 xa[R];
     if constexpr (DMA) {
         const unsigned wv = __builtin_amdgcn_readfirstlane(tid & ~63u);  // a wave's 64 slots of one r are 1 KiB of contiguous LDS
@@ -368,6 +440,11 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
     // Every request of the top is retired here, on both paths (round A's barrier needs all of them anyway: x_a sits in LDS before it).
     // Left pending on the path of a chain's first launch, which does not use them, they would make the start stage of the OTHER path
     // wait for the acknowledgement of its mu_out stores: the compiler places its waits after the join of the two paths.
+#ifdef RYDIFF_TIMELINE
+#pragma unroll
+    for (int r = 0; r < R; ++r) asm volatile("" ::"v"(uu[r].x), "v"(uu[r].y));
+    RYDIFF_TL(8);  // (tuning builds: mu landed in this wave, apart from w and x_a)
+#endif
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         asm volatile("" ::"v"(uu[r].x), "v"(uu[r].y), "v"(ww[r].x), "v"(ww[r].y));
@@ -495,7 +572,7 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
             }
         }
 #pragma unroll
-        for (int r = 0; r < R; ++r) stream_store(a.mu_out + boff + xg[r], y[r]);
+        for (int r = 0; r < R; ++r) out_store<(WT >= 1)>(a.mu_out + boff, a.dim, xg[r], y[r]);
         RYDIFF_TL(5);
     } else {
 #pragma unroll
@@ -524,7 +601,7 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
     double2 w2[R], ds[R];
     partner_sums<LT, LGT, false, true>(put(y), y, ~0u, tid, w2, ds);
 #pragma unroll
-    for (int r = 0; r < R; ++r) stream_store(a.w_out + boff + xg[r], w2[r]);
+    for (int r = 0; r < R; ++r) out_store<(WT >= 2)>(a.w_out + boff, a.dim, xg[r], w2[r]);
     RYDIFF_TL(6);
     double2 z[R];
 #pragma unroll
@@ -535,7 +612,7 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
     double2 t2[R];
     partner_sums<LT, LGT, false, true>(put(z), z, ~0u, tid, t2, ds);
 #pragma unroll
-    for (int r = 0; r < R; ++r) stream_store(a.t_out + boff + xg[r], t2[r]);
+    for (int r = 0; r < R; ++r) out_store<(WT >= 3)>(a.t_out + boff, a.dim, xg[r], t2[r]);
     RYDIFF_TL(7);
     flush();  // (the barriers of the start rounds published the parked partials)
 }

@@ -55,12 +55,38 @@ void fill_chain2(Args& ca, const Runtime& rt, char* ws, const std::vector<ChainI
     }
 }
 
-template <int LGT>
+// Request order and store policy of the block kernels (template parameters ORD / WT of k_chain2 and k_chain2_bwd, pair_kernels.hpp).
+// Automatic: vector-major requests and every output stored write-through, the combination that measured fastest on C3 (variant 28:
+// +2.7 % on the bench line); variants 22..30 select the others for A/B runs, 30 the kernels before this choice.
+constexpr bool kPairVecMajorDefault = true;
+constexpr int kPairThroughDefault = 3;
+bool pair_vec_major(const Runtime& rt) { return rt.pair_phases >= 0 ? (rt.pair_phases >> 2) != 0 : kPairVecMajorDefault; }
+int pair_through(const Runtime& rt) { return rt.pair_phases >= 0 ? (rt.pair_phases & 3) : kPairThroughDefault; }
+
+// f(bool_constant<ORD>, integral_constant<int, WT>) for the run-time pair (ord, wt): the instantiations that exist
+template <class F>
+int with_pair_phases(bool ord, int wt, F f) {
+    using std::bool_constant;
+    using std::integral_constant;
+    switch ((ord ? 4 : 0) | wt) {
+        case 0: return f(bool_constant<false>{}, integral_constant<int, 0>{});
+        case 1: return f(bool_constant<false>{}, integral_constant<int, 1>{});
+        case 2: return f(bool_constant<false>{}, integral_constant<int, 2>{});
+        case 3: return f(bool_constant<false>{}, integral_constant<int, 3>{});
+        case 4: return f(bool_constant<true>{}, integral_constant<int, 0>{});
+        case 5: return f(bool_constant<true>{}, integral_constant<int, 1>{});
+        case 6: return f(bool_constant<true>{}, integral_constant<int, 2>{});
+        case 7: return f(bool_constant<true>{}, integral_constant<int, 3>{});
+    }
+    return fail(RYDIFF_EINVAL, "internal: no such block kernel");
+}
+
+template <int LGT, bool ORD, int WT>
 int launch_chain2_t(const Chain2Args& ca, unsigned tiles, hipStream_t stream) {
     constexpr int LT = kTileBits;
     const size_t lds = 2 * (size_t(1) << LT) * sizeof(double2) + 256;  // two tile buffers + one double per wave
-    if (int rc = set_max_dynamic_lds_once<&k_chain2<LT, LGT>>(lds)) return rc;
-    hipLaunchKernelGGL((k_chain2<LT, LGT>), dim3(tiles, unsigned(ca.b_count)), dim3(1 << LGT), lds, stream, ca);
+    if (int rc = set_max_dynamic_lds_once<&k_chain2<LT, LGT, ORD, WT>>(lds)) return rc;
+    hipLaunchKernelGGL((k_chain2<LT, LGT, ORD, WT>), dim3(tiles, unsigned(ca.b_count)), dim3(1 << LGT), lds, stream, ca);
     LAUNCH_CHECK();
     return RYDIFF_OK;
 }
@@ -120,7 +146,9 @@ int run_chain2(const Runtime& rt, char* ws, const std::vector<ChainItem>& items,
             ca.n_obs = cs.n_obs;
             ca.exp_ostride = cs.exp_ostride;
         }
-        int rc = launch_chain2_t<10>(ca, tiles, stream);
+        int rc = with_pair_phases(pair_vec_major(rt), pair_through(rt), [&](auto ord, auto wt) {
+            return launch_chain2_t<10, decltype(ord)::value, decltype(wt)::value>(ca, tiles, stream);
+        });
         if (rc) return rc;
         if (ca.has_p) {
             if (ca.vmid_out) {
@@ -138,7 +166,8 @@ int run_chain2(const Runtime& rt, char* ws, const std::vector<ChainItem>& items,
 // ---- adjoint in blocks of two factors (k_chain2_bwd, pair_kernels.hpp) -------------------------------------------------
 // Where the forward blocks are, for the real-drive adjoint (RydProblem.real_amp_grad: no signed sums) on the 2^12 two-layout
 // tiles; variant 19 keeps the one-factor adjoint (k_chain) next to automatic forward blocks.  Variants 20 / 21: blocks wherever
-// legal (as 17) with the tape vectors staged through registers / by LDS-DMA (k_chain2_bwd<.., false / true>).
+// legal (as 17) with the tape vectors staged through registers / by LDS-DMA (k_chain2_bwd<.., false / true>).  Variants 22..30: as
+// 20, with a request order and a store policy of their own (pair_vec_major, pair_through); 29 alone stages by LDS-DMA.
 bool pair_bwd_enabled(const Runtime& rt) {
     const ChainGeom g = chain_geom(rt);
     return !rt.pair_bwd_off && rt.real_amp_grad && pair_enabled(rt) && g.lt == kTileBits && g.layouts == 2;
@@ -149,15 +178,29 @@ bool pair_bwd_enabled(const Runtime& rt) {
 constexpr bool kPairBwdDmaDefault = false;
 bool pair_bwd_dma(const Runtime& rt) { return rt.pair_bwd_stage ? rt.pair_bwd_stage > 0 : kPairBwdDmaDefault; }
 
-template <int LGT, bool DMA>
+template <int LGT, bool ORD, int WT, bool DMA>
 int launch_chain2_bwd_t(const Chain2BwdArgs& ca, unsigned tiles, hipStream_t stream) {
     constexpr int LT = kTileBits;
     constexpr size_t lds = chain2_bwd_lds_bytes<LT, LGT, DMA>();
     static_assert(lds <= 160 * 1024, "k_chain2_bwd: more LDS than a gfx950 workgroup can have");
-    if (int rc = set_max_dynamic_lds_once<&k_chain2_bwd<LT, LGT, DMA>>(lds)) return rc;
-    hipLaunchKernelGGL((k_chain2_bwd<LT, LGT, DMA>), dim3(tiles, unsigned(ca.b_count)), dim3(1 << LGT), lds, stream, ca);
+    if (int rc = set_max_dynamic_lds_once<&k_chain2_bwd<LT, LGT, ORD, WT, DMA>>(lds)) return rc;
+    hipLaunchKernelGGL((k_chain2_bwd<LT, LGT, ORD, WT, DMA>), dim3(tiles, unsigned(ca.b_count)), dim3(1 << LGT), lds, stream, ca);
     LAUNCH_CHECK();
     return RYDIFF_OK;
+}
+
+// The LDS-DMA staging exists with vector-major requests only: with the automatic store policy (variant 21) and with streaming
+// stores (variant 29).
+int launch_chain2_bwd(const Runtime& rt, const Chain2BwdArgs& ca, unsigned tiles, hipStream_t stream) {
+    const bool ord = pair_vec_major(rt);
+    if (pair_bwd_dma(rt)) {
+        if (ord && pair_through(rt) == 3) return launch_chain2_bwd_t<10, true, 3, true>(ca, tiles, stream);
+        if (ord && pair_through(rt) == 0) return launch_chain2_bwd_t<10, true, 0, true>(ca, tiles, stream);
+        return fail(RYDIFF_EINVAL, "internal: no such block kernel");
+    }
+    return with_pair_phases(ord, pair_through(rt), [&](auto o, auto wt) {
+        return launch_chain2_bwd_t<10, decltype(o)::value, decltype(wt)::value, false>(ca, tiles, stream);
+    });
 }
 
 // Same contract as run_chain_bwd (un-sharded, no trajectory-per-XCD placement), in blocks of two factors of one exponential.
@@ -230,7 +273,7 @@ int run_chain2_bwd(const Runtime& rt, char* ws, const std::vector<ChainItem>& it
             if (ca.mu_out == cur) return fail(RYDIFF_EINVAL, "internal: cotangent ping-pong clash");
             fill_inject(ca, inj, save_k[fb], pl);  // (inside has_p: every finishing launch completes a cotangent, mu_out)
         }
-        rc = pair_bwd_dma(rt) ? launch_chain2_bwd_t<10, true>(ca, tiles, stream) : launch_chain2_bwd_t<10, false>(ca, tiles, stream);
+        rc = launch_chain2_bwd(rt, ca, tiles, stream);
         if (rc) return rc;
         if (ca.has_p) {
             cur = ca.mu_out;  // complete cotangent at the input of forward factor fb

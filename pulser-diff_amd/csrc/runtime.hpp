@@ -69,6 +69,7 @@ struct Runtime {
     int pair_mode = 0;            // block-of-two passes (k_chain2, k_chain2_bwd): 0 automatic | 1 variant 17, wherever legal | -1 variant 18, never
     bool pair_bwd_off = false;    // variant 19: automatic, but one factor per adjoint launch (k_chain)
     int pair_bwd_stage = 0;       // tape vectors of k_chain2_bwd: 0 automatic | -1 variant 20, through registers | 1 variant 21, by LDS-DMA
+    int pair_phases = -1;         // request order and store policy of the block kernels: -1 automatic | variants 22..30: 4 * ORD + WT (pair_launch.hpp)
     int chain_lgt = 9;            // log2(threads per tile workgroup) of explicitly chosen chained variants
     // state-sharded run: where the partner slabs arrive and who moves them (RydProblem.shard_recv / shard_exchange)
     void* const* shard_recv = nullptr;
@@ -93,11 +94,15 @@ struct Runtime {
 // RydProblem.kernel_variant -> Runtime (include/rydiff.h lists the values)
 int decode_variant(const RydProblem* p, Runtime& rt) {
     int v = p->kernel_variant;
-    if (v < 0 || v > 21 || v == 5 || v == 6) return fail(RYDIFF_EINVAL, "kernel_variant must be 0..4 or 7..21");
-    rt.pair_mode = (v == 17 || v == 20 || v == 21) ? 1 : (v == 18 ? -1 : 0);
+    if (v < 0 || v > 30 || v == 5 || v == 6) return fail(RYDIFF_EINVAL, "kernel_variant must be 0..4 or 7..30");
+    rt.pair_mode = (v == 17 || v >= 20) ? 1 : (v == 18 ? -1 : 0);
     rt.pair_bwd_off = v == 19;
-    rt.pair_bwd_stage = v == 20 ? -1 : (v == 21 ? 1 : 0);
-    if (v >= 17 && v <= 21) v = 0;
+    rt.pair_bwd_stage = (v == 21 || v == 29) ? 1 : (v >= 20 ? -1 : 0);
+    // 22: requests vector-major | 23..25: write-through level 1..3 | 26..28: both | 29: vector-major with LDS-DMA staging | 30: neither
+    // (17, 20 and 21 take the automatic combination)
+    static constexpr int kPhases[9] = {4, 1, 2, 3, 5, 6, 7, 4, 0};
+    rt.pair_phases = v >= 22 ? kPhases[v - 22] : -1;
+    if (v >= 17) v = 0;
     rt.generic_direct = v == 9;
     if (v == 9) v = 1;
     rt.force_three = v == 7 ? 1 : (v == 11 ? 2 : 0);

@@ -84,9 +84,10 @@ void describe_kernels(const Runtime& rt, const RydProblem* p, bool backward, Ryd
             const int lgt = rt.variant == 0 ? ((bwd && cplx) ? 9 : 10) : rt.chain_lgt;
             const bool res = xcd_group_size(rt, bwd != 0) > 0;
             if (!bwd && pairs)
-                std::snprintf(info->kernel_fwd, sizeof(info->kernel_fwd), "k_chain2<%d,10>", kTileBits);
+                std::snprintf(info->kernel_fwd, sizeof(info->kernel_fwd), "k_chain2<%d,10,%s,%d>", kTileBits, b(pair_vec_major(rt)), pair_through(rt));
             else if (bwd && pairs_bwd)
-                std::snprintf(info->kernel_bwd, sizeof(info->kernel_bwd), "k_chain2_bwd<%d,10,%s>", kTileBits, b(pair_bwd_dma(rt)));
+                std::snprintf(info->kernel_bwd, sizeof(info->kernel_bwd), "k_chain2_bwd<%d,10,%s,%d,%s>", kTileBits, b(pair_vec_major(rt)),
+                              pair_through(rt), b(pair_bwd_dma(rt)));
             else if (chain_geom(rt).lt == kWideTileBits)
                 std::snprintf(bwd ? info->kernel_bwd : info->kernel_fwd, sizeof(info->kernel_fwd), "k_chain_wide<%d,%s,%s,%s>", kWideTileBits,
                               b(cplx), b(bwd != 0), b(fast));
