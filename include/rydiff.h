@@ -141,6 +141,10 @@ typedef struct RydProblem {
      *     3: all).  22 vector-major | 23 / 24 / 25 write-through level 1 / 2 / 3 | 26 / 27 / 28 both | 29 vector-major with LDS-DMA
      *     staging and streaming stores | 30 neither (wave-major requests, streaming stores).  DESIGN.md section 3; automatic, 17, 20
      *     and 21 take the combination that measured fastest (that of 28)
+     *  31..34 as 20, with PACED input requests: a wave requests w (adjoint: w and x_a) only once half of its v
+     *     (mu) is back, awaits v alone for the first finishing round, and requests t behind that round once half of its w is back.
+     *     31 forward | 32 adjoint | 33 both | 34 forward, with t requested before the first round instead.  17 and 20..30 never pace;
+     *     automatic takes the paced adjoint kernel (that of 32) and the unpaced forward kernel
      * "automatic" takes the one-launch sweeps up to 12 qubits, the direct kernels while few tiles are in flight
      * (B * 2^N <= 2^18, with gradients 2^19) and the chained passes beyond.  Results do not depend on the variant beyond rounding. */
     int32_t kernel_variant;

@@ -292,12 +292,13 @@ __device__ __forceinline__ void partner_sums_lanes(const double2& own, uint32_t 
 }
 
 #ifdef RYDIFF_TIMELINE
-// tuning builds: per-workgroup phase timestamps of the last launch, [4096][8]; a ninth stamp (slot 8) lives behind them, [4096]
-__device__ unsigned long long g_timeline[4096 * 9];
+// tuning builds: per-workgroup phase timestamps of the last launch, [4096][8]; the stamps of slots 8, 9 and 10 live behind them,
+// [3][4096]
+__device__ unsigned long long g_timeline[4096 * 11];
 #define RYDIFF_TL(slot)                                                                                   \
     do {                                                                                                  \
         if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.x < 4096 && a.has_p && a.has_q)               \
-            g_timeline[(slot) < 8 ? blockIdx.x * 8 + (slot) : 4096 * 8 + blockIdx.x] = __builtin_readcyclecounter(); \
+            g_timeline[(slot) < 8 ? blockIdx.x * 8 + (slot) : 4096 * (slot) + blockIdx.x] = __builtin_readcyclecounter(); \
     } while (0)
 #else
 #define RYDIFF_TL(slot)

@@ -51,10 +51,20 @@ struct Chain2Args {
 // still awaits each input where it uses it.  (The early return above the loads is workgroup-uniform.)
 // WT: which outputs are stored write-through (through_store) instead of streaming (stream_store, dirty in L2 until the end of the
 // kernel): 0 none | 1 v_mid and y, which have the whole start stage behind them | 2 also w' | 3 all, t' included.
-template <int LT, int LGT, bool ORD = false, int WT = 0>
+// PACE (with ORD; replaces its two barriers): w and t are kept OUT of the memory system while v is wanted, so that the finishing
+// rounds run inside the load phase.  Each wave requests v, waits (counted s_waitcnt) until half of its v is back and only then
+// requests w; it awaits v alone for round A.  1: t is requested after round A's partner sums, once half of the wave's w is back,
+// in program order ahead of the v_mid stores, and round B runs while it lands | 2: t is requested before round A's barrier, as
+// soon as the wave's v is complete, without a look at w.  The four v_mid stores are issued whether there is a destination or not
+// (without one the buffer has no records and the range check drops them), so that the wait for t is a counted one that leaves
+// exactly these four outstanding: behind a branch around them it would be vmcnt(0), the counter retires in order, and t would wait
+// for their acknowledgement.  A chain's first launch requests v and w only and takes y from w; a one-factor block retires t unused.
+// No arithmetic statement differs: every stored value is bit-identical.
+template <int LT, int LGT, bool ORD = false, int WT = 0, int PACE = 0>
 __global__ __launch_bounds__(1 << LGT) void k_chain2(Chain2Args a) {
     constexpr int NT = 1 << LGT, R = 1 << (LT - LGT);
     static_assert(WT >= 0 && WT <= 3);
+    static_assert(PACE >= 0 && PACE <= 2 && (!PACE || ORD) && (!PACE || R == 4), "pacing: vector-major kernels with four elements per thread");
     extern __shared__ __attribute__((aligned(16))) double2 tiles[];
     double* red = reinterpret_cast<double*>(tiles + 2 * (size_t(1) << LT));
     const unsigned tid = threadIdx.x;
@@ -92,14 +102,23 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2(Chain2Args a) {
         xg[r] = xbase | (i & lomask) | ((i >> a.lo) << a.hs);
         uu[r] = stream_load(a.v + boff + xg[r]);
     }
-    if constexpr (ORD) __builtin_amdgcn_s_barrier();  // every wave's v is requested before any wave's w
+    if constexpr (ORD && !PACE) __builtin_amdgcn_s_barrier();  // every wave's v is requested before any wave's w
+    if constexpr (PACE) {  // ... PACE: not before half of this wave's own v is back (the table entries were requested ahead of v)
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+    }
     // w and t requested with v, outside of control flow (the host passes valid pointers for the first launch too): each is awaited
     // where it is first used — w after the first round, t after the second
 #pragma unroll
     for (int r = 0; r < R; ++r) ww[r] = stream_load(a.w + boff + xg[r]);
-    if constexpr (ORD) __builtin_amdgcn_s_barrier();  // ... and every wave's w before any wave's t
+    if constexpr (ORD && !PACE) __builtin_amdgcn_s_barrier();  // ... and every wave's w before any wave's t
+    if constexpr (!PACE) {
 #pragma unroll
-    for (int r = 0; r < R; ++r) tt[r] = stream_load(a.t + boff + xg[r]);
+        for (int r = 0; r < R; ++r) tt[r] = stream_load(a.t + boff + xg[r]);
+    } else {
+        __builtin_amdgcn_sched_barrier(0);  // (w is requested before anything below is awaited)
+    }
     // ORD: the amplitude indices are taken afresh for each stage's stores, from a copy of tid the compiler cannot see through (as in
     // k_chain2_bwd): otherwise the 64-bit addresses of the loads stay live up to the stores and spill
     auto reindex = [&]() {
@@ -154,6 +173,14 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2(Chain2Args a) {
         return tile;
     };
     auto cmul = [](double xr, double xi, const double2& z) { return make_double2(xr * z.x - xi * z.y, xr * z.y + xi * z.x); };
+    auto request_t = [&]() {  // (PACE) nothing moves across the request: it stands where it is written
+        __builtin_amdgcn_sched_barrier(0);
+        // (uniform base + 32-bit byte offset, which the 2^20 amplitudes of the largest legal shape fit: no 64-bit address per element)
+        const char* tbase = reinterpret_cast<const char*>(a.t + boff);
+#pragma unroll
+        for (int r = 0; r < R; ++r) tt[r] = stream_load(reinterpret_cast<const double2*>(tbase + xg[r] * unsigned(sizeof(double2))));
+        __builtin_amdgcn_sched_barrier(0);
+    };
 
     double2 y[R];
     if (a.has_p) {
@@ -162,9 +189,30 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2(Chain2Args a) {
         if constexpr (ORD) c = c_fin;
         else c = cf[0];
         double2 s[R], h1[R], ds[R];
-        const double2* vtile = put(uu);
+        const double2* vtile;
+        if constexpr (PACE == 2) {  // put(uu), with t requested between the tile's write (v is complete) and round A's barrier
+            double2* tile = tiles + (size_t(buf) << LT);
+#pragma unroll
+            for (int r = 0; r < R; ++r) tile[unsigned(r) * NT + tid] = uu[r];
+            request_t();
+            __syncthreads();
+            buf ^= 1;
+            vtile = tile;
+        } else {
+            vtile = put(uu);
+        }
         RYDIFF_TL(1);
         partner_sums<LT, LGT, false>(vtile, uu, a.fin_mask, tid, s, ds);
+        if constexpr (PACE == 1) {  // only w is outstanding here: t follows once half of it is back
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            request_t();
+        }
+#ifdef RYDIFF_TIMELINE
+#pragma unroll
+        for (int r = 0; r < R; ++r) asm volatile("" ::"v"(ww[r].x), "v"(ww[r].y));
+        RYDIFF_TL(8);  // (tuning builds: w landed in this wave)
+#endif
         double d[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -175,7 +223,19 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2(Chain2Args a) {
             y[r] = make_double2(p.x + q.x, p.y + q.y);
         }
         RYDIFF_TL(2);
-        if (a.vmid_out) {
+        if constexpr (PACE) {
+            // Always four stores, so that the wait for t is a counted one that leaves exactly these four outstanding: behind a
+            // branch it would be vmcnt(0), the counter retires in order, and t would wait for their acknowledgement.  Without a
+            // destination the buffer has no records, and the range check drops every element.
+            static_assert(WT >= 1, "pacing: v_mid goes through through_store");
+            double2* mid_base = a.vmid_out ? a.vmid_out + boff : nullptr;
+            const uint32_t mid_n = a.vmid_out ? a.dim : 0u;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double2 p = cmul(a.g1_r, a.g1_i, uu[r]), q = cmul(a.b1_r, a.b1_i, h1[r]);
+                through_store(mid_base, mid_n, xg[r], make_double2(p.x + q.x, p.y + q.y));
+            }
+        } else if (a.vmid_out) {
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const double2 p = cmul(a.g1_r, a.g1_i, uu[r]), q = cmul(a.b1_r, a.b1_i, h1[r]);
@@ -187,6 +247,11 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2(Chain2Args a) {
 #pragma unroll
             for (int r = 0; r < R; ++r) e[r] = make_double2(h1[r].x + c * ww[r].x, h1[r].y + c * ww[r].y);
             partner_sums<LT, LGT, false>(put(e), e, a.fin_mask, tid, pe, ds);
+#ifdef RYDIFF_TIMELINE
+#pragma unroll
+            for (int r = 0; r < R; ++r) asm volatile("" ::"v"(tt[r].x), "v"(tt[r].y));
+            RYDIFF_TL(9);  // (tuning builds: t landed in this wave)
+#endif
 #pragma unroll
             for (int r = 0; r < R; ++r) {  // H^2 v = D h1 + c (t + P_Y' e)
                 const double2 z = make_double2(d[r] * h1[r].x + c * (tt[r].x + pe[r].x), d[r] * h1[r].y + c * (tt[r].y + pe[r].y));
@@ -194,6 +259,10 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2(Chain2Args a) {
                 y[r].x += k.x;
                 y[r].y += k.y;
             }
+        } else if constexpr (PACE) {
+            // a one-factor block has no use for t: its request is retired here, not behind the y stores (see the first launch, below)
+#pragma unroll
+            for (int r = 0; r < R; ++r) asm volatile("" ::"v"(tt[r].x), "v"(tt[r].y));
         }
         RYDIFF_TL(3);
 #pragma unroll
@@ -211,8 +280,9 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2(Chain2Args a) {
         // A chain's first launch has no block to finish, and the host passes v for w and t as well.  ORD: y is taken from the LAST of
         // the three requests, which retires all of them on this path.  Left pending, they would make the start stage of the OTHER
         // path wait for the acknowledgement of its y stores: the compiler places its waits after the join of the two paths.
+        // PACE: t is requested inside the other path, so the last request here is w.
 #pragma unroll
-        for (int r = 0; r < R; ++r) y[r] = ORD ? tt[r] : uu[r];
+        for (int r = 0; r < R; ++r) y[r] = PACE ? ww[r] : (ORD ? tt[r] : uu[r]);
     }
     if (!a.has_q) return;
 
@@ -326,10 +396,17 @@ constexpr size_t chain2_bwd_lds_bytes() {
 // before round A's barrier and read after it, by the wave that issued it.  !DMA: the register-staged kernel described above.
 // ORD, WT: as in k_chain2.  ORD: every wave requests mu, then (behind a bare execution barrier) w, then (behind another) the tape
 // vectors.  WT: 1 mu_out, which has the whole start stage behind it | 2 also w' | 3 all.
-template <int LT, int LGT, bool ORD, int WT, bool DMA>
+// PACE (with ORD, !DMA; replaces the two barriers): as in k_chain2.  Each wave requests mu, waits (counted s_waitcnt) until half of
+// its mu is back, and only then requests w and x_a.  Round A awaits mu alone and runs while the two land; x_a is not parked in LDS
+// at all: it waits out round A's partner sums in registers (x_b and t are not live yet) and is consumed straight from them where P mu
+// is formed, which is also where w is awaited.  Not on the LDS-DMA staging: with a global_load_lds pending next to ordinary loads
+// the compiler treats the counter as retiring out of order and awaits mu with vmcnt(0), x_a and w included (seen in the gfx950 ISA).
+// A chain's first launch retires w and x_a where it takes y.
+template <int LT, int LGT, bool ORD, int WT, bool DMA, int PACE = 0>
 __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
     constexpr int NT = 1 << LGT, R = 1 << (LT - LGT), NW = NT / 64;
     static_assert(WT >= 0 && WT <= 3);
+    static_assert(PACE >= 0 && PACE <= 1 && (!PACE || (ORD && !DMA && R == 4)), "pacing: the vector-major register-staged kernel, four elements per thread");
     constexpr int XBL = DMA ? kChain2BwdXbLds : 0;
     static_assert(XBL <= R && (2 * NW * sizeof(double)) % sizeof(double2) == 0);
     extern __shared__ __attribute__((aligned(16))) double2 tiles[];
@@ -382,11 +459,16 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
         xg[r] = xbase | (i & lomask) | ((i >> a.lo) << a.hs);
         uu[r] = stream_load(a.mu + boff + xg[r]);
     }
-    if constexpr (ORD) __builtin_amdgcn_s_barrier();  // every wave's mu is requested before any wave's w
+    if constexpr (ORD && !PACE) __builtin_amdgcn_s_barrier();  // every wave's mu is requested before any wave's w
+    if constexpr (PACE) {  // ... PACE: not before half of this wave's own mu is back (the table entries were requested ahead of mu)
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+    }
     // w and x_a requested with mu, outside of control flow (the host passes valid pointers for the first launch too)
 #pragma unroll
     for (int r = 0; r < R; ++r) ww[r] = stream_load(a.w + boff + xg[r]);
-    if constexpr (ORD) __builtin_amdgcn_s_barrier();  // ... and every wave's w before any wave's tape vector
+    if constexpr (ORD && !PACE) __builtin_amdgcn_s_barrier();  // ... and every wave's w before any wave's tape vector
     [[maybe_unused]] double2 xa[R];
     if constexpr (DMA) {
         const unsigned wv = __builtin_amdgcn_readfirstlane(tid & ~63u);  // a wave's 64 slots of one r are 1 KiB of contiguous LDS
@@ -445,11 +527,16 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
     for (int r = 0; r < R; ++r) asm volatile("" ::"v"(uu[r].x), "v"(uu[r].y));
     RYDIFF_TL(8);  // (tuning builds: mu landed in this wave, apart from w and x_a)
 #endif
+    // PACE: mu alone is awaited here; w and x_a are retired behind round A's partner sums, or on the first launch's path
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        asm volatile("" ::"v"(uu[r].x), "v"(uu[r].y), "v"(ww[r].x), "v"(ww[r].y));
-        if constexpr (!DMA) asm volatile("" ::"v"(xa[r].x), "v"(xa[r].y));
-        if (DMA && r >= XBL) asm volatile("" ::"v"(xb[r].x), "v"(xb[r].y));
+        if constexpr (PACE) {
+            asm volatile("" ::"v"(uu[r].x), "v"(uu[r].y));
+        } else {
+            asm volatile("" ::"v"(uu[r].x), "v"(uu[r].y), "v"(ww[r].x), "v"(ww[r].y));
+            if constexpr (!DMA) asm volatile("" ::"v"(xa[r].x), "v"(xa[r].y));
+            if (DMA && r >= XBL) asm volatile("" ::"v"(xb[r].x), "v"(xb[r].y));
+        }
     }
     double2 y[R];
     if (a.has_p) {
@@ -462,19 +549,42 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
             // x_a waits out round A in this thread's own slots of the other LDS buffer (not in registers); e replaces it there
             // (DMA: it is there already, retired by the vmcnt(0) in front of round A's barrier)
             double2* etile = tiles + (size_t(buf ^ 1) << LT);
-            if constexpr (DMA) {
+            if constexpr (PACE) {
+                // (nothing: x_a stays in registers and is awaited behind the partner sums)
+            } else if constexpr (DMA) {
+#ifdef RYDIFF_TIMELINE
+                RYDIFF_TL(9);  // (tuning builds: w landed in this wave, retired above)
+#endif
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             } else {
+#ifdef RYDIFF_TIMELINE
+                RYDIFF_TL(9);
+#endif
 #pragma unroll
                 for (int r = 0; r < R; ++r) etile[unsigned(r) * NT + tid] = xa[r];
             }
+#ifdef RYDIFF_TIMELINE
+            if constexpr (!PACE) RYDIFF_TL(10);  // (tuning builds: x_a landed in this wave)
+#endif
             double2 s[R], ds[R];
             const double2* mtile = put(uu);
             RYDIFF_TL(1);
             partner_sums<LT, LGT, false>(mtile, uu, a.fin_mask, tid, s, ds);
+#ifdef RYDIFF_TIMELINE
+            if constexpr (PACE) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) asm volatile("" ::"v"(ww[r].x), "v"(ww[r].y));
+                RYDIFF_TL(9);
+#pragma unroll
+                for (int r = 0; r < R; ++r) asm volatile("" ::"v"(xa[r].x), "v"(xa[r].y));
+                RYDIFF_TL(10);
+            }
+#endif
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const double2 xav = etile[unsigned(r) * NT + tid];
+                double2 xav;
+                if constexpr (PACE) xav = xa[r];
+                else xav = etile[unsigned(r) * NT + tid];
                 const double d = du[r] + cdet * cnt(r);
                 pm[r] = make_double2(ww[r].x + s[r].x, ww[r].y + s[r].y);
                 const double2 h1 = make_double2(d * uu[r].x + c * pm[r].x, d * uu[r].y + c * pm[r].y);  // H mu
@@ -578,6 +688,7 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             y[r] = uu[r];
+            if constexpr (PACE) asm volatile("" ::"v"(ww[r].x), "v"(ww[r].y), "v"(xa[r].x), "v"(xa[r].y));  // (every request of the top retired)
         }
     }
     auto flush = [&]() {  // after the barrier that follows the parks: one atomic per quantity and workgroup

@@ -63,6 +63,17 @@ constexpr int kPairThroughDefault = 3;
 bool pair_vec_major(const Runtime& rt) { return rt.pair_phases >= 0 ? (rt.pair_phases >> 2) != 0 : kPairVecMajorDefault; }
 int pair_through(const Runtime& rt) { return rt.pair_phases >= 0 ? (rt.pair_phases & 3) : kPairThroughDefault; }
 
+// Paced input requests of the block kernels (their template parameter PACE; variants 31..34).  They exist next to the automatic
+// request order and store policy only (vector-major, everything written through), the adjoint one with register staging only.
+// Automatic (C3, the only shape where the blocks are automatic): the paced ADJOINT kernel, +1.9 % on the bench
+// line and past the bar of ten spreads; the paced forward kernels did not clear it (31: +0.5 %, 34: -0.6 %) and stay selectable.
+constexpr int kPairPaceFwdDefault = 0;
+constexpr int kPairPaceBwdDefault = 1;
+int pair_pace_fwd(const Runtime& rt) {
+    if (!pair_vec_major(rt) || pair_through(rt) != 3) return 0;
+    return rt.pair_pace_fwd >= 0 ? rt.pair_pace_fwd : kPairPaceFwdDefault;
+}
+
 // f(bool_constant<ORD>, integral_constant<int, WT>) for the run-time pair (ord, wt): the instantiations that exist
 template <class F>
 int with_pair_phases(bool ord, int wt, F f) {
@@ -81,14 +92,24 @@ int with_pair_phases(bool ord, int wt, F f) {
     return fail(RYDIFF_EINVAL, "internal: no such block kernel");
 }
 
-template <int LGT, bool ORD, int WT>
+template <int LGT, bool ORD, int WT, int PACE = 0>
 int launch_chain2_t(const Chain2Args& ca, unsigned tiles, hipStream_t stream) {
     constexpr int LT = kTileBits;
     const size_t lds = 2 * (size_t(1) << LT) * sizeof(double2) + 256;  // two tile buffers + one double per wave
-    if (int rc = set_max_dynamic_lds_once<&k_chain2<LT, LGT, ORD, WT>>(lds)) return rc;
-    hipLaunchKernelGGL((k_chain2<LT, LGT, ORD, WT>), dim3(tiles, unsigned(ca.b_count)), dim3(1 << LGT), lds, stream, ca);
+    if (int rc = set_max_dynamic_lds_once<&k_chain2<LT, LGT, ORD, WT, PACE>>(lds)) return rc;
+    hipLaunchKernelGGL((k_chain2<LT, LGT, ORD, WT, PACE>), dim3(tiles, unsigned(ca.b_count)), dim3(1 << LGT), lds, stream, ca);
     LAUNCH_CHECK();
     return RYDIFF_OK;
+}
+
+int launch_chain2(const Runtime& rt, const Chain2Args& ca, unsigned tiles, hipStream_t stream) {
+    switch (pair_pace_fwd(rt)) {
+        case 1: return launch_chain2_t<10, true, 3, 1>(ca, tiles, stream);
+        case 2: return launch_chain2_t<10, true, 3, 2>(ca, tiles, stream);
+    }
+    return with_pair_phases(pair_vec_major(rt), pair_through(rt), [&](auto ord, auto wt) {
+        return launch_chain2_t<10, decltype(ord)::value, decltype(wt)::value>(ca, tiles, stream);
+    });
 }
 
 // Forward chain in blocks of two factors of one exponential (an exponential of odd degree ends in a one-factor block).  Same
@@ -146,9 +167,7 @@ int run_chain2(const Runtime& rt, char* ws, const std::vector<ChainItem>& items,
             ca.n_obs = cs.n_obs;
             ca.exp_ostride = cs.exp_ostride;
         }
-        int rc = with_pair_phases(pair_vec_major(rt), pair_through(rt), [&](auto ord, auto wt) {
-            return launch_chain2_t<10, decltype(ord)::value, decltype(wt)::value>(ca, tiles, stream);
-        });
+        int rc = launch_chain2(rt, ca, tiles, stream);
         if (rc) return rc;
         if (ca.has_p) {
             if (ca.vmid_out) {
@@ -168,6 +187,7 @@ int run_chain2(const Runtime& rt, char* ws, const std::vector<ChainItem>& items,
 // tiles; variant 19 keeps the one-factor adjoint (k_chain) next to automatic forward blocks.  Variants 20 / 21: blocks wherever
 // legal (as 17) with the tape vectors staged through registers / by LDS-DMA (k_chain2_bwd<.., false / true>).  Variants 22..30: as
 // 20, with a request order and a store policy of their own (pair_vec_major, pair_through); 29 alone stages by LDS-DMA.
+// Variants 31..34: as 20, with paced input requests (pair_pace_fwd, pair_pace_bwd).
 bool pair_bwd_enabled(const Runtime& rt) {
     const ChainGeom g = chain_geom(rt);
     return !rt.pair_bwd_off && rt.real_amp_grad && pair_enabled(rt) && g.lt == kTileBits && g.layouts == 2;
@@ -178,13 +198,18 @@ bool pair_bwd_enabled(const Runtime& rt) {
 constexpr bool kPairBwdDmaDefault = false;
 bool pair_bwd_dma(const Runtime& rt) { return rt.pair_bwd_stage ? rt.pair_bwd_stage > 0 : kPairBwdDmaDefault; }
 
-template <int LGT, bool ORD, int WT, bool DMA>
+int pair_pace_bwd(const Runtime& rt) {
+    if (!pair_vec_major(rt) || pair_through(rt) != 3 || pair_bwd_dma(rt)) return 0;
+    return rt.pair_pace_bwd >= 0 ? rt.pair_pace_bwd : kPairPaceBwdDefault;
+}
+
+template <int LGT, bool ORD, int WT, bool DMA, int PACE = 0>
 int launch_chain2_bwd_t(const Chain2BwdArgs& ca, unsigned tiles, hipStream_t stream) {
     constexpr int LT = kTileBits;
     constexpr size_t lds = chain2_bwd_lds_bytes<LT, LGT, DMA>();
     static_assert(lds <= 160 * 1024, "k_chain2_bwd: more LDS than a gfx950 workgroup can have");
-    if (int rc = set_max_dynamic_lds_once<&k_chain2_bwd<LT, LGT, ORD, WT, DMA>>(lds)) return rc;
-    hipLaunchKernelGGL((k_chain2_bwd<LT, LGT, ORD, WT, DMA>), dim3(tiles, unsigned(ca.b_count)), dim3(1 << LGT), lds, stream, ca);
+    if (int rc = set_max_dynamic_lds_once<&k_chain2_bwd<LT, LGT, ORD, WT, DMA, PACE>>(lds)) return rc;
+    hipLaunchKernelGGL((k_chain2_bwd<LT, LGT, ORD, WT, DMA, PACE>), dim3(tiles, unsigned(ca.b_count)), dim3(1 << LGT), lds, stream, ca);
     LAUNCH_CHECK();
     return RYDIFF_OK;
 }
@@ -193,6 +218,7 @@ int launch_chain2_bwd_t(const Chain2BwdArgs& ca, unsigned tiles, hipStream_t str
 // stores (variant 29).
 int launch_chain2_bwd(const Runtime& rt, const Chain2BwdArgs& ca, unsigned tiles, hipStream_t stream) {
     const bool ord = pair_vec_major(rt);
+    if (pair_pace_bwd(rt)) return launch_chain2_bwd_t<10, true, 3, false, 1>(ca, tiles, stream);
     if (pair_bwd_dma(rt)) {
         if (ord && pair_through(rt) == 3) return launch_chain2_bwd_t<10, true, 3, true>(ca, tiles, stream);
         if (ord && pair_through(rt) == 0) return launch_chain2_bwd_t<10, true, 0, true>(ca, tiles, stream);

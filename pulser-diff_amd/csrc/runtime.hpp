@@ -70,6 +70,8 @@ struct Runtime {
     bool pair_bwd_off = false;    // variant 19: automatic, but one factor per adjoint launch (k_chain)
     int pair_bwd_stage = 0;       // tape vectors of k_chain2_bwd: 0 automatic | -1 variant 20, through registers | 1 variant 21, by LDS-DMA
     int pair_phases = -1;         // request order and store policy of the block kernels: -1 automatic | variants 22..30: 4 * ORD + WT (pair_launch.hpp)
+    int pair_pace_fwd = -1;       // paced input requests of k_chain2 (its PACE): -1 automatic | 0 variants 17, 20..30, 32 | 1 variants 31, 33 | 2 variant 34
+    int pair_pace_bwd = -1;       // ... of k_chain2_bwd: -1 automatic | 0 variants 17, 20..31, 34 | 1 variants 32, 33
     int chain_lgt = 9;            // log2(threads per tile workgroup) of explicitly chosen chained variants
     // state-sharded run: where the partner slabs arrive and who moves them (RydProblem.shard_recv / shard_exchange)
     void* const* shard_recv = nullptr;
@@ -94,14 +96,19 @@ struct Runtime {
 // RydProblem.kernel_variant -> Runtime (include/rydiff.h lists the values)
 int decode_variant(const RydProblem* p, Runtime& rt) {
     int v = p->kernel_variant;
-    if (v < 0 || v > 30 || v == 5 || v == 6) return fail(RYDIFF_EINVAL, "kernel_variant must be 0..4 or 7..30");
+    if (v < 0 || v > 34 || v == 5 || v == 6) return fail(RYDIFF_EINVAL, "kernel_variant must be 0..4 or 7..34");
     rt.pair_mode = (v == 17 || v >= 20) ? 1 : (v == 18 ? -1 : 0);
     rt.pair_bwd_off = v == 19;
     rt.pair_bwd_stage = (v == 21 || v == 29) ? 1 : (v >= 20 ? -1 : 0);
     // 22: requests vector-major | 23..25: write-through level 1..3 | 26..28: both | 29: vector-major with LDS-DMA staging | 30: neither
     // (17, 20 and 21 take the automatic combination)
     static constexpr int kPhases[9] = {4, 1, 2, 3, 5, 6, 7, 4, 0};
-    rt.pair_phases = v >= 22 ? kPhases[v - 22] : -1;
+    rt.pair_phases = (v >= 22 && v <= 30) ? kPhases[v - 22] : -1;
+    // 31..34: as 20 (register staging, the automatic order and store policy) with paced input requests: 31 forward | 32 adjoint |
+    // 33 both | 34 forward, t requested before round A.  17 and 20..30 keep the unpaced kernels whatever the automatic choice is.
+    const bool pair_forced = v == 17 || v >= 20;
+    rt.pair_pace_fwd = (v == 31 || v == 33) ? 1 : (v == 34 ? 2 : (pair_forced ? 0 : -1));
+    rt.pair_pace_bwd = (v == 32 || v == 33) ? 1 : (pair_forced ? 0 : -1);
     if (v >= 17) v = 0;
     rt.generic_direct = v == 9;
     if (v == 9) v = 1;

@@ -83,8 +83,12 @@ void describe_kernels(const Runtime& rt, const RydProblem* p, bool backward, Ryd
             const bool cplx = (rt.flags & 1) != 0 || (bwd && !p->real_amp_grad);
             const int lgt = rt.variant == 0 ? ((bwd && cplx) ? 9 : 10) : rt.chain_lgt;
             const bool res = xcd_group_size(rt, bwd != 0) > 0;
-            if (!bwd && pairs)
+            if (!bwd && pairs && pair_pace_fwd(rt))
+                std::snprintf(info->kernel_fwd, sizeof(info->kernel_fwd), "k_chain2<%d,10,true,3,%d>", kTileBits, pair_pace_fwd(rt));
+            else if (!bwd && pairs)
                 std::snprintf(info->kernel_fwd, sizeof(info->kernel_fwd), "k_chain2<%d,10,%s,%d>", kTileBits, b(pair_vec_major(rt)), pair_through(rt));
+            else if (bwd && pairs_bwd && pair_pace_bwd(rt))
+                std::snprintf(info->kernel_bwd, sizeof(info->kernel_bwd), "k_chain2_bwd<%d,10,true,3,false,%d>", kTileBits, pair_pace_bwd(rt));
             else if (bwd && pairs_bwd)
                 std::snprintf(info->kernel_bwd, sizeof(info->kernel_bwd), "k_chain2_bwd<%d,10,%s,%d,%s>", kTileBits, b(pair_vec_major(rt)),
                               pair_through(rt), b(pair_bwd_dma(rt)));
