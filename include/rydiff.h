@@ -208,6 +208,24 @@ typedef struct RydProblem {
      * knows where that is (pulser-diff_amd/hamiltonian.py: piece_refinement) and the library does not have to read them back. */
     const uint8_t* dp5_piece_refine;
 
+    /* OCCUPATION CORRELATIONS OF A DENSITY-MATRIX REGISTER (dm_atoms = n > 0, below): the bit moments of the diagonal of rho.  With
+     * v = vec(rho), p[x] = Re v[x (2^n + 1)] (x < 2^n) and x_q the index bit of atom q (atom q <-> bit n-1-q of x):
+     *   S = sum_x p[x],   B_q = sum_x p[x] x_q  (q = 0..n-1),   B_qr = sum_x p[x] x_q x_r  (0 <= q < r < n)
+     * dm_moments = 1 adds 1 + n + n(n-1)/2 rows to expect_out / grad_expect BEHIND the dm_rdm rows (the last block of all): S, then
+     * B_q in ascending q, then B_qr in lexicographic (q, r) — the order of the ket block of bit_moments with N = n.  p is NOT clamped
+     * (the shots clamp, these rows do not): every row is linear in rho, and rho is assumed neither Hermitian nor normalised.  One
+     * workgroup per (save point, trajectory) forms all rows in float64 in one fixed order (no atomics): two calls on the same input
+     * give bit-identical rows, and every row is written.  rydiff_backward: with g the rows of grad_expect at (k, b), the cotangent
+     * added to Re v[x (2^n + 1)] is q(x) = g_S + sum_q g_q x_q + sum_{q<r} g_qr x_q x_r (factor 1, the convention of the dm_diag
+     * rows), added behind the other density-matrix cotangents in the same workspace buffer.  Honoured wherever the other dm_* rows
+     * are: every kernel family, every tape mode, states_out == NULL without a tape.  rydiff_forward_tangent (with
+     * RYDIFF_TANGENT_DENSITY_MATRIX): the rows are linear, so the rows of dexpect_out are the same kernel on d rho_d.  RYDIFF_EINVAL:
+     * a value other than 0 or 1 (with dm_atoms > 0).  bit_moments keeps its meaning (kets) and stays RYDIFF_ENOTIMPL with
+     * dm_atoms > 0.  Traffic per state: the 2^n real parts of the diagonal (2^n * 8 B); nothing of size 2^n or 4^n is written.
+     * dm_atoms = 0: the field is ignored, like the other dm_* fields.  dm_moments = 0: nothing changes.  (The field sits in front of
+     * n_shots: the shot block, the 14 fields dm_atoms .. dm_shots, the overlap block and the Pauli block keep their neighbours.) */
+    int32_t dm_moments;           /* 0: off; 1: all atoms */
+
     /* MEASUREMENT SHOTS: amplitude indices sampled from |psi_b(t_k)|^2 at chosen save points by rydiff_forward, while the state is
      * on the device — no stored trajectory, no 2^N probabilities on the host.  The caller supplies the uniforms (its own generator and
      * seeding), which makes the rule deterministic.  For sampled save point k, trajectory b, shot s with uniform u:
@@ -303,6 +321,7 @@ typedef struct RydProblem {
      *                        normalised by the library; dm_fid_batch = 1: shared by the trajectories, B: one per trajectory)
      *   dm_purity row        sum_i |v_i|^2                                                  (Tr rho^2 for Hermitian rho)
  *   n_dm_rdms blocks     2 * 4^{m_o} rows each: the reduced density matrices above
+     *   dm_moments block     1 + n + n(n-1)/2 rows: the occupation correlations of the diagonal (dm_moments, above)
      * None of them assumes a Hermitian or normalised rho.  rydiff_backward differentiates every row: with g the row's entry of
      * grad_expect at (k, b), the cotangent added to v (torch's dL/dRe + i dL/dIm) is  g o[x] on the diagonal entries;
      * g w_s conj(phase_s(x)) at entry (x ^ xm, x);  g phi[x] conj(phi[y]);  2 g v — formed per save point in the workspace buffer of the
@@ -313,7 +332,7 @@ typedef struct RydProblem {
      * The ket-style fields keep their meaning on the doubled register.  Honoured by rydiff_forward in every kernel family and with
      * every tape mode (states_out == NULL without a tape included: rydiff_plan adds the trajectory the one-launch sweeps are
      * evaluated from).  Not together with shard_bits > 0 (RYDIFF_ENOTIMPL).  rydiff_forward_tangent evaluates the diag / Pauli /
-     * fidelity / purity rows and their tangents (not the RDMs, not the shots); rydiff_forward_geometry refuses dm_atoms > 0.  RYDIFF_EINVAL:
+     * fidelity / purity / moment rows and their tangents (not the RDMs, not the shots); rydiff_forward_geometry refuses dm_atoms > 0.  RYDIFF_EINVAL:
      * n_qubits != 2 * dm_atoms, dm_atoms outside [0, RYDIFF_MAX_DM_ATOMS], a count out of range (n_dm_diag <= RYDIFF_MAX_DM_DIAG,
      * strings <= RYDIFF_MAX_PAULI_STRINGS, n_dm_fid <= RYDIFF_MAX_OVERLAPS, dm_purity / dm_shots 0 or 1), a mask bit at or above n,
      * a NULL table with a non-zero count, dm_shots without n_shots.  Traffic per save point and trajectory: 2^n * 16 B per distinct
@@ -430,7 +449,8 @@ int rydiff_plan(const RydProblem* p, int need_tape, int need_backward, void* scr
  *   expect_out  DEVICE float64 [n_obs + n_pauli_obs + 2 * n_overlaps + 2 * sum_o 4^{m_o} + moment rows + dm rows][n_tsave][B] (diagonal observables
  *               first, then the Pauli ones, then Re / Im of every overlap, then Re / Im of every reduced-density-matrix entry, then with
  *               bit_moments the 1 + N + N(N-1)/2 moment rows S, B_q, B_qr, then the
- *               density-matrix rows n_dm_diag + n_dm_pauli_obs + n_dm_fid + dm_purity + 2 * sum_o 4^{m_o} over dm_rdm_masks), or NULL
+ *               density-matrix rows n_dm_diag + n_dm_pauli_obs + n_dm_fid + dm_purity + 2 * sum_o 4^{m_o} over dm_rdm_masks
+ *               + with dm_moments the 1 + n + n(n-1)/2 rows S, B_q, B_qr of the diagonal of rho), or NULL
  * With RydProblem.n_shots > 0 the measurement shots of the save points in shot_times go to RydProblem.shots_out on the way. */
 int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi0, void* states_out, double* expect_out,
                    void* workspace, size_t workspace_bytes, int need_tape, void* stream);
@@ -499,7 +519,7 @@ size_t rydiff_tangent_workspace_bytes_flags(const RydProblem* p, const RydPlanIn
  *                entry (a, a') at 2 (a 2^m + a'), Re then Im); with RYDIFF_TANGENT_MOMENTS and bit_moments = 1 followed by the
  *                Moments block behind the RDM block, as in rydiff_forward (1 + N + N(N-1)/2 rows: S, B_q in ascending q, B_qr at
  *                1 + N + q(2N-q-1)/2 + (r-q-1)); with dm_atoms > 0 followed by n_dm_diag + n_dm_pauli_obs + n_dm_fid + dm_purity
- *                rows, as there
+ *                rows and, with dm_moments, the 1 + n + n(n-1)/2 rows of the DmMoments block, as there
  *   dexpect_out  DEVICE float64 [n_dir][rows][n_tsave][B] (required): diagonal rows 2 sum_y o[y] Re(conj psi[y] dpsi_d[y]), Pauli
  *                rows 2 sum_s w_s Re<psi|P_s|dpsi_d>, overlap rows Re / Im <phi_o|dpsi_d>, RDM rows the entries of
  *                d rho_A = Tr_E(|dpsi_d><psi| + |psi><dpsi_d|) (the mirror entry is the exact conjugate, Im of the diagonal an exact
@@ -507,8 +527,9 @@ size_t rydiff_tangent_workspace_bytes_flags(const RydProblem* p, const RydPlanIn
  *                dp_d[y] = 2 Re(conj psi[y] dpsi_d[y]): dS_d = sum_y dp_d[y], dB_q = sum_y dp_d[y] y_q, dB_qr = sum_y dp_d[y] y_q y_r
  *                (no atomics, one fixed order: two calls give the same bits; only the n_dir real directions are evaluated); every
  *                save point, k = 0 included.  Need not be cleared.
- *                Density-matrix rows (dm_atoms > 0; v = vec(rho), dv_d its tangent): the diagonal, Pauli and fidelity rows are
- *                linear in v — the row's functional of dv_d — and the purity row is 2 Re sum_i conj(v_i) dv_d,i
+ *                Density-matrix rows (dm_atoms > 0; v = vec(rho), dv_d its tangent): the diagonal, Pauli, fidelity and moment rows
+ *                (dm_moments: k_dm_moments on dv_d, fixed order, no atomics) are linear in v — the row's functional of dv_d — and
+ *                the purity row is 2 Re sum_i conj(v_i) dv_d,i
  *   workspace    DEVICE, >= rydiff_tangent_workspace_bytes(p, info, n_dir)
  * Both solvers, coeff_batch 1 or B, dp5_piece_refine honoured (same plan); kernel_variant is ignored: the sweep has one kernel
  * family (launch per factor, one amplitude per thread).  With RYDIFF_TANGENT_PAIR_TERMS in tangent->flags dense pair terms

@@ -77,6 +77,7 @@ class RydProblem(ctypes.Structure):
         ("amp_conditioned_terms", ctypes.c_uint64),
         ("det_ones_terms", ctypes.c_uint64),
         ("dp5_piece_refine", ctypes.c_void_p),
+        ("dm_moments", ctypes.c_int32),
         ("n_shots", ctypes.c_int32),
         ("n_shot_times", ctypes.c_int32),
         ("shot_times", ctypes.c_void_p),

@@ -407,7 +407,9 @@ class TorchEmulator:
         strings (``PauliObservable``, e.g. from ``build_observable``) and overlaps with target states (``StateOverlap``; read with
         ``results.overlap``) and states of subsystems (``ReducedDensityMatrix``, e.g. from ``build_reduced_density_matrix``; read
         with ``results.reduced_density_matrix`` / ``results.entanglement_entropy`` / ``results.negativity``; master-equation runs
-        serve them — ``Tr_E rho`` — with ``store_states=False``) to be evaluated natively at every evaluation time; ``store_states=False`` keeps the trajectory out of the results.
+        serve them — ``Tr_E rho`` — with ``store_states=False``) and the occupation correlations (``OccupationCorrelations``; read
+        with ``results.occupations`` / ``occupation_correlations`` / ``structure_factor``; master-equation runs serve them — the
+        moments of the diagonal of rho — with ``store_states=False``) to be evaluated natively at every evaluation time; ``store_states=False`` keeps the trajectory out of the results.
 
         ``shots`` (extension): measurement shots drawn natively while the state is on the device — an int (that many at the final
         evaluation time) or a ``ShotRequest`` (``times="all"``: every evaluation time).  ``results.sample_state`` /
@@ -438,9 +440,6 @@ class TorchEmulator:
         moments = False
         for obs in observables or []:
             if isinstance(obs, OccupationCorrelations):
-                if solver == SolverType.DP5_ME:
-                    raise NotImplementedError("OccupationCorrelations is evaluated natively on kets only: in a master-equation run "
-                                              "the moments of diag(rho) are a follow-up; hand run() DiagonalObservable projectors.")
                 if ham.basis_name == "all":
                     raise NotImplementedError("OccupationCorrelations is not available in the three-level all-basis (an atom is "
                                               "two qubits there); reduce the stored states instead.")
@@ -508,16 +507,21 @@ class TorchEmulator:
                 raise NotImplementedError("StateOverlap observables of master-equation runs are evaluated natively (the fidelity "
                                           "<phi|rho|phi>) with store_states=False only; with stored states results.fidelity(obs) "
                                           "computes it from the density matrices without the observable being handed to run().")
+            if moments and solver == SolverType.DP5_ME and store_states:
+                raise NotImplementedError("OccupationCorrelations of master-equation runs is evaluated natively (the moments of the "
+                                          "diagonal of rho) with store_states=False only; with stored states results.occupations() / "
+                                          "occupation_correlations() / structure_factor() compute them from the density matrices "
+                                          "without the observable being handed to run().")
             if shots is not None and solver == SolverType.DP5_ME and store_states:
                 raise NotImplementedError("Native measurement shots of master-equation runs are drawn (from the diagonal of rho) with "
                                           "store_states=False only; with stored states sample_state draws from the stored density "
                                           "matrices.")
             if solver == SolverType.DP5_ME:  # density matrices (backend.py:495-509); without collapse noise L = 0
                 # diagonal tables, Pauli strings (unrotated: this path runs in no rotating frame), fidelities, the purity, reduced
-                # density matrices and the shots are taken from rho while it is on the device; store_states=False keeps the (n_t, 4^N) trajectory out
+                # density matrices, the occupation correlations and the shots are taken from rho while it is on the device; store_states=False keeps the (n_t, 4^N) trajectory out
                 res = mesolve(ham, psi0.to(dev), self._eval_times_array, ham.config, options,
-                              observables=obs_objs + pauli_objs + overlap_objs + purity_objs + rdm_objs, shots=shots,
-                              store_states=store_states)
+                              observables=obs_objs + pauli_objs + overlap_objs + purity_objs + rdm_objs
+                              + ([OccupationCorrelations()] if moments else []), shots=shots, store_states=store_states)
                 n_ex, n_ov = len(obs_objs) + len(pauli_objs), len(overlap_objs)
                 return CoherentResults(res.states, ham._size, ham.basis_name, self._eval_times_array, self._meas_basis, meas_errors,
                                        atom_order=tuple(ham._qdict), stats=res.stats, density=True,
@@ -525,7 +529,8 @@ class TorchEmulator:
                                        native_observables=obs_objs + pauli_objs, overlap_observables=overlap_objs,
                                        native_fidelities=res.expect[n_ex:n_ex + n_ov] if n_ov else None,
                                        native_purity=res.expect[n_ex + n_ov] if purity_objs else None, native_shots=res.shots,
-                                       native_rdms=res.rdms if rdm_objs else None, rdm_observables=rdm_objs)
+                                       native_rdms=res.rdms if rdm_objs else None, rdm_observables=rdm_objs,
+                                       native_moments=res.moments)
             result = sesolve(ham, psi0.to(dev), self._eval_times_array, solver=solver, options=options, obs_diag=obs_diag,
                              store_states=store_states, pauli_obs=pauli_objs, overlap_obs=overlap_objs, shots=shots, rdm_obs=rdm_objs,
                              moments=moments)

@@ -18,6 +18,12 @@
 //                   through LDS — one owner per output, plain stores, no atomics: bit-reproducible.  2^(n+m) entries per RDM and state
 //   k_dm_rdm_scatter  cotangent of ONE RDM, in place behind k_dm_apply / k_dm_scatter (one launch per RDM, stream-ordered: two RDMs, or an
 //                   RDM and a Pauli row, may own the same entry): thread (a, y) adds G[a][ext_A(y)] at entry (dep_A(a) | (y & E), y)
+//   k_dm_moments    occupation correlations of the diagonal (RydProblem.dm_moments): S, B_q, B_qr of p[x] = Re v[x (2^n + 1)], NOT clamped
+//                   (the rows are linear in rho).  2^n <= 2^12: the diagonal is one tile of moments_kernels.hpp — one workgroup per
+//                   state gathers it (real parts only, 2^n * 8 B) and runs moments_tile_body: fixed order, no atomics, plain stores
+//   k_dm_moments_scatter  their cotangent, in place behind everything above (the diagonal is also owned by the dm_diag rows, the
+//                   xm = 0 strings and the RDMs: stream order): thread x adds q(x) = g_S + sum_q g_q x_q + sum_{q<r} g_qr x_q x_r to
+//                   Re of entry (x, x)
 // The final sums of the first two follow the other observable kernels: wave shuffle, LDS, one atomic per block and row.
 #pragma once
 
@@ -372,4 +378,75 @@ __global__ __launch_bounds__(256) void k_dm_rdm_scatter(DmRdmScatterArgs a) {
     double2* dst = a.out + (size_t(blockIdx.z) * a.B + b) * (size_t(D) << a.n) + (size_t(x) << a.n) + y;
     const double2 cur = *dst;
     *dst = make_double2(cur.x + gr, cur.y + gi);
+}
+
+struct DmMomentsArgs {
+    const double2* v;    // state at save point k0, trajectory 0
+    size_t kstride;
+    double* out;         // the DmMoments block of expect_out: [1 + n + n(n-1)/2][n_tsave][B]
+    int n_tsave, k0, B, b_first, b_count, n;
+};
+
+// the weights of a density matrix: the real parts of its diagonal, as they are (no clamp: the rows are linear in rho)
+struct MomLoadDmDiag {
+    const double2* __restrict__ v;  // vec(rho) of this state
+    uint32_t D;                     // 2^n <= 2^kMomTileBits: positions past D hold 0
+    __device__ __forceinline__ void operator()(double* p) const {
+#pragma unroll
+        for (uint32_t r = 0; r < (1u << kMomLocalBits); ++r) {  // all loads in flight together
+            const uint32_t x = r * 256u + threadIdx.x;
+            p[r] = x < D ? v[size_t(x) * (size_t(D) + 1u)].x : 0.0;
+        }
+    }
+};
+
+// grid (1, b_count * n_k), 256 threads: the diagonal is one tile, the rows go straight to expect_out
+static_assert(RYDIFF_MAX_DM_ATOMS <= kMomTileBits, "k_dm_moments: the diagonal of rho must fit one tile");
+__global__ __launch_bounds__(256) void k_dm_moments(DmMomentsArgs a) {
+    const int b = a.b_first + int(blockIdx.y) % a.b_count;
+    const int kk = int(blockIdx.y) / a.b_count;
+    const double2* v = a.v + size_t(kk) * a.kstride + (size_t(b) << (2 * a.n));
+    MomentsTileArgs t{};  // what the body reads: the diagonal is a "register" of n bits in one tile
+    t.N = a.n;
+    t.n_tsave = a.n_tsave;
+    t.k0 = a.k0;
+    t.B = a.B;
+    t.tiles = 1u;
+    moments_tile_body(MomLoadDmDiag{v, 1u << a.n}, t, b, kk, 0u, a.out, nullptr);
+}
+
+struct DmMomentsScatterArgs {
+    double2* out;        // [n_k][B][4^n], already holding everything else
+    const double* gexp;  // the DmMoments block of grad_expect: [1 + n + n(n-1)/2][n_tsave][B]
+    int n_tsave, k0, B, n;
+};
+
+// grid (max(2^n / 256, 1), B, n_k), 256 threads: thread x owns entry (x, x); atom q <-> bit n-1-q of x
+__global__ __launch_bounds__(256) void k_dm_moments_scatter(DmMomentsScatterArgs a) {
+    __shared__ double g2[RYDIFF_MAX_DM_ATOMS * RYDIFF_MAX_DM_ATOMS];  // [ba][bb] over index bits: g of the pair, diagonal: g of the single
+    const int n = a.n, b = blockIdx.y, k = a.k0 + int(blockIdx.z);
+    const uint32_t D = 1u << n;
+    const size_t row = size_t(a.n_tsave) * a.B;
+    const double* __restrict__ g = a.gexp + size_t(k) * a.B + b;
+    const double gS = g[0];
+    int any = gS != 0.0;
+    for (int c = threadIdx.x; c < n * n; c += 256) {
+        const int ba = c / n, bb = c % n;
+        const double val = g[size_t(ba == bb ? mom_row1(n, ba) : mom_row2(n, ba, bb)) * row];
+        g2[c] = val;
+        any |= val != 0.0;
+    }
+    any = __syncthreads_or(any);
+    if (!any) return;  // (uniform) cotangents usually sit at one or a few save points
+    const uint32_t x = blockIdx.x * 256u + threadIdx.x;
+    if (x >= D) return;
+    double q = gS;
+    for (int i = 0; i < n; ++i) {
+        if (!(x >> i & 1u)) continue;
+        q += g2[i * n + i];
+        for (int i2 = i + 1; i2 < n; ++i2)
+            if (x >> i2 & 1u) q += g2[i * n + i2];
+    }
+    double2* dst = a.out + (size_t(blockIdx.z) * a.B + b) * (size_t(D) << n) + size_t(x) * (size_t(D) + 1u);
+    dst->x += q;
 }

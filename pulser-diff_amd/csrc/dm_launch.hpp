@@ -42,7 +42,7 @@ void launch_dm_fidelity_n(const DmFidArgs& a, dim3 grid, hipStream_t stream) {
 }
 
 // every density-matrix row on the states of save points k0 .. k0 + nk - 1 (kstride amplitudes apart; `v` is the one at k0,
-// trajectory 0), trajectories of `bs`.  `linear_only`: the rows that are linear in vec(rho) — diagonal, Pauli, fidelity — and nothing
+// trajectory 0), trajectories of `bs`.  `linear_only`: the rows that are linear in vec(rho) — diagonal, Pauli, fidelity, moments — and nothing
 // else: what the tangent sweep runs on a tangent vector d rho_d, with c.dm_out redirected to direction d's rows of dexpect_out (the
 // purity row, quadratic, is k_dm_purity_tangent's)
 int launch_dm_expect(const ForwardCtx& c, const double2* v, size_t kstride, int k0, int nk, const BatchSlice& bs, bool linear_only = false) {
@@ -114,6 +114,20 @@ int launch_dm_expect(const ForwardCtx& c, const double2* v, size_t kstride, int 
                 m_max = std::max(m_max, pl.dm_rdm_m[o]);
             }
             hipLaunchKernelGGL(k_dm_rdm, dim3(1u << m_max, gy, unsigned(pl.n_dm_rdm)), dim3(256), 0, c.stream, a);
+            LAUNCH_CHECK();
+        }
+        if (pl.dm_moments) {  // linear in vec(rho): also what the tangent sweep runs on d rho_d
+            DmMomentsArgs a{};
+            a.v = v + size_t(k) * kstride;
+            a.kstride = kstride;
+            a.out = c.dm_out + rows.offset(ExpectRows::DmMoments, ExpectRows::DmTrace);
+            a.n_tsave = pl.T + 1;
+            a.k0 = k0 + k;
+            a.B = pl.B;
+            a.b_first = bs.first;
+            a.b_count = bs.count;
+            a.n = pl.dm_n;
+            hipLaunchKernelGGL(k_dm_moments, dim3(1, gy), dim3(256), 0, c.stream, a);
             LAUNCH_CHECK();
         }
     }
@@ -205,6 +219,16 @@ void launch_dm_apply(const PauliInject& pi, const double2* psi, const int32_t* e
         a.m = pl.dm_rdm_m[o];
         a.am = pl.dm_rdm_am[o];
         hipLaunchKernelGGL(k_dm_rdm_scatter, dim3(unsigned(((D << a.m) + 255) / 256), unsigned(pl.B), unsigned(nk)), dim3(256), 0, pi.stream, a);
+    }
+    if (pl.dm_moments) {  // behind them all: the diagonal rows, the xm = 0 strings and the RDMs own the same entries
+        DmMomentsScatterArgs a{};
+        a.out = out;
+        a.gexp = pi.dm_gexp + rows.offset(ExpectRows::DmMoments, ExpectRows::DmTrace);
+        a.n_tsave = pl.T + 1;
+        a.k0 = k0;
+        a.B = pl.B;
+        a.n = pl.dm_n;
+        hipLaunchKernelGGL(k_dm_moments_scatter, dim3(unsigned((D + 255) / 256), unsigned(pl.B), unsigned(nk)), dim3(256), 0, pi.stream, a);
     }
 }
 

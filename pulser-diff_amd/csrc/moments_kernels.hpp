@@ -9,6 +9,8 @@
 //                    (registers), across the 6 lane bits by exchanges with the partner lane (every lane leaves a step with the merged
 //                    record), across the 4 waves through LDS.  Up to 12 qubits the tile is the state and the rows go straight to
 //                    expect_out; beyond, the tile's 79 doubles go to the workspace ([state][entry][tile], plan.hpp: off_moments).
+//                    The body (moments_tile_body) takes the 16 weights of a thread from a loader: MomLoadKet here, MomLoadTangent
+//                    below, MomLoadDmDiag for the diagonal of a density matrix (dm_kernels.hpp: k_dm_moments).
 // k_moments_tangent  the same body (moments_tile<TAN>) on the signed weight dp[y] = 2 Re(conj psi[y] dpsi_d[y]): the tangent of a moment
 //                    of p is that moment of dp.  One direction per grid.z; rows into direction d's Moments block of dexpect_out, or
 //                    the tile records into the tangent sweep's region ([D][B][79][tiles], tangent_launch.hpp: off_dmoments).
@@ -115,39 +117,16 @@ struct MomentsTileArgs {
     uint32_t dim, tiles;
 };
 
-// The tile reduction, one body for the moments of p = |psi|^2 (TAN = false: k_moments_tile) and for their tangents, the same moments
-// of the signed weight dp = 2 Re(conj psi . dpsi) (TAN = true: k_moments_tangent).  `dvec`: the tangent vector laid out like a.psi
-// (TAN only); `out` / `rec`: where this launch's rows / tile records go.
-template <bool TAN>
-__device__ __forceinline__ void moments_tile(const MomentsTileArgs& a, const double2* dvec, double* out, double* rec) {
+// The tile reduction, one body for every weight: `load` fills p[r] with the weight of tile position r * 256 + threadIdx.x (0 past the
+// end of the state).  Thread-local over the 4 bits of r, across the 6 lane bits, across the 4 waves through LDS; entry e of the
+// tile's record leaves through thread e: to the rows of `out` at (a.k0 + kk, b) when the tile is the state (a.tiles == 1), else to
+// `rec` as tile `tau` of state kk * a.B + b.  Of `a` the body reads N, n_tsave, k0, B and tiles.
+template <class Loader>
+__device__ __forceinline__ void moments_tile_body(const Loader& load, const MomentsTileArgs& a, int b, int kk, uint32_t tau, double* out,
+                                                  double* rec) {
     __shared__ double wrec[4][kMomWaveEntries];
-    const int b = a.b_first + int(blockIdx.y) % a.b_count;
-    const int kk = int(blockIdx.y) / a.b_count;
-    const uint32_t tau = blockIdx.x;
-    const size_t first = size_t(kk) * a.kstride + size_t(b) * a.dim + (size_t(tau) << kMomTileBits);
-    const double2* __restrict__ psi = a.psi + first;
-    const uint32_t left = a.dim - (tau << kMomTileBits);  // amplitudes from the tile's first one on (a tile past the state: none)
-    double2 v[1 << kMomLocalBits];
-#pragma unroll
-    for (uint32_t r = 0; r < (1u << kMomLocalBits); ++r) {  // all loads in flight together, consecutive lanes on consecutive amplitudes
-        const uint32_t t = r * 256u + threadIdx.x;
-        v[r] = t < left ? psi[t] : make_double2(0.0, 0.0);
-    }
     double p[1 << kMomLocalBits];
-    if constexpr (TAN) {
-        const double2* __restrict__ dpsi = dvec + first;
-        double2 w[1 << kMomLocalBits];
-#pragma unroll
-        for (uint32_t r = 0; r < (1u << kMomLocalBits); ++r) {
-            const uint32_t t = r * 256u + threadIdx.x;
-            w[r] = t < left ? dpsi[t] : make_double2(0.0, 0.0);
-        }
-#pragma unroll
-        for (uint32_t r = 0; r < (1u << kMomLocalBits); ++r) p[r] = 2.0 * (v[r].x * w[r].x + v[r].y * w[r].y);
-    } else {
-#pragma unroll
-        for (uint32_t r = 0; r < (1u << kMomLocalBits); ++r) p[r] = v[r].x * v[r].x + v[r].y * v[r].y;
-    }
+    load(p);
     const MomRec<4> r4 = mom_local<4>(p);
     const MomRec<5> r5 = mom_lane_merge<4>(r4, 0);
     const MomRec<6> r6 = mom_lane_merge<5>(r5, 1);
@@ -191,6 +170,58 @@ __device__ __forceinline__ void moments_tile(const MomentsTileArgs& a, const dou
     if (ba >= a.N || bb >= a.N) return;  // a bit the register does not have
     const int row = nb == 0 ? 0 : (nb == 1 ? mom_row1(a.N, ba) : mom_row2(a.N, ba, bb));
     out[(size_t(row) * a.n_tsave + a.k0 + kk) * a.B + b] = val;
+}
+
+// the weights of a ket: p = |psi|^2
+struct MomLoadKet {
+    const double2* __restrict__ psi;  // the tile's first amplitude
+    uint32_t left;                    // amplitudes from there to the end of the state (a tile past the state: none)
+    __device__ __forceinline__ void operator()(double* p) const {
+        double2 v[1 << kMomLocalBits];
+#pragma unroll
+        for (uint32_t r = 0; r < (1u << kMomLocalBits); ++r) {  // all loads in flight together, consecutive lanes on consecutive amplitudes
+            const uint32_t t = r * 256u + threadIdx.x;
+            v[r] = t < left ? psi[t] : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (uint32_t r = 0; r < (1u << kMomLocalBits); ++r) p[r] = v[r].x * v[r].x + v[r].y * v[r].y;
+    }
+};
+
+// the signed weights of a tangent: dp = 2 Re(conj psi . dpsi)
+struct MomLoadTangent {
+    const double2* __restrict__ psi;
+    const double2* __restrict__ dpsi;  // laid out like psi
+    uint32_t left;
+    __device__ __forceinline__ void operator()(double* p) const {
+        double2 v[1 << kMomLocalBits], w[1 << kMomLocalBits];
+#pragma unroll
+        for (uint32_t r = 0; r < (1u << kMomLocalBits); ++r) {
+            const uint32_t t = r * 256u + threadIdx.x;
+            v[r] = t < left ? psi[t] : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (uint32_t r = 0; r < (1u << kMomLocalBits); ++r) {
+            const uint32_t t = r * 256u + threadIdx.x;
+            w[r] = t < left ? dpsi[t] : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (uint32_t r = 0; r < (1u << kMomLocalBits); ++r) p[r] = 2.0 * (v[r].x * w[r].x + v[r].y * w[r].y);
+    }
+};
+
+// The moments of p = |psi|^2 (TAN = false: k_moments_tile) and their tangents, the same moments of dp (TAN = true:
+// k_moments_tangent).  `dvec`: the tangent vector laid out like a.psi (TAN only); `out` / `rec`: where this launch's rows / tile
+// records go.
+template <bool TAN>
+__device__ __forceinline__ void moments_tile(const MomentsTileArgs& a, const double2* dvec, double* out, double* rec) {
+    const int b = a.b_first + int(blockIdx.y) % a.b_count;
+    const int kk = int(blockIdx.y) / a.b_count;
+    const uint32_t tau = blockIdx.x;
+    const size_t first = size_t(kk) * a.kstride + size_t(b) * a.dim + (size_t(tau) << kMomTileBits);
+    const uint32_t left = a.dim - (tau << kMomTileBits);
+    if constexpr (TAN) moments_tile_body(MomLoadTangent{a.psi + first, dvec + first, left}, a, b, kk, tau, out, rec);
+    else moments_tile_body(MomLoadKet{a.psi + first, left}, a, b, kk, tau, out, rec);
 }
 
 // grid (tiles, b_count * n_k), 256 threads

@@ -110,7 +110,10 @@ struct Plan {
     int n_dm_rdm = 0, dm_rdm_rows = 0;
     uint32_t dm_rdm_am[RYDIFF_MAX_RDMS] = {0};
     int dm_rdm_m[RYDIFF_MAX_RDMS] = {0}, dm_rdm_row[RYDIFF_MAX_RDMS] = {0};
-    int dm_rows() const { return n_dm_diag + n_dm_pobs + n_dm_fid + dm_purity + dm_rdm_rows; }
+    // occupation correlations of the diagonal of rho (RydProblem.dm_moments): S, B_q, B_qr over the n atoms, the last density-matrix rows
+    int dm_moments = 0;
+    int dm_moment_rows() const { return dm_moments ? 1 + dm_n + dm_n * (dm_n - 1) / 2 : 0; }
+    int dm_rows() const { return n_dm_diag + n_dm_pobs + n_dm_fid + dm_purity + dm_rdm_rows + dm_moment_rows(); }
     size_t dm_gfirst_bytes() const { return (dm_gfirst.size() * sizeof(int32_t) + 7) / 8 * 8; }
     size_t dm_bytes() const {
         return dm_gfirst_bytes() + (dm_groups.size() + dm_agroups.size()) * sizeof(PauliGroup) +
@@ -137,12 +140,13 @@ struct Plan {
 // the blocks of the enumeration, in its order.  The only place that adds row counts up; every launch takes its pointers from at().
 struct ExpectRows {
     // Moments: S, B_q, B_qr of the occupation correlations (empty unless bit_moments), the last block of a ket's rows;
-    // DmTrace (dm_diag rows, then the density-matrix Pauli rows) .. DmRdm: the density-matrix rows
-    enum Block { Diag, Pauli, Overlap, Rdm, Moments, DmTrace, DmFid, DmPurity, DmRdm, End };
+    // DmTrace (dm_diag rows, then the density-matrix Pauli rows) .. DmMoments (S, B_q, B_qr of diag rho; empty unless dm_moments):
+    // the density-matrix rows
+    enum Block { Diag, Pauli, Overlap, Rdm, Moments, DmTrace, DmFid, DmPurity, DmRdm, DmMoments, End };
     size_t stride = 0;        // doubles per row: (T + 1) * B
     int first[End + 1] = {};  // first row of each block; first[End]: all rows
     explicit ExpectRows(const Plan& pl) : stride(size_t(pl.T + 1) * pl.B) {
-        const int count[End] = {pl.n_obs, pl.n_pobs, 2 * pl.n_ov, pl.rdm_rows, pl.moment_rows(), pl.n_dm_diag + pl.n_dm_pobs, pl.n_dm_fid, pl.dm_purity, pl.dm_rdm_rows};
+        const int count[End] = {pl.n_obs, pl.n_pobs, 2 * pl.n_ov, pl.rdm_rows, pl.moment_rows(), pl.n_dm_diag + pl.n_dm_pobs, pl.n_dm_fid, pl.dm_purity, pl.dm_rdm_rows, pl.dm_moment_rows()};
         for (int b = 0; b < End; ++b) first[b + 1] = first[b] + count[b];
     }
     int count(Block b) const { return first[b + 1] - first[b]; }
@@ -390,7 +394,7 @@ inline bool build_shots(const RydProblem* p, Plan& pl, std::string& err) {
 // RydProblem.dm_*: the doubled register, counts, masks, tables; the string groups of the evaluation and of the cotangent scatter
 inline bool build_dm(const RydProblem* p, Plan& pl, std::string& err) {
     pl.dm_n = pl.n_dm_diag = pl.n_dm_pobs = pl.n_dm_fid = pl.dm_purity = pl.dm_shots = 0;
-    pl.n_dm_rdm = pl.dm_rdm_rows = 0;
+    pl.n_dm_rdm = pl.dm_rdm_rows = pl.dm_moments = 0;
     pl.dm_fid_batch = 1;
     pl.dm_gfirst.clear();
     pl.dm_groups.clear();
@@ -467,6 +471,10 @@ inline bool build_dm(const RydProblem* p, Plan& pl, std::string& err) {
         err = "dm_purity and dm_shots must be 0 or 1";
         return false;
     }
+    if (p->dm_moments != 0 && p->dm_moments != 1) {
+        err = "dm_moments must be 0 or 1";
+        return false;
+    }
     if (p->dm_shots && p->n_shots <= 0) {
         err = "dm_shots needs n_shots > 0 (and the shot arrays)";
         return false;
@@ -513,6 +521,7 @@ inline bool build_dm(const RydProblem* p, Plan& pl, std::string& err) {
     pl.dm_fid_batch = p->n_dm_fid ? p->dm_fid_batch : 1;
     pl.dm_purity = p->dm_purity;
     pl.dm_shots = p->dm_shots;
+    pl.dm_moments = p->dm_moments;
     static const double ph[4][2] = {{1, 0}, {0, 1}, {-1, 0}, {0, -1}};  // i^ny
     auto make_string = [&](int s, uint32_t row) {
         const int ny = __builtin_popcount(p->dm_pauli_x[s] & p->dm_pauli_z[s]) & 3;

@@ -27,7 +27,7 @@ int tangent_validate(const RydProblem* p, const RydPlanInfo* info, int n_dir, in
     if (p->amp_conditioned_terms || p->det_ones_terms)
         return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented with conditioned flips / ones-counting terms (three-level registers)");
     if (p->n_shots > 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: measurement shots are not implemented (n_shots > 0): draw them in rydiff_forward");
-    if (p->bit_moments != 0 && (!(flags & RYDIFF_TANGENT_MOMENTS) || p->dm_atoms != 0))  // (moments of diag rho: no kernel, whatever the flags)
+    if (p->bit_moments != 0 && (!(flags & RYDIFF_TANGENT_MOMENTS) || p->dm_atoms != 0))  // (the ket block; a density-matrix register asks with dm_moments)
         return fail(RYDIFF_ENOTIMPL, "tangent sweep: bit moments are not implemented (bit_moments != 0) unless RydTangent.flags has "
                                      "RYDIFF_TANGENT_MOMENTS (kets only, dm_atoms = 0): request them from rydiff_forward");
     if (p->n_rdms > 0 && !(flags & RYDIFF_TANGENT_RDMS))
@@ -219,7 +219,7 @@ int launch_expect_tangent(const ForwardCtx& c, const double2* vec, int n_dir, in
     if (pl.moments)  // d S, d B_q, d B_qr: the moments of 2 Re(conj psi . dpsi_d), k_moments_tangent over all directions
         if (const int rc = launch_moments_tangent(c, vec, n_dir, k, rows.at(dexp, ExpectRows::Moments), dstride)) return rc;
     if (pl.dm_rows()) {
-        // diagonal, Pauli and fidelity rows are linear in vec(rho): k_dm_trace / k_dm_fidelity as they are, on d rho_d, into direction
+        // diagonal, Pauli, fidelity and moment rows are linear in vec(rho): k_dm_trace / k_dm_fidelity / k_dm_moments as they are, on d rho_d, into direction
         // d's density-matrix rows; the purity |v|^2 has the tangent 2 Re <v|dv_d>
         double* first = rows.at(dexp, ExpectRows::DmTrace, ExpectRows::End);
         for (int d = 0; d < n_dir; ++d) {

@@ -26,10 +26,11 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from .observables import DensityMatrixObservables, PauliObservable, Purity, ReducedDensityMatrix, StateOverlap, pack_overlaps
+from .observables import (DensityMatrixObservables, OccupationCorrelations, PauliObservable, Purity, ReducedDensityMatrix, StateOverlap,
+                          pack_overlaps)
 from .shots import ShotRequest
 from .simconfig import NoiseModel
-from .solver import ProblemSpec, SolverType, evolve, split_observables, tolerance_from_options
+from .solver import ProblemSpec, SolverType, evolve, split_dm_moments, split_observables, tolerance_from_options
 from .utils import DiagonalObservable, real_diagonal
 
 CD = torch.complex128
@@ -125,6 +126,7 @@ class MasterEquationResult:
     expect: list = field(default_factory=list)  # one real (n_t, B) tensor per non-RDM entry of `observables`, evaluated natively (differentiable)
     shots: Optional[ShotRequest] = None  # the request, holding the native shots (.indices: basis-state indices of the ATOMS)
     rdms: list = field(default_factory=list)  # one complex (n_t, B, 2^m, 2^m) per ReducedDensityMatrix of `observables`, in order (native, differentiable)
+    moments: Optional[Tensor] = None  # (1 + n + n(n-1)/2, n_t, B) with OccupationCorrelations in `observables`: S, B_q, B_qr of diag rho (native, differentiable)
 
     def __iter__(self):
         return iter((self.states, self.stats))
@@ -134,13 +136,18 @@ def pack_dm_observables(observables: Sequence, n: int, batch: int, device, shots
     """``observables`` of a master-equation run -> (``DensityMatrixObservables`` or None, the row of every observable).  Takes
     ``DiagonalObservable`` / diagonal ``(dim, dim)`` tensors / ``(dim,)`` diagonals, ``PauliObservable``, ``StateOverlap`` (the
     fidelity ``<phi|rho|phi>``), ``Purity`` and ``ReducedDensityMatrix`` (``Tr_E rho``: its ``2 * 4^m`` rows sit behind all the real
-    rows; the row listed for it is the first of them, and ``DensityMatrixObservables.rdms`` keeps the objects in order).  Strings go
+    rows; the row listed for it is the first of them, and ``DensityMatrixObservables.rdms`` keeps the objects in order) and
+    ``OccupationCorrelations`` (the moments of the diagonal of rho: ``DensityMatrixObservables.moments``, the last block of all; the
+    row listed for it is -1: it takes no slot of the real rows).  Strings go
     to the library as they are: the master equation runs in no rotating frame (``mesolve`` hands ``ham.amp_tables`` over, never
     ``amp_tables_frame``)."""
     dim = 2 ** n
-    diags, paulis, overlaps, purity, kinds, rdms = [], [], [], False, [], []
+    diags, paulis, overlaps, purity, kinds, rdms, moments = [], [], [], False, [], [], False
     for obs in observables:
-        if isinstance(obs, ReducedDensityMatrix):
+        if isinstance(obs, OccupationCorrelations):
+            moments = True
+            kinds.append(("moments", 0))
+        elif isinstance(obs, ReducedDensityMatrix):
             obs.check(n)
             kinds.append(("rdm", sum(2 * 4 ** o.n_sub for o in rdms)))
             rdms.append(obs)
@@ -162,7 +169,7 @@ def pack_dm_observables(observables: Sequence, n: int, batch: int, device, shots
                 d = obs.real if obs.is_complex() else obs
             else:
                 raise TypeError("observables of a master-equation run must be DiagonalObservable / PauliObservable / StateOverlap / "
-                                f"Purity / ReducedDensityMatrix objects or diagonal tensors, got {type(obs)}")
+                                f"Purity / ReducedDensityMatrix / OccupationCorrelations objects or diagonal tensors, got {type(obs)}")
             if d.shape[0] != dim:
                 raise ValueError(f"diagonal observable of dimension {d.shape[0]} handed to a register of dimension {dim}")
             kinds.append(("diag", len(diags)))
@@ -171,9 +178,9 @@ def pack_dm_observables(observables: Sequence, n: int, batch: int, device, shots
         return None, []
     dm = DensityMatrixObservables(n, diag=torch.stack(diags) if diags else None, pauli=paulis or None,
                                   targets=pack_overlaps(overlaps, dim, batch, device) if overlaps else None, purity=purity, shots=shots,
-                                  rdms=rdms or None)
+                                  rdms=rdms or None, moments=moments)
     n_real = len(diags) + len(paulis) + len(overlaps) + int(purity)
-    first = {"diag": 0, "pauli": len(diags), "fid": len(diags) + len(paulis), "purity": n_real - 1, "rdm": n_real}
+    first = {"diag": 0, "pauli": len(diags), "fid": len(diags) + len(paulis), "purity": n_real - 1, "rdm": n_real, "moments": -1}
     return dm, [first[kind] + i for kind, i in kinds]
 
 
@@ -186,7 +193,9 @@ def mesolve(ham, psi0: Tensor, tsave: Tensor, noise: NoiseModel, options: Option
     ``observables`` (see ``pack_dm_observables``) are evaluated natively at every evaluation time while rho is on the device
     (``MasterEquationResult.expect``, differentiable); ``shots``: an int (that many at the final time) or a ``ShotRequest``, drawn
     natively from the diagonal of rho; ``ReducedDensityMatrix`` entries come back in ``MasterEquationResult.rdms`` (complex
-    ``(n_t, B, 2^m, 2^m)``, in the order of their ``qubits``) and take no slot of ``expect``; ``store_states=False`` keeps the ``(n_t, 4^n)`` trajectory out of the result (``states``
+    ``(n_t, B, 2^m, 2^m)``, in the order of their ``qubits``) and take no slot of ``expect``; ``OccupationCorrelations()`` comes back as
+    ``MasterEquationResult.moments`` (``(1 + n + n(n-1)/2, n_t, B)``: ``S, B_q, B_qr`` of the diagonal of rho, differentiable) and takes
+    no slot of ``expect`` either; ``store_states=False`` keeps the ``(n_t, 4^n)`` trajectory out of the result (``states``
     is then empty) — gradients of the native values need no stored state."""
     n = ham._size
     if n > MAX_ME_QUBITS:
@@ -213,9 +222,12 @@ def mesolve(ham, psi0: Tensor, tsave: Tensor, noise: NoiseModel, options: Option
     states, expect = evolve(amp2, det2, u2, tsave, rho0, spec, None)  # (n_t, B, dim^2), (rows, n_t, B)
     rho = states.reshape(states.shape[0], states.shape[1], dim, dim).permute(0, 2, 3, 1)
     obs_list = list(observables or [])
+    moments = None
+    if dm is not None and dm.moments:
+        expect, moments = split_dm_moments(expect, n)
     expect, _, rdms = split_observables(expect, 0, dm.rdms if dm is not None else None)
-    real_rows = [r for r, o in zip(rows, obs_list) if not isinstance(o, ReducedDensityMatrix)]
-    return MasterEquationResult(rho, dict(spec.options.get("_last_stats", {})), [expect[r] for r in real_rows], shots, rdms or [])
+    real_rows = [r for r, o in zip(rows, obs_list) if not isinstance(o, (ReducedDensityMatrix, OccupationCorrelations))]
+    return MasterEquationResult(rho, dict(spec.options.get("_last_stats", {})), [expect[r] for r in real_rows], shots, rdms or [], moments)
 
 
 def doubled_table_tangents(d_amp: Optional[Tensor], d_det: Optional[Tensor], d_u: Optional[Tensor], n: int) -> tuple:
@@ -237,12 +249,15 @@ def doubled_table_tangents(d_amp: Optional[Tensor], d_det: Optional[Tensor], d_u
 
 def mesolve_tangent(ham, psi0: Tensor, tsave: Tensor, noise: NoiseModel, options: Optional[dict] = None,
                     observables: Optional[Sequence] = None, d_amp: Optional[Tensor] = None, d_det: Optional[Tensor] = None,
-                    d_u: Optional[Tensor] = None, d_psi0: Optional[Tensor] = None) -> tuple:
+                    d_u: Optional[Tensor] = None, d_psi0: Optional[Tensor] = None, moments: bool = False) -> tuple:
     """Forward-mode twin of ``mesolve(..., store_states=False)``: ONE tangent sweep (``solver.evolve_tangent``) on the doubled
     register carries vec(rho) and its tangents in up to 8 directions (more: chunks of 8) and returns ``(expect, dexpect)`` — the
     values (n_obs, n_t, B) of ``observables`` and their directional derivatives (n_dir, n_obs, n_t, B) at EVERY evaluation time,
     in the order of ``observables`` (diagonal / ``PauliObservable`` / ``StateOverlap`` = the fidelity ``<phi|rho|phi>`` /
-    ``Purity``; a ``ReducedDensityMatrix`` raises ``NotImplementedError``).
+    ``Purity``; a ``ReducedDensityMatrix`` raises ``NotImplementedError``).  ``moments=True``: the occupation correlations of the
+    diagonal of rho join — the return is ``(expect, dexpect, moments, dmoments)`` with ``moments`` (1 + n + n(n-1)/2, n_t, B) and
+    ``dmoments`` (n_dir, 1 + n + n(n-1)/2, n_t, B), the same rows of ``d rho_d`` (they are linear in rho); an
+    ``OccupationCorrelations`` in ``observables`` is a ``TypeError`` here (ask with the keyword).
 
     A direction d is a tangent of the UNDOUBLED inputs: ``d_amp[d]`` shaped like ``ham.amp_tables``, ``d_det[d]`` like
     ``ham.det_tables``, ``d_u[d]`` like ``ham.u_pairs``, ``d_psi0[d]`` like ``psi0`` (dim, B) — the tangent of rho0 is then
@@ -258,6 +273,8 @@ def mesolve_tangent(ham, psi0: Tensor, tsave: Tensor, noise: NoiseModel, options
     if any(isinstance(o, ReducedDensityMatrix) for o in obs_list):
         raise NotImplementedError("mesolve_tangent evaluates no reduced density matrices (the tangent sweep has no tangents of them); "
                                   "differentiate mesolve(..., store_states=False).rdms instead")
+    if any(isinstance(o, OccupationCorrelations) for o in obs_list):
+        raise TypeError("mesolve_tangent takes the occupation correlations through moments=True, not as an entry of observables")
     options = dict(options or {})
     dev = ham.amp_tables.device
     amp2, det2, u2, am2, dm2 = doubled_tables(ham.amp_tables.detach(), ham.det_tables.detach(), ham.u_pairs.detach(), ham.amp_masks,
@@ -268,7 +285,8 @@ def mesolve_tangent(ham, psi0: Tensor, tsave: Tensor, noise: NoiseModel, options
     if psi.ndim == 1:
         psi = psi.unsqueeze(1)
     dim, batch = psi.shape
-    dm, rows = pack_dm_observables(obs_list, n, batch, dev)
+    dm, rows = pack_dm_observables(obs_list + ([OccupationCorrelations()] if moments else []), n, batch, dev)
+    rows = rows[:len(obs_list)]
     spec = ProblemSpec(2 * n, ham.dt, ham.n_samples, am2, dm2, solver=SolverType.DP5_SE,
                        tol=tolerance_from_options(options) or ME_DEFAULT_TOL, store_states=False, pair_terms=pair_terms,
                        piece_refine=getattr(ham, "piece_refine", None), dm=dm)
@@ -284,4 +302,7 @@ def mesolve_tangent(ham, psi0: Tensor, tsave: Tensor, noise: NoiseModel, options
         d_rho0 = d_rho0.reshape(dpsi.shape[0], batch, dim * dim).contiguous()
     expect, dexpect = evolve_tangent(amp2, det2, u2, tsave, rho0, spec, None, d_amp=d_amp2, d_det=d_det2, d_u=d_u2, d_psi0=d_rho0,
                                      flags=_native.TANGENT_PAIR_TERMS | _native.TANGENT_DENSITY_MATRIX)
-    return expect[rows], dexpect[:, rows]
+    if not moments:
+        return expect[rows], dexpect[:, rows]
+    first = expect.shape[0] - dm.moment_rows()
+    return expect[rows], dexpect[:, rows], expect[first:], dexpect[:, first:]

@@ -215,6 +215,7 @@ class QuantumModel(Module):
     def occupation_correlations(self, connected: bool = False) -> tuple[Tensor, Tensor]:
         """Evaluation times and ``<n_i n_j>`` (``connected=True``: ``g_ij = <n_i n_j> - <n_i><n_j>``), real ``(n_t, N, N)`` with
         ``<n_i>`` on the diagonal, evaluated and differentiated natively from one read of the state per evaluation time: no
-        trajectory is stored or handed to autograd.  Ket models only."""
+        trajectory is stored or handed to autograd.  Noisy models (collapse-operator noise: the master equation) return the same
+        quantities of the diagonal of rho(t), ``Tr(rho n_i n_j)``."""
         evaluation_times, results = self._run(observables=[OccupationCorrelations()], store_states=False)
         return evaluation_times, results.occupation_correlations(connected=connected)

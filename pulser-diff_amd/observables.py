@@ -413,7 +413,8 @@ class OccupationCorrelations:
     ``run(observables=[...])`` of a ket run it is evaluated and differentiated natively (``include/rydiff.h``:
     ``RydProblem.bit_moments``; ``csrc/moments_kernels.hpp``), no stored trajectory and no ``2^N`` table.  Read it with
     ``results.occupations()``, ``results.occupation_correlations(connected=...)`` and ``results.structure_factor(signs)``.  Not an
-    operator: ``results.expect`` does not take it.  All qubits, or off: there is no subset."""
+    operator: ``results.expect`` does not take it.  All qubits, or off: there is no subset.  A master-equation run with
+    ``store_states=False`` serves it from the diagonal of rho (``RydProblem.dm_moments``; ``csrc/dm_kernels.hpp``: ``k_dm_moments``)."""
 
 
 def moment_rows(n_qubits: int) -> int:
@@ -450,6 +451,33 @@ def occupation_moments(states: Tensor) -> Tensor:
         rows.append(torch.einsum("qy,tyb->qtb", bits, p))
     if n > 1:
         iq, ir = torch.triu_indices(n, n, offset=1, device=states.device)  # lexicographic (q, r), q < r
+        rows.append(torch.einsum("ey,tyb->etb", bits[iq] * bits[ir], p))
+    return torch.cat(rows, dim=0)
+
+
+def dm_occupation_moments(rho: Tensor) -> Tensor:
+    """The rows of ``RydProblem.dm_moments`` in torch on stored density matrices ``(n_t, dim, dim, B)``: real
+    ``(1 + n + n(n-1)/2, n_t, B)``, differentiable.  With ``p[x] = Re rho[x][x]`` — as it is: no clamp, no Hermitian part, nothing
+    but the real diagonal counts — and ``x_q`` the index bit of atom ``q`` (index bit ``n-1-q``): ``S = sum p``, then
+    ``B_q = sum p x_q`` in ascending ``q``, then ``B_qr = sum p x_q x_r`` in lexicographic ``(q, r)``: the order of
+    ``occupation_moments`` on kets, and equal to it on ``rho = |psi><psi|``."""
+    if rho.is_sparse:
+        rho = rho.to_dense()
+    if rho.ndim != 4 or rho.shape[1] != rho.shape[2]:
+        raise ValueError(f"expected density matrices (n_t, dim, dim, B), got {tuple(rho.shape)}")
+    dim = rho.shape[1]
+    n = dim.bit_length() - 1
+    if dim != 1 << n:
+        raise ValueError(f"OccupationCorrelations needs a register of qubits (dim a power of two), got dim {dim}")
+    diag = torch.diagonal(rho, dim1=1, dim2=2)  # (n_t, B, dim)
+    p = (diag.real if diag.is_complex() else diag).to(torch.float64).permute(0, 2, 1)  # (n_t, dim, B)
+    x = torch.arange(dim, device=rho.device)
+    bits = torch.stack([((x >> (n - 1 - q)) & 1).to(torch.float64) for q in range(n)]) if n else torch.zeros(0, dim, dtype=torch.float64)
+    rows = [p.sum(dim=1)[None]]
+    if n:
+        rows.append(torch.einsum("qy,tyb->qtb", bits, p))
+    if n > 1:
+        iq, ir = torch.triu_indices(n, n, offset=1, device=rho.device)  # lexicographic (q, r), q < r
         rows.append(torch.einsum("ey,tyb->etb", bits[iq] * bits[ir], p))
     return torch.cat(rows, dim=0)
 
@@ -515,10 +543,14 @@ class DensityMatrixObservables:
     ``purity``   one row ``sum |rho_xy|^2``
     ``rdms``     list of ``ReducedDensityMatrix`` over the ATOMS (or raw masks, bit j = atom j): ``2 * 4^m`` rows each, Re / Im of
                  every entry of ``Tr_E rho`` in ascending atom order (``solver.split_observables`` takes them out)
-    ``shots``    the shots of ``ProblemSpec.shots`` are drawn from ``max(Re rho[x][x], 0)`` (atom indices ``x < 2^n``)"""
+    ``shots``    the shots of ``ProblemSpec.shots`` are drawn from ``max(Re rho[x][x], 0)`` (atom indices ``x < 2^n``)
+    ``moments``  the occupation correlations of the diagonal (``RydProblem.dm_moments``): ``1 + n + n(n-1)/2`` rows ``S``, ``B_q``,
+                 ``B_qr`` of ``Re rho[x][x]``, the last rows of all (``solver.split_dm_moments`` takes them off the end)"""
 
-    def __init__(self, n_atoms: int, diag=None, pauli=None, targets=None, purity: bool = False, shots: bool = False, rdms=None):
+    def __init__(self, n_atoms: int, diag=None, pauli=None, targets=None, purity: bool = False, shots: bool = False, rdms=None,
+                 moments: bool = False):
         self.n_atoms = int(n_atoms)
+        self.moments = bool(moments)
         self.rdms = None if rdms is None or len(rdms) == 0 else list(rdms)
         self.diag = diag
         self.pauli = pauli
@@ -579,7 +611,11 @@ class DensityMatrixObservables:
         return 0 if masks is None else sum(2 * 4 ** bin(int(v)).count("1") for v in masks)
 
     def rows(self) -> int:
-        return self.n_diag + self.n_pauli + self.n_fid + int(self.purity) + self.rdm_rows()
+        return self.n_diag + self.n_pauli + self.n_fid + int(self.purity) + self.rdm_rows() + self.moment_rows()
+
+    def moment_rows(self) -> int:
+        """Rows of the occupation correlations of the diagonal: ``1 + n + n(n-1)/2``, or 0."""
+        return moment_rows(self.n_atoms) if self.moments else 0
 
     def check(self, n_qubits: int, batch: int, device=None) -> None:
         """Every buffer against the register (the C ABI sees raw pointers): ValueError, never a bad device read."""

@@ -19,8 +19,8 @@ import torch
 from torch import Tensor
 
 from .result import SampledResult, TorchResult
-from .observables import (PauliObservable, ReducedDensityMatrix, StateOverlap, fidelity_states, occupation_moments, overlap_states,
-                          purity_states, reduced_density_matrix)
+from .observables import (PauliObservable, ReducedDensityMatrix, StateOverlap, dm_occupation_moments, fidelity_states,
+                          occupation_moments, overlap_states, purity_states, reduced_density_matrix)
 from .shots import ShotRequest, bitstring_counts, indices_to_bitstrings
 from .utils import (DiagonalObservable, connected_correlations, expect, negativity, occupation_correlations_from_moments,
                     occupations_from_moments, structure_factor, von_neumann_entropy)
@@ -198,18 +198,18 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
     def _occupation_moments(self) -> tuple[Tensor, int]:
         """(the moments S, B_q, B_qr summed over the columns of the initial state like ``expect``: (rows, n_t); the index value of
         the level ``sample_state`` reports as "1": r = 0 in the ground-rydberg basis, 1 in the digital and XY bases)."""
-        if self._density:
-            raise NotImplementedError("Occupation correlations are defined on kets; this is a master-equation run: hand run() "
-                                      "DiagonalObservable projectors instead.")
         if self._basis_name == "all":
             raise NotImplementedError("Occupation correlations are not available in the three-level all-basis.")
-        rows = self._native_moments if self._native_moments is not None else occupation_moments(self.states)
+        if self._native_moments is not None:
+            rows = self._native_moments
+        else:  # a master-equation run: the moments of the diagonal of rho, the same rows
+            rows = dm_occupation_moments(self.states) if self._density else occupation_moments(self.states)
         return rows.sum(dim=-1), 0 if self._basis_name == "ground-rydberg" else 1
 
     def occupations(self) -> Tensor:
         """``<n_i>`` of every atom (in ``atom_order``) at every evaluation time, real ``(n_t, N)``; "occupied" is the level
         ``sample_state`` reports as "1".  The native values when the run was handed ``OccupationCorrelations()``, else computed
-        from the stored states.  Not normalised by the library (``S = <psi|psi>`` enters as it is)."""
+        from the stored states (kets, or the density matrices of a master-equation run: ``Tr(rho n_i)``).  Not normalised by the library (``S = <psi|psi>`` enters as it is)."""
         rows, bit = self._occupation_moments()
         return occupations_from_moments(rows, self._size, bit)
 

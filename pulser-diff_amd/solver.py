@@ -262,6 +262,7 @@ class _Call:
                 p.dm_fid_targets = targets.data_ptr()
             p.dm_purity = int(dm.purity)
             p.dm_shots = int(dm.shots)
+            p.dm_moments = int(dm.moments)
         self.problem = p
         self.shot_buffers = None
 
@@ -638,6 +639,16 @@ def split_moments(expect: Tensor, n_qubits: int) -> tuple[Tensor, Tensor]:
     n = moment_rows(n_qubits)
     if expect.shape[0] < n:
         raise ValueError(f"expect holds {expect.shape[0]} rows: fewer than the {n} moment rows of {n_qubits} qubits")
+    return expect[:expect.shape[0] - n], expect[expect.shape[0] - n:]
+
+
+def split_dm_moments(expect: Tensor, n_atoms: int) -> tuple[Tensor, Tensor]:
+    """Takes the occupation correlations of a density-matrix register (``DensityMatrixObservables.moments``), the last block of
+    all, off the END of `expect` — before ``split_observables`` takes the reduced density matrices in front of it:
+    -> (the other rows; the moments (1 + n + n(n-1)/2, n_t, B): S, B_q, B_qr of the diagonal of rho)."""
+    n = moment_rows(n_atoms)
+    if expect.shape[0] < n:
+        raise ValueError(f"expect holds {expect.shape[0]} rows: fewer than the {n} moment rows of {n_atoms} atoms")
     return expect[:expect.shape[0] - n], expect[expect.shape[0] - n:]
 
 
