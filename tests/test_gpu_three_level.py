@@ -4,12 +4,12 @@ det_ones_terms).  Reference values: the oracle's literal dense restatement of th
 (oracle/restatement.py:reference_style_dense_H_t_three_level) evolved with the KRYLOV_SE map / DOP853, and torch autograd through it."""
 import itertools
 
-import numpy as np
 import pytest
 import torch
 
 from oracle import restatement as R
-from tests.helpers import dense_from_structured_terms, rel_err
+from tests import structured_reference as S
+from tests.helpers import rel_err
 from tests.test_host_logic import _three_level_emulator
 
 pytestmark = pytest.mark.gpu
@@ -21,8 +21,9 @@ def test_conditioned_flips_and_ones_counting_terms_through_the_c_abi(cuda_device
     """Random structured problems with the two new term flags straight through `evolve`: states, <O>(t) and all five gradient kinds
     against the explicit matrix of the SAME term list (tests/helpers.py:dense_from_structured_terms) under the KRYLOV_SE map, on
     every kernel family that takes conditioned flips: the one-wave lane kernels, the one-workgroup persistent kernels (variant 8
-    forces them at 6 qubits; 12 qubits = persistent forward + direct adjoint) and the generic direct kernels.  14 qubits (dense
-    2^14 is out of reach): norm conservation and the unused codes staying empty."""
+    forces them at 6 qubits; 12 qubits = persistent forward + direct adjoint) and the generic direct kernels.  12 and 14 qubits (the
+    dense matrix is out of reach): the same quantities against the matrix-free reference (tests/structured_reference.py), next to
+    norm conservation, the unused codes staying empty and the direct kernels on the same inputs."""
     from pulser_diff_amd.solver import ProblemSpec, SolverType, evolve
 
     gen = torch.Generator().manual_seed(77 + n_qubits)
@@ -45,7 +46,7 @@ def test_conditioned_flips_and_ones_counting_terms_through_the_c_abi(cuda_device
     obs = torch.rand(1, 2**n_qubits, generator=gen, dtype=torch.float64).to(cuda_device)
     spec = ProblemSpec(n_qubits, dt, ns, amp_masks, det_masks, solver=SolverType.KRYLOV_SE, store_states=True,
                        amp_conditioned=amp_cond, det_ones=det_ones, kernel_variant=variant)
-    if n_qubits > 10:  # the dense reference is out of reach: structure checks, and the other kernel family as the reference
+    if n_qubits > 10:  # structure checks, and the other kernel family on the same inputs
         with torch.no_grad():
             states, expect = evolve(amp, det, u, tsave, psi, spec, obs)
         assert dict(spec.options["_last_stats"])["kernel_family"] == family
@@ -59,7 +60,6 @@ def test_conditioned_flips_and_ones_counting_terms_through_the_c_abi(cuda_device
             with torch.no_grad():
                 ref, ref_e = evolve(amp, det, u, tsave, psi, direct, obs)
             assert (states - ref).abs().max() < 1e-11 and (expect - ref_e).abs().max() < 1e-11
-        return
     leaves = [amp.clone().requires_grad_(True), det.clone().requires_grad_(True), u.clone().requires_grad_(True),
               tsave.clone().requires_grad_(True), psi.clone().requires_grad_(True)]
     states, expect = evolve(*leaves, spec, obs)
@@ -68,39 +68,37 @@ def test_conditioned_flips_and_ones_counting_terms_through_the_c_abi(cuda_device
     loss.backward()
     assert dict(spec.options["_last_stats"])["kernel_family"] == family  # one wave / one workgroup / one amplitude per thread
 
-    # reference: dense matrix of the same term list, KRYLOV_SE map (right-endpoint H), torch autograd
+    # reference: the same term list under the KRYLOV_SE map (right-endpoint H), torch autograd — up to 10 qubits through its explicit
+    # matrix and accurate_matrix_exp (torch.linalg.matrix_exp alone is off by up to 3.6e-9 in the detuning gradient at 4 and 6 qubits:
+    # its degree-4 branch on small arguments), beyond through the matrix-free map
     ref_leaves = [t.detach().cpu().clone().requires_grad_(True) for t in leaves]
     r_amp, r_det, r_u, r_ts, r_psi = ref_leaves
-
-    def interp(tab, t):
-        i1 = max(int(min(np.floor(float(t) / dt), ns - 2)), 0)
-        i2 = min(i1 + 1, ns - 2)
-        return tab[..., i1] + (tab[..., i2] - tab[..., i1]) * (t - i1 * dt) / dt
-
-    def H_t(t):
-        a, d = interp(r_amp[0], t), interp(r_det[0], t)
-        return dense_from_structured_terms(n_qubits, r_u, [(a[k], amp_masks[k]) for k in range(3)],
-                                           [(d[k], det_masks[k]) for k in range(3)], amp_cond, det_ones)
-
-    ref_states = R.krylov_map_from_dense_H(H_t, r_psi.T, r_ts)  # (n_t, dim, B)
-    ref_expect = (ref_states.abs() ** 2 * obs.cpu()[0][None, :, None]).sum(1)
-    ref_loss = (ref_expect * w.cpu()[:, None]).sum() + (ref_states[-1, 3, :].real * 0.7).sum()
+    st = S.Structure(n_qubits, dt, ns, amp_masks, det_masks, amp_cond, det_ones)
+    ref_states = (S.dense_krylov_map if n_qubits <= 10 else S.krylov_map)(st, r_amp[0], r_det[0], r_u, r_ts, r_psi)  # (n_t, B, dim)
+    ref_expect = (ref_states.abs() ** 2 * obs.cpu()[0][None, None, :]).sum(2)
+    ref_loss = (ref_expect * w.cpu()[:, None]).sum() + (ref_states[-1, :, 3].real * 0.7).sum()
     ref_loss.backward()
-    assert rel_err(states.detach().cpu().permute(0, 2, 1).numpy(), ref_states.detach().numpy()) < 1e-9
+    assert rel_err(states.detach().cpu().numpy(), ref_states.detach().numpy()) < 1e-9
     assert rel_err(expect[0].detach().cpu().numpy(), ref_expect.detach().numpy()) < 1e-9
     for name, got, ref in zip(("amp", "det", "u", "tsave", "psi0"), leaves, ref_leaves):
         assert rel_err(got.grad.detach().cpu().numpy(), ref.grad.numpy()) < 1e-8, name
 
 
-@pytest.mark.parametrize("n_qubits,batch,variant,tape", [(14, 2, 2, "full"), (14, 1, 4, "steps"), (16, 1, 3, "full"), (20, 1, 0, "full"),
-                                                         (22, 1, 4, "steps"), (24, 1, 2, "partial")])
-def test_conditioned_flips_on_the_chained_tiles_match_the_direct_kernels(cuda_device, n_qubits, batch, variant, tape):
+_CHAINED_CASES = [(14, 2, 2, "full", "KRYLOV_SE"), (14, 1, 4, "steps", "KRYLOV_SE"), (16, 1, 3, "full", "KRYLOV_SE"), (20, 1, 0, "full", "KRYLOV_SE"),
+                  (22, 1, 4, "steps", "KRYLOV_SE"), (24, 1, 2, "partial", "KRYLOV_SE"), (14, 1, 2, "full", "DP5_SE")]
+
+
+@pytest.mark.parametrize("n_qubits,batch,variant,tape,solver_name", _CHAINED_CASES,
+                         ids=["-".join(str(x) for x in c[:4]) + ("" if c[4] == "KRYLOV_SE" else "-" + c[4]) for c in _CHAINED_CASES])
+def test_conditioned_flips_on_the_chained_tiles_match_the_direct_kernels(cuda_device, n_qubits, batch, variant, tape, solver_name):
     """Three-level style problems (every flip conditioned on its sibling qubit, ones-counting detunings) on the chained LDS-tile passes —
     512 / 1024 / 256 threads forced at 14 / 16 / 22 / 24 qubits, the automatic choice at 20 (two tile layouts up to 22, three at 24;
     tiles of 2^12 amplitudes, which keep sibling pairs together; beyond 20 qubits automatic stays on the direct kernels, which are faster there) — against the generic one-amplitude-per-thread kernels: <O>(t_k), the
-    final state (on the device), every gradient kind, all three tape modes; the unused code 00 stays empty."""
+    final state (on the device), every gradient kind, all three tape modes; the unused code 00 stays empty.  One case runs the continuous
+    solver (DP5_SE: two Magnus exponentials per piece and sub-step) through the same chained passes at 14 qubits."""
     from pulser_diff_amd.solver import ProblemSpec, SolverType, evolve
 
+    solver = SolverType[solver_name]
     gen = torch.Generator().manual_seed(177 + n_qubits)
     ns, dt = 7, 0.004
     n_atoms = n_qubits // 2
@@ -129,7 +127,7 @@ def test_conditioned_flips_on_the_chained_tiles_match_the_direct_kernels(cuda_de
     del x
     out = {}
     for v in (1, variant):
-        spec = ProblemSpec(n_qubits, dt, ns, amp_masks, det_masks, solver=SolverType.KRYLOV_SE, store_states=False,
+        spec = ProblemSpec(n_qubits, dt, ns, amp_masks, det_masks, solver=solver, store_states=False,
                            amp_conditioned=amp_cond, det_ones=det_ones, kernel_variant=v, tape=tape,
                            tape_steps=2 if tape == "partial" else None)
         leaves = [amp.clone().requires_grad_(True), det.clone().requires_grad_(True), u.clone().requires_grad_(True),
@@ -146,7 +144,7 @@ def test_conditioned_flips_on_the_chained_tiles_match_the_direct_kernels(cuda_de
     for name, ref, got in zip(("expect", "amp", "det", "u", "tsave", "psi0"), out[1], out[variant]):
         scale = float(ref.abs().max())
         assert float((got - ref).abs().max()) <= 1e-9 * max(scale, 1e-30), name
-    spec = ProblemSpec(n_qubits, dt, ns, amp_masks, det_masks, solver=SolverType.KRYLOV_SE, store_states=True,
+    spec = ProblemSpec(n_qubits, dt, ns, amp_masks, det_masks, solver=solver, store_states=True,
                        amp_conditioned=amp_cond, det_ones=det_ones, kernel_variant=variant)
     with torch.no_grad():
         states, _ = evolve(amp, det, u, tsave, psi, spec, obs)
