@@ -145,6 +145,11 @@ typedef struct RydProblem {
      *     (mu) is back, awaits v alone for the first finishing round, and requests t behind that round once half of its w is back.
      *     31 forward | 32 adjoint | 33 both | 34 forward, with t requested before the first round instead.  17 and 20..30 never pace;
      *     automatic takes the paced adjoint kernel (that of 32) and the unpaced forward kernel
+     *  35 as 20, with "w on the tape" (DESIGN.md section 3): where the full tape is read by the adjoint block kernel alone, the slot
+     *     between the two factors of a block holds the forward block's own partial sum P_X v and not the mid-block state, which the
+     *     adjoint kernel rebuilds with one more partner-sum round (forward 3R+3W instead of 3R+4W per block).  The backward call must
+     *     be made with the kernel_variant and real_amp_grad of the forward call that wrote the tape: a tape of the other format is
+     *     refused (RYDIFF_EINVAL).  17 and 19..34 keep the mid-block state on the tape
      * "automatic" takes the one-launch sweeps up to 12 qubits, the direct kernels while few tiles are in flight
      * (B * 2^N <= 2^18, with gradients 2^19) and the chained passes beyond.  Results do not depend on the variant beyond rounding. */
     int32_t kernel_variant;

@@ -292,9 +292,9 @@ __device__ __forceinline__ void partner_sums_lanes(const double2& own, uint32_t 
 }
 
 #ifdef RYDIFF_TIMELINE
-// tuning builds: per-workgroup phase timestamps of the last launch, [4096][8]; the stamps of slots 8, 9 and 10 live behind them,
-// [3][4096]
-__device__ unsigned long long g_timeline[4096 * 11];
+// tuning builds: per-workgroup phase timestamps of the last launch, [4096][8]; the stamps of slots 8 .. 11 live behind them,
+// [4][4096]
+__device__ unsigned long long g_timeline[4096 * 12];
 #define RYDIFF_TL(slot)                                                                                   \
     do {                                                                                                  \
         if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.x < 4096 && a.has_p && a.has_q)               \

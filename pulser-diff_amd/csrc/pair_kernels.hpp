@@ -354,6 +354,7 @@ struct Chain2BwdArgs {
     double k_r, k_i;                      // conj beta_a beta_b: the H^2 coefficient of the block (0: one factor)
     double ga_r, ga_i, ba_r, ba_i;        // conj gamma_a, conj beta_a (mu_mid)
     double cba_r, cba_i, cbb_r, cbb_i;    // beta_a, beta_b un-conjugated (contraction weights; one-factor block: beta_a = 0)
+    double cgb_r, cgb_i;                  // gamma_b un-conjugated (XW: x_a is rebuilt with the forward pass's own scalars, no sign flipped on the way)
     int lo, hs, hb;                       // layout of this launch (as ChainArgs)
     uint32_t dim;
     int has_p, has_q;
@@ -402,10 +403,20 @@ constexpr size_t chain2_bwd_lds_bytes() {
 // is formed, which is also where w is awaited.  Not on the LDS-DMA staging: with a global_load_lds pending next to ordinary loads
 // the compiler treats the counter as retiring out of order and awaits mu with vmcnt(0), x_a and w included (seen in the gfx950 ISA).
 // A chain's first launch retires w and x_a where it takes y.
-template <int LT, int LGT, bool ORD, int WT, bool DMA, int PACE = 0>
+// XW (vector-major, register-staged, everything written through; a pacing of its own, PACE = 0): the tape holds w_x = P_X x_b, the
+// forward block's own w, where x_a would be (pair_wtape, pair_launch.hpp), and the kernel rebuilds x_a, the forward pass's v_mid:
+//     s_x = P_Y' x_b,   x_a = gamma_b x_b + beta_b ((D x_b) + c (w_x + s_x))
+// in the statement order of k_chain2, so to the last bit.  The host runs the launch in the layout in which the forward pass finished
+// the block, so the Y' bits are those of this launch's fin_mask.  Requests: x_b; once half of it is back, w_x and mu; w when x_b is
+// complete.  x_b goes as a tile into the idle LDS buffer (this thread's slots are where x_a is parked by the unpaced kernel), one
+// barrier, the x-round's partner sums, x_a in registers; then round A on mu as in the paced kernel.  Round A's barrier retires every
+// partner read of the x_b tile, and x_b's own elements are read back from this thread's slots just before e replaces them: x_b has
+// no second load phase and only t is requested behind round A.  A one-factor block (x_a is not used: beta_a = 0) skips the x-round.
+template <int LT, int LGT, bool ORD, int WT, bool DMA, int PACE = 0, bool XW = false>
 __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
     constexpr int NT = 1 << LGT, R = 1 << (LT - LGT), NW = NT / 64;
     static_assert(WT >= 0 && WT <= 3);
+    static_assert(!XW || (ORD && WT == 3 && !DMA && !PACE && R == 4), "P_X x_b on the tape: one instantiation");
     static_assert(PACE >= 0 && PACE <= 1 && (!PACE || (ORD && !DMA && R == 4)), "pacing: the vector-major register-staged kernel, four elements per thread");
     constexpr int XBL = DMA ? kChain2BwdXbLds : 0;
     static_assert(XBL <= R && (2 * NW * sizeof(double)) % sizeof(double2) == 0);
@@ -453,24 +464,33 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
         cdet_fin = a.coef_fin[bt * a.coef_bstride + 2];
         cdet_sta = a.coef_sta[bt * a.coef_bstride + 2];
     }
+    [[maybe_unused]] double2 xa[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const unsigned i = unsigned(r) * NT + tid;
         xg[r] = xbase | (i & lomask) | ((i >> a.lo) << a.hs);
-        uu[r] = stream_load(a.mu + boff + xg[r]);
+        if constexpr (XW) xb[r] = stream_load(a.xb + boff + xg[r]);
+        else uu[r] = stream_load(a.mu + boff + xg[r]);
     }
-    if constexpr (ORD && !PACE) __builtin_amdgcn_s_barrier();  // every wave's mu is requested before any wave's w
-    if constexpr (PACE) {  // ... PACE: not before half of this wave's own mu is back (the table entries were requested ahead of mu)
+    if constexpr (ORD && !PACE && !XW) __builtin_amdgcn_s_barrier();  // every wave's mu is requested before any wave's w
+    if constexpr (PACE || XW) {  // ... PACE: not before half of this wave's own mu is back (the table entries were requested ahead of mu)
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
     }
     // w and x_a requested with mu, outside of control flow (the host passes valid pointers for the first launch too)
+    // (XW: w_x, in the slot of x_a, and mu behind half of x_b; w follows inside the has_p path, once x_b is complete)
+    if constexpr (!XW) {
 #pragma unroll
-    for (int r = 0; r < R; ++r) ww[r] = stream_load(a.w + boff + xg[r]);
-    if constexpr (ORD && !PACE) __builtin_amdgcn_s_barrier();  // ... and every wave's w before any wave's tape vector
-    [[maybe_unused]] double2 xa[R];
-    if constexpr (DMA) {
+        for (int r = 0; r < R; ++r) ww[r] = stream_load(a.w + boff + xg[r]);
+    }
+    if constexpr (ORD && !PACE && !XW) __builtin_amdgcn_s_barrier();  // ... and every wave's w before any wave's tape vector
+    if constexpr (XW) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) xa[r] = stream_load(a.xa + boff + xg[r]);
+#pragma unroll
+        for (int r = 0; r < R; ++r) uu[r] = stream_load(a.mu + boff + xg[r]);
+    } else if constexpr (DMA) {
         const unsigned wv = __builtin_amdgcn_readfirstlane(tid & ~63u);  // a wave's 64 slots of one r are 1 KiB of contiguous LDS
         double2* xat = tiles + (size_t(1) << LT);                        // the idle buffer of round A (buf ^ 1)
 #pragma unroll
@@ -530,7 +550,9 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
     // PACE: mu alone is awaited here; w and x_a are retired behind round A's partner sums, or on the first launch's path
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        if constexpr (PACE) {
+        if constexpr (XW) {
+            asm volatile("" ::"v"(xb[r].x), "v"(xb[r].y));  // (x_b alone: w_x and mu are retired where they are used, or on the first launch's path)
+        } else if constexpr (PACE) {
             asm volatile("" ::"v"(uu[r].x), "v"(uu[r].y));
         } else {
             asm volatile("" ::"v"(uu[r].x), "v"(uu[r].y), "v"(ww[r].x), "v"(ww[r].y));
@@ -549,7 +571,39 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
             // x_a waits out round A in this thread's own slots of the other LDS buffer (not in registers); e replaces it there
             // (DMA: it is there already, retired by the vmcnt(0) in front of round A's barrier)
             double2* etile = tiles + (size_t(buf ^ 1) << LT);
-            if constexpr (PACE) {
+            if constexpr (XW) {
+                __builtin_amdgcn_sched_barrier(0);  // w is requested now that x_b is complete: it lands under the x-round and round A
+                {
+                    const char* wbase = reinterpret_cast<const char*>(a.w + boff);
+#pragma unroll
+                    for (int r = 0; r < R; ++r) ww[r] = stream_load(reinterpret_cast<const double2*>(wbase + xg[r] * unsigned(sizeof(double2))));
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int r = 0; r < R; ++r) etile[unsigned(r) * NT + tid] = xb[r];
+                if (two) {  // the x-round: x_a = v_mid of the forward block, statement for statement as in k_chain2
+                    __syncthreads();
+                    RYDIFF_TL(11);
+                    double2 sx[R], dsx[R];
+                    partner_sums<LT, LGT, false>(etile, xb, a.fin_mask, tid, sx, dsx);
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        double d = du[r];
+                        if (a.gd) d += cdet * double(a.dcnt - popc_i(xg[r] & a.dmask));
+                        double2 h1;
+                        h1.x = d * xb[r].x + c * (xa[r].x + sx[r].x);
+                        h1.y = d * xb[r].y + c * (xa[r].y + sx[r].y);
+                        const double2 p = cmul(a.cgb_r, a.cgb_i, xb[r]), q = cmul(a.cbb_r, a.cbb_i, h1);
+                        xa[r] = make_double2(p.x + q.x, p.y + q.y);
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        asm volatile("" ::"v"(xa[r].x), "v"(xa[r].y));  // (its request retired)
+                        xa[r] = xb[r];
+                    }
+                }
+            } else if constexpr (PACE) {
                 // (nothing: x_a stays in registers and is awaited behind the partner sums)
             } else if constexpr (DMA) {
 #ifdef RYDIFF_TIMELINE
@@ -564,14 +618,14 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
                 for (int r = 0; r < R; ++r) etile[unsigned(r) * NT + tid] = xa[r];
             }
 #ifdef RYDIFF_TIMELINE
-            if constexpr (!PACE) RYDIFF_TL(10);  // (tuning builds: x_a landed in this wave)
+            if constexpr (!PACE && !XW) RYDIFF_TL(10);  // (tuning builds: x_a landed in this wave)
 #endif
             double2 s[R], ds[R];
             const double2* mtile = put(uu);
             RYDIFF_TL(1);
             partner_sums<LT, LGT, false>(mtile, uu, a.fin_mask, tid, s, ds);
 #ifdef RYDIFF_TIMELINE
-            if constexpr (PACE) {
+            if constexpr (PACE || XW) {
 #pragma unroll
                 for (int r = 0; r < R; ++r) asm volatile("" ::"v"(ww[r].x), "v"(ww[r].y));
                 RYDIFF_TL(9);
@@ -583,8 +637,9 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 double2 xav;
-                if constexpr (PACE) xav = xa[r];
+                if constexpr (PACE || XW) xav = xa[r];
                 else xav = etile[unsigned(r) * NT + tid];
+                if constexpr (XW) xb[r] = etile[unsigned(r) * NT + tid];  // x_b's own element, before e replaces it
                 const double d = du[r] + cdet * cnt(r);
                 pm[r] = make_double2(ww[r].x + s[r].x, ww[r].y + s[r].y);
                 const double2 h1 = make_double2(d * uu[r].x + c * pm[r].x, d * uu[r].y + c * pm[r].y);  // H mu
@@ -601,7 +656,7 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
         zc = 0.0;
         RYDIFF_TL(2);
         // the second tape vector (!DMA) and t (needed as tp = t + P_Y' e only) are requested once round A is done
-        if constexpr (!DMA) {
+        if constexpr (!DMA && !XW) {
 #pragma unroll
             for (int r = 0; r < R; ++r) xb[r] = stream_load(a.xb + boff + xg[r]);
         }
@@ -689,6 +744,7 @@ __global__ __launch_bounds__(1 << LGT) void k_chain2_bwd(Chain2BwdArgs a) {
         for (int r = 0; r < R; ++r) {
             y[r] = uu[r];
             if constexpr (PACE) asm volatile("" ::"v"(ww[r].x), "v"(ww[r].y), "v"(xa[r].x), "v"(xa[r].y));  // (every request of the top retired)
+            if constexpr (XW) asm volatile("" ::"v"(xa[r].x), "v"(xa[r].y));
         }
     }
     auto flush = [&]() {  // after the barrier that follows the parks: one atomic per quantity and workgroup

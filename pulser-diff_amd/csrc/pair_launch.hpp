@@ -20,20 +20,45 @@ bool pair_enabled(const Runtime& rt) {
     return rt.pair_mode == 1 || (rt.pl.N == 20 && rt.pl.B == 1);
 }
 
+// The forward pass's blocks of a chain: factors paired from the start of each exponential (an exponential with an odd number of
+// factors ends in a one-factor block).  (first factor, second factor or -1)
+std::vector<std::pair<int, int>> forward_blocks(const std::vector<ChainItem>& items) {
+    std::vector<std::pair<int, int>> blk;
+    const int F = int(items.size());
+    for (int i = 0; i < F;) {
+        if (i + 1 < F && items[i + 1].stage == items[i].stage) {
+            blk.push_back({i, i + 1});
+            i += 2;
+        } else {
+            blk.push_back({i, -1});
+            ++i;
+        }
+    }
+    return blk;
+}
+
+// forward blocks in the factors of interval k (step_factor_count counts its factors)
+int64_t step_block_count(const Runtime& rt, int k) {
+    int64_t b = 0;
+    for (int e = rt.pl.step_begin[k]; e < rt.pl.step_begin[k + 1]; ++e) b += (int64_t(rt.pl.stages[e].nsub) * rt.poly.degree + 1) / 2;
+    return b;
+}
+
 // What launch j of a block chain fills whatever the direction (Chain2Args / Chain2BwdArgs): it finishes block j-1 and starts
-// block j of `blk` (first factor, second factor or -1), in layout j & 1.  The w / t of a started block go to pp0 / pp1 and
-// pp2 / pp3 alternately; `cur` is the complete vector the launch works on.
+// block j of `blk` (first factor, second factor or -1), in layout (j + par) & 1.  The w / t of a started block go to pp0 / pp1 and
+// pp2 / pp3 alternately; `cur` is the complete vector the launch works on.  `par`: the layout of the chain's first launch (the
+// layout, the split tables, the Y' mask and the w / t buffers all follow it).
 template <class Args>
 void fill_chain2(Args& ca, const Runtime& rt, char* ws, const std::vector<ChainItem>& items, const std::vector<std::pair<int, int>>& blk,
-                 int j, const double2* cur, const BatchSlice& bs) {
+                 int j, const double2* cur, const BatchSlice& bs, int par = 0) {
     const Plan& pl = rt.pl;
     double2* wt[2][2] = {{reinterpret_cast<double2*>(ws + pl.off_pp0), reinterpret_cast<double2*>(ws + pl.off_pp1)},
                          {reinterpret_cast<double2*>(ws + pl.off_pp2), reinterpret_cast<double2*>(ws + pl.off_pp3)}};
     const ChainGeom geom{kTileBits, 2};
-    const int nb = int(blk.size()), L = j & 1;
+    const int nb = int(blk.size()), jp = j + (par & 1), L = jp & 1;
     const LayoutDesc Y = chain_layout(pl.NL, L, geom), X = chain_layout(pl.NL, L ^ 1, geom);
-    ca.w = j ? wt[(j - 1) & 1][0] : cur;  // (always loadable: the kernels request their inputs outside of control flow)
-    ca.t = j ? wt[(j - 1) & 1][1] : cur;
+    ca.w = j ? wt[(jp - 1) & 1][0] : cur;  // (always loadable: the kernels request their inputs outside of control flow)
+    ca.t = j ? wt[(jp - 1) & 1][1] : cur;
     ca.utt = split_tables(pl, ws, kTileBits) + size_t(L) * rt.per_layout(kTileBits);
     ca.vr = ca.utt + (size_t(1) << kTileBits);
     ca.coef_bstride = rt.coef_bstride();
@@ -50,8 +75,8 @@ void fill_chain2(Args& ca, const Runtime& rt, char* ws, const std::vector<ChainI
     ca.b_count = bs.count;
     if (ca.has_p) ca.fin_mask = to_tile_mask(Y, kTileBits, uint32_t(pl.dim - 1) & ~X.bits);
     if (ca.has_q) {
-        ca.w_out = wt[j & 1][0];
-        ca.t_out = wt[j & 1][1];
+        ca.w_out = wt[jp & 1][0];
+        ca.t_out = wt[jp & 1][1];
     }
 }
 
@@ -114,22 +139,17 @@ int launch_chain2(const Runtime& rt, const Chain2Args& ca, unsigned tiles, hipSt
 
 // Forward chain in blocks of two factors of one exponential (an exponential of odd degree ends in a one-factor block).  Same
 // contract as run_chain (no skip_last_finish); keep_mid: the output of a block's first factor is stored too (dst of that factor).
+// wtape (with keep_mid; pair_wtape): that slot takes the block's w = P_X v instead.  The launch that starts the block writes it there
+// and not into the ping-pong buffers, the launch that finishes it reads it from there, and no v_mid is stored: 3R+3W per block.
+// One-factor blocks keep w in the ping-pong buffers; t always stays there.  The kernel and its arithmetic are the same.
 template <class DstFn, class DoneFn, class ExpFn>
 int run_chain2(const Runtime& rt, char* ws, const std::vector<ChainItem>& items, const double2* start, DstFn dst, bool keep_mid,
-               DoneFn on_done, ExpFn exp_slot, const BatchSlice& bs, hipStream_t stream) {
+               bool wtape, DoneFn on_done, ExpFn exp_slot, const BatchSlice& bs, hipStream_t stream) {
     const Plan& pl = rt.pl;
     const int F = int(items.size());
     if (F <= 0) return RYDIFF_OK;
-    std::vector<std::pair<int, int>> blk;  // (first factor, second factor or -1)
-    for (int i = 0; i < F;) {
-        if (i + 1 < F && items[i + 1].stage == items[i].stage) {
-            blk.push_back({i, i + 1});
-            i += 2;
-        } else {
-            blk.push_back({i, -1});
-            ++i;
-        }
-    }
+    if (wtape && !keep_mid) return fail(RYDIFF_EINVAL, "internal: P_X v is taped with the full tape only");
+    const std::vector<std::pair<int, int>> blk = forward_blocks(items);
     const unsigned tiles = unsigned(pl.dim >> kTileBits);
     const int nb = int(blk.size());
     const double2* cur = start;
@@ -157,7 +177,8 @@ int run_chain2(const Runtime& rt, char* ws, const std::vector<ChainItem>& items,
             ca.g1_i = s1.gi;
             ca.b1_r = s1.br;
             ca.b1_i = s1.bi;
-            ca.vmid_out = (f1 >= 0 && keep_mid) ? dst(f0) : nullptr;
+            ca.vmid_out = (f1 >= 0 && keep_mid && !wtape) ? dst(f0) : nullptr;
+            if (f1 >= 0 && wtape) ca.w = dst(f0);
             ca.y_out = dst(last);
             if (!ca.y_out) return fail(RYDIFF_EINVAL, "internal: chain destination missing");
             ChainStep cs{};
@@ -166,6 +187,10 @@ int run_chain2(const Runtime& rt, char* ws, const std::vector<ChainItem>& items,
             ca.expect_slot = cs.expect_slot;
             ca.n_obs = cs.n_obs;
             ca.exp_ostride = cs.exp_ostride;
+        }
+        if (wtape && ca.has_q && blk[j].second >= 0) {
+            ca.w_out = dst(blk[j].first);
+            if (!ca.w_out) return fail(RYDIFF_EINVAL, "internal: chain destination missing");
         }
         int rc = launch_chain2(rt, ca, tiles, stream);
         if (rc) return rc;
@@ -193,6 +218,22 @@ bool pair_bwd_enabled(const Runtime& rt) {
     return !rt.pair_bwd_off && rt.real_amp_grad && pair_enabled(rt) && g.lt == kTileBits && g.layouts == 2;
 }
 
+// What the full tape holds between the two factors of a block.  v_mid, the first factor's output, has one reader, the adjoint block
+// kernel, and v_mid = gamma_1 v + beta_1 (D v + c (P_X v + P_Y' v)) with w = P_X v written by the forward chain anyway.  With w in
+// that slot ("w on the tape") the forward block is 3R+3W instead of 3R+4W, and the adjoint kernel (its XW instantiation) rebuilds
+// v_mid from the two tape vectors it reads as before, with one more partner-sum round over the Y' bits.
+// Only where the full tape's one reader is that kernel: the block adjoint is on and no pass is placed one trajectory per XCD.  The
+// one-factor adjoint (variant 19, complex tables), the partial tape and the recomputed factor inputs keep v_mid.  The forward call
+// records the format it wrote next to the workspace (tape_format_record, rydiff.hip); the backward call reads that record.
+// Automatic (C3, the only shape where the blocks are automatic): on, +2.5 % on the bench line, 31 of the parent's spreads above the
+// parent, and +1.6 %, 18 spreads, in a second session (profiles/r10_bench.jsonl); variant 35 selects it wherever the blocks are
+// legal, 17 and 19..34 keep v_mid.
+constexpr bool kPairWtapeDefault = true;
+bool pair_wtape(const Runtime& rt) {
+    const bool sel = rt.pair_wtape ? rt.pair_wtape > 0 : kPairWtapeDefault;
+    return sel && rt.pl.tape_mode == 2 && pair_bwd_enabled(rt) && xcd_group_size(rt, false) == 0 && xcd_group_size(rt, true) == 0;
+}
+
 // Tape staging of the adjoint block kernel.  Automatic stays with the registers: on C3 the LDS-DMA version measured the same per
 // launch (26.3 us both) and within noise on the bench line; it remains selectable for A/B runs.
 constexpr bool kPairBwdDmaDefault = false;
@@ -203,21 +244,25 @@ int pair_pace_bwd(const Runtime& rt) {
     return rt.pair_pace_bwd >= 0 ? rt.pair_pace_bwd : kPairPaceBwdDefault;
 }
 
-template <int LGT, bool ORD, int WT, bool DMA, int PACE = 0>
+template <int LGT, bool ORD, int WT, bool DMA, int PACE = 0, bool XW = false>
 int launch_chain2_bwd_t(const Chain2BwdArgs& ca, unsigned tiles, hipStream_t stream) {
     constexpr int LT = kTileBits;
     constexpr size_t lds = chain2_bwd_lds_bytes<LT, LGT, DMA>();
     static_assert(lds <= 160 * 1024, "k_chain2_bwd: more LDS than a gfx950 workgroup can have");
-    if (int rc = set_max_dynamic_lds_once<&k_chain2_bwd<LT, LGT, ORD, WT, DMA, PACE>>(lds)) return rc;
-    hipLaunchKernelGGL((k_chain2_bwd<LT, LGT, ORD, WT, DMA, PACE>), dim3(tiles, unsigned(ca.b_count)), dim3(1 << LGT), lds, stream, ca);
+    if (int rc = set_max_dynamic_lds_once<&k_chain2_bwd<LT, LGT, ORD, WT, DMA, PACE, XW>>(lds)) return rc;
+    hipLaunchKernelGGL((k_chain2_bwd<LT, LGT, ORD, WT, DMA, PACE, XW>), dim3(tiles, unsigned(ca.b_count)), dim3(1 << LGT), lds, stream, ca);
     LAUNCH_CHECK();
     return RYDIFF_OK;
 }
 
 // The LDS-DMA staging exists with vector-major requests only: with the automatic store policy (variant 21) and with streaming
 // stores (variant 29).
-int launch_chain2_bwd(const Runtime& rt, const Chain2BwdArgs& ca, unsigned tiles, hipStream_t stream) {
+int launch_chain2_bwd(const Runtime& rt, const Chain2BwdArgs& ca, unsigned tiles, bool wtape, hipStream_t stream) {
     const bool ord = pair_vec_major(rt);
+    if (wtape) {  // one instantiation: vector-major, register-staged, everything written through, with a pacing of its own
+        if (!ord || pair_through(rt) != 3 || pair_bwd_dma(rt)) return fail(RYDIFF_EINVAL, "internal: no such block kernel");
+        return launch_chain2_bwd_t<10, true, 3, false, 0, true>(ca, tiles, stream);
+    }
     if (pair_pace_bwd(rt)) return launch_chain2_bwd_t<10, true, 3, false, 1>(ca, tiles, stream);
     if (pair_bwd_dma(rt)) {
         if (ord && pair_through(rt) == 3) return launch_chain2_bwd_t<10, true, 3, true>(ca, tiles, stream);
@@ -233,15 +278,24 @@ int launch_chain2_bwd(const Runtime& rt, const Chain2BwdArgs& ca, unsigned tiles
 // Factors are paired from the end of each exponential backwards (an exponential of odd degree starts with a one-factor block),
 // so a block never spans two exponentials and only its first factor's input can be a save point.  Launch j finishes the adjoint
 // of block j-1 and starts block j, in layout j & 1 (w / t of a started block: pp0 / pp1 and pp2 / pp3, alternately).
+// wtape (pair_wtape: xs holds P_X x_b where a two-factor block's x_a would be): the blocks are the FORWARD pass's, in reverse (an
+// exponential of odd degree starts, in adjoint order, with its one-factor block), and each is finished in the layout in which the
+// forward pass finished it: the taped P_X x_b covers the bits of the layout the forward block was started in, so only then are the
+// bits it lacks (Y') local to the tile.  The forward pass finished its block g (counted over the whole run) in layout (g + 1) & 1;
+// with g_hi the run-wide index of this chain's last block, launch j finishes block g_hi - (j - 1) and runs in layout (j + g_hi) & 1.
 template <class StageEndFn>
 int run_chain2_bwd(const Runtime& rt, char* ws, const std::vector<ChainItem>& items, const std::vector<const double2*>& xs,
                    const std::vector<int>& save_k, const double2* lam_in, double2* lam_bufs[2], int& cl, double* wtot,
-                   StageEndFn on_stage_end, const BatchSlice& bs, const InjectSource& inj, hipStream_t stream) {
+                   StageEndFn on_stage_end, const BatchSlice& bs, const InjectSource& inj, bool wtape, int64_t g_hi, hipStream_t stream) {
     const Plan& pl = rt.pl;
     const int M = int(items.size());
     if (M <= 0) return RYDIFF_OK;
     std::vector<std::pair<int, int>> blk;  // adjoint order: (first forward factor b, second forward factor a or -1)
-    for (int f = M - 1; f >= 0;) {
+    if (wtape) {
+        blk = forward_blocks(items);
+        std::reverse(blk.begin(), blk.end());
+    }
+    for (int f = wtape ? -1 : M - 1; f >= 0;) {
         if (f >= 1 && items[f - 1].stage == items[f].stage) {
             blk.push_back({f - 1, f});
             f -= 2;
@@ -252,12 +306,13 @@ int run_chain2_bwd(const Runtime& rt, char* ws, const std::vector<ChainItem>& it
     }
     const unsigned tiles = unsigned(pl.dim >> kTileBits);
     const int nb = int(blk.size());
+    const int par = wtape ? int(g_hi & 1) : 0;
     const double2* cur = lam_in;
     int rc = on_stage_end(items[M - 1].stage, cur, xs[M]);  // the cotangent at the chain's output: exponential boundary for dL/dtau
     if (rc) return rc;
     for (int j = 0; j <= nb; ++j) {
         Chain2BwdArgs ca{};
-        fill_chain2(ca, rt, ws, items, blk, j, cur, bs);
+        fill_chain2(ca, rt, ws, items, blk, j, cur, bs, par);
         ca.mu = cur;
         ca.xa = ca.xb = cur;  // (loadable, as w and t)
         if (pl.gd.n) {
@@ -291,15 +346,17 @@ int run_chain2_bwd(const Runtime& rt, char* ws, const std::vector<ChainItem>& it
             ca.cba_i = sa.bi;
             ca.cbb_r = sb.br;
             ca.cbb_i = sb.bi;
+            ca.cgb_r = sb.gr;
+            ca.cgb_i = sb.gi;
             ca.xb = xs[fb];
-            ca.xa = fa >= 0 ? xs[fa] : xs[fb];
+            ca.xa = fa >= 0 ? xs[fa] : xs[fb];  // (wtape: P_X x_b, in the slot of x_a)
             ca.ge_fin = rt.ge(ws, items[fb].stage);
             cl ^= 1;
             ca.mu_out = lam_bufs[cl];
             if (ca.mu_out == cur) return fail(RYDIFF_EINVAL, "internal: cotangent ping-pong clash");
             fill_inject(ca, inj, save_k[fb], pl);  // (inside has_p: every finishing launch completes a cotangent, mu_out)
         }
-        rc = launch_chain2_bwd(rt, ca, tiles, stream);
+        rc = launch_chain2_bwd(rt, ca, tiles, wtape, stream);
         if (rc) return rc;
         if (ca.has_p) {
             cur = ca.mu_out;  // complete cotangent at the input of forward factor fb

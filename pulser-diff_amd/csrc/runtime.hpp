@@ -72,6 +72,7 @@ struct Runtime {
     int pair_phases = -1;         // request order and store policy of the block kernels: -1 automatic | variants 22..30: 4 * ORD + WT (pair_launch.hpp)
     int pair_pace_fwd = -1;       // paced input requests of k_chain2 (its PACE): -1 automatic | 0 variants 17, 20..30, 32 | 1 variants 31, 33 | 2 variant 34
     int pair_pace_bwd = -1;       // ... of k_chain2_bwd: -1 automatic | 0 variants 17, 20..31, 34 | 1 variants 32, 33
+    int pair_wtape = 0;           // mid-block tape entry of the block passes (pair_launch.hpp): 0 automatic | 1 variant 35, P_X v | -1 variants 17, 19..34: v_mid
     int chain_lgt = 9;            // log2(threads per tile workgroup) of explicitly chosen chained variants
     // state-sharded run: where the partner slabs arrive and who moves them (RydProblem.shard_recv / shard_exchange)
     void* const* shard_recv = nullptr;
@@ -96,7 +97,7 @@ struct Runtime {
 // RydProblem.kernel_variant -> Runtime (include/rydiff.h lists the values)
 int decode_variant(const RydProblem* p, Runtime& rt) {
     int v = p->kernel_variant;
-    if (v < 0 || v > 34 || v == 5 || v == 6) return fail(RYDIFF_EINVAL, "kernel_variant must be 0..4 or 7..34");
+    if (v < 0 || v > 35 || v == 5 || v == 6) return fail(RYDIFF_EINVAL, "kernel_variant must be 0..4 or 7..35");
     rt.pair_mode = (v == 17 || v >= 20) ? 1 : (v == 18 ? -1 : 0);
     rt.pair_bwd_off = v == 19;
     rt.pair_bwd_stage = (v == 21 || v == 29) ? 1 : (v >= 20 ? -1 : 0);
@@ -109,6 +110,9 @@ int decode_variant(const RydProblem* p, Runtime& rt) {
     const bool pair_forced = v == 17 || v >= 20;
     rt.pair_pace_fwd = (v == 31 || v == 33) ? 1 : (v == 34 ? 2 : (pair_forced ? 0 : -1));
     rt.pair_pace_bwd = (v == 32 || v == 33) ? 1 : (pair_forced ? 0 : -1);
+    // 35: as 20, with P_X v on the tape between the two factors of a block (the adjoint block kernel rebuilds the mid-block state);
+    // 17 and 19..34 keep v_mid there whatever the automatic choice is
+    rt.pair_wtape = v == 35 ? 1 : ((pair_forced || v == 19) ? -1 : 0);
     if (v >= 17) v = 0;
     rt.generic_direct = v == 9;
     if (v == 9) v = 1;
@@ -631,6 +635,7 @@ struct SweepCtx {
     hipStream_t stream;
     size_t sv;     // complex elements per saved state
     TapeMap tmap;  // partial tape only
+    bool wtape = false;  // full tape: P_X v, not v_mid, between the two factors of a block (pair_wtape, pair_launch.hpp)
     bool full_tape() const { return rt.pl.tape_mode == 2; }
     bool partial_tape() const { return rt.pl.tape_mode == 3; }
 };

@@ -87,6 +87,8 @@ void describe_kernels(const Runtime& rt, const RydProblem* p, bool backward, Ryd
                 std::snprintf(info->kernel_fwd, sizeof(info->kernel_fwd), "k_chain2<%d,10,true,3,%d>", kTileBits, pair_pace_fwd(rt));
             else if (!bwd && pairs)
                 std::snprintf(info->kernel_fwd, sizeof(info->kernel_fwd), "k_chain2<%d,10,%s,%d>", kTileBits, b(pair_vec_major(rt)), pair_through(rt));
+            else if (bwd && pairs_bwd && pair_wtape(rt))
+                std::snprintf(info->kernel_bwd, sizeof(info->kernel_bwd), "k_chain2_bwd<%d,10,true,3,false,0,true>", kTileBits);
             else if (bwd && pairs_bwd && pair_pace_bwd(rt))
                 std::snprintf(info->kernel_bwd, sizeof(info->kernel_bwd), "k_chain2_bwd<%d,10,true,3,false,%d>", kTileBits, pair_pace_bwd(rt));
             else if (bwd && pairs_bwd)
@@ -118,6 +120,25 @@ void describe_kernels(const Runtime& rt, const RydProblem* p, bool backward, Ryd
         else if (backward)
             std::snprintf(info->kernel_bwd, sizeof(info->kernel_bwd), "k_factor_bwd_direct");
     }
+}
+
+// ---- format of the full workspace tape -------------------------------------------------------------------------------------
+// Which of the two mid-block entries (pair_wtape, pair_launch.hpp) the last rydiff_forward call wrote into the full tape of a
+// workspace: kept here, by workspace address, and not among the bytes of the workspace, which the library never reads back on
+// the host.  Only the workspaces that hold P_X v are listed; every forward call that writes a full tape updates its entry.
+std::mutex g_tape_format_mutex;
+std::vector<const void*> g_wtape_workspaces;
+
+void tape_format_record(const void* workspace, bool wtape) {
+    std::lock_guard<std::mutex> lk(g_tape_format_mutex);
+    auto it = std::find(g_wtape_workspaces.begin(), g_wtape_workspaces.end(), workspace);
+    if (wtape && it == g_wtape_workspaces.end()) g_wtape_workspaces.push_back(workspace);
+    else if (!wtape && it != g_wtape_workspaces.end()) g_wtape_workspaces.erase(it);
+}
+
+bool tape_format_wtape(const void* workspace) {
+    std::lock_guard<std::mutex> lk(g_tape_format_mutex);
+    return std::find(g_wtape_workspaces.begin(), g_wtape_workspaces.end(), workspace) != g_wtape_workspaces.end();
 }
 
 // ---- forward sweeps (launch per factor; the one-launch sweep: persist_launch.hpp) ------------------------------------------
@@ -195,7 +216,7 @@ int forward_chained(const ForwardCtx& c) {
             }
         };
         const int rc = (!c.partial_tape() && !bs.xcd && pair_enabled(rt))
-                           ? run_chain2(rt, c.ws, all, c.start, dst, c.full_tape(), done, exp_slot, bs, stream)
+                           ? run_chain2(rt, c.ws, all, c.start, dst, c.full_tape(), c.wtape, done, exp_slot, bs, stream)
                            : run_chain(rt, c.ws, all, c.start, dst, done, exp_slot, false, bs, stream);
         if (rc) return rc;
     }
@@ -285,15 +306,17 @@ int gather_factor_inputs(const BackwardCtx& c, const BatchSlice& bs, int k, int 
     return RYDIFF_OK;
 }
 
+// g_hi: the run-wide index of the last forward block of `chain` (read with P_X v on the tape only, run_chain2_bwd)
 int adjoint_chained(const BackwardCtx& c, const BatchSlice& bs, const std::vector<ChainItem>& chain, const std::vector<const double2*>& xs,
-                    const std::vector<int>& save_k, int& cl) {
+                    const std::vector<int>& save_k, int64_t g_hi, int& cl) {
     const Runtime& rt = c.rt;
     double2* lam[2] = {c.lam[0], c.lam[1]};
     auto dot_h = [&](int stage, const double2* g, const double2* xout) -> int {
         return c.want_tau ? launch_dot_h(rt, c.ws, stage, g, xout, bs, c.stream) : RYDIFF_OK;
     };
     // sharded: dot_h reads the partners' copies of the cotangent it is handed, like the completing launch that follows it
-    return (!bs.xcd && pair_bwd_enabled(rt)) ? run_chain2_bwd(rt, c.ws, chain, xs, save_k, lam[cl], lam, cl, c.wtot, dot_h, bs, c.inj, c.stream)
+    if (c.wtape && (bs.xcd || !pair_bwd_enabled(rt))) return fail(RYDIFF_EINVAL, "internal: P_X v on the tape without the block adjoint");
+    return (!bs.xcd && pair_bwd_enabled(rt)) ? run_chain2_bwd(rt, c.ws, chain, xs, save_k, lam[cl], lam, cl, c.wtot, dot_h, bs, c.inj, c.wtape, g_hi, c.stream)
                                              : run_chain_bwd(rt, c.ws, chain, xs, save_k, lam[cl], lam, cl, c.wtot, dot_h, c.want_tau, bs, c.inj, c.stream);
 }
 
@@ -327,6 +350,9 @@ int adjoint_sweep(const BackwardCtx& c, const BatchSlice& bs, int& cl) {
     std::vector<ChainItem> chain, part;
     std::vector<const double2*> xs;
     std::vector<int> save_k;
+    std::vector<int64_t> bprefix(pl.T + 1, 0);  // forward blocks before interval k (as fprefix counts factors)
+    if (c.wtape)
+        for (int k = 0; k < pl.T; ++k) bprefix[k + 1] = bprefix[k] + step_block_count(rt, k);
     cl = 0;
     for (int k = pl.T - 1; k >= 0; --k) {
         // With every factor input on the tape, consecutive intervals run as ONE chain: the launch that finishes the adjoint
@@ -343,7 +369,7 @@ int adjoint_sweep(const BackwardCtx& c, const BatchSlice& bs, int& cl) {
             chain.insert(chain.end(), part.begin(), part.end());
         }
         int rc = gather_factor_inputs(c, bs, k, k_hi, chain, xs);
-        if (!rc) rc = chained ? adjoint_chained(c, bs, chain, xs, save_k, cl) : adjoint_direct(c, bs, chain, xs, save_k, cl);
+        if (!rc) rc = chained ? adjoint_chained(c, bs, chain, xs, save_k, bprefix[k_hi + 1] - 1, cl) : adjoint_direct(c, bs, chain, xs, save_k, cl);
         if (rc) return rc;
     }
     return RYDIFF_OK;
@@ -479,6 +505,10 @@ int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi
     c.buf[1] = reinterpret_cast<double2*>(c.ws + pl.off_buf1);
     if (c.partial_tape()) c.tmap = partial_tape_map(rt, p->tape_steps);
     const bool ws_tape = c.full_tape() || c.partial_tape();  // (prepare downgrades the request where such a tape is not possible)
+    if (c.full_tape()) {  // the mid-block entries of the tape this call writes: chosen here, recorded for the backward call
+        c.wtape = pair_wtape(rt);
+        tape_format_record(workspace, c.wtape);
+    }
     double2* sout = static_cast<double2*>(states_out);
     // final_state_only: no per-step states; the state at the last evaluation time is copied to states_out at the end
     if (p->final_state_only && sout) {
@@ -528,6 +558,13 @@ int rydiff_backward(const RydProblem* p, const RydPlanInfo* info, const void* st
         c.tmap = partial_tape_map(rt, p->tape_steps);
         c.tape_b = c.tape + size_t(pl.T + 1) * c.sv;
     }
+    // the mid-block entries of a full tape are what the forward call recorded, and this call's kernels have to be the ones that read them
+    c.wtape = c.full_tape() && tape_format_wtape(workspace);
+    if (c.full_tape() && c.wtape != pair_wtape(rt))
+        return fail(RYDIFF_EINVAL, c.wtape ? "the full tape in this workspace holds P_X v between the factors of a block (written by a forward call with the "
+                                             "block adjoint in view), and this backward call would read it as the mid-block state: use the forward call's kernel_variant and real_amp_grad"
+                                           : "the full tape in this workspace holds the mid-block state between the factors of a block, and this backward call "
+                                             "expects P_X v there: use the forward call's kernel_variant and real_amp_grad");
     c.fprefix.assign(pl.T + 1, 0);
     for (int k = 0; k < pl.T; ++k) c.fprefix[k + 1] = c.fprefix[k] + step_factor_count(rt, k);
     c.lam[0] = reinterpret_cast<double2*>(c.ws + pl.off_buf0);

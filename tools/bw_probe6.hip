@@ -4,6 +4,8 @@
 //   3R+3W, 4 rounds   block of two, forward without tape        (v, w, t in;  y, w', t' out)
 //   3R+4W, 4 rounds   block of two, forward with the full tape  (+ v_mid)
 //   5R+3W, 4 rounds   block of two, adjoint with the full tape  (mu, w, t + two tape vectors in)
+//   5R+3W, 5 rounds   ... with P_X x on the tape: one more finishing round (8 bits) on a tape vector, in a second tile buffer,
+//                     with a barrier of its own, ahead of the other four (it rebuilds the mid-block state from x and P_X x)
 // A round is: tile write, barrier, partner sums over the tile bits of the stage (8 Y' bits in the finishing rounds, all 12 in
 // the starting rounds: 10 through LDS, 2 register renaming), barrier — the LDS work of the real passes.  Back-to-back
 // launches alternating the two tile layouts; the tape vectors cycle through a pool larger than the Infinity Cache.
@@ -43,7 +45,8 @@ __device__ __forceinline__ void round_sum(const double2* sh, const double2 (&own
 }
 
 // LIGHT: one LDS partner read per round instead of the partner sums (the exchange of tools/bw_probe5.hip: bandwidth + barriers only)
-template <int NR, int NW, int ROUNDS, bool LIGHT>
+// XR: the extra finishing round on the tape vector x[NR - 2], folded into the tape vector x[NR - 1]
+template <int NR, int NW, int ROUNDS, bool LIGHT, bool XR = false>
 __global__ __launch_bounds__(NT) void k_probe(int layout, Vecs v) {
   extern __shared__ __attribute__((aligned(16))) double2 sh[];
   const unsigned t = blockIdx.x;
@@ -56,6 +59,19 @@ __global__ __launch_bounds__(NT) void k_probe(int layout, Vecs v) {
       x[k][r].x = __builtin_nontemporal_load(&v.in[k][g].x);
       x[k][r].y = __builtin_nontemporal_load(&v.in[k][g].y);
     }
+  if constexpr (XR) {
+    double2* sh2 = sh + TILE;
+#pragma unroll
+    for (int r = 0; r < R; ++r) sh2[r * NT + threadIdx.x] = x[NR - 2][r];
+    __syncthreads();
+    double2 ts[R];
+    round_sum(sh2, x[NR - 2], 4, ts);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      x[NR - 1][r].x = 0.5 * x[NR - 2][r].x + 1e-3 * ts[r].x + 0.25 * x[NR - 1][r].x;
+      x[NR - 1][r].y = 0.5 * x[NR - 2][r].y + 1e-3 * ts[r].y + 0.25 * x[NR - 1][r].y;
+    }
+  }
   double2 cur[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) cur[r] = x[0][r];
@@ -94,10 +110,10 @@ __global__ __launch_bounds__(NT) void k_probe(int layout, Vecs v) {
   }
 }
 
-template <int NR, int NW, int ROUNDS, bool LIGHT>
+template <int NR, int NW, int ROUNDS, bool LIGHT, bool XR = false>
 static int run(const char* name, double2** pool, int npool, int iters, double per_factor_div, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
-  const size_t lds = TILE * sizeof(double2);
-  CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_probe<NR, NW, ROUNDS, LIGHT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const size_t lds = (XR ? 2 : 1) * TILE * sizeof(double2);
+  CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_probe<NR, NW, ROUNDS, LIGHT, XR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   // buffers 0..4: set A, 5..9: set B (the chained vectors ping-pong); 10..npool-1: tape pool
   auto launch = [&](int i) {
     Vecs v{};
@@ -105,7 +121,7 @@ static int run(const char* name, double2** pool, int npool, int iters, double pe
     const int chained = NW < NR ? NW : NR;
     for (int k = 0; k < NR; ++k) v.in[k] = k < chained ? pool[src + k] : pool[10 + (i * 2 + k) % (npool - 10)];
     for (int k = 0; k < NW; ++k) v.out[k] = pool[dst + k];
-    hipLaunchKernelGGL((k_probe<NR, NW, ROUNDS, LIGHT>), dim3(256), dim3(NT), lds, s, i & 1, v);
+    hipLaunchKernelGGL((k_probe<NR, NW, ROUNDS, LIGHT, XR>), dim3(256), dim3(NT), lds, s, i & 1, v);
   };
   for (int i = 0; i < 4; ++i) launch(i);
   CK(hipEventRecord(e0, s));
@@ -143,6 +159,7 @@ int main() {
     if (run<3, 3, 4, false>("3R+3W, 2 factors (no tape)", pool, kPool, it, 2.0, s, e0, e1)) return 1;
     if (run<3, 4, 4, false>("3R+4W, 2 factors (tape)", pool, kPool, it, 2.0, s, e0, e1)) return 1;
     if (run<5, 3, 4, false>("5R+3W, 2 factors (adjoint)", pool, kPool, it, 2.0, s, e0, e1)) return 1;
+    if (run<5, 3, 4, false, true>("5R+3W, 5 rounds (adjoint, w tape)", pool, kPool, it, 2.0, s, e0, e1)) return 1;
   }
   for (int i = 0; i < kPool; ++i) CK(hipFree(pool[i]));
   return 0;
