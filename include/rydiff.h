@@ -206,6 +206,35 @@ typedef struct RydProblem {
     uint64_t amp_conditioned_terms;
     uint64_t det_ones_terms;
 
+    /* XY EXCHANGE (the reference's microwave / "XY" interaction mode, hamiltonian.py:346-366) as a term of its own: one real number
+     * per pair of qubits and one partner amplitude, instead of a dense 4x4 pair term.  With b_q(x) the index bit of qubit q (bit
+     * N-1-q of the amplitude index x) and m_q = 1 << (N-1-q):
+     *   xy_mode = 1 (Hermitian):  (H v)[x] += sum_{i<j, b_i(x) != b_j(x)} J_ij * v[x ^ m_i ^ m_j]
+     *   xy_mode = 2 (one-directional, as the reference writes it: its 2 * int_mat without the adjoint): only the rows with
+     *               b_i(x) = 0 and b_j(x) = 1 for i < j are kept — source |d_i u_j>, target |u_i d_j>, the pair-term block[1][2] = J.
+     * J_ij is the full coefficient of the generator (the reference's 2 U); real, any sign, zero allowed; shared by the trajectories
+     * like u_pairs, next to which it may be used (u_pairs != 0 is fine).  Runs on the direct family (launch per factor, kernels of its
+     * own: xy_kernels.hpp) at every N from 1 to RYDIFF_MAX_QUBITS, RydPlanInfo.kernel_family = 2; kernel_variant 0, 1 and 9 only.
+     * need_tape = 2 / 3 are downgraded to 1 as for pair terms.  batch / coeff_batch, every ket observable row and the shots are
+     * honoured (they read states at save points only).  rydiff_plan reads xy_pairs in the kernel that inspects the tables (still
+     * one synchronisation) and widens the spectral interval by sum |J_ij| on either side — a Gershgorin bound on the exchange rows;
+     * in mode 2 (H not Hermitian) it bounds the numerical range, as the radius of non-Hermitian pair terms does.
+     * rydiff_backward delivers g_amp, g_det, g_u, g_tsave, g_psi0 as usual (the Im<mu, H x> pass carries the exchange on x: no side
+     * swap, H need not be Hermitian) and g_xy[p] = dL/dJ_p through every factor pass with the plan constants frozen — the discrete
+     * map that g_u differentiates, scaled like it under KRYLOV_SE, DP5_SE and sub-stepped exponentials.  It sits in the struct so
+     * that the signature of rydiff_backward stays.  Every workgroup reduces its N(N-1)/2 contributions and adds them with one atomic
+     * per pair into a few replicas in the workspace (zeroed by the call; rydiff_plan sizes them), summed in a fixed order at the end:
+     * g_xy is overwritten, and two calls agree up to the rounding of the order in which the atomics land.
+     * RYDIFF_EINVAL: xy_mode outside 0..2; xy_pairs == NULL with xy_mode != 0 and N > 1.  RYDIFF_ENOTIMPL, before anything touches a
+     * device: xy_mode != 0 together with n_pair_terms > 0, shard_bits > 0, dm_atoms > 0, conditioned or ones-counting terms, a
+     * kernel_variant other than 0, 1, 9, and in rydiff_forward_tangent / rydiff_forward_geometry / rydiff_forward_fisher /
+     * rydiff_apply_factor.  Follow-ups: the tangent sweep and the one-launch sweeps up to 12 qubits.
+     * xy_mode = 0: the other two fields are ignored and nothing changes.  (The fields sit in front of dp5_piece_refine: every later
+     * block keeps its neighbours, and the Pauli block stays the tail of the struct.) */
+    int32_t xy_mode;          /* 0: none; 1: Hermitian exchange; 2: one-directional, as the reference writes it */
+    const double* xy_pairs;   /* DEVICE float64 [N(N-1)/2], J_ij in itertools.combinations order (the order of u_pairs) */
+    double* g_xy;             /* rydiff_backward: DEVICE float64 [N(N-1)/2] or NULL; overwritten */
+
     /* RYDIFF_SOLVER_DP5_SE only, optional (NULL: none).  HOST uint8 [n_samples - 1]: entry i multiplies the number of Magnus
      * sub-steps taken on the linear piece between samples i and i + 1 (0 and 1: unchanged).  The sub-step is sized from the
      * generator's width; the error constant also carries dH/dt, so a piece across which a table JUMPS (the edge of a constant
@@ -411,10 +440,10 @@ typedef struct RydPlanInfo {
     size_t workspace_bytes;          /* device workspace needed by forward/backward for the flags given to rydiff_plan */
     int32_t tape_mode;               /* the tape the workspace was sized for: 0 none, 1 one state per tsave, 2 full, 3 partial (one state per
                                         tsave + every factor output of the last RydProblem.tape_steps intervals); need_tape = 2 / 3 are granted
-                                        from 12 / 13 qubits on and without pair terms, otherwise downgraded to 1 */
+                                        from 12 / 13 qubits on, without pair terms and without the XY exchange (xy_mode), otherwise downgraded to 1 */
     int32_t kernel_family;           /* which forward kernels the problem will run on (reporting only): 0 one-wave lane sweep
-                                        (<= 6 qubits), 1 one-workgroup persistent sweep (<= 12 qubits), 2 direct launch per factor,
-                                        3 chained LDS-tile launch per factor */
+                                        (<= 6 qubits), 1 one-workgroup persistent sweep (<= 12 qubits), 2 direct launch per factor
+                                        (always, at every N, with the XY exchange: xy_mode != 0), 3 chained LDS-tile launch per factor */
     char kernel_fwd[80];             /* reporting only: the instantiation the forward factor passes of THIS problem run on, as a profiler
                                         prints it, e.g. "k_chain<12,10,false,false,true,false>" (tile bits, log2 threads, complex tables,
                                         adjoint, loop-free, L2-resident) — bench.py names its roofline kernel from here */

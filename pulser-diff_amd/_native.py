@@ -39,6 +39,7 @@ TANGENT_MOMENTS = 8         # RYDIFF_TANGENT_MOMENTS: take the occupation correl
                             # RYDIFF_EINVAL on a problem without them
 MAX_DM_ATOMS = 12  # atoms of a density-matrix register (RydProblem.dm_atoms)
 MAX_DM_DIAG = 64  # diagonal observables of a density-matrix register
+XY_NONE, XY_HERMITIAN, XY_ONE_DIRECTIONAL = 0, 1, 2  # RydProblem.xy_mode
 MAX_SHOTS = 1 << 20  # shots per (sampled save point, trajectory)
 SHOT_NONE = 0xFFFFFFFF  # the sampled state was identically zero
 
@@ -76,6 +77,9 @@ class RydProblem(ctypes.Structure):
         ("final_state_only", ctypes.c_int32),
         ("amp_conditioned_terms", ctypes.c_uint64),
         ("det_ones_terms", ctypes.c_uint64),
+        ("xy_mode", ctypes.c_int32),
+        ("xy_pairs", ctypes.c_void_p),
+        ("g_xy", ctypes.c_void_p),
         ("dp5_piece_refine", ctypes.c_void_p),
         ("dm_moments", ctypes.c_int32),
         ("n_shots", ctypes.c_int32),

@@ -17,6 +17,7 @@ What changes for a user switching over:
 """
 from __future__ import annotations
 
+import functools
 from bisect import bisect_left
 from collections import Counter
 from dataclasses import dataclass, replace
@@ -158,6 +159,25 @@ class OccupationSensitivities:
                                                                      self.occupied_bit), 0)
 
 
+def _keeps_xy_route(method):
+    """XY mode: a call that needs the dense pair terms (``Hamiltonian.require_dense_xy``) borrows them for its own duration.  When
+    the outermost such call returns or raises, the Hamiltonian is back on the route ``Hamiltonian.xy_route()`` names, so a later
+    ``run()`` on the native exchange term still delivers the gradient of the geometry."""
+
+    @functools.wraps(method)
+    def wrapper(self, *args, **kwargs):
+        self._xy_route_depth = getattr(self, "_xy_route_depth", 0) + 1
+        try:
+            return method(self, *args, **kwargs)
+        finally:
+            self._xy_route_depth -= 1
+            ham = self._hamiltonian
+            if self._xy_route_depth == 0 and ham._interaction == "XY" and (ham.xy_mode != 0) != (ham.xy_route() == "native"):
+                ham._select_xy_route()
+
+    return wrapper
+
+
 class TorchEmulator:
     r"""Emulator of a pulse sequence using the MI355X-native solver.
 
@@ -171,11 +191,14 @@ class TorchEmulator:
         compute_device: torch device of the native solver (extension; default "cuda").
         xy_hermitian: XY mode only (extension): True = the physical exchange U (s+s- + s-s+); None / False = the exchange as the
             reference assembles it (one-directional, non-Hermitian generator; a warning is issued once).
+        xy_native: XY mode only (extension): True = the exchange runs as the library's native exchange term (any register size,
+            gradients of the geometry); False = as dense pair terms (at most 8 atoms); None = automatic: native past 8 atoms or when
+            the coordinates or distances carry a gradient.
     """
 
     def __init__(self, sampled_seq, register, device, sampling_rate: float = 1.0, config: Optional[SimConfig] = None,
                  evaluation_times: Union[float, str, Any] = "Full", compute_device: Union[str, torch.device] = "cuda",
-                 xy_hermitian: Optional[bool] = None) -> None:
+                 xy_hermitian: Optional[bool] = None, xy_native: Optional[bool] = None) -> None:
         # real Pulser objects are converted by attribute access (pulser_adapter.py); anything else is a TypeError
         sampled_seq = pulser_adapter.adapt_samples(sampled_seq)
         register = pulser_adapter.adapt_register(register)
@@ -211,7 +234,8 @@ class TorchEmulator:
         noise_model = config.to_noise_model() if config else SimConfig().to_noise_model()
         self._config = config if config else SimConfig()
         self._hamiltonian = Hamiltonian(self.samples_obj, self._register.qubits, device, sampling_rate, noise_model,
-                                        compute_device=self._compute_device, xy_hermitian=xy_hermitian)
+                                        compute_device=self._compute_device, xy_hermitian=xy_hermitian,
+                                        xy_native=xy_native)
         self._eval_times_array: Tensor
         self.set_evaluation_times(evaluation_times)
         # backend.py:141-147: the sequence's measurement basis, else the Hamiltonian's ("digital" for the three-level basis)
@@ -386,9 +410,6 @@ class TorchEmulator:
 
     def _enable_dist_grad(self) -> None:
         """backend.py:456-460: the distances r_ij become differentiable inputs (``qq_distances``)."""
-        if self._hamiltonian._interaction == "XY":
-            raise NotImplementedError("dist_grad is not available in the XY mode: its exchange terms enter the native solver as "
-                                      "constant two-qubit blocks (pulser_diff_amd/hamiltonian.py:_xy_pair_terms).")
         for k, v in self._hamiltonian._dist_dict.items():
             if v.requires_grad:
                 v.retain_grad()
@@ -396,8 +417,23 @@ class TorchEmulator:
                 v.requires_grad_(True)  # constant register: make r_ij a leaf and reconnect U_ij to it
             self.dist_dict[k] = v
         self._hamiltonian._rebuild_u_pairs()
+        if self._hamiltonian._interaction == "XY":
+            # J_ij = C3 (1 - 3 cos^2 theta_ij) / r_ij^3 from the leaves, the angular factor a constant of the register; the couplings
+            # now carry a gradient, which the native exchange term delivers (Hamiltonian.xy_route)
+            self._hamiltonian._xy_dist_grad = True
+            self._hamiltonian._rebuild_xy_pairs()
+
+    def _dense_xy_for(self, what: str, dist_grad: bool) -> None:
+        """XY mode: `what` runs on the dense pair terms (constants, at most 8 atoms), not on the native exchange term."""
+        if self._hamiltonian._interaction != "XY":
+            return
+        if dist_grad:
+            raise NotImplementedError(f"dist_grad is not available in the XY mode for {what}: it runs on the dense pair terms, whose "
+                                      "exchange blocks are constants (run(dist_grad=True) differentiates the native exchange term).")
+        self._hamiltonian.require_dense_xy(what)
 
     # ---- run (backend.py:430-611) -------------------------------------------------------------------------
+    @_keeps_xy_route
     def run(self, time_grad: bool = False, dist_grad: bool = False, solver: SolverType = SolverType.DP5_SE,
             observables: Optional[list] = None, store_states: bool = True, shots: Union[None, int, ShotRequest] = None,
             native_shots: bool = False, **options: Any) -> SimulationResults:
@@ -425,11 +461,18 @@ class TorchEmulator:
         if time_grad:
             self._eval_times_array.requires_grad_(True)  # backend.py:453-455
         if dist_grad:
+            # XY mode: the master equation and the averaged noisy runs stay on the dense pair terms, whose blocks are constants
+            if solver == SolverType.DP5_ME or set(self.config.noise) & COLLAPSE_NOISES:
+                self._dense_xy_for("the master-equation solver (DP5_ME)", True)
+            if not (self._no_resampling() and ("SPAM" not in self.config.noise or self.config.eta == 0)):
+                self._dense_xy_for("noisy runs that average over realisations", True)
             self._enable_dist_grad()
         if set(self.config.noise) & COLLAPSE_NOISES:  # backend.py:482-488: collapse operators force the master equation
             solver = SolverType.DP5_ME
         if solver not in (SolverType.DP5_SE, SolverType.KRYLOV_SE, SolverType.DP5_ME):
             raise ValueError(f"Solver {solver} not available.")
+        if solver == SolverType.DP5_ME:
+            self._hamiltonian.require_dense_xy("the master-equation solver (DP5_ME)")
         if solver == SolverType.DP5_ME and self._hamiltonian.basis_name == "all":
             raise NotImplementedError("The master-equation solver is not available in the three-level all-basis "
                                       "(the reference admits no collapse-operator noise there, hamiltonian.py:98-103).")
@@ -566,6 +609,7 @@ class TorchEmulator:
         if shots is not None:
             raise NotImplementedError("A ShotRequest belongs to one coherent run; noisy runs that average over realisations return "
                                       "their measurements as NoisyResults (native_shots=True draws them natively).")
+        ham.require_dense_xy("noisy runs that average over realisations")
         return self._run_noisy(psi0, solver, options, reps, bad_atom_configs, meas_errors, native_shots=native_shots)
 
     # ---- sensitivities at every evaluation time (extension) ---------------------------------------------------
@@ -674,6 +718,7 @@ class TorchEmulator:
             d0 += m
         return out
 
+    @_keeps_xy_route
     def run_sensitivities(self, x: list, observables: list, solver: SolverType = SolverType.DP5_SE, dist_grad: bool = False,
                           route: Optional[str] = None, **options: Any) -> "Sensitivities":
         """Values AND derivatives of observables at EVERY evaluation time w.r.t. the tensors in ``x`` — what a loop of
@@ -717,6 +762,7 @@ class TorchEmulator:
                                 "(master-equation runs: StateOverlap and Purity too)")
             if tuple(obs.shape) != (full, full):
                 raise ValueError(f"Incompatible shape of observable.Expected {(full, full)}, got {tuple(obs.shape)}.")
+        self._dense_xy_for("run_sensitivities", dist_grad)
         if dist_grad:
             self._enable_dist_grad()
         times = self._eval_times_array.detach()
@@ -778,6 +824,7 @@ class TorchEmulator:
         dvals = dexpect.sum(dim=-1)[:, rows]         # (n_dir, n_obs, n_t)
         return Sensitivities(values, self._per_tensor(dvals, x), "tangent", times)
 
+    @_keeps_xy_route
     def run_rdm_sensitivities(self, x: list, subsystems: list, solver: SolverType = SolverType.DP5_SE, dist_grad: bool = False,
                               **options: Any) -> "SubsystemSensitivities":
         """Reduced density matrices of up to 8 subsystems AND their derivatives w.r.t. the tensors in ``x`` at EVERY evaluation time,
@@ -805,6 +852,7 @@ class TorchEmulator:
             raise ValueError(f"run_rdm_sensitivities takes 1 to {_native.MAX_RDMS} subsystems per call, got {len(rdm_objs)}")
         for obs in rdm_objs:
             obs.check(ham._size)
+        self._dense_xy_for("run_rdm_sensitivities", dist_grad)
         if dist_grad:
             self._enable_dist_grad()
         times = self._eval_times_array.detach()
@@ -828,6 +876,7 @@ class TorchEmulator:
         drho = [self._per_tensor(torch.stack([per_dir[d][o] for d in range(n_dir)]), x) for o in range(len(rdm_objs))]
         return SubsystemSensitivities(rho, drho, times)
 
+    @_keeps_xy_route
     def run_occupation_sensitivities(self, x: list, solver: SolverType = SolverType.DP5_SE, dist_grad: bool = False,
                                      **options: Any) -> "OccupationSensitivities":
         """The occupation correlations — the moments behind every ``<n_i>`` and ``<n_i n_j>`` — AND their derivatives w.r.t. the
@@ -848,6 +897,7 @@ class TorchEmulator:
             all_basis="run_occupation_sensitivities is not available in the three-level all-basis: an atom is two qubits "
                       "there, and the native tangent sweep takes no conditioned flips / ones-counting terms.")
         ham, dev = self._hamiltonian, self._compute_device
+        self._dense_xy_for("run_occupation_sensitivities", dist_grad)
         if dist_grad:
             self._enable_dist_grad()
         times = self._eval_times_array.detach()
@@ -920,7 +970,9 @@ class TorchEmulator:
         table tangents, the sweep.  ``(gram, cgram or None, values, grads, times)``."""
         ham, dev = self._hamiltonian, self._compute_device
         sweep = evolve_fisher if fisher else (lambda *a, **k: evolve_geometry(*a, **k) + (None,))
-        if getattr(ham, "pair_terms", ()):
+        if getattr(ham, "pair_terms", ()) or getattr(ham, "xy_mode", 0):
+            if ham._size > ham.MAX_XY_QUBITS:
+                raise NotImplementedError(ham.dense_xy_limit(name))
             raise NotImplementedError(f"{name} is not available with the XY exchange: this route hands no dense pair terms "
                                       "to the tangent sweep (solver.evolve_geometry takes them on request).")
         observables = list(observables)
@@ -1122,6 +1174,7 @@ class TorchEmulator:
         ham.samples_obj = self.samples_obj
         ham._qdict = {k: (v if isinstance(v, Tensor) else torch.as_tensor(v)).to(torch.float64) for k, v in register.qubits.items()}
         ham._dist_dict = {}
+        ham._xy_dist_grad = False  # the new distances are functions of the coordinates again, and so is the angular factor
         ham._construct_hamiltonian()
         self.dist_dict = {}
         # a fresh leaf for the evaluation times: with time_grad the old one has requires_grad set and would ACCUMULATE its
@@ -1132,7 +1185,8 @@ class TorchEmulator:
     @classmethod
     def from_sequence(cls, sequence, sampling_rate: float = 1.0, config: Optional[SimConfig] = None,
                       evaluation_times: Union[float, str, Any] = "Full", with_modulation: bool = False,
-                      compute_device: Union[str, torch.device] = "cuda", xy_hermitian: Optional[bool] = None) -> "TorchEmulator":
+                      compute_device: Union[str, torch.device] = "cuda", xy_hermitian: Optional[bool] = None,
+                      xy_native: Optional[bool] = None) -> "TorchEmulator":
         r"""backend.py:651-711."""
         native = isinstance(sequence, pulses.Sequence)
         if not native and not all(hasattr(sequence, a) for a in ("is_parametrized", "is_register_mappable", "_schedule",
@@ -1156,4 +1210,4 @@ class TorchEmulator:
             sampler(sequence, modulation=with_modulation,
                     extended_duration=sequence.get_duration(include_fall_time=with_modulation)),
             sequence.register, sequence.device, sampling_rate, config, evaluation_times, compute_device=compute_device,
-            xy_hermitian=xy_hermitian)
+            xy_hermitian=xy_hermitian, xy_native=xy_native)

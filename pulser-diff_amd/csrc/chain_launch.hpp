@@ -41,7 +41,7 @@ uint32_t to_tile_mask(const LayoutDesc& d, int lt, uint32_t index_mask) {
 
 bool chain_enabled(const Runtime& rt) {
     const int N = rt.pl.NL;
-    if (rt.variant == 1 || rt.pl.n_pair) return false;  // pair terms: direct kernels
+    if (rt.variant == 1 || rt.pl.n_pair || rt.pl.xy_mode) return false;  // pair terms, the XY exchange: direct kernels
     // conditioned flips (three-level registers): measured (tools/time_three_level.py) the chained passes win up to 20 qubits (10 atoms:
     // 29.6 -> 20.6 us per pass, fwd+grad +23 %); beyond, the 2^12 tiles' short runs / third layout and the 512-thread signed-sum adjoint
     // lose to the generic direct kernels (22 qubits: 758 vs 687 steps/s fwd+grad).  Explicit chained variants still take them (tests).

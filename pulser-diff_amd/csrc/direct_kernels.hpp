@@ -101,12 +101,14 @@ __global__ void k_ugrad(double* __restrict__ g_u, const double* __restrict__ wto
 //   stats[3] = sum of max(U_ij, 0)     stats[5] = sum of max(-U_ij, 0)   (the doubled register of the master-equation path
 //                                                                        carries -U_ij on its column qubits)
 //   stats[4] = max_i sum_g |Im c_g[i]|   (non-zero: some drive has a phase)
+//   stats[6] = sum of |J_ij|   (XY exchange, RydProblem.xy_pairs: every row of the exchange has at most this absolute sum)
 // all non-negative doubles -> their bit patterns order like unsigned integers (atomicMax on u64).
 // ------------------------------------------------------------------------------------------------
 struct StatsArgs {
     const double2* amp;
     const double* det;
     const double* u_pairs;
+    const double* xy_pairs;  // nullptr: no exchange
     int n_samples, Ka, Kd, n_pairs, Bc;
     int ga, gd;
     uint64_t amem[kMaxGroups], dmem[kMaxGroups];
@@ -152,6 +154,10 @@ __global__ void k_table_stats(unsigned long long* __restrict__ stats, StatsArgs 
         }
         stats[3] = (unsigned long long)__double_as_longlong(sp);
         stats[5] = (unsigned long long)__double_as_longlong(sn);
+        double sj = 0.0;
+        if (a.xy_pairs)
+            for (int k = 0; k < a.n_pairs; ++k) sj += fabs(a.xy_pairs[k]);
+        stats[6] = (unsigned long long)__double_as_longlong(sj);
     }
 }
 

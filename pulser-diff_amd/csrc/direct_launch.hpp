@@ -3,10 +3,16 @@
 
 namespace {
 
+// the XY exchange family (xy_launch.hpp): every launch below hands over to it when the problem carries the exchange
+int launch_factor_xy(const Runtime& rt, char* ws, const double2* xin, double2* xout, int stage, const FactorScalars& s, hipStream_t stream);
+int launch_factor_bwd_xy(const Runtime& rt, char* ws, const double2* gin, const double2* xin, double2* gout, int stage,
+                         const FactorScalars& s, double* wtot, const InjectSource& inj, int save_k, hipStream_t stream);
+int launch_dot_h_xy(const Runtime& rt, char* ws, int stage, const double2* g, const double2* xout, const BatchSlice& bs, hipStream_t stream);
+
 // one global drive on a 12..20-qubit register without pair terms: the unrolled direct kernels (k_factor_direct_global)
 bool direct_global_ok(const Runtime& rt) {
     const Plan& pl = rt.pl;
-    return !rt.generic_direct && !pl.shard_bits && pl.N >= 12 && pl.N <= 20 && pl.n_pair == 0 && pl.ga.n == 1 &&
+    return !rt.generic_direct && !pl.shard_bits && !pl.xy_mode && pl.N >= 12 && pl.N <= 20 && pl.n_pair == 0 && pl.ga.n == 1 &&
            pl.ga.amp_index_mask[0] == (1u << pl.N) - 1u;
 }
 
@@ -52,6 +58,7 @@ int launch_factor(const Runtime& rt, char* ws, const double2* xin, double2* xout
                   const double* obs = nullptr, double* expect_slot = nullptr, bool* fused = nullptr) {
     const Plan& pl = rt.pl;
     if (fused) *fused = false;
+    if (pl.xy_mode) return launch_factor_xy(rt, ws, xin, xout, stage, s, stream);
     FactorArgs fa{};
     fill_factor(fa, rt, ws, stage, s);
     fa.xin = xin;
@@ -72,6 +79,7 @@ int launch_factor(const Runtime& rt, char* ws, const double2* xin, double2* xout
 int launch_factor_bwd(const Runtime& rt, char* ws, const double2* gin, const double2* xin, double2* gout, int stage,
                       const FactorScalars& s, double* wtot, const InjectSource& inj, int save_k, hipStream_t stream) {
     const Plan& pl = rt.pl;
+    if (pl.xy_mode) return launch_factor_bwd_xy(rt, ws, gin, xin, gout, stage, s, wtot, inj, save_k, stream);
     FactorBwdArgs ba{};
     fill_factor(ba, rt, ws, stage, s);
     ba.gin = gin;
@@ -92,6 +100,7 @@ int launch_factor_bwd(const Runtime& rt, char* ws, const double2* gin, const dou
 // State-sharded runs apply H to g instead (DotHArgs); with ranks elsewhere shard_recv[] must hold the partners' copies of g by now.
 int launch_dot_h(const Runtime& rt, char* ws, int stage, const double2* g, const double2* xout, const BatchSlice& bs, hipStream_t stream) {
     const Plan& pl = rt.pl;
+    if (pl.xy_mode) return launch_dot_h_xy(rt, ws, stage, g, xout, bs, stream);
     DotHArgs da{};
     da.g = g;
     da.x = xout;

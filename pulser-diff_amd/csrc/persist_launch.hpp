@@ -5,7 +5,7 @@
 namespace {
 
 // ---- persistent small-N forward (k_persist) ------------------------------------------------------------------------
-bool persist_enabled(const Runtime& rt) { return rt.variant != 1 && rt.pl.N <= kTileBits && !rt.pl.shard_bits; }
+bool persist_enabled(const Runtime& rt) { return rt.variant != 1 && rt.pl.N <= kTileBits && !rt.pl.shard_bits && !rt.pl.xy_mode; }
 
 // every amplitude and every detuning group is ONE qubit and there are more than two of either (stochastic-noise runs, several local
 // channels): the per-bit form of the forward sweep (k_persist<..., PERBIT>) instead of the generic group loops

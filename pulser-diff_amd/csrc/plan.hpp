@@ -76,6 +76,9 @@ struct Plan {
     std::vector<double> pair_tab;
     double pair_radius = 0.0;  // Gershgorin radius of the pair terms (sum over terms of the largest absolute row sum)
     size_t off_pair = 0;
+    // XY exchange (RydProblem.xy_mode, xy_kernels.hpp): 0 none | 1 Hermitian | 2 one-directional; gradient replicas [kXyReplicas][N(N-1)/2]
+    int xy_mode = 0;
+    size_t off_xy_ge = 0;
     // Pauli-string observables: groups of observable o are [pauli_gfirst[o], pauli_gfirst[o + 1])
     int n_pobs = 0;
     std::vector<int32_t> pauli_gfirst;
@@ -564,6 +567,34 @@ inline bool build_dm(const RydProblem* p, Plan& pl, std::string& err) {
     return true;
 }
 
+// RydProblem.xy_*: what the exchange term is refused with (host only; "not implemented" in the message -> RYDIFF_ENOTIMPL)
+inline bool xy_validate(const RydProblem* p, std::string& err) {
+    if (p->xy_mode < 0 || p->xy_mode > 2) {
+        err = "xy_mode must be 0 (none), 1 (Hermitian exchange) or 2 (one-directional)";
+        return false;
+    }
+    if (p->xy_mode == 0) return true;
+    if (p->n_qubits > 1 && !p->xy_pairs) {
+        err = "xy_pairs is required with xy_mode != 0 on more than one qubit";
+        return false;
+    }
+    const char* with = nullptr;
+    if (p->n_pair_terms > 0) with = "dense pair terms (n_pair_terms > 0)";
+    else if (p->shard_bits > 0) with = "state sharding (shard_bits > 0)";
+    else if (p->dm_atoms > 0) with = "density-matrix registers (dm_atoms > 0)";
+    else if (p->amp_conditioned_terms || p->det_ones_terms) with = "conditioned flips / ones-counting terms";
+    else if (p->kernel_variant != 0 && p->kernel_variant != 1 && p->kernel_variant != 9)
+        with = "this kernel_variant (the exchange runs on the direct family: 0, 1 or 9)";
+    if (with) {
+        err = std::string("XY exchange (xy_mode != 0): not implemented together with ") + with;
+        return false;
+    }
+    return true;
+}
+
+// number of XY gradient replicas in the workspace (xy_kernels.hpp)
+constexpr int kXyReplicas = 32;
+
 // `width`: half spectral width of the generator when it is already known (<= 0: not yet) — the continuous solver's
 // sub-step shrinks with it.
 inline bool build_plan(const RydProblem* p, Plan& pl, std::string& err, double width = -1.0) {
@@ -615,6 +646,8 @@ inline bool build_plan(const RydProblem* p, Plan& pl, std::string& err, double w
         err = "bad pair terms";
         return false;
     }
+    if (!xy_validate(p, err)) return false;
+    pl.xy_mode = p->xy_mode;
     pl.n_pair = p->n_pair_terms;
     pl.pair_tab.assign(size_t(pl.n_pair) * 64, 0.0);
     pl.pair_radius = 0.0;
@@ -898,6 +931,7 @@ inline size_t carve(Plan& pl, int tape_mode, bool need_backward, int chain_slots
         // (one-launch adjoints: every k)
         pl.off_pauli_cot = take((pl.n_pobs || pl.n_ov || pl.n_rdm || pl.moments || pl.dm_rows()) ? size_t(pl.N <= 12 ? pl.T + 1 : 1) * pl.state_bytes : 0);
         pl.off_meta2 = take(std::max(E * 40, size_t(pl.T + 1) * sizeof(int32_t)));  // StageBwdDev records, or the save-point flags of the one-launch adjoint
+        pl.off_xy_ge = take(pl.xy_mode ? size_t(kXyReplicas) * (pl.N * (pl.N - 1) / 2) * sizeof(double) : 0);  // XY gradient replicas (zeroed by rydiff_backward)
     }
     return off;
 }

@@ -80,6 +80,8 @@ struct Runtime {
     void* shard_user = nullptr;
     GroupArgs garg{};
     PairArgs parg{};
+    XyArgs xarg{};               // XY exchange (xy_kernels.hpp); mode 0: none
+    double* xy_ge = nullptr;     // rydiff_backward with g_xy: the gradient replicas in the workspace
 
     // strides of the per-exponential records in the workspace (doubles; 0 between trajectories: one record shared by the batch)
     long coef_bstride() const { return pl.Bc > 1 ? long(pl.stages.size()) * pl.NC : 0; }
@@ -265,6 +267,7 @@ int run_stats(const RydProblem* p, const Plan& pl, void* scratch, hipStream_t st
     sa.amp = static_cast<const double2*>(p->amp_tables);
     sa.det = p->det_tables;
     sa.u_pairs = p->u_pairs;
+    sa.xy_pairs = pl.xy_mode ? p->xy_pairs : nullptr;
     sa.n_samples = pl.n_samples;
     sa.Ka = pl.Ka;
     sa.Kd = pl.Kd;
@@ -286,7 +289,7 @@ int run_stats(const RydProblem* p, const Plan& pl, void* scratch, hipStream_t st
     dim3 grid((ns + 127) / 128, pl.Bc);
     hipLaunchKernelGGL(k_table_stats, grid, dim3(128), 0, stream, static_cast<unsigned long long*>(scratch), sa);
     LAUNCH_CHECK();
-    double host[6] = {0, 0, 0, 0, 0, 0};
+    double host[7] = {0, 0, 0, 0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(host, scratch, sizeof(host), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));  // the ONE synchronisation of the library: the bounds decide how many launches follow
     // interpolation weights: KRYLOV_SE uses convex combinations (sum |w| = 1); keep the general bound
@@ -300,6 +303,11 @@ int run_stats(const RydProblem* p, const Plan& pl, void* scratch, hipStream_t st
     // detuning range; the flip part has norm host[0] exactly (commuting single-qubit terms)
     hi = host[3] + wsum * (host[1] + host[0]);
     lo = -host[5] - wsum * (host[2] + host[0]);
+    // XY exchange: every row of it sums to at most sum |J_ij| in absolute value — Gershgorin for the Hermitian mode; in the
+    // one-directional mode the same number bounds the numerical range (row and column sums alike), as pair_radius does for
+    // non-Hermitian pair terms.  Folded into the reported interval, so a call that is handed the plan needs no second look.
+    hi += host[6];
+    lo -= host[6];
     flags = (host[4] != 0.0) ? 1 : 0;  // bit 0: some flip coefficient has a non-zero imaginary part (phase != 0)
     return RYDIFF_OK;
 }
@@ -339,7 +347,7 @@ bool few_tiles(const Runtime& rt, bool with_gradients) {
 // one state per tsave.
 // ... and the one-launch adjoint sweeps (<= 11 qubits), which in tape mode walk the factors without recomputing anything.
 bool full_tape_possible(const Plan& pl) {
-    if (pl.shard_bits) return false;
+    if (pl.shard_bits || pl.xy_mode) return false;  // (the exchange: direct kernels, one state per tsave, as for pair terms past 11 qubits)
     if (pl.N <= kPersistBwdMaxQubits) return pl.ga.n <= kPersistGroups && pl.gd.n <= kPersistGroups;
     return pl.n_pair == 0;
 }
@@ -388,6 +396,9 @@ int plan_runtime(const RydProblem* p, const RydPlanInfo* info, void* scratch, si
         if (rc) return rc;
     }
     rt.real_amp_grad = p->real_amp_grad != 0;
+    rt.xarg.mode = rt.pl.xy_mode;
+    rt.xarg.N = rt.pl.N;
+    rt.xarg.J = rt.pl.xy_mode ? p->xy_pairs : nullptr;
     // the stage list of the continuous solver depends on the spectral width: rebuild it now that the width is known
     if (!build_plan(p, rt.pl, err, generator_half_width(rt.pl, lo, hi))) return fail(RYDIFF_EINVAL, err);
     rc = finish_runtime(rt, lo, hi);

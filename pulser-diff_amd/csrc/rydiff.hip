@@ -37,6 +37,7 @@ using namespace rydiff;
 
 #include "common.hpp"
 #include "direct_kernels.hpp"
+#include "xy_kernels.hpp"
 #include "chain_kernels.hpp"
 #include "pair_kernels.hpp"
 #include "persist_kernels.hpp"
@@ -55,6 +56,7 @@ static_assert(sizeof(PersistFactor) == 48, "plan.hpp sizes the factor table with
 #include "runtime.hpp"
 #include "pauli_launch.hpp"
 #include "direct_launch.hpp"
+#include "xy_launch.hpp"
 #include "chain_launch.hpp"
 #include "pair_launch.hpp"
 #include "shots_launch.hpp"
@@ -102,7 +104,10 @@ void describe_kernels(const Runtime& rt, const RydProblem* p, bool backward, Ryd
                               chain_geom(rt).lt == kTileBits ? lgt : 10, b(cplx), b(bwd != 0), b(fast), b(res));
         }
     } else if (info->kernel_family == 2) {
-        if (direct_global_ok(rt)) {
+        if (pl.xy_mode) {
+            std::snprintf(info->kernel_fwd, sizeof(info->kernel_fwd), "k_factor_xy");
+            if (backward) std::snprintf(info->kernel_bwd, sizeof(info->kernel_bwd), "k_factor_bwd_xy");
+        } else if (direct_global_ok(rt)) {
             std::snprintf(info->kernel_fwd, sizeof(info->kernel_fwd), "k_factor_direct_global<%d,%s>", pl.N, b(pl.N <= 13));
             if (backward) std::snprintf(info->kernel_bwd, sizeof(info->kernel_bwd), "k_factor_bwd_direct_global<%d,%s>", pl.N, b(pl.N <= 13));
         } else {
@@ -424,7 +429,7 @@ int scatter_gradients(const BackwardCtx& c, void* g_amp, double* g_det, double* 
                            pl.rank_first);
         LAUNCH_CHECK();
     }
-    return RYDIFF_OK;
+    return xy_contract(c.rt, c.p->g_xy, stream);  // (the exchange gradient: its replicas -> g_xy)
 }
 
 }  // namespace
@@ -551,6 +556,10 @@ int rydiff_backward(const RydProblem* p, const RydPlanInfo* info, const void* st
     if (rc) return rc;
     const Plan& pl = rt.pl;
     if (!states && !pl.tape_mode) return fail(RYDIFF_EINVAL, "backward needs the trajectory: pass states or use the workspace tape");
+    if (pl.xy_mode && p->g_xy && pl.N > 1) {  // dL/dJ: replicas in the workspace, zeroed here, contracted by scatter_gradients
+        rt.xy_ge = reinterpret_cast<double*>(static_cast<char*>(workspace) + pl.off_xy_ge);
+        HIP_TRY(hipMemsetAsync(rt.xy_ge, 0, size_t(kXyReplicas) * (pl.N * (pl.N - 1) / 2) * sizeof(double), stream));
+    }
     BackwardCtx c{{rt, p, static_cast<char*>(workspace), stream, size_t(pl.B) * pl.dim}};
     // the full workspace tape (written by a forward call with need_tape = 2) is preferred over `states`
     c.tape = (pl.tape_mode >= 2 || !states) ? reinterpret_cast<const double2*>(c.ws + pl.off_tape) : static_cast<const double2*>(states);
@@ -778,6 +787,7 @@ int rydiff_apply_factor(const RydProblem* p, const double* c_amp_reim, const dou
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (!p) return fail(RYDIFF_EINVAL, "null problem");
     if (!x || !y || !workspace || !gamma_reim || !beta_reim) return fail(RYDIFF_EINVAL, "null buffer");
+    if (p->xy_mode != 0) return fail(RYDIFF_ENOTIMPL, "rydiff_apply_factor: not implemented with the XY exchange (xy_mode != 0)");
     if ((p->n_amp_terms > 0 && !c_amp_reim) || (p->n_det_terms > 0 && !c_det))
         return fail(RYDIFF_EINVAL, "missing coefficient values (c_amp_reim / c_det) for the problem's terms");
     if (n_remote < 0 || n_remote > kMaxRemote || (n_remote > 0 && (!remote || !remote_coef_reim)))

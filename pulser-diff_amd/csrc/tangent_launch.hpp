@@ -11,6 +11,8 @@ int tangent_validate(const RydProblem* p, const RydPlanInfo* info, int n_dir, in
     if (n_dir < 1 || n_dir > RYDIFF_MAX_TANGENTS)
         return fail(RYDIFF_EINVAL, "n_dir must be in [1, " + std::to_string(RYDIFF_MAX_TANGENTS) + "], got " + std::to_string(n_dir));
     if (!info) return fail(RYDIFF_EINVAL, "the tangent sweep needs the plan of rydiff_plan(p, 0, 0, ...): null info");
+    if (p->xy_mode < 0 || p->xy_mode > 2) return fail(RYDIFF_EINVAL, "xy_mode must be 0 (none), 1 (Hermitian exchange) or 2 (one-directional)");
+    if (p->xy_mode != 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented with the XY exchange (xy_mode != 0)");
     if (p->shard_bits > 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented for state-sharded runs (shard_bits > 0)");
     if (flags & ~(RYDIFF_TANGENT_PAIR_TERMS | RYDIFF_TANGENT_DENSITY_MATRIX | RYDIFF_TANGENT_RDMS | RYDIFF_TANGENT_MOMENTS))
         return fail(RYDIFF_EINVAL, "RydTangent.flags: unknown bits " + std::to_string(flags));

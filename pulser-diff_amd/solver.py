@@ -87,6 +87,9 @@ class ProblemSpec:
     # occupation correlations (RydProblem.bit_moments): the moments S, B_q, B_qr of |psi|^2 over the index bits, 1 + N + N(N-1)/2 rows
     # behind the reduced-density-matrix rows of `expect` (split_moments takes them off the end); kets only
     moments: bool = False
+    # XY exchange as a term of its own (RydProblem.xy_mode): 0 none | 1 Hermitian | 2 one-directional, as the reference writes it; the
+    # couplings J_ij are the `xy_pairs` input of ``evolve`` (N(N-1)/2 values in the order of u_pairs; they take part in autograd)
+    xy_mode: int = 0
 
     def moment_rows(self) -> int:
         """Rows of `expect` the occupation correlations take: 1 + N + N(N-1)/2, or 0."""
@@ -164,12 +167,12 @@ class _Call:
     """Keeps the ctypes structures and every buffer they point to alive for the duration of a native call."""
 
     def __init__(self, spec: ProblemSpec, amp: Tensor, det: Tensor, u_pairs: Tensor, tsave_host: np.ndarray,
-                 batch: int, obs: Optional[Tensor], real_amp_grad: bool = False):
+                 batch: int, obs: Optional[Tensor], real_amp_grad: bool = False, xy_pairs: Optional[Tensor] = None):
         self.spec = spec
         self.amp_masks = np.asarray(spec.amp_masks, dtype=np.uint32)
         self.det_masks = np.asarray(spec.det_masks, dtype=np.uint32)
         self.tsave = np.ascontiguousarray(tsave_host, dtype=np.float64)
-        self.tensors = (amp, det, u_pairs, obs)
+        self.tensors = (amp, det, u_pairs, obs, xy_pairs)
         p = _native.RydProblem()
         p.n_qubits = spec.n_qubits
         p.batch = batch
@@ -232,6 +235,8 @@ class _Call:
             p.n_rdms = len(self.rdm_masks)
             p.rdm_masks = self.rdm_masks.ctypes.data
         p.bit_moments = int(spec.moments)
+        p.xy_mode = int(spec.xy_mode)
+        p.xy_pairs = xy_pairs.data_ptr() if (spec.xy_mode and xy_pairs is not None and xy_pairs.numel()) else None
         self.dm_buffers = None
         if spec.dm is not None:
             dm = spec.dm
@@ -304,7 +309,7 @@ def _check_overlaps(spec: ProblemSpec, batch: int, device: Optional[torch.device
 
 
 def _check_shapes(spec: ProblemSpec, amp: Tensor, det: Tensor, u_pairs: Tensor, obs: Optional[Tensor], batch: int,
-                  device: Optional[torch.device] = None) -> None:
+                  device: Optional[torch.device] = None, xy_pairs: Optional[Tensor] = None) -> None:
     """The C ABI sees raw pointers only: every buffer is checked against the spec here, so that a mismatch is a ValueError and
     never an out-of-bounds device read."""
     ka, kd, n, nq = len(spec.amp_masks), len(spec.det_masks), spec.n_samples, spec.n_qubits
@@ -324,6 +329,16 @@ def _check_shapes(spec: ProblemSpec, amp: Tensor, det: Tensor, u_pairs: Tensor, 
     n_pairs = nq * (nq - 1) // 2
     if u_pairs.numel() != n_pairs:
         raise ValueError(f"u_pairs must hold N(N-1)/2 = {n_pairs} values, got {u_pairs.numel()}")
+    if spec.xy_mode not in (0, 1, 2):
+        raise ValueError(f"ProblemSpec.xy_mode must be 0 (none), 1 (Hermitian exchange) or 2 (one-directional), got {spec.xy_mode}")
+    if spec.xy_mode and xy_pairs is None:
+        raise ValueError("ProblemSpec.xy_mode is set: evolve needs the couplings xy_pairs")
+    if not spec.xy_mode and xy_pairs is not None:
+        raise ValueError("xy_pairs given without ProblemSpec.xy_mode")
+    if xy_pairs is not None and xy_pairs.numel() != n_pairs:
+        raise ValueError(f"xy_pairs must hold N(N-1)/2 = {n_pairs} values, got {xy_pairs.numel()}")
+    if xy_pairs is not None and device is not None and xy_pairs.device != torch.device(device):
+        raise ValueError(f"xy_pairs must live on the device of the states ({device}), got {xy_pairs.device}")
     if obs is not None and obs.numel() and (obs.ndim != 2 or obs.shape[1] != 2 ** nq):
         raise ValueError(f"obs_diag must have shape (n_obs, {2 ** nq}), got {tuple(obs.shape)}")
     spec.packed_pauli()  # raises ValueError on a mask bit at or above N, inconsistent counts, too many strings
@@ -392,10 +407,11 @@ class _Prepared(NamedTuple):
     dim: int
     n_t: int
     call: _Call
+    xy: Optional[Tensor] = None
 
 
 def _prepare(amp: Tensor, det: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Tensor, spec: ProblemSpec, obs: Optional[Tensor],
-             real_amp_grad: bool = False) -> _Prepared:
+             real_amp_grad: bool = False, xy_pairs: Optional[Tensor] = None) -> _Prepared:
     """What every entry point does first: the inputs must be on the GPU; detached, contiguous copies in the library's dtypes; their
     shapes against the spec; the ctypes problem."""
     for t, name in ((amp, "amp_tables"), (det, "det_tables"), (u_pairs, "u_pairs"), (psi0, "psi0")):
@@ -405,28 +421,32 @@ def _prepare(amp: Tensor, det: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Ten
     u_c = u_pairs.detach().to(torch.float64).contiguous()
     psi_c = psi0.detach().to(torch.complex128).contiguous()
     obs_c = None if obs is None else obs.detach().to(torch.float64).contiguous()
+    xy_c = None if xy_pairs is None else xy_pairs.detach().to(torch.float64).contiguous()
     ts_host = tsave.detach().to("cpu", torch.float64).numpy()
     if psi_c.ndim != 2:
         raise ValueError(f"psi0 must be (batch, 2^N), got shape {tuple(psi_c.shape)}")
     batch, dim = psi_c.shape
     if dim != 2 ** spec.n_qubits:
         raise ValueError(f"Incompatible shape of initial state.Expected {2 ** spec.n_qubits}, got {dim}.")
-    _check_shapes(spec, amp_c, det_c, u_c, obs_c, batch, psi0.device)
-    call = _Call(spec, amp_c, det_c, u_c, ts_host, batch, obs_c, real_amp_grad=real_amp_grad)
-    return _Prepared(amp_c, det_c, u_c, psi_c, obs_c, ts_host, batch, dim, len(ts_host), call)
+    _check_shapes(spec, amp_c, det_c, u_c, obs_c, batch, psi0.device, xy_c)
+    call = _Call(spec, amp_c, det_c, u_c, ts_host, batch, obs_c, real_amp_grad=real_amp_grad, xy_pairs=xy_c)
+    return _Prepared(amp_c, det_c, u_c, psi_c, obs_c, ts_host, batch, dim, len(ts_host), call, xy_c)
 
 
 class _RydbergEvolve(torch.autograd.Function):
-    """states, expect = evolve(amp_tables, det_tables, u_pairs, tsave, psi0; obs_diag, spec)."""
+    """states, expect = evolve(amp_tables, det_tables, u_pairs, tsave, psi0; obs_diag, spec; xy_pairs)."""
 
     @staticmethod
     def forward(ctx, amp: Tensor, det: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Tensor,
-                obs: Optional[Tensor], spec: ProblemSpec):
+                obs: Optional[Tensor], spec: ProblemSpec, xy_pairs: Optional[Tensor] = None):
         L = _native.lib()
         dev = psi0.device
         # (real_amp_grad only matters to the adjoint launches; set here as well so that the plan's kernel_bwd names what will run)
-        amp_c, det_c, u_c, psi_c, obs_c, ts_host, batch, dim, n_t, call = _prepare(amp, det, u_pairs, tsave, psi0, spec, obs,
-                                                                                   real_amp_grad=not amp.is_complex())
+        if xy_pairs is not None:
+            _require_cuda(xy_pairs, "xy_pairs")
+        amp_c, det_c, u_c, psi_c, obs_c, ts_host, batch, dim, n_t, call, xy_c = _prepare(amp, det, u_pairs, tsave, psi0, spec, obs,
+                                                                                         real_amp_grad=not amp.is_complex(),
+                                                                                         xy_pairs=xy_pairs)
         # the kernel variant this call resolved to (spec field, else the CALLING thread's default): the backward pass runs on the
         # autograd engine's device thread, where that thread-local default is not visible
         ctx.kernel_variant = int(call.problem.kernel_variant)
@@ -440,7 +460,7 @@ class _RydbergEvolve(torch.autograd.Function):
                 shot_out = torch.empty(shot_u.shape, dtype=torch.int32, device=dev)
             call.set_shots(shot_times, shot_u, shot_out)
             ctx.shot_buffers = call.shot_buffers
-        needs_grad = any(ctx.needs_input_grad[:5])
+        needs_grad = any(ctx.needs_input_grad[:5]) or ctx.needs_input_grad[7]
         need_tape = int(bool(needs_grad and not spec.store_states))
         with torch.cuda.device(dev):
             stream = _stream_ptr(dev)
@@ -513,6 +533,8 @@ class _RydbergEvolve(torch.autograd.Function):
         ctx.tsave_host = ts_host
         ctx.tsave_meta = (tsave.device, tsave.dtype)
         ctx.in_dtypes = (amp.dtype, det.dtype, u_pairs.dtype, psi0.dtype)
+        ctx.xy = xy_c  # (a constant of the backward pass, like the masks: not an output, kept on the context)
+        ctx.xy_dtype = None if xy_pairs is None else xy_pairs.dtype
         ctx.need_tape = need_tape
         ctx.tape_steps = int(call.problem.tape_steps)
         ctx.keep_tape = True  # retain_graph=True callers may run backward again
@@ -540,7 +562,8 @@ class _RydbergEvolve(torch.autograd.Function):
         dev = psi_c.device
         batch, dim = psi_c.shape
         obs = obs_c if ctx.has_obs else None
-        call = _Call(spec, amp_c, det_c, u_c, ctx.tsave_host, batch, obs, real_amp_grad=not ctx.in_dtypes[0].is_complex)
+        call = _Call(spec, amp_c, det_c, u_c, ctx.tsave_host, batch, obs, real_amp_grad=not ctx.in_dtypes[0].is_complex,
+                     xy_pairs=ctx.xy)
         call.problem.kernel_variant = ctx.kernel_variant  # same kernel family as the forward pass (see forward)
         call.problem.tape_steps = ctx.tape_steps
         if ctx.shot_buffers is not None:  # ignored by the adjoint sweep, but the counts are part of the workspace layout
@@ -559,6 +582,8 @@ class _RydbergEvolve(torch.autograd.Function):
             g_u = torch.empty_like(u_c) if need[2] and u_c.numel() else None
             g_ts = torch.empty(len(ctx.tsave_host), dtype=torch.float64, device=dev) if need[3] else None
             g_psi = torch.empty_like(psi_c) if need[4] else None
+            g_xy = torch.empty_like(ctx.xy) if (need[7] and ctx.xy is not None and ctx.xy.numel()) else None
+            call.problem.g_xy = None if g_xy is None else g_xy.data_ptr()
             info = ctx.info
             if ctx.need_tape:
                 workspace = ctx.tape_workspace  # sized for forward + backward by the forward call
@@ -584,7 +609,9 @@ class _RydbergEvolve(torch.autograd.Function):
             g_ts = g_ts.to(ts_dev, ts_dt)
         if g_psi is not None:
             g_psi = g_psi.to(p_dt)
-        return g_amp, g_det, g_u, g_ts, g_psi, None, None
+        if g_xy is not None:
+            g_xy = g_xy.to(ctx.xy_dtype)
+        return g_amp, g_det, g_u, g_ts, g_psi, None, None, g_xy
 
 
 @dataclass
@@ -660,11 +687,12 @@ def frame_factor(n_sub: int, phi: float) -> Tensor:
 
 
 def evolve(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Tensor,
-           spec: ProblemSpec, obs_diag: Optional[Tensor] = None) -> tuple[Tensor, Tensor]:
+           spec: ProblemSpec, obs_diag: Optional[Tensor] = None, xy_pairs: Optional[Tensor] = None) -> tuple[Tensor, Tensor]:
     """Low-level entry: psi0 is (B, dim); returns states (n_t, B, dim) and expect (n_obs + n_pauli + 2 n_overlaps, n_t, B)
     (``split_expect`` takes the overlap rows of ``spec.overlaps`` out as complex numbers).  ``spec.shots`` (a ``ShotRequest``)
-    receives its measurement shots as a by-product; the return value does not change."""
-    return _RydbergEvolve.apply(amp_tables, det_tables, u_pairs, tsave, psi0, obs_diag, spec)
+    receives its measurement shots as a by-product; the return value does not change.  ``xy_pairs`` (with ``spec.xy_mode``): the
+    N(N-1)/2 exchange couplings J_ij in the order of ``u_pairs``, a device tensor that takes part in autograd (``g_xy``)."""
+    return _RydbergEvolve.apply(amp_tables, det_tables, u_pairs, tsave, psi0, obs_diag, spec, xy_pairs)
 
 
 def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverType.DP5_SE,
@@ -749,7 +777,8 @@ def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverTyp
             targets = targets * rot[None, None, :]
     if targets is not None:
         spec.overlaps = targets.contiguous()
-    states, expect = evolve(amp_tables, problem.det_tables, problem.u_pairs, tsave, psi_bd, spec, obs_diag)
+    states, expect = evolve(amp_tables, problem.det_tables, problem.u_pairs, tsave, psi_bd, spec, obs_diag,
+                            xy_pairs=problem.xy_pairs if spec.xy_mode else None)
     if rot is not None and states.numel():
         states = states * rot.conj()[None, None, :]
     if embed is not None and states.numel():
@@ -860,6 +889,9 @@ def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsav
                                   "flags has _native.TANGENT_MOMENTS (kets only); or request them from evolve")
     if spec.shots is not None or (spec.dm is not None and spec.dm.shots):
         raise NotImplementedError("evolve_tangent draws no measurement shots (rydiff_forward_tangent: RYDIFF_ENOTIMPL); request them from evolve")
+    if spec.xy_mode:
+        raise NotImplementedError("evolve_tangent takes no XY exchange term (rydiff_forward_tangent: RYDIFF_ENOTIMPL with xy_mode != 0); "
+                                  "differentiate evolve, or run the dense pair-term route with _native.TANGENT_PAIR_TERMS")
     L = _native.lib()
     dev = psi0.device
     n_dir, pre, rows = _sweep_prepare("evolve_tangent", amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag,
@@ -942,6 +974,9 @@ def _evolve_gram(fisher: bool, amp_tables, det_tables, u_pairs, tsave, psi0, spe
                                   "flags has _native.TANGENT_MOMENTS; or request them from evolve")
     if spec.shots is not None:
         raise NotImplementedError(f"{name} draws no measurement shots ({native}: RYDIFF_ENOTIMPL); request them from evolve")
+    if spec.xy_mode:
+        raise NotImplementedError(f"{name} takes no XY exchange term ({native}: RYDIFF_ENOTIMPL with xy_mode != 0); "
+                                  "run the dense pair-term route with _native.TANGENT_PAIR_TERMS")
     L = _native.lib()
     dev = psi0.device
     n_dir, pre, rows = _sweep_prepare(name, amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag,
