@@ -227,8 +227,9 @@ typedef struct RydProblem {
      * g_xy is overwritten, and two calls agree up to the rounding of the order in which the atomics land.
      * RYDIFF_EINVAL: xy_mode outside 0..2; xy_pairs == NULL with xy_mode != 0 and N > 1.  RYDIFF_ENOTIMPL, before anything touches a
      * device: xy_mode != 0 together with n_pair_terms > 0, shard_bits > 0, dm_atoms > 0, conditioned or ones-counting terms, a
-     * kernel_variant other than 0, 1, 9, and in rydiff_forward_tangent / rydiff_forward_geometry / rydiff_forward_fisher /
-     * rydiff_apply_factor.  Follow-ups: the tangent sweep and the one-launch sweeps up to 12 qubits.
+     * kernel_variant other than 0, 1, 9, in rydiff_apply_factor, and in rydiff_forward_tangent / rydiff_forward_geometry /
+     * rydiff_forward_fisher unless RydTangent.flags has RYDIFF_TANGENT_XY (the tangent sweep with the exchange stencil; the tangents of
+     * xy_pairs are RydTangent.d_xy).  Follow-up: the one-launch sweeps up to 12 qubits.
      * xy_mode = 0: the other two fields are ignored and nothing changes.  (The fields sit in front of dp5_piece_refine: every later
      * block keeps its neighbours, and the Pauli block stays the tail of the struct.) */
     int32_t xy_mode;          /* 0: none; 1: Hermitian exchange; 2: one-directional, as the reference writes it */
@@ -523,6 +524,8 @@ typedef struct RydTangent {
     const double* d_u;      /* DEVICE float64    [n_dir][N(N-1)/2] or NULL */
     const void*   d_psi0;   /* DEVICE complex128 [n_dir][B][2^N] or NULL */
     int32_t flags;          /* 0, or RYDIFF_TANGENT_* ored: what the caller asks the sweep to take beyond plain Ising kets */
+    const double* d_xy;     /* DEVICE float64    [n_dir][N(N-1)/2] or NULL: tangents of xy_pairs (RYDIFF_TANGENT_XY); RYDIFF_EINVAL when
+                             * given with xy_mode = 0.  A valid tangent input on its own.  (Last: the fields before it keep their offsets.) */
 } RydTangent;
 /* Without its flag a problem with dense pair terms / a density-matrix register / reduced density matrices / bit moments is
  * RYDIFF_ENOTIMPL, as before the sweep took them. */
@@ -531,6 +534,8 @@ typedef struct RydTangent {
 #define RYDIFF_TANGENT_RDMS 4            /* n_rdms > 0: the RDM block of rydiff_forward joins expect_out and dexpect_out */
 #define RYDIFF_TANGENT_MOMENTS 8         /* bit_moments = 1 (kets): the Moments block of rydiff_forward joins expect_out and dexpect_out;
                                           * RYDIFF_EINVAL with bit_moments = 0 */
+#define RYDIFF_TANGENT_XY 16             /* xy_mode != 0: the exchange stencil rides in the pass (k_factor_tangent<D, false, true>) and its
+                                          * couplings have tangents, RydTangent.d_xy; RYDIFF_EINVAL with xy_mode = 0 */
 
 /* sizeof(RydTangent) as this library was compiled (see rydiff_sizeof_problem). */
 size_t rydiff_sizeof_tangent(void);
@@ -572,9 +577,15 @@ size_t rydiff_tangent_workspace_bytes_flags(const RydProblem* p, const RydPlanIn
  * the reduced density matrices of a ket (n_rdms > 0) get values and tangents (one k_rdm_tangent launch per RDM and save point); with
  * RYDIFF_TANGENT_MOMENTS the bit moments of a ket (bit_moments = 1) get values and tangents (one k_moments_tangent launch per save
  * point over all directions, beyond 12 qubits followed by k_moments_finish).  The flags combine.
+ * With RYDIFF_TANGENT_XY a problem with the XY exchange (xy_mode != 0) is taken, on the forward plan (whose spectral interval already
+ * holds sum |J|): the stencil of xy_kernels.hpp rides in the factor pass over the state and all tangent states,
+ *   y = (gamma + beta (H + X(J))) x,   dy_d = (gamma + beta (H + X(J))) dx_d + beta (dH_d + X(dJ_d)) x,
+ * with dJ_d = tangent->d_xy[d] (NULL: zero).  All ket rows, RYDIFF_TANGENT_RDMS / _MOMENTS, batches and coeff_batch as for Ising kets.
+ * xy_mode != 0 without the flag: RYDIFF_ENOTIMPL; the flag or a non-NULL d_xy with xy_mode = 0: RYDIFF_EINVAL.  What the exchange
+ * is refused with in rydiff_forward stays refused: pair terms together with it, sharding, dm_atoms > 0, conditioned terms.
  * Not implemented (RYDIFF_ENOTIMPL): pair terms / dm_atoms > 0 / n_rdms > 0 / bit_moments without their flag, state-sharded runs,
  * conditioned / ones-counting terms, shots, partial traces of a density matrix (n_dm_rdms > 0), bit_moments with dm_atoms > 0 whatever
- * the flags.  RYDIFF_EINVAL: flag bits from 16 up, and RYDIFF_TANGENT_MOMENTS on a problem with bit_moments = 0 (the flag asks for a
+ * the flags.  RYDIFF_EINVAL: flag bits from 32 up, and RYDIFF_TANGENT_MOMENTS on a problem with bit_moments = 0 (the flag asks for a
  * block the problem does not have; callers that predate it and probe bit 8 as an unknown one keep their answer).  Every argument is validated
  * before anything touches a device. */
 int rydiff_forward_tangent(const RydProblem* p, const RydPlanInfo* info, const RydTangent* tangent, const void* psi0,

@@ -37,6 +37,8 @@ TANGENT_DENSITY_MATRIX = 2  # RYDIFF_TANGENT_DENSITY_MATRIX: take a density-matr
 TANGENT_RDMS = 4            # RYDIFF_TANGENT_RDMS: take the reduced density matrices of a ket (n_rdms > 0), values and tangents
 TANGENT_MOMENTS = 8         # RYDIFF_TANGENT_MOMENTS: take the occupation correlations of a ket (bit_moments = 1), values and tangents;
                             # RYDIFF_EINVAL on a problem without them
+TANGENT_XY = 16             # RYDIFF_TANGENT_XY: take the native XY exchange (xy_mode != 0) and the tangents of its couplings (d_xy);
+                            # RYDIFF_EINVAL on a problem without the exchange
 MAX_DM_ATOMS = 12  # atoms of a density-matrix register (RydProblem.dm_atoms)
 MAX_DM_DIAG = 64  # diagonal observables of a density-matrix register
 XY_NONE, XY_HERMITIAN, XY_ONE_DIRECTIONAL = 0, 1, 2  # RydProblem.xy_mode
@@ -151,6 +153,7 @@ class RydTangent(ctypes.Structure):
         ("d_u", ctypes.c_void_p),
         ("d_psi0", ctypes.c_void_p),
         ("flags", ctypes.c_int32),
+        ("d_xy", ctypes.c_void_p),
     ]
 
 

@@ -193,7 +193,10 @@ class TorchEmulator:
             reference assembles it (one-directional, non-Hermitian generator; a warning is issued once).
         xy_native: XY mode only (extension): True = the exchange runs as the library's native exchange term (any register size,
             gradients of the geometry); False = as dense pair terms (at most 8 atoms); None = automatic: native past 8 atoms or when
-            the coordinates or distances carry a gradient.
+            the coordinates or distances carry a gradient.  Only True also puts the all-times entry points (``run_sensitivities``,
+            ``run_rdm_sensitivities``, ``run_occupation_sensitivities``, ``run_quantum_fisher``, ``run_classical_fisher``) on the
+            native term: the tangent sweep with the exchange stencil, any register size, ``dist_grad=True`` and coordinates as
+            directions.  With None / False they borrow the dense pair terms as before (8 atoms, no ``dist_grad``, no Fisher routes).
     """
 
     def __init__(self, sampled_seq, register, device, sampling_rate: float = 1.0, config: Optional[SimConfig] = None,
@@ -423,9 +426,25 @@ class TorchEmulator:
             self._hamiltonian._xy_dist_grad = True
             self._hamiltonian._rebuild_xy_pairs()
 
-    def _dense_xy_for(self, what: str, dist_grad: bool) -> None:
-        """XY mode: `what` runs on the dense pair terms (constants, at most 8 atoms), not on the native exchange term."""
+    def _xy_native_sweep(self) -> bool:
+        """XY mode with ``xy_native=True``: the all-times entry points run the tangent sweep on the native exchange term (any
+        register size, couplings with tangents of their own).  None / False: they borrow the dense pair terms as they always have."""
+        ham = self._hamiltonian
+        return ham._interaction == "XY" and ham._xy_native is True
+
+    def _xy_sweep_inputs(self, spec, *d_xy) -> dict:
+        """The exchange's keyword arguments of the solver's entry points on the native route (nothing off it): the couplings and,
+        for the sweeps, which hand in `d_xy`, their tangents."""
+        if not spec.xy_mode:
+            return {}
+        return dict(xy_pairs=self._hamiltonian.xy_pairs, **({"d_xy": d_xy[0]} if d_xy else {}))
+
+    def _dense_xy_for(self, what: str, dist_grad: bool, native_ok: bool = False) -> None:
+        """XY mode: `what` runs on the dense pair terms (constants, at most 8 atoms), not on the native exchange term — unless the
+        emulator was built with ``xy_native=True`` and `what` has a native sweep (`native_ok`)."""
         if self._hamiltonian._interaction != "XY":
+            return
+        if native_ok and self._xy_native_sweep():
             return
         if dist_grad:
             raise NotImplementedError(f"dist_grad is not available in the XY mode for {what}: it runs on the dense pair terms, whose "
@@ -613,19 +632,23 @@ class TorchEmulator:
         return self._run_noisy(psi0, solver, options, reps, bad_atom_configs, meas_errors, native_shots=native_shots)
 
     # ---- sensitivities at every evaluation time (extension) ---------------------------------------------------
-    def _table_tangents(self, x: list) -> tuple:
-        """d(amp_tables, det_tables, u_pairs) / d(every scalar entry of every tensor in x), direction-major, through the host-side
+    def _table_tangents(self, x: list, with_xy: bool = False) -> tuple:
+        """d(amp_tables, det_tables, u_pairs) / d(every scalar entry of every tensor in x) — with ``with_xy`` a fourth entry, the
+        tangent of the couplings ``Hamiltonian.xy_pairs`` of the native XY exchange (None off that route) —, direction-major, through the host-side
         torch graph tables(x) by the double-backward trick: the VJP g(w) = J^T w with a dummy cotangent w under create_graph=True is
         linear in w, so the gradient of its entry j w.r.t. w is column j of J — the table tangent of that scalar.  Outputs that do
         not require grad are skipped (None: zero tangent); the complex table goes through view_as_real."""
         ham = self._hamiltonian
         outs = {"amp": torch.view_as_real(ham.amp_tables) if ham.amp_tables.numel() else ham.amp_tables.real,
                 "det": ham.det_tables, "u": ham.u_pairs}
+        if with_xy and getattr(ham, "xy_mode", 0):
+            outs["xy"] = ham.xy_pairs  # (on the compute device like the tables, where the sweep reads its tangent)
         live = {k: v for k, v in outs.items() if v.requires_grad and v.numel()}
         n_dir = sum(int(t.numel()) for t in x)
         tangents = {k: None for k in outs}
+        pick = lambda: (tangents["amp"], tangents["det"], tangents["u"]) + ((tangents.get("xy"),) if with_xy else ())  # noqa: E731
         if not live or n_dir == 0:
-            return tangents["amp"], tangents["det"], tangents["u"]
+            return pick()
         dummies = {k: torch.zeros_like(v, requires_grad=True) for k, v in live.items()}
         vjp = torch.autograd.grad(list(live.values()), x, grad_outputs=list(dummies.values()), create_graph=True, allow_unused=True)
         cols = {k: [] for k in live}
@@ -639,7 +662,7 @@ class TorchEmulator:
         for k in live:
             stacked = torch.stack(cols[k])
             tangents[k] = torch.view_as_complex(stacked.contiguous()) if k == "amp" else stacked
-        return tangents["amp"], tangents["det"], tangents["u"]
+        return pick()
 
     def _no_resampling(self) -> bool:
         """The noise asks for no averaging over several runs of resampled tables (backend.py:531-569; a random state preparation,
@@ -734,7 +757,9 @@ class TorchEmulator:
         basis run the loop of one-hot reverse sweeps, as they always have.  ``"tangent"`` asks for the sweep: master-equation runs
         (``lindblad.mesolve_tangent``: vec(rho) and its tangents on the doubled register, the dissipator and the exchange as constant
         pair terms) and XY runs take it too; the three-level basis, which the sweep does not take, raises.  ``"adjoint-loop"`` forces
-        the loop anywhere (the A/B partner of the sweep).  ``Sensitivities.route`` says which ran.  Derivatives w.r.t. the evaluation
+        the loop anywhere (the A/B partner of the sweep).  An XY emulator built with ``xy_native=True`` takes the sweep on the native
+        exchange term by default (``RYDIFF_TANGENT_XY``: coordinates and distances reach the couplings' tangents ``d_xy``), and its
+        ``"adjoint-loop"`` loops over native reverse sweeps.  ``Sensitivities.route`` says which ran.  Derivatives w.r.t. the evaluation
         times come from ``deriv_time``."""
         if route not in (None, "tangent", "adjoint-loop"):
             raise ValueError(f'route must be None, "tangent" or "adjoint-loop", got {route!r}')
@@ -762,7 +787,7 @@ class TorchEmulator:
                                 "(master-equation runs: StateOverlap and Purity too)")
             if tuple(obs.shape) != (full, full):
                 raise ValueError(f"Incompatible shape of observable.Expected {(full, full)}, got {tuple(obs.shape)}.")
-        self._dense_xy_for("run_sensitivities", dist_grad)
+        self._dense_xy_for("run_sensitivities", dist_grad, native_ok=solver != SolverType.DP5_ME)
         if dist_grad:
             self._enable_dist_grad()
         times = self._eval_times_array.detach()
@@ -805,21 +830,24 @@ class TorchEmulator:
             return Sensitivities(expect.sum(dim=-1), self._per_tensor(dexpect.sum(dim=-1), x), "tangent", times)
 
         obs_diag, pauli_objs, _, rows = self._pack_row_observables(observables)
-        d_amp, d_det, d_u = self._table_tangents(x)
+        d_amp, d_det, d_u, d_xy = self._table_tangents(x, with_xy=True)
         n_dir = sum(int(t.numel()) for t in x)
         psi0 = self.initial_state
         psi_bd = psi0.reshape(psi0.shape[0], -1).transpose(0, 1).to(dev)
         spec = ham.problem_spec(solver=solver, tol=tolerance_from_options(dict(options)), store_states=False)
         if pauli_objs:
             spec.pauli = pauli_objs
-        if d_amp is None and d_det is None and d_u is None:  # nothing in x reaches the tables: zero derivatives, values from a plain run
+        xy_in = self._xy_sweep_inputs(spec, d_xy)
+        if d_amp is None and d_det is None and d_u is None and d_xy is None:  # nothing in x reaches the tables: zero derivatives, values from a plain run
             expect, dexpect = self._plain_run_with_zero_tangents(
-                n_dir, lambda: evolve(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, obs_diag)[1])
+                n_dir, lambda: evolve(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, obs_diag,
+                                      **self._xy_sweep_inputs(spec))[1])
         else:
             # the complex tables and the unrotated psi0: the rotating frame is a per-call device of sesolve, not of this path
             expect, dexpect = evolve_tangent(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, obs_diag,
                                              d_amp=d_amp, d_det=d_det, d_u=d_u,
-                                             flags=_native.TANGENT_PAIR_TERMS if spec.pair_terms else 0)  # (the XY exchange)
+                                             flags=_native.TANGENT_PAIR_TERMS if spec.pair_terms else 0,  # (the dense XY exchange)
+                                             **xy_in)
         values = expect.sum(dim=-1)[rows]            # (n_obs, n_t): summed over the columns of psi0 like results.expect
         dvals = dexpect.sum(dim=-1)[:, rows]         # (n_dir, n_obs, n_t)
         return Sensitivities(values, self._per_tensor(dvals, x), "tangent", times)
@@ -852,24 +880,27 @@ class TorchEmulator:
             raise ValueError(f"run_rdm_sensitivities takes 1 to {_native.MAX_RDMS} subsystems per call, got {len(rdm_objs)}")
         for obs in rdm_objs:
             obs.check(ham._size)
-        self._dense_xy_for("run_rdm_sensitivities", dist_grad)
+        self._dense_xy_for("run_rdm_sensitivities", dist_grad, native_ok=True)
         if dist_grad:
             self._enable_dist_grad()
         times = self._eval_times_array.detach()
-        d_amp, d_det, d_u = self._table_tangents(x)
+        d_amp, d_det, d_u, d_xy = self._table_tangents(x, with_xy=True)
         n_dir = sum(int(t.numel()) for t in x)
         psi0 = self.initial_state
         psi_bd = psi0.reshape(psi0.shape[0], -1).transpose(0, 1).to(dev)
         spec = ham.problem_spec(solver=solver, tol=tolerance_from_options(dict(options)), store_states=False)
         spec.rdms = rdm_objs
-        if d_amp is None and d_det is None and d_u is None:  # nothing in x reaches the tables: zero derivatives, values from a plain run
+        xy_in = self._xy_sweep_inputs(spec, d_xy)
+        if d_amp is None and d_det is None and d_u is None and d_xy is None:  # nothing in x reaches the tables: zero derivatives, values from a plain run
             expect, dexpect = self._plain_run_with_zero_tangents(
-                n_dir, lambda: evolve(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, None)[1])
+                n_dir, lambda: evolve(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, None,
+                                      **self._xy_sweep_inputs(spec))[1])
         else:
             # the complex tables and the unrotated psi0, as in run_sensitivities: the matrices are lab-frame ones
             expect, dexpect = evolve_tangent(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, None,
                                              d_amp=d_amp, d_det=d_det, d_u=d_u,
-                                             flags=_native.TANGENT_RDMS | (_native.TANGENT_PAIR_TERMS if spec.pair_terms else 0))
+                                             flags=_native.TANGENT_RDMS | (_native.TANGENT_PAIR_TERMS if spec.pair_terms else 0),
+                                             **xy_in)
         rho = split_observables(expect, 0, rdm_objs)[2]
         per_dir = [split_observables(dexpect[d], 0, rdm_objs)[2] for d in range(n_dir)]
         # per subsystem: (n_dir, n_t, B, 2^m, 2^m) -> one (n_t, B, 2^m, 2^m, *x_i.shape) per x_i
@@ -897,24 +928,27 @@ class TorchEmulator:
             all_basis="run_occupation_sensitivities is not available in the three-level all-basis: an atom is two qubits "
                       "there, and the native tangent sweep takes no conditioned flips / ones-counting terms.")
         ham, dev = self._hamiltonian, self._compute_device
-        self._dense_xy_for("run_occupation_sensitivities", dist_grad)
+        self._dense_xy_for("run_occupation_sensitivities", dist_grad, native_ok=True)
         if dist_grad:
             self._enable_dist_grad()
         times = self._eval_times_array.detach()
-        d_amp, d_det, d_u = self._table_tangents(x)
+        d_amp, d_det, d_u, d_xy = self._table_tangents(x, with_xy=True)
         n_dir = sum(int(t.numel()) for t in x)
         psi0 = self.initial_state
         psi_bd = psi0.reshape(psi0.shape[0], -1).transpose(0, 1).to(dev)
         spec = ham.problem_spec(solver=solver, tol=tolerance_from_options(dict(options)), store_states=False)
         spec.moments = True
-        if d_amp is None and d_det is None and d_u is None:  # nothing in x reaches the tables: zero derivatives, values from a plain run
+        xy_in = self._xy_sweep_inputs(spec, d_xy)
+        if d_amp is None and d_det is None and d_u is None and d_xy is None:  # nothing in x reaches the tables: zero derivatives, values from a plain run
             expect, dexpect = self._plain_run_with_zero_tangents(
-                n_dir, lambda: evolve(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, None)[1])
+                n_dir, lambda: evolve(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, None,
+                                      **self._xy_sweep_inputs(spec))[1])
         else:
             # the complex tables and the unrotated psi0, as in run_sensitivities (the moments are diagonal: they see no frame)
             expect, dexpect = evolve_tangent(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, None,
                                              d_amp=d_amp, d_det=d_det, d_u=d_u,
-                                             flags=_native.TANGENT_MOMENTS | (_native.TANGENT_PAIR_TERMS if spec.pair_terms else 0))
+                                             flags=_native.TANGENT_MOMENTS | (_native.TANGENT_PAIR_TERMS if spec.pair_terms else 0),
+                                             **xy_in)
         moments = split_moments(expect, ham._size)[1]
         dmom = torch.stack([split_moments(dexpect[d], ham._size)[1] for d in range(n_dir)])  # (n_dir, rows, n_t, B)
         return OccupationSensitivities(moments, self._per_tensor(dmom, x), times, 0 if ham.basis_name == "ground-rydberg" else 1)
@@ -970,7 +1004,7 @@ class TorchEmulator:
         table tangents, the sweep.  ``(gram, cgram or None, values, grads, times)``."""
         ham, dev = self._hamiltonian, self._compute_device
         sweep = evolve_fisher if fisher else (lambda *a, **k: evolve_geometry(*a, **k) + (None,))
-        if getattr(ham, "pair_terms", ()) or getattr(ham, "xy_mode", 0):
+        if (getattr(ham, "pair_terms", ()) or getattr(ham, "xy_mode", 0)) and not self._xy_native_sweep():
             if ham._size > ham.MAX_XY_QUBITS:
                 raise NotImplementedError(ham.dense_xy_limit(name))
             raise NotImplementedError(f"{name} is not available with the XY exchange: this route hands no dense pair terms "
@@ -991,7 +1025,7 @@ class TorchEmulator:
         times = self._eval_times_array.detach()
         n_t = int(times.shape[0])
         obs_diag, pauli_objs, overlap_objs, rows = self._pack_row_observables(observables, overlaps=True)
-        d_amp, d_det, d_u = self._table_tangents(x)
+        d_amp, d_det, d_u, d_xy = self._table_tangents(x, with_xy=True)
         n_dir = sum(int(t.numel()) for t in x)
         psi0 = self.initial_state
         psi_bd = psi0.reshape(psi0.shape[0], -1).transpose(0, 1).to(dev)
@@ -1001,10 +1035,11 @@ class TorchEmulator:
             spec.pauli = pauli_objs
         if overlap_objs:  # the complex tables and the unrotated psi0 (as in run_sensitivities): the targets stay in the lab frame too
             spec.overlaps = pack_overlaps(overlap_objs, int(psi_bd.shape[1]), batch, dev)
-        if d_amp is None and d_det is None and d_u is None:
+        xy_in = self._xy_sweep_inputs(spec, d_xy)  # (the native exchange of an xy_native=True emulator: the couplings and their tangents)
+        if d_amp is None and d_det is None and d_u is None and d_xy is None:
             # nothing in x reaches the tables: every tangent state is zero — <psi|psi> and the values from one sweep with one zero direction
             expect, _, g1, c1 = sweep(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, obs_diag,
-                                      d_psi0=torch.zeros((1,) + tuple(psi_bd.shape), dtype=torch.complex128, device=dev))
+                                      d_psi0=torch.zeros((1,) + tuple(psi_bd.shape), dtype=torch.complex128, device=dev), **xy_in)
             dexpect = torch.zeros((n_dir,) + tuple(expect.shape), dtype=torch.float64, device=expect.device)
             gram = torch.zeros((n_t, batch, 1 + n_dir, 1 + n_dir), dtype=torch.complex128, device=g1.device)
             gram[:, :, 0, 0] = g1[:, :, 0, 0]
@@ -1014,7 +1049,7 @@ class TorchEmulator:
                 cgram[:, :, 0, 0] = c1[:, :, 0, 0]
         else:
             expect, dexpect, gram, cgram = sweep(ham.amp_tables, ham.det_tables, ham.u_pairs, times, psi_bd, spec, obs_diag,
-                                                 d_amp=d_amp, d_det=d_det, d_u=d_u)
+                                                 d_amp=d_amp, d_det=d_det, d_u=d_u, **xy_in)
         if batch == 1:
             gram = gram[:, 0]
             cgram = cgram[:, 0] if fisher else None

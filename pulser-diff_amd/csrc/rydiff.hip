@@ -680,8 +680,9 @@ int tangent_sweep(const RydProblem* p, const RydPlanInfo* info, const RydTangent
     int rc = tangent_validate(p, info, tg->n_dir, tg->flags);  // n_dir, the plan, what the sweep does not implement
     if (rc) return rc;
     if (geometry && (rc = geometry_validate(p))) return rc;
-    if (!tg->d_amp && !tg->d_det && !tg->d_u && !tg->d_psi0)
-        return fail(RYDIFF_EINVAL, "tangent: all of d_amp, d_det, d_u, d_psi0 are NULL (nothing to differentiate)");
+    if (tg->d_xy && p->xy_mode == 0) return fail(RYDIFF_EINVAL, "tangent: d_xy given on a problem without the XY exchange (xy_mode = 0)");
+    if (!tg->d_amp && !tg->d_det && !tg->d_u && !tg->d_psi0 && !tg->d_xy)
+        return fail(RYDIFF_EINVAL, "tangent: all of d_amp, d_det, d_u, d_psi0 are NULL, and so is d_xy (nothing to differentiate)");
     if (!geometry && !dexpect_out) return fail(RYDIFF_EINVAL, "null dexpect_out");
     if (geometry && !fisher && !gram_out) return fail(RYDIFF_EINVAL, "null gram_out");
     if (fisher && !cgram_out) return fail(RYDIFF_EINVAL, "null cgram_out");
@@ -740,7 +741,7 @@ int tangent_sweep(const RydProblem* p, const RydPlanInfo* info, const RydTangent
     rc = save_point(vec[0], 0);
     if (rc) return rc;
     TangentFactorArgs fa{};
-    fill_tangent_factor(fa, rt, ws, lay, tg->d_u != nullptr);
+    fill_tangent_factor(fa, rt, ws, lay, tg->d_u != nullptr, tg->d_xy != nullptr);
     std::vector<ChainItem> chain;
     int cur = 0;
     for (int k = 0; k < pl.T; ++k) {

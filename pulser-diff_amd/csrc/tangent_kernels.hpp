@@ -12,6 +12,11 @@
 // k_factor_tangent<D, true>  the same pass with dense pair terms P (constants in every direction: M = H + P, dM_d has no pair part):
 //                         beta P on all 1 + D vectors by pair_apply_all (common.hpp) — the collapse operators of a master-equation run
 //                         on the doubled register, the XY exchange on kets.  <D, false> is the pass without them, unchanged.
+// k_factor_tangent<D, false, true>  the same pass with the XY exchange X(J) of xy_kernels.hpp (RYDIFF_TANGENT_XY), whose couplings have
+//                         tangents dJ_d of their own:  dy_d += beta (X(J) dx_d + X(dJ_d) x).  One walk of the stencil (xy_stencil_n)
+//                         over all 1 + D vectors: per pair the partner of x is loaded once and serves J x and the D products dJ_d x,
+//                         the partners of the dx_d serve J dx_d; TangentChunk<D> pairs of one row in flight together; J and dJ are
+//                         read with wave-uniform indices; beta once on each vector's whole exchange sum.
 // (the overlap rows are k_overlap_expect on dpsi_d, as it is; the density-matrix rows of a doubled register are k_dm_trace /
 // k_dm_fidelity on dpsi_d and k_dm_purity_tangent, dm_kernels.hpp).  Complex coefficients throughout, no rotating frame,
 // no conditioned flips, no sharding (refused by the C ABI).
@@ -34,6 +39,7 @@ struct TangentFactorArgs {
     int dcnt[kMaxGroups];
     uint32_t fbg[RYDIFF_MAX_QUBITS];  // the driven qubits, one word each: amplitude-index bit number | flip group << 8
     PairArgs pair;         // dense pair terms (read by the PAIR instantiations only): constants in every tangent direction
+    XyTangentArgs xyt;     // XY exchange and the tangents of its couplings (read by the XY instantiations only)
 };
 
 // flip bits whose partner loads are in flight together: CH * (1 + D) loads of 16 bytes per thread
@@ -42,7 +48,7 @@ struct TangentChunk {
     static constexpr int value = D <= 1 ? 8 : (D <= 3 ? 4 : 2);
 };
 
-template <int D, bool PAIR>
+template <int D, bool PAIR, bool XY = false>
 __global__ __launch_bounds__(256) void k_factor_tangent(TangentFactorArgs a) {
     constexpr int CH = TangentChunk<D>::value;
     const uint32_t x = blockIdx.x * 256u + threadIdx.x;
@@ -129,6 +135,29 @@ __global__ __launch_bounds__(256) void k_factor_tangent(TangentFactorArgs a) {
                 accr[1 + d] += kr * part[c][0].x - ki * part[c][0].y;
                 acci[1 + d] += kr * part[c][0].y + ki * part[c][0].x;
             }
+        }
+    }
+    if constexpr (XY) {
+        // X(J) on all 1 + D vectors and X(dJ_d) x into vector 1 + d, from the same partner loads
+        double er[1 + D], ei[1 + D];
+#pragma unroll
+        for (int v = 0; v <= D; ++v) er[v] = ei[v] = 0.0;
+        const double* __restrict__ dJ = a.xyt.dJ;
+        const int P = a.xyt.P;
+        xy_stencil_n<false, 1 + D, CH>(a.xyt.xy, xin, a.vstride, x, true, er, ei, [&](int p, const double2(&part)[1 + D]) {
+            if (dJ) {  // uniform
+#pragma unroll
+                for (int d = 0; d < D; ++d) {
+                    const double dj = dJ[d * P + p];  // wave-uniform index
+                    er[1 + d] = fma(dj, part[0].x, er[1 + d]);
+                    ei[1 + d] = fma(dj, part[0].y, ei[1 + d]);
+                }
+            }
+        });
+#pragma unroll
+        for (int v = 0; v <= D; ++v) {  // beta once, on each vector's whole exchange sum
+            accr[v] += a.br * er[v] - a.bi * ei[v];
+            acci[v] += a.br * ei[v] + a.bi * er[v];
         }
     }
 #pragma unroll

@@ -12,10 +12,15 @@ int tangent_validate(const RydProblem* p, const RydPlanInfo* info, int n_dir, in
         return fail(RYDIFF_EINVAL, "n_dir must be in [1, " + std::to_string(RYDIFF_MAX_TANGENTS) + "], got " + std::to_string(n_dir));
     if (!info) return fail(RYDIFF_EINVAL, "the tangent sweep needs the plan of rydiff_plan(p, 0, 0, ...): null info");
     if (p->xy_mode < 0 || p->xy_mode > 2) return fail(RYDIFF_EINVAL, "xy_mode must be 0 (none), 1 (Hermitian exchange) or 2 (one-directional)");
-    if (p->xy_mode != 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented with the XY exchange (xy_mode != 0)");
+    // the exchange runs only where the caller asks for it, like the pair terms below: a caller that does not know the flag keeps its refusal
+    if (p->xy_mode != 0 && !(flags & RYDIFF_TANGENT_XY))
+        return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented with the XY exchange (xy_mode != 0) unless RydTangent.flags has "
+                                     "RYDIFF_TANGENT_XY");
     if (p->shard_bits > 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented for state-sharded runs (shard_bits > 0)");
-    if (flags & ~(RYDIFF_TANGENT_PAIR_TERMS | RYDIFF_TANGENT_DENSITY_MATRIX | RYDIFF_TANGENT_RDMS | RYDIFF_TANGENT_MOMENTS))
+    if (flags & ~(RYDIFF_TANGENT_PAIR_TERMS | RYDIFF_TANGENT_DENSITY_MATRIX | RYDIFF_TANGENT_RDMS | RYDIFF_TANGENT_MOMENTS | RYDIFF_TANGENT_XY))
         return fail(RYDIFF_EINVAL, "RydTangent.flags: unknown bits " + std::to_string(flags));
+    if (p->xy_mode == 0 && (flags & RYDIFF_TANGENT_XY))  // (the flag asks for a term the problem does not have)
+        return fail(RYDIFF_EINVAL, "RydTangent.flags: RYDIFF_TANGENT_XY (16) on a problem without the XY exchange (xy_mode = 0)");
     // the moments flag is valid only on a problem that has the block: callers written before it existed probe bit 8 as an unknown one on
     // problems without bit moments and keep their RYDIFF_EINVAL
     if ((flags & RYDIFF_TANGENT_MOMENTS) && p->bit_moments == 0)
@@ -57,6 +62,7 @@ struct TangentLayout {
     size_t off_vec[2] = {0, 0};  // ping-pong: [1 + D][B][dim] amplitudes each
     size_t off_dcoef = 0;        // [D][Bc][E][NC] doubles
     size_t off_dudiag = 0;       // [D][dim] doubles
+    size_t off_dxy = 0;          // XY exchange: [D][N(N-1)/2] doubles, the tangents of the couplings (padded directions zero)
     size_t off_dmoments = 0;     // bit moments past 12 qubits: the tile records of the moment tangents, [n_dir][B][79][dim >> 12] doubles
     size_t total = 0;
     long dcoef_dstride = 0;      // doubles
@@ -83,6 +89,7 @@ TangentLayout tangent_layout(const Plan& pl, size_t base, int n_real) {
     t.off_dudiag = take(size_t(n_dir) * pl.dim * sizeof(double));
     // (only the real directions' moments are evaluated; the values' records go through the plan's own region, off_moments)
     t.off_dmoments = take((pl.moments && pl.moment_tiles() > 1) ? size_t(n_real) * pl.B * kMomEntries * pl.moment_tiles() * sizeof(double) : 0);
+    t.off_dxy = take(pl.xy_mode ? size_t(n_dir) * (pl.N * (pl.N - 1) / 2) * sizeof(double) : 0);
     t.total = off;
     return t;
 }
@@ -127,17 +134,24 @@ int tangent_tables(const Runtime& rt, const RydProblem* p, const RydTangent* tg,
         }
         if (Dp > tg->n_dir) HIP_TRY(hipMemsetAsync(dud + size_t(tg->n_dir) * pl.dim, 0, size_t(Dp - tg->n_dir) * pl.dim * sizeof(double), stream));
     }
+    if (tg->d_xy && pl.xy_mode && pl.N > 1) {  // the caller's [n_dir][P] into the sweep's [Dp][P]: a padded direction reads zeros
+        const size_t P = size_t(pl.N) * (pl.N - 1) / 2;
+        double* dxy = reinterpret_cast<double*>(ws + lay.off_dxy);
+        HIP_TRY(hipMemcpyAsync(dxy, tg->d_xy, size_t(tg->n_dir) * P * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        if (Dp > tg->n_dir) HIP_TRY(hipMemsetAsync(dxy + size_t(tg->n_dir) * P, 0, size_t(Dp - tg->n_dir) * P * sizeof(double), stream));
+    }
     return RYDIFF_OK;
 }
 
 template <int D>
 void launch_factor_tangent_n(const TangentFactorArgs& a, dim3 grid, hipStream_t stream) {
-    if (a.pair.n) hipLaunchKernelGGL((k_factor_tangent<D, true>), grid, dim3(256), 0, stream, a);
+    if (a.xyt.xy.mode) hipLaunchKernelGGL((k_factor_tangent<D, false, true>), grid, dim3(256), 0, stream, a);
+    else if (a.pair.n) hipLaunchKernelGGL((k_factor_tangent<D, true>), grid, dim3(256), 0, stream, a);
     else hipLaunchKernelGGL((k_factor_tangent<D, false>), grid, dim3(256), 0, stream, a);
 }
 
 // what every factor launch of one call shares
-void fill_tangent_factor(TangentFactorArgs& a, const Runtime& rt, char* ws, const TangentLayout& lay, bool have_du) {
+void fill_tangent_factor(TangentFactorArgs& a, const Runtime& rt, char* ws, const TangentLayout& lay, bool have_du, bool have_dxy) {
     const Plan& pl = rt.pl;
     a.vstride = size_t(pl.B) * pl.dim;
     a.udiag = reinterpret_cast<const double*>(ws + pl.off_udiag);
@@ -149,6 +163,9 @@ void fill_tangent_factor(TangentFactorArgs& a, const Runtime& rt, char* ws, cons
     a.gd = pl.gd.n;
     fill_detuning(a.dmask, a.dcnt, pl);
     a.pair = rt.parg;  // (tables uploaded by prepare)
+    a.xyt.xy = rt.xarg;
+    a.xyt.P = pl.N * (pl.N - 1) / 2;
+    a.xyt.dJ = (have_dxy && pl.xy_mode && pl.N > 1) ? reinterpret_cast<const double*>(ws + lay.off_dxy) : nullptr;
     a.nflip = 0;
     for (int q = 0; q < pl.ga.n; ++q)
         for (uint32_t m = pl.ga.amp_index_mask[q]; m; m &= m - 1) {

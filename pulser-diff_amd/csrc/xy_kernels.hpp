@@ -14,49 +14,74 @@ struct XyArgs {
     const double* J = nullptr;  // [N(N-1)/2]
 };
 
+// what the tangent sweep's factor pass adds (k_factor_tangent<D, false, true>, tangent_kernels.hpp): the tangents of the couplings
+struct XyTangentArgs {
+    XyArgs xy;
+    const double* dJ = nullptr;  // [D][P], direction outermost, padded directions zero; nullptr: no d_xy (zero)
+    int P = 0;                   // N(N-1)/2
+};
+
 constexpr int kXyRow = 8;  // partner loads of one row in flight together (16 bytes each)
 constexpr int kXyMaxPairs = RYDIFF_MAX_QUBITS * (RYDIFF_MAX_QUBITS - 1) / 2;
 
-// (er, ei) += sum_p J_p * v[partner_p(x)] over the pairs whose row x belongs to the stencil (ADJ: that of X^dagger), and
-// each(p, part) for EVERY pair in order, wave-uniformly, with part = the partner amplitude where the stencil has one and 0 elsewhere.
+// For each of the NV vectors v + w * vstride (w = 0 .. NV-1):  (er[w], ei[w]) += sum_p J_p * v_w[partner_p(x)] over the pairs whose row x
+// belongs to the stencil (ADJ: that of X^dagger), and each(p, part) for EVERY pair in order, wave-uniformly, with part[w] = the partner
+// amplitude of vector w where the stencil has one and 0 elsewhere.  ROW pairs of one row at a time: ROW * NV loads in flight.
 // x < 2^N always (dead threads pass live = false and x = 0: no loads).
-template <bool ADJ, class Each>
-__device__ __forceinline__ void xy_stencil(const XyArgs& xy, const double2* __restrict__ v, uint32_t x, bool live, double& er, double& ei,
-                                           Each&& each) {
+template <bool ADJ, int NV, int ROW, class Each>
+__device__ __forceinline__ void xy_stencil_n(const XyArgs& xy, const double2* __restrict__ v, size_t vstride, uint32_t x, bool live,
+                                             double (&er)[NV], double (&ei)[NV], Each&& each) {
     const int N = xy.N;
     int p0 = 0;
     for (int i = 0; i + 1 < N; ++i) {  // uniform
         const uint32_t mi = 1u << (N - 1 - i);
         const bool bi = (x & mi) != 0u;
         const int len = N - 1 - i;
-        for (int c0 = 0; c0 < len; c0 += kXyRow) {
-            double2 part[kXyRow];
+        for (int c0 = 0; c0 < len; c0 += ROW) {
+            double2 part[ROW][NV];
 #pragma unroll
-            for (int c = 0; c < kXyRow; ++c) {
+            for (int c = 0; c < ROW; ++c) {
                 const int jj = c0 + c;
-                part[c] = make_double2(0.0, 0.0);
+#pragma unroll
+                for (int w = 0; w < NV; ++w) part[c][w] = make_double2(0.0, 0.0);
                 if (jj < len) {  // uniform
                     const uint32_t mj = mi >> (jj + 1);
                     const bool bj = (x & mj) != 0u;
                     bool act = live && bi != bj;
                     if (xy.mode == 2) act = act && bi == ADJ;
-                    if (act) part[c] = v[x ^ mi ^ mj];
+                    if (act) {
+#pragma unroll
+                        for (int w = 0; w < NV; ++w) part[c][w] = v[size_t(w) * vstride + (x ^ mi ^ mj)];
+                    }
                 }
             }
             __builtin_amdgcn_sched_barrier(0);  // no sum of this row before all of its loads are issued
 #pragma unroll
-            for (int c = 0; c < kXyRow; ++c) {
+            for (int c = 0; c < ROW; ++c) {
                 const int jj = c0 + c;
                 if (jj < len) {  // uniform
                     const double Jv = xy.J[p0 + jj];
-                    er = fma(Jv, part[c].x, er);
-                    ei = fma(Jv, part[c].y, ei);
+#pragma unroll
+                    for (int w = 0; w < NV; ++w) {
+                        er[w] = fma(Jv, part[c][w].x, er[w]);
+                        ei[w] = fma(Jv, part[c][w].y, ei[w]);
+                    }
                     each(p0 + jj, part[c]);
                 }
             }
         }
         p0 += len;
     }
+}
+
+// one vector, kXyRow loads in flight: each(p, part) with the one partner amplitude
+template <bool ADJ, class Each>
+__device__ __forceinline__ void xy_stencil(const XyArgs& xy, const double2* __restrict__ v, uint32_t x, bool live, double& er, double& ei,
+                                           Each&& each) {
+    double r[1] = {er}, i[1] = {ei};
+    xy_stencil_n<ADJ, 1, kXyRow>(xy, v, 0, x, live, r, i, [&](int p, const double2(&part)[1]) { each(p, part[0]); });
+    er = r[0];
+    ei = i[0];
 }
 
 // c_g * (partner sum over the set bits of x) + conj(c_g) * (partner sum over the clear bits), summed over the flip groups

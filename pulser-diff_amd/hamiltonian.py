@@ -619,7 +619,8 @@ class Hamiltonian:
 
     def dense_xy_limit(self, what: str) -> str:
         return (f"The XY mode is limited to {self.MAX_XY_QUBITS} qubits for {what}: it runs on the dense pair terms (one per pair), "
-                "not on the native exchange term.")
+                "not on the native exchange term.  TorchEmulator(..., xy_native=True) runs the all-times sensitivities and the Fisher "
+                "routes on the native exchange term at any register size.")
 
     @staticmethod
     def _warn_one_directional() -> None:

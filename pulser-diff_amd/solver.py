@@ -805,24 +805,30 @@ def _tangent_take(t: Optional[Tensor], sel, shape: tuple, dtype: torch.dtype, na
     return t[sel].detach().to(dev, dtype).contiguous()
 
 
-def _tangent_buffers(sel, pre: _Prepared, d_amp, d_det, d_u, d_psi0, dev) -> tuple:
-    """(d_amp, d_det, d_u, d_psi0)[sel] for RydTangent; None: not given, or the tangent of an input this problem does not have."""
+def _tangent_buffers(sel, pre: _Prepared, d_amp, d_det, d_u, d_psi0, dev, d_xy=None) -> tuple:
+    """(d_amp, d_det, d_u, d_psi0, d_xy)[sel] for RydTangent; None: not given, or the tangent of an input this problem does not have."""
     return (_tangent_take(d_amp, sel, pre.amp.shape, torch.complex128, "d_amp", dev) if pre.amp.numel() else None,
             _tangent_take(d_det, sel, pre.det.shape, torch.float64, "d_det", dev) if pre.det.numel() else None,
             _tangent_take(d_u, sel, pre.u.shape, torch.float64, "d_u", dev) if pre.u.numel() else None,
-            _tangent_take(d_psi0, sel, pre.psi.shape, torch.complex128, "d_psi0", dev))
+            _tangent_take(d_psi0, sel, pre.psi.shape, torch.complex128, "d_psi0", dev),
+            _tangent_take(d_xy, sel, pre.xy.shape, torch.float64, "d_xy", dev) if (pre.xy is not None and pre.xy.numel()) else None)
 
 
-def _sweep_prepare(name: str, amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag, d_amp, d_det, d_u, d_psi0):
+def _sweep_prepare(name: str, amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag, d_amp, d_det, d_u, d_psi0,
+                   xy_pairs=None, d_xy=None):
     """What ``evolve_tangent`` and ``evolve_geometry`` (`name`) share behind their refusals: the number of directions, the inputs of
     the call, its row count."""
-    given = [t for t in (d_amp, d_det, d_u, d_psi0) if t is not None]
+    if d_xy is not None and xy_pairs is None:
+        raise ValueError(f"{name}: d_xy given without xy_pairs (the tangent of couplings the problem does not have)")
+    given = [t for t in (d_amp, d_det, d_u, d_psi0, d_xy) if t is not None]
     if not given:
-        raise ValueError(f"{name} needs at least one of d_amp, d_det, d_u, d_psi0")
+        raise ValueError(f"{name} needs at least one of d_amp, d_det, d_u, d_psi0" + (", d_xy" if xy_pairs is not None else ""))
     n_dir = int(given[0].shape[0])
     if n_dir < 1 or any(int(t.shape[0]) != n_dir for t in given):
         raise ValueError("d_amp, d_det, d_u, d_psi0 must agree on the number of directions (their first axis), at least one")
-    pre = _prepare(amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag)
+    if xy_pairs is not None:
+        _require_cuda(xy_pairs, "xy_pairs")
+    pre = _prepare(amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag, xy_pairs=xy_pairs)
     pre.call.problem.kernel_variant = 0  # the tangent sweep has one kernel family
     return n_dir, pre, pre.call.expect_rows()
 
@@ -839,7 +845,7 @@ def _sweep_plan(L, p, dev) -> tuple:
 def _sweep_tangent(n_dir: int, bufs: tuple, flags: int) -> "_native.RydTangent":
     tg = _native.RydTangent()
     tg.n_dir = n_dir
-    tg.d_amp, tg.d_det, tg.d_u, tg.d_psi0 = (None if b is None else b.data_ptr() for b in bufs)
+    tg.d_amp, tg.d_det, tg.d_u, tg.d_psi0, tg.d_xy = (None if b is None else b.data_ptr() for b in bufs)
     tg.flags = int(flags)
     return tg
 
@@ -858,7 +864,8 @@ def _sweep_workspace(size_fn, size_name: str, sweep, p, info, tg, workspace: Opt
 
 def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Tensor, spec: ProblemSpec,
                    obs_diag: Optional[Tensor] = None, d_amp: Optional[Tensor] = None, d_det: Optional[Tensor] = None,
-                   d_u: Optional[Tensor] = None, d_psi0: Optional[Tensor] = None, flags: int = 0) -> tuple[Tensor, Tensor]:
+                   d_u: Optional[Tensor] = None, d_psi0: Optional[Tensor] = None, flags: int = 0,
+                   xy_pairs: Optional[Tensor] = None, d_xy: Optional[Tensor] = None) -> tuple[Tensor, Tensor]:
     """Forward-mode twin of ``evolve`` (``rydiff_forward_tangent``): ONE sweep carries the state and the tangent states of up to 8
     directions through every factor and returns the observable values ``expect`` (rows, n_t, B) and their directional derivatives
     ``dexpect`` (n_dir, rows, n_t, B) at EVERY evaluation time — rows = diagonal observables, then the Pauli observables and Re / Im
@@ -877,7 +884,12 @@ def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsav
     ``_native.TANGENT_MOMENTS``: the occupation correlations of ``spec.moments`` (kets only) join the rows behind the RDM block — the
     moments ``S, B_q, B_qr`` in ``expect``, the same moments of ``2 Re(conj psi . dpsi_d)`` in ``dexpect[d]``, formed in a fixed order
     (two calls return the same bits); ``split_moments`` takes the block off ``expect`` and off each ``dexpect[d]``.  The flag without
-    ``spec.moments`` is a ``ValueError`` (``RYDIFF_EINVAL``: it asks for a block the problem does not have)."""
+    ``spec.moments`` is a ``ValueError`` (``RYDIFF_EINVAL``: it asks for a block the problem does not have).
+
+    ``xy_pairs`` (with ``spec.xy_mode``): the couplings of the native XY exchange, as in ``evolve``; handing them in is the opt-in
+    (``_native.TANGENT_XY`` is set here) and the exchange stencil rides in the sweep at every register size.  ``d_xy[d]`` shaped like
+    ``xy_pairs`` is direction d's tangent of the couplings — a tangent input like the others, valid on its own.  ``spec.xy_mode``
+    without ``xy_pairs`` stays the ``NotImplementedError`` it was."""
     if (spec.rdms is not None and not (int(flags) & _native.TANGENT_RDMS)) or (spec.dm is not None and spec.dm.rdms is not None):
         raise NotImplementedError("evolve_tangent evaluates no reduced density matrices (rydiff_forward_tangent: RYDIFF_ENOTIMPL) unless "
                                   "flags has _native.TANGENT_RDMS (kets only); or request them from evolve")
@@ -889,13 +901,15 @@ def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsav
                                   "flags has _native.TANGENT_MOMENTS (kets only); or request them from evolve")
     if spec.shots is not None or (spec.dm is not None and spec.dm.shots):
         raise NotImplementedError("evolve_tangent draws no measurement shots (rydiff_forward_tangent: RYDIFF_ENOTIMPL); request them from evolve")
-    if spec.xy_mode:
+    if spec.xy_mode and xy_pairs is None:
         raise NotImplementedError("evolve_tangent takes no XY exchange term (rydiff_forward_tangent: RYDIFF_ENOTIMPL with xy_mode != 0); "
                                   "differentiate evolve, or run the dense pair-term route with _native.TANGENT_PAIR_TERMS")
     L = _native.lib()
     dev = psi0.device
+    if xy_pairs is not None:
+        flags = int(flags) | _native.TANGENT_XY
     n_dir, pre, rows = _sweep_prepare("evolve_tangent", amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag,
-                                      d_amp, d_det, d_u, d_psi0)
+                                      d_amp, d_det, d_u, d_psi0, xy_pairs, d_xy)
     p, n_t, batch = pre.call.problem, pre.n_t, pre.batch
     expect = torch.empty((rows, n_t, batch), dtype=torch.float64, device=dev)
     dexpect = torch.empty((n_dir, rows, n_t, batch), dtype=torch.float64, device=dev)
@@ -905,7 +919,7 @@ def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsav
         values_done = False
         for d0 in range(0, n_dir, _native.MAX_TANGENTS):
             d1 = min(n_dir, d0 + _native.MAX_TANGENTS)
-            bufs = _tangent_buffers(slice(d0, d1), pre, d_amp, d_det, d_u, d_psi0, dev)
+            bufs = _tangent_buffers(slice(d0, d1), pre, d_amp, d_det, d_u, d_psi0, dev, d_xy)
             out = dexpect[d0:d1]
             if all(b is None for b in bufs):  # tangents of inputs this problem does not have: the derivative is zero
                 out.zero_()
@@ -924,13 +938,15 @@ def evolve_tangent(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsav
             _native.check(sweep(workspace))
     if rows and not values_done:  # no chunk reached the library (tangents of inputs the problem does not have)
         with torch.no_grad():
-            expect = evolve(pre.amp, pre.det, pre.u, tsave.detach(), pre.psi, replace(spec, store_states=False), pre.obs)[1]
+            expect = evolve(pre.amp, pre.det, pre.u, tsave.detach(), pre.psi, replace(spec, store_states=False), pre.obs,
+                            xy_pairs=pre.xy)[1]
     return expect, dexpect
 
 
 def evolve_geometry(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Tensor, spec: ProblemSpec,
                     obs_diag: Optional[Tensor] = None, d_amp: Optional[Tensor] = None, d_det: Optional[Tensor] = None,
-                    d_u: Optional[Tensor] = None, d_psi0: Optional[Tensor] = None, flags: int = 0) -> tuple[Tensor, Tensor, Tensor]:
+                    d_u: Optional[Tensor] = None, d_psi0: Optional[Tensor] = None, flags: int = 0,
+                    xy_pairs: Optional[Tensor] = None, d_xy: Optional[Tensor] = None) -> tuple[Tensor, Tensor, Tensor]:
     """``evolve_tangent`` that also returns the Gram matrix of the state and its tangents at EVERY evaluation time
     (``rydiff_forward_geometry``): ``(expect, dexpect, gram)`` with ``gram`` complex128 of shape (n_t, B, 1 + n_dir, 1 + n_dir),
     ``gram[k, b, i, j] = <v_i|v_j>``, ``v_0 = psi_b(t_k)``, ``v_{1+d} = d psi_b(t_k) / d theta_d`` — what
@@ -940,13 +956,16 @@ def evolve_geometry(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsa
     ``flags=_native.TANGENT_PAIR_TERMS`` takes dense pair terms on kets, ``_native.TANGENT_RDMS`` the reduced density matrices of
     ``spec.rdms`` (rows as in ``evolve_tangent``; their sums use atomics and are not part of the fixed order),
     ``_native.TANGENT_MOMENTS`` the occupation correlations of ``spec.moments`` (fixed order, like the Gram matrix, which they leave
-    as it is); density-matrix registers stay refused."""
-    return _evolve_gram(False, amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag, d_amp, d_det, d_u, d_psi0, flags)[:3]
+    as it is); density-matrix registers stay refused.  ``xy_pairs`` / ``d_xy``: the native XY exchange and the tangents of its
+    couplings, as in ``evolve_tangent``."""
+    return _evolve_gram(False, amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag, d_amp, d_det, d_u, d_psi0, flags,
+                        xy_pairs, d_xy)[:3]
 
 
 def evolve_fisher(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Tensor, spec: ProblemSpec,
                   obs_diag: Optional[Tensor] = None, d_amp: Optional[Tensor] = None, d_det: Optional[Tensor] = None,
-                  d_u: Optional[Tensor] = None, d_psi0: Optional[Tensor] = None, flags: int = 0) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+                  d_u: Optional[Tensor] = None, d_psi0: Optional[Tensor] = None, flags: int = 0,
+                  xy_pairs: Optional[Tensor] = None, d_xy: Optional[Tensor] = None) -> tuple[Tensor, Tensor, Tensor, Tensor]:
     """``evolve_geometry`` that also returns the classical Gram matrix of the occupation-basis measurement at EVERY evaluation time
     (``rydiff_forward_fisher``): ``(expect, dexpect, gram, cgram)`` with ``cgram`` float64 of shape (n_t, B, 1 + n_dir, 1 + n_dir),
     ``cgram[k, b, i, j] = sum_y w_i[y] w_j[y]``, ``w_0 = |psi_b(t_k)|``, ``w_{1+d} = 2 Re(conj(psi / |psi|) d psi_b(t_k) / d theta_d)``
@@ -955,10 +974,12 @@ def evolve_fisher(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsave
     classical Fisher information.  Fixed order: two calls on the same inputs return bit-identical matrices.  Same arguments, flags and
     refusals as ``evolve_geometry``; tangents of inputs the problem does not have give zero rows and columns (``cgram[..., 0, 0]``
     stays ``<psi|psi>``).  More than 8 directions run one sweep per pair of groups of 4 (``geometry.geometry_sweeps``)."""
-    return _evolve_gram(True, amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag, d_amp, d_det, d_u, d_psi0, flags)
+    return _evolve_gram(True, amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag, d_amp, d_det, d_u, d_psi0, flags,
+                        xy_pairs, d_xy)
 
 
-def _evolve_gram(fisher: bool, amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag, d_amp, d_det, d_u, d_psi0, flags):
+def _evolve_gram(fisher: bool, amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag, d_amp, d_det, d_u, d_psi0, flags,
+                 xy_pairs=None, d_xy=None):
     """``evolve_geometry`` (``cgram`` None) and ``evolve_fisher``: the refusals, the sweeps over groups of directions, the assembly."""
     from .geometry import geometry_sweeps, place_sweep_block
 
@@ -974,13 +995,15 @@ def _evolve_gram(fisher: bool, amp_tables, det_tables, u_pairs, tsave, psi0, spe
                                   "flags has _native.TANGENT_MOMENTS; or request them from evolve")
     if spec.shots is not None:
         raise NotImplementedError(f"{name} draws no measurement shots ({native}: RYDIFF_ENOTIMPL); request them from evolve")
-    if spec.xy_mode:
+    if spec.xy_mode and xy_pairs is None:
         raise NotImplementedError(f"{name} takes no XY exchange term ({native}: RYDIFF_ENOTIMPL with xy_mode != 0); "
                                   "run the dense pair-term route with _native.TANGENT_PAIR_TERMS")
     L = _native.lib()
     dev = psi0.device
+    if xy_pairs is not None:
+        flags = int(flags) | _native.TANGENT_XY
     n_dir, pre, rows = _sweep_prepare(name, amp_tables, det_tables, u_pairs, tsave, psi0, spec, obs_diag,
-                                      d_amp, d_det, d_u, d_psi0)
+                                      d_amp, d_det, d_u, d_psi0, xy_pairs, d_xy)
     p, n_t, batch = pre.call.problem, pre.n_t, pre.batch
     expect = torch.empty((rows, n_t, batch), dtype=torch.float64, device=dev)
     dexpect = torch.empty((n_dir, rows, n_t, batch), dtype=torch.float64, device=dev)
@@ -989,7 +1012,8 @@ def _evolve_gram(fisher: bool, amp_tables, det_tables, u_pairs, tsave, psi0, spe
     # tangents of inputs this problem does not have are zero: where nothing else is given the tangent states are identically zero,
     # and ONE sweep with a single zero direction delivers <psi|psi> and the values; every other entry is an exact zero
     live = ((d_amp is not None and pre.amp.numel() > 0) or (d_det is not None and pre.det.numel() > 0)
-            or (d_u is not None and pre.u.numel() > 0) or d_psi0 is not None)
+            or (d_u is not None and pre.u.numel() > 0) or d_psi0 is not None
+            or (d_xy is not None and pre.xy is not None and pre.xy.numel() > 0))
     sweeps = geometry_sweeps(n_dir) if live else [[0]]
     size_fn = L.rydiff_fisher_workspace_bytes_flags if fisher else L.rydiff_geometry_workspace_bytes_flags
     size_name = "rydiff_fisher_workspace_bytes_flags" if fisher else "rydiff_geometry_workspace_bytes"
@@ -999,9 +1023,9 @@ def _evolve_gram(fisher: bool, amp_tables, det_tables, u_pairs, tsave, psi0, spe
         done = torch.zeros(n_dir, dtype=torch.bool)
         for s, idx in enumerate(sweeps):
             if live:
-                bufs = _tangent_buffers(idx, pre, d_amp, d_det, d_u, d_psi0, dev)
+                bufs = _tangent_buffers(idx, pre, d_amp, d_det, d_u, d_psi0, dev, d_xy)
             else:
-                bufs = (None, None, None, torch.zeros((1,) + tuple(pre.psi.shape), dtype=torch.complex128, device=dev))
+                bufs = (None, None, None, torch.zeros((1,) + tuple(pre.psi.shape), dtype=torch.complex128, device=dev), None)
             tg = _sweep_tangent(len(idx), bufs, flags)
             g = torch.empty((n_t, batch, 1 + len(idx), 1 + len(idx)), dtype=torch.complex128, device=dev)
             c = torch.empty((n_t, batch, 1 + len(idx), 1 + len(idx)), dtype=torch.float64, device=dev) if fisher else None
