@@ -206,6 +206,46 @@ typedef struct RydProblem {
     uint64_t amp_conditioned_terms;
     uint64_t det_ones_terms;
 
+    /* ENERGY OBSERVABLES: the expectation of the run's own Hamiltonian and its second moment at every tsave, from the state while
+     * it is on the device — the score of a state-preparation or annealing sequence that needs no target state, and (as the variance
+     * M2 - E^2) the distance from any eigenstate.  H_k is the Hamiltonian the factor passes apply (same groups, masks, diagonal rule,
+     * u_pairs, and with xy_mode = 1 the Hermitian exchange with xy_pairs), built from COLUMN k of two tables the caller interpolates
+     * to the save points itself:
+     *   E[k][b]  = Re sum_x conj(psi[x]) (H_k psi)[x]        M2[k][b] = sum_x |(H_k psi)[x]|^2        (psi = psi_b(t_k), not normalised)
+     * energy_rows = 1 adds the row E, 2 the rows E then M2, to expect_out / grad_expect BEHIND the bit_moments block (the last block
+     * of a ket's rows, in front of the density-matrix rows).  Every workgroup writes its two partial sums to the workspace and a
+     * second launch adds them in index order (no atomics): two calls on the same input give bit-identical rows, and every row is
+     * written.  rydiff_plan adds the scratch to workspace_bytes: the (n_tsave) coefficient records and the partial sums, for
+     * rydiff_backward one more state per trajectory (n_tsave of them up to 12 qubits) and the gradient records.
+     * rydiff_backward, with g_E, g_M the rows of grad_expect at (k, b) (g_M = 0 with one row): the cotangent added to psi_b(t_k) is
+     *   2 H_k (g_E psi + g_M H_k psi)                                       (the factor-2 convention of the diagonal rows)
+     * formed in two passes (z = g_E psi + g_M H_k psi into the scratch state, then 2 H_k z) in the workspace buffer of the Pauli /
+     * overlap / RDM / moment cotangents (after them) and injected through the grad_states route.  The EXPLICIT derivative w.r.t. a
+     * coefficient c of H_k, Re<g_E psi + 2 g_M H_k psi| dH_k/dc |psi>, goes for the drive and detuning coefficients to column k of
+     * g_energy_amp / g_energy_det (members of a group as in g_amp / g_det; both parts of g_energy_amp whatever real_amp_grad says),
+     * for u_pairs into g_u and for xy_pairs into g_xy, in their plain units dL/dU_p, dL/dJ_p, next to what the factor passes put there.
+     * Honoured wherever bit_moments is: every kernel family and kernel_variant (the block reads save-point states only: up to 12
+     * qubits the trajectory the one-launch sweeps leave in the workspace), every tape mode, final_state_only, states_out == NULL
+     * without a tape, batch / coeff_batch, next to every other ket row and the shots, N = 1 .. RYDIFF_MAX_QUBITS.  One kernel family
+     * of its own (energy_kernels.hpp) in two versions, energy_kernel: direct (one amplitude per thread, partners from global memory,
+     * as k_dot_hx; every N, and the only one with the exchange) and LDS-tile (13 .. 24 qubits).
+     * RYDIFF_EINVAL: energy_rows outside 0..2; energy_amp == NULL with n_amp_terms > 0; energy_det == NULL with n_det_terms > 0.
+     * RYDIFF_ENOTIMPL, before anything touches a device: energy_rows > 0 together with n_pair_terms > 0, dm_atoms > 0, shard_bits > 0,
+     * conditioned or ones-counting terms, xy_mode = 2 (the expectation of a non-Hermitian generator is not an energy), and in
+     * rydiff_forward_tangent / rydiff_forward_geometry / rydiff_forward_fisher.  Follow-ups, not built: the Tr(rho H) rows of
+     * master-equation runs (dm_atoms > 0) and the tangents of the rows in the tangent sweep.
+     * energy_rows = 0: the other five fields are ignored and nothing changes.  (The fields sit in front of xy_mode: every later block
+     * keeps its neighbours, and the Pauli block stays the tail of the struct.) */
+    int32_t energy_rows;       /* 0: off; 1: E; 2: E then M2 */
+    const void* energy_amp;    /* DEVICE complex128 [coeff_batch][n_amp_terms][n_tsave]: 0.5*amp*exp(-i*phase) AT the save points */
+    const double* energy_det;  /* DEVICE float64    [coeff_batch][n_det_terms][n_tsave]: -0.5*det AT the save points */
+    void* g_energy_amp;        /* rydiff_backward: DEVICE complex128, the shape of energy_amp, or NULL; overwritten */
+    double* g_energy_det;      /* rydiff_backward: DEVICE float64, the shape of energy_det, or NULL; overwritten */
+    int32_t energy_kernel;     /* 0: automatic (what production callers pass); 1: the direct version (one amplitude per thread, every N);
+                                * 2: the LDS-tile version (2^12 amplitudes staged per workgroup; 13 <= N <= 24, xy_mode = 0: elsewhere
+                                * RYDIFF_ENOTIMPL) — for parity tests and timing, like kernel_variant.  Results do not depend on it
+                                * beyond rounding.  RYDIFF_EINVAL outside 0..2 (with energy_rows > 0; ignored with energy_rows = 0) */
+
     /* XY EXCHANGE (the reference's microwave / "XY" interaction mode, hamiltonian.py:346-366) as a term of its own: one real number
      * per pair of qubits and one partner amplitude, instead of a dense 4x4 pair term.  With b_q(x) the index bit of qubit q (bit
      * N-1-q of the amplitude index x) and m_q = 1 << (N-1-q):
@@ -483,7 +523,7 @@ int rydiff_plan(const RydProblem* p, int need_tape, int need_backward, void* scr
  *               save points are copied out of it — stored states plus a later gradient without (or with less) recomputation.
  *   expect_out  DEVICE float64 [n_obs + n_pauli_obs + 2 * n_overlaps + 2 * sum_o 4^{m_o} + moment rows + dm rows][n_tsave][B] (diagonal observables
  *               first, then the Pauli ones, then Re / Im of every overlap, then Re / Im of every reduced-density-matrix entry, then with
- *               bit_moments the 1 + N + N(N-1)/2 moment rows S, B_q, B_qr, then the
+ *               bit_moments the 1 + N + N(N-1)/2 moment rows S, B_q, B_qr, then with energy_rows the rows E (and M2), then the
  *               density-matrix rows n_dm_diag + n_dm_pauli_obs + n_dm_fid + dm_purity + 2 * sum_o 4^{m_o} over dm_rdm_masks
  *               + with dm_moments the 1 + n + n(n-1)/2 rows S, B_q, B_qr of the diagonal of rho), or NULL
  * With RydProblem.n_shots > 0 the measurement shots of the save points in shot_times go to RydProblem.shots_out on the way. */
@@ -497,7 +537,7 @@ int rydiff_forward(const RydProblem* p, const RydPlanInfo* info, const void* psi
  *   states       DEVICE: the states_out of the forward call, or NULL to use the workspace tape (with need_tape = 2 / 3 the
  *                granted workspace tape is used even when states is given)
  *   grad_states  DEVICE complex128 [n_tsave][B][2^N] or NULL
- *   grad_expect  DEVICE float64 [n_obs + n_pauli_obs + 2 * n_overlaps + 2 * sum_o 4^{m_o} + moment rows + dm rows][n_tsave][B] or NULL
+ *   grad_expect  DEVICE float64 [n_obs + n_pauli_obs + 2 * n_overlaps + 2 * sum_o 4^{m_o} + moment rows + energy rows + dm rows][n_tsave][B] or NULL
  *   g_amp        DEVICE complex128 [coeff_batch][n_amp_terms][n_samples] or NULL   (overwritten)
  *   g_det        DEVICE float64    [coeff_batch][n_det_terms][n_samples] or NULL   (overwritten)
  *   g_u          DEVICE float64 [N(N-1)/2] or NULL  (dist_grad, backend.py:456-460 / hamiltonian.py:341-344)

@@ -10,11 +10,11 @@ from pulser_diff_amd.model import QuantumModel  # noqa: F401
 from pulser_diff_amd.simconfig import SimConfig  # noqa: F401
 from pulser_diff_amd.solver import SolverType  # noqa: F401
 from pulser_diff_amd.utils import DiagonalObservable, logarithmic_negativity, negativity, partial_transpose  # noqa: F401
-from pulser_diff_amd.observables import OccupationCorrelations, PauliObservable, Purity, ReducedDensityMatrix, StateOverlap  # noqa: F401
+from pulser_diff_amd.observables import Energy, OccupationCorrelations, PauliObservable, Purity, ReducedDensityMatrix, StateOverlap  # noqa: F401
 from pulser_diff_amd.geometry import (MeasurementFisher, QuantumGeometry, berry_curvature, classical_fisher_information,  # noqa: F401
                                       fisher_efficiency, quantum_fisher_information, quantum_geometric_tensor)
 
-__all__ = ["TorchEmulator", "SimConfig", "SolverType", "DiagonalObservable", "PauliObservable", "StateOverlap", "ReducedDensityMatrix", "Purity", "OccupationCorrelations", "OccupationSensitivities", "QuantumModel",
+__all__ = ["TorchEmulator", "SimConfig", "SolverType", "DiagonalObservable", "PauliObservable", "StateOverlap", "ReducedDensityMatrix", "Purity", "OccupationCorrelations", "Energy", "OccupationSensitivities", "QuantumModel",
            "QuantumGeometry", "quantum_geometric_tensor", "quantum_fisher_information", "berry_curvature",
            "MeasurementFisher", "classical_fisher_information", "fisher_efficiency",
            "partial_transpose", "negativity", "logarithmic_negativity"]

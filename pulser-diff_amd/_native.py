@@ -79,6 +79,12 @@ class RydProblem(ctypes.Structure):
         ("final_state_only", ctypes.c_int32),
         ("amp_conditioned_terms", ctypes.c_uint64),
         ("det_ones_terms", ctypes.c_uint64),
+        ("energy_rows", ctypes.c_int32),
+        ("energy_amp", ctypes.c_void_p),
+        ("energy_det", ctypes.c_void_p),
+        ("g_energy_amp", ctypes.c_void_p),
+        ("g_energy_det", ctypes.c_void_p),
+        ("energy_kernel", ctypes.c_int32),
         ("xy_mode", ctypes.c_int32),
         ("xy_pairs", ctypes.c_void_p),
         ("g_xy", ctypes.c_void_p),

@@ -36,7 +36,7 @@ from .simconfig import SimConfig
 from .simresults import CoherentResults, NoisyResults, SimulationResults
 from .solver import (ProblemSpec, SolverType, evolve, evolve_fisher, evolve_geometry, evolve_tangent, sesolve, split_moments,
                      split_observables, tolerance_from_options)
-from .observables import OccupationCorrelations, PauliObservable, Purity, ReducedDensityMatrix, StateOverlap, pack_overlaps
+from .observables import Energy, OccupationCorrelations, PauliObservable, Purity, ReducedDensityMatrix, StateOverlap, pack_overlaps
 from .geometry import (MeasurementFisher, QuantumGeometry, classical_fisher_information, quantum_fisher_information,
                        quantum_geometric_tensor)
 from .shots import MAX_SHOTS, ShotRequest, indices_to_bitstrings
@@ -464,7 +464,8 @@ class TorchEmulator:
         with ``results.reduced_density_matrix`` / ``results.entanglement_entropy`` / ``results.negativity``; master-equation runs
         serve them — ``Tr_E rho`` — with ``store_states=False``) and the occupation correlations (``OccupationCorrelations``; read
         with ``results.occupations`` / ``occupation_correlations`` / ``structure_factor``; master-equation runs serve them — the
-        moments of the diagonal of rho — with ``store_states=False``) to be evaluated natively at every evaluation time; ``store_states=False`` keeps the trajectory out of the results.
+        moments of the diagonal of rho — with ``store_states=False``) and the energy under the sequence's own Hamiltonian (``Energy``; read
+        with ``results.energy`` / ``energy_second_moment`` / ``energy_variance``; ket runs only) to be evaluated natively at every evaluation time; ``store_states=False`` keeps the trajectory out of the results.
 
         ``shots`` (extension): measurement shots drawn natively while the state is on the device — an int (that many at the final
         evaluation time) or a ``ShotRequest`` (``times="all"``: every evaluation time).  ``results.sample_state`` /
@@ -500,7 +501,20 @@ class TorchEmulator:
         ham = self._hamiltonian
         obs_tensors, obs_objs, pauli_objs, overlap_objs, rdm_objs, purity_objs = [], [], [], [], [], []
         moments = False
+        energy = 0
         for obs in observables or []:
+            if isinstance(obs, Energy):
+                if ham.basis_name == "all":
+                    raise NotImplementedError("Energy is not available in the three-level all-basis (the native energy rows do not "
+                                              "take conditioned terms); apply get_hamiltonian to the stored states instead.")
+                if solver == SolverType.DP5_ME:
+                    raise NotImplementedError("Energy is not available in master-equation runs (Tr(rho H) is not evaluated natively "
+                                              "yet); apply get_hamiltonian to the stored density matrices instead.")
+                if ham._interaction == "XY" and (ham.xy_mode != 1 or ham.pair_terms):
+                    raise NotImplementedError("Energy in the XY mode runs on the native, Hermitian exchange term only: "
+                                              "TorchEmulator(..., xy_native=True, xy_hermitian=True).")
+                energy = max(energy, obs.rows)
+                continue
             if isinstance(obs, OccupationCorrelations):
                 if ham.basis_name == "all":
                     raise NotImplementedError("OccupationCorrelations is not available in the three-level all-basis (an atom is "
@@ -535,7 +549,7 @@ class TorchEmulator:
                 continue
             if not isinstance(obs, DiagonalObservable) and not (isinstance(obs, Tensor) and obs.ndim == 2):
                 raise TypeError("observables must be DiagonalObservable / PauliObservable / StateOverlap / ReducedDensityMatrix / Purity / "
-                                "OccupationCorrelations objects or diagonal (dim, dim) tensors")
+                                "OccupationCorrelations / Energy objects or diagonal (dim, dim) tensors")
             diag = real_diagonal(obs, "Only diagonal observables can be evaluated natively; use results.expect on the states.")
             obs_tensors.append(diag.to(dev, torch.float64))
             obs_objs.append(obs)
@@ -595,14 +609,15 @@ class TorchEmulator:
                                        native_moments=res.moments)
             result = sesolve(ham, psi0.to(dev), self._eval_times_array, solver=solver, options=options, obs_diag=obs_diag,
                              store_states=store_states, pauli_obs=pauli_objs, overlap_obs=overlap_objs, shots=shots, rdm_obs=rdm_objs,
-                             moments=moments)
+                             moments=moments, energy=energy)
             states_tbd = result.states.permute(0, 2, 1) if result.states.numel() else result.states
             return CoherentResults(states_tbd, ham._size, ham.basis_name, self._eval_times_array, self._meas_basis,
                                    meas_errors, atom_order=tuple(ham._qdict),
                                    native_expect=result.expect if (obs_diag is not None or pauli_objs) else None,
                                    native_observables=obs_objs + pauli_objs, stats=result.stats,
                                    native_overlaps=result.overlaps, overlap_observables=overlap_objs, native_shots=result.shots,
-                                   native_rdms=result.rdms, rdm_observables=rdm_objs, native_moments=result.moments)
+                                   native_rdms=result.rdms, rdm_observables=rdm_objs, native_moments=result.moments,
+                                   native_energy=result.energy, hamiltonian_at=ham._hamiltonian)
 
         # does the noise ask for averaging over several runs?  (backend.py:531-569)
         bad_atom_configs = None
@@ -625,6 +640,8 @@ class TorchEmulator:
             raise NotImplementedError("Purity observables stay refused in noisy runs that average over realisations.")
         if moments:
             raise NotImplementedError("OccupationCorrelations stays refused in noisy runs that average over realisations.")
+        if energy:
+            raise NotImplementedError("Energy stays refused in noisy runs that average over realisations.")
         if shots is not None:
             raise NotImplementedError("A ShotRequest belongs to one coherent run; noisy runs that average over realisations return "
                                       "their measurements as NoisyResults (native_shots=True draws them natively).")

@@ -48,6 +48,7 @@ int launch_observables_expect(const ForwardCtx& c, const double2* psi, size_t ks
     if (const int rc = launch_overlap_expect(c, psi, kstride, k0, nk, bs)) return rc;
     if (const int rc = launch_rdm_expect(c, psi, kstride, k0, nk, bs)) return rc;
     if (const int rc = launch_moments_expect(c, psi, kstride, k0, nk, bs)) return rc;
+    if (const int rc = launch_energy_expect(c, psi, kstride, k0, nk, bs)) return rc;
     if (const int rc = launch_dm_expect(c, psi, kstride, k0, nk, bs)) return rc;
     return c.rt.pl.dm_shots ? launch_dm_shots(c, psi, kstride, k0, nk, bs) : launch_shots(c, psi, kstride, k0, nk, bs);
 }
@@ -85,13 +86,17 @@ void launch_observable_cotangent(const PauliInject& pi, const double2* psi, cons
         launch_moments_apply(pi, psi, entry, kmul, k0, nk, base, out);
         base = out;
     }
+    if (pi.energy_gexp) {  // (a failed launch is kept for rydiff_backward to report: PauliInject::rc)
+        if (const int rc = launch_energy_apply(pi, psi, entry, kmul, k0, nk, base, out)) pi.rc = rc;
+        base = out;
+    }
     if (pi.dm_gexp) launch_dm_apply(pi, psi, entry, kmul, k0, nk, base, out);
 }
 
 // launch-per-factor adjoint sweeps: the cotangent injected at save point k, written into the one reused workspace buffer right
 // before the launch that reads it (stream order keeps the previous reader ahead of this write)
 const double2* observable_cotangent(const PauliInject& pi, int k) {
-    launch_observable_cotangent(pi, (pi.gexp || pi.rdm_gexp || pi.moments_gexp || (pi.dm_gexp && pi.rt->pl.dm_purity)) ? pi.state_at(k) : nullptr, nullptr, 0, k, 1, pi.buf);
+    launch_observable_cotangent(pi, (pi.gexp || pi.rdm_gexp || pi.moments_gexp || pi.energy_gexp || (pi.dm_gexp && pi.rt->pl.dm_purity)) ? pi.state_at(k) : nullptr, nullptr, 0, k, 1, pi.buf);
     return pi.buf;
 }
 

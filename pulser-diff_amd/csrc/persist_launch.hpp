@@ -191,7 +191,7 @@ int forward_persist(const ForwardCtx& c) {
     pa.expect = c.expect_out;
     pa.n_obs = c.want_exp ? rt.pl.n_obs : 0;
     const Plan& pl = rt.pl;
-    if ((c.pauli_out || c.overlap_out || c.rdm_out || c.moments_out || c.dm_out || c.shots_out) && !pa.states) {  // the caller keeps no trajectory: the Pauli / overlap observables and the shots read one in the workspace
+    if ((c.pauli_out || c.overlap_out || c.rdm_out || c.moments_out || c.energy_out || c.dm_out || c.shots_out) && !pa.states) {  // the caller keeps no trajectory: the Pauli / overlap observables and the shots read one in the workspace
         pa.states = reinterpret_cast<double2*>(c.ws + pl.off_pauli_traj);
         HIP_TRY(hipMemcpyAsync(pa.states, c.psi0, pl.state_bytes, hipMemcpyDeviceToDevice, c.stream));
     }

@@ -98,6 +98,13 @@ struct Plan {
     int moment_rows() const { return moments ? 1 + N + N * (N - 1) / 2 : 0; }
     size_t moment_tiles() const { return dim >> 12; }  // (kMomTileBits)
     size_t off_moments = 0;
+    // energy observables (RydProblem.energy_rows, energy_kernels.hpp): E (and M2) behind the moment rows.  Workspace: one StageDev and
+    // one coefficient record per save point, the workgroups' partial sums; backward: the scratch state(s) z and the gradient records
+    int energy = 0;
+    int energy_kernel = 0;  // RydProblem.energy_kernel: 0 automatic | 1 direct | 2 LDS-tile
+    bool energy_tile_legal() const { return !xy_mode && N >= 13 && N <= 24; }  // (2^(N-12) <= energy_blocks() partial sums per state)
+    size_t energy_blocks() const { return std::min<size_t>(std::max<size_t>(dim >> 8, 1), 4096); }  // workgroups of one (save point, trajectory)
+    size_t off_energy_meta = 0, off_energy_coef = 0, off_energy_part = 0, off_energy_z = 0, off_energy_ge = 0;
     // measurement shots (shots_kernels.hpp): the sampled save points; scratch = chunk sums and their prefix, [B][shot_chunks()] doubles each
     int n_shots = 0;
     std::vector<int32_t> shot_times;
@@ -142,14 +149,15 @@ struct Plan {
 // The row order of expect_out / grad_expect / dexpect_out ([rows][n_tsave][B] each, dexpect_out one such array per direction):
 // the blocks of the enumeration, in its order.  The only place that adds row counts up; every launch takes its pointers from at().
 struct ExpectRows {
-    // Moments: S, B_q, B_qr of the occupation correlations (empty unless bit_moments), the last block of a ket's rows;
+    // Moments: S, B_q, B_qr of the occupation correlations (empty unless bit_moments); Energy: E, M2 (empty unless energy_rows), the
+    // last block of a ket's rows;
     // DmTrace (dm_diag rows, then the density-matrix Pauli rows) .. DmMoments (S, B_q, B_qr of diag rho; empty unless dm_moments):
     // the density-matrix rows
-    enum Block { Diag, Pauli, Overlap, Rdm, Moments, DmTrace, DmFid, DmPurity, DmRdm, DmMoments, End };
+    enum Block { Diag, Pauli, Overlap, Rdm, Moments, Energy, DmTrace, DmFid, DmPurity, DmRdm, DmMoments, End };
     size_t stride = 0;        // doubles per row: (T + 1) * B
     int first[End + 1] = {};  // first row of each block; first[End]: all rows
     explicit ExpectRows(const Plan& pl) : stride(size_t(pl.T + 1) * pl.B) {
-        const int count[End] = {pl.n_obs, pl.n_pobs, 2 * pl.n_ov, pl.rdm_rows, pl.moment_rows(), pl.n_dm_diag + pl.n_dm_pobs, pl.n_dm_fid, pl.dm_purity, pl.dm_rdm_rows, pl.dm_moment_rows()};
+        const int count[End] = {pl.n_obs, pl.n_pobs, 2 * pl.n_ov, pl.rdm_rows, pl.moment_rows(), pl.energy, pl.n_dm_diag + pl.n_dm_pobs, pl.n_dm_fid, pl.dm_purity, pl.dm_rdm_rows, pl.dm_moment_rows()};
         for (int b = 0; b < End; ++b) first[b + 1] = first[b] + count[b];
     }
     int count(Block b) const { return first[b + 1] - first[b]; }
@@ -592,6 +600,41 @@ inline bool xy_validate(const RydProblem* p, std::string& err) {
     return true;
 }
 
+// RydProblem.energy_*: the range, the tables, and what the block is refused with (host only; "not implemented" -> RYDIFF_ENOTIMPL)
+inline bool energy_validate(const RydProblem* p, std::string& err) {
+    if (p->energy_rows < 0 || p->energy_rows > 2) {
+        err = "energy_rows must be 0 (off), 1 (E) or 2 (E and M2)";
+        return false;
+    }
+    if (p->energy_rows == 0) return true;
+    if (p->energy_kernel < 0 || p->energy_kernel > 2) {
+        err = "energy_kernel must be 0 (automatic), 1 (direct) or 2 (LDS-tile)";
+        return false;
+    }
+    if ((p->n_amp_terms > 0 && !p->energy_amp) || (p->n_det_terms > 0 && !p->energy_det)) {
+        err = "energy_rows > 0 needs energy_amp / energy_det (the coefficients at the save points) for the problem's terms";
+        return false;
+    }
+    const char* with = nullptr;
+    if (p->n_pair_terms > 0) with = "dense pair terms (n_pair_terms > 0)";
+    else if (p->dm_atoms > 0) with = "density-matrix registers (dm_atoms > 0: the Tr(rho H) rows are a follow-up)";
+    else if (p->shard_bits > 0) with = "state sharding (shard_bits > 0)";
+    else if (p->amp_conditioned_terms || p->det_ones_terms) with = "conditioned flips / ones-counting terms";
+    else if (p->xy_mode == 2) with = "the one-directional exchange (xy_mode = 2: the expectation of a non-Hermitian generator is not an energy)";
+    if (with) {
+        err = std::string("energy observables (energy_rows > 0): not implemented together with ") + with;
+        return false;
+    }
+    if (p->energy_kernel == 2 && (p->xy_mode != 0 || p->n_qubits < 13 || p->n_qubits > 24)) {
+        err = "energy_kernel = 2: the LDS-tile version is not implemented outside 13 .. 24 qubits or with the XY exchange";
+        return false;
+    }
+    return true;
+}
+
+// number of gradient replicas of the energy block's coefficient records (energy_kernels.hpp)
+constexpr int kEnergyReplicas = 16;
+
 // number of XY gradient replicas in the workspace (xy_kernels.hpp)
 constexpr int kXyReplicas = 32;
 
@@ -648,6 +691,9 @@ inline bool build_plan(const RydProblem* p, Plan& pl, std::string& err, double w
     }
     if (!xy_validate(p, err)) return false;
     pl.xy_mode = p->xy_mode;
+    if (!energy_validate(p, err)) return false;
+    pl.energy = p->energy_rows;
+    pl.energy_kernel = p->energy_rows ? p->energy_kernel : 0;
     pl.n_pair = p->n_pair_terms;
     pl.pair_tab.assign(size_t(pl.n_pair) * 64, 0.0);
     pl.pair_radius = 0.0;
@@ -912,11 +958,17 @@ inline size_t carve(Plan& pl, int tape_mode, bool need_backward, int chain_slots
     pl.off_pauli = take(pl.pauli_bytes());
     // one-launch sweeps: the trajectory the Pauli and overlap observables are evaluated on (and the shots drawn from) where the
     // caller keeps none
-    pl.off_pauli_traj = take(((pl.n_pobs || pl.n_ov || pl.n_rdm || pl.moments || pl.n_shots || pl.dm_rows()) && pl.N <= 12) ? size_t(pl.T + 1) * pl.state_bytes : 0);
+    pl.off_pauli_traj = take(((pl.n_pobs || pl.n_ov || pl.n_rdm || pl.moments || pl.energy || pl.n_shots || pl.dm_rows()) && pl.N <= 12) ? size_t(pl.T + 1) * pl.state_bytes : 0);
     pl.off_dm = take(pl.dm_n ? pl.dm_bytes() : 0);  // string tables of the density-matrix observables
     pl.off_shot_sums = take(pl.n_shots ? size_t(pl.B) * pl.shot_chunks() * sizeof(double) : 0);
     pl.off_shot_prefix = take(pl.n_shots ? size_t(pl.B) * pl.shot_chunks() * sizeof(double) : 0);
     pl.off_moments = take((pl.moments && pl.moment_tiles() > 1) ? size_t(pl.B) * 79 * pl.moment_tiles() * sizeof(double) : 0);  // kMomEntries per tile
+    if (pl.energy) {  // (nothing is taken with the block off: every other offset stays where it was)
+        pl.off_energy_meta = take(size_t(pl.T + 1) * 24);  // StageDev records: column k with weight 1
+        pl.off_energy_coef = take(size_t(pl.Bc) * (pl.T + 1) * std::max(pl.NC, 1) * sizeof(double));
+        // partial sums [save points of one launch][B][workgroups][2]: up to 12 qubits one launch covers the whole trajectory
+        pl.off_energy_part = take(size_t(pl.N <= 12 ? pl.T + 1 : 1) * pl.B * pl.energy_blocks() * 2 * sizeof(double));
+    }
     pl.total_fwd = off;
     pl.tape_mode = tape_mode;
     if (tape_mode == 2) pl.off_tape = take(size_t(total_factors + 1) * pl.state_bytes);
@@ -929,8 +981,12 @@ inline size_t carve(Plan& pl, int tape_mode, bool need_backward, int chain_slots
         pl.off_wtot = take(pl.dim * (pl.shard_bits ? size_t(pl.B) : 1) * sizeof(double));  // sharded: one weight slab per rank of the call
         // observable cotangent grad_states[k] + 2 sum_o g_o O_o psi_k + sum_o (gRe + i gIm)_o phi_o: one state, reused in stream order
         // (one-launch adjoints: every k)
-        pl.off_pauli_cot = take((pl.n_pobs || pl.n_ov || pl.n_rdm || pl.moments || pl.dm_rows()) ? size_t(pl.N <= 12 ? pl.T + 1 : 1) * pl.state_bytes : 0);
+        pl.off_pauli_cot = take((pl.n_pobs || pl.n_ov || pl.n_rdm || pl.moments || pl.energy || pl.dm_rows()) ? size_t(pl.N <= 12 ? pl.T + 1 : 1) * pl.state_bytes : 0);
         pl.off_meta2 = take(std::max(E * 40, size_t(pl.T + 1) * sizeof(int32_t)));  // StageBwdDev records, or the save-point flags of the one-launch adjoint
+        if (pl.energy) {  // z = g_E psi + g_M H_k psi (one state; one-launch adjoints: every k) and the records [Bc][n_tsave][replica][NC]
+            pl.off_energy_z = take(size_t(pl.N <= 12 ? pl.T + 1 : 1) * pl.state_bytes);
+            pl.off_energy_ge = take(size_t(pl.Bc) * (pl.T + 1) * kEnergyReplicas * std::max(pl.NC, 1) * sizeof(double));
+        }
         pl.off_xy_ge = take(pl.xy_mode ? size_t(kXyReplicas) * (pl.N * (pl.N - 1) / 2) * sizeof(double) : 0);  // XY gradient replicas (zeroed by rydiff_backward)
     }
     return off;

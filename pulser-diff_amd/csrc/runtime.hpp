@@ -173,6 +173,7 @@ struct Runtime;
 void assign_pauli_layouts(Runtime& rt);                                  // pauli_launch.hpp
 int upload_pauli_tables(const Plan& pl, char* ws, hipStream_t stream);  // pauli_launch.hpp
 int upload_dm_tables(const Plan& pl, char* ws, hipStream_t stream);     // dm_launch.hpp
+int energy_prepare(const Runtime& rt, const RydProblem* p, char* ws, hipStream_t stream);  // energy_launch.hpp
 
 std::mutex g_poly_mutex;
 std::vector<PolyDesign> g_poly_cache;
@@ -414,15 +415,16 @@ int plan_runtime(const RydProblem* p, const RydPlanInfo* info, void* scratch, si
 
 // K0 on one set of tables: per-exponential coefficient records [Bc][E][NC] into `coef`, from the StageDev records already in the
 // workspace.  A nullptr table is a zero table (its terms are left out of the sums): the tangent sweep hands in tangent tables.
-int launch_expand(const Plan& pl, char* ws, const double2* amp, const double* det, double* coef, hipStream_t stream) {
-    const size_t E = pl.stages.size();
+// launch_expand_at: the same for E records `st` on the device and tables of n_samples samples (the energy block's save-point records).
+int launch_expand_at(const Plan& pl, const StageDev* st, size_t E, int n_samples, const double2* amp, const double* det, double* coef,
+                     hipStream_t stream) {
     ExpandArgs ea{};
     ea.amp = amp;
     ea.det = det;
-    ea.st = reinterpret_cast<const StageDev*>(ws + pl.off_meta_idx);
+    ea.st = st;
     ea.coef = coef;
     ea.E = int(E);
-    ea.n_samples = pl.n_samples;
+    ea.n_samples = n_samples;
     ea.Ka = amp ? pl.Ka : 0;
     ea.Kd = det ? pl.Kd : 0;
     ea.NC = pl.NC;
@@ -433,6 +435,10 @@ int launch_expand(const Plan& pl, char* ws, const double2* amp, const double* de
     hipLaunchKernelGGL(k_expand_coeffs, dim3((unsigned(E) + 127) / 128, pl.Bc), dim3(128), 0, stream, ea);
     LAUNCH_CHECK();
     return RYDIFF_OK;
+}
+
+int launch_expand(const Plan& pl, char* ws, const double2* amp, const double* det, double* coef, hipStream_t stream) {
+    return launch_expand_at(pl, reinterpret_cast<const StageDev*>(ws + pl.off_meta_idx), pl.stages.size(), pl.n_samples, amp, det, coef, stream);
 }
 
 // common prologue of forward / backward: plan_runtime, upload metadata, expand coefficients, udiag.
@@ -476,6 +482,8 @@ int prepare(const RydProblem* p, const RydPlanInfo* info, void* workspace, size_
                                       reinterpret_cast<double*>(ws + pl.off_coef), stream);
         if (rc2) return rc2;
     }
+    rc = energy_prepare(rt, p, ws, stream);
+    if (rc) return rc;
     double* udiag = reinterpret_cast<double*>(ws + pl.off_udiag);
     if (pl.N > 1) {
         if (pl.shard_bits)  // one table per slab, evaluated at the global index
@@ -564,7 +572,8 @@ void shard_groups(const Plan& pl, int (&grp)[kShardMaxBits]) {
 // writes grad_states[k] + 2 sum_o g_o O_o psi_k into a workspace buffer, k_overlap_apply (overlap_launch.hpp) adds
 // sum_o (gRe + i gIm)_o phi_o to it (or to grad_states[k] where no Pauli observable has a cotangent), and the injecting launch reads
 // that buffer instead of grad_states[k]; k_rdm_apply (rdm_launch.hpp) adds sum_o ((G + G^dagger)_{A_o} (x) 1) psi_k the same way, and
-// k_moments_apply (moments_launch.hpp) 2 q_k psi_k of the occupation-correlation rows, k_dm_apply / k_dm_scatter (dm_launch.hpp) the
+// k_moments_apply (moments_launch.hpp) 2 q_k psi_k of the occupation-correlation rows, k_energy_bwd1 / k_energy_bwd2 (energy_launch.hpp)
+// 2 H_k (g_E + g_M H_k) psi_k of the energy rows, k_dm_apply / k_dm_scatter (dm_launch.hpp) the
 // cotangents of the density-matrix rows
 struct PauliInject {
     const Runtime* rt = nullptr;
@@ -577,6 +586,9 @@ struct PauliInject {
     const double2* ov_targets = nullptr;
     const double* rdm_gexp = nullptr; // Rdm
     const double* moments_gexp = nullptr;  // Moments
+    const double* energy_gexp = nullptr;   // Energy
+    mutable int rc = 0;                    // the first failure of a cotangent launch that reports one (the energy passes), for rydiff_backward
+    double* wtot = nullptr;                // the U_ij gradient weights of the backward call (the energy block's explicit dL/dU), or nullptr
     const double* dm_gexp = nullptr;  // DmTrace .. End: the first density-matrix row
     const double* dm_diag = nullptr;  // RydProblem.dm_diag / dm_fid_targets
     const double2* dm_phi = nullptr;
@@ -667,6 +679,7 @@ struct ForwardCtx : SweepCtx {
     double* overlap_out = nullptr; // Overlap
     double* rdm_out = nullptr;     // Rdm
     double* moments_out = nullptr; // Moments
+    double* energy_out = nullptr;  // Energy
     double* moments_drec = nullptr;  // tangent sweep past 12 qubits: the tile records of the moment tangents (TangentLayout::off_dmoments)
     double* dm_out = nullptr;      // DmTrace .. End: the first density-matrix row
     const double* shot_u = nullptr;  // RydProblem.shot_uniforms / shots_out where shots are drawn (rydiff_forward with n_shots > 0)

@@ -46,6 +46,7 @@ using namespace rydiff;
 #include "overlap_kernels.hpp"
 #include "rdm_kernels.hpp"
 #include "moments_kernels.hpp"
+#include "energy_kernels.hpp"
 #include "shots_kernels.hpp"
 #include "dm_kernels.hpp"
 #include "tangent_kernels.hpp"
@@ -62,6 +63,7 @@ static_assert(sizeof(PersistFactor) == 48, "plan.hpp sizes the factor table with
 #include "shots_launch.hpp"
 #include "rdm_launch.hpp"
 #include "moments_launch.hpp"
+#include "energy_launch.hpp"
 #include "dm_launch.hpp"
 #include "overlap_launch.hpp"
 #include "tangent_launch.hpp"
@@ -168,6 +170,7 @@ int bind_expect_rows(ForwardCtx& c, double* expect_out) {
     c.overlap_out = rows.at(expect_out, ExpectRows::Overlap);
     c.rdm_out = rows.at(expect_out, ExpectRows::Rdm);
     c.moments_out = rows.at(expect_out, ExpectRows::Moments);
+    c.energy_out = rows.at(expect_out, ExpectRows::Energy);
     c.dm_out = rows.at(expect_out, ExpectRows::DmTrace, ExpectRows::End);
     if (expect_out && rows.total()) HIP_TRY(hipMemsetAsync(expect_out, 0, rows.size() * sizeof(double), c.stream));
     return RYDIFF_OK;
@@ -598,6 +601,8 @@ int rydiff_backward(const RydProblem* p, const RydPlanInfo* info, const void* st
         c.pauli.ov_targets = static_cast<const double2*>(p->overlap_targets);
         c.pauli.rdm_gexp = rows.at(grad_expect, ExpectRows::Rdm);
         c.pauli.moments_gexp = rows.at(grad_expect, ExpectRows::Moments);
+        c.pauli.energy_gexp = rows.at(grad_expect, ExpectRows::Energy);
+        c.pauli.wtot = c.wtot;
         c.pauli.dm_gexp = rows.at(grad_expect, ExpectRows::DmTrace, ExpectRows::End);
         c.pauli.dm_diag = p->dm_diag;
         c.pauli.dm_phi = static_cast<const double2*>(p->dm_fid_targets);
@@ -609,6 +614,8 @@ int rydiff_backward(const RydProblem* p, const RydPlanInfo* info, const void* st
 
     HIP_TRY(hipMemsetAsync(c.ge, 0, size_t(pl.Bc) * pl.stages.size() * rt.ge_rec() * sizeof(double), stream));
     if (c.wtot) HIP_TRY(hipMemsetAsync(c.wtot, 0, pl.dim * (pl.shard_bits ? size_t(pl.B) : 1) * sizeof(double), stream));
+    rc = energy_clear_gradients(rt, c.ws, stream);
+    if (rc) return rc;
     int cl = 0;  // c.lam[cl]: the cotangent w.r.t. psi0 once the sweep is through
     if (persist_bwd_enabled(rt)) {
         rc = backward_persist(c);
@@ -627,8 +634,10 @@ int rydiff_backward(const RydProblem* p, const RydPlanInfo* info, const void* st
             if (rc) return rc;
         }
     }
+    if (c.pauli.rc) return c.pauli.rc;  // (a cotangent launch failed: rydiff_last_error names it)
     if (g_psi0) HIP_TRY(hipMemcpyAsync(g_psi0, c.lam[cl], pl.state_bytes, hipMemcpyDeviceToDevice, stream));
-    return scatter_gradients(c, g_amp, g_det, g_u, g_tsave);
+    rc = scatter_gradients(c, g_amp, g_det, g_u, g_tsave);
+    return rc ? rc : energy_scatter(rt, p, c.ws, stream);  // (the explicit dL/d(energy tables); dL/dU and dL/dJ went into wtot / the exchange replicas)
 }
 
 size_t rydiff_tangent_workspace_bytes_flags(const RydProblem* p, const RydPlanInfo* info, int n_dir, int flags) {

@@ -33,6 +33,8 @@ int tangent_validate(const RydProblem* p, const RydPlanInfo* info, int n_dir, in
                                      "has RYDIFF_TANGENT_PAIR_TERMS");
     if (p->amp_conditioned_terms || p->det_ones_terms)
         return fail(RYDIFF_ENOTIMPL, "tangent sweep: not implemented with conditioned flips / ones-counting terms (three-level registers)");
+    if (p->energy_rows != 0)
+        return fail(RYDIFF_ENOTIMPL, "tangent sweep: energy observables are not implemented (energy_rows > 0): request them from rydiff_forward");
     if (p->n_shots > 0) return fail(RYDIFF_ENOTIMPL, "tangent sweep: measurement shots are not implemented (n_shots > 0): draw them in rydiff_forward");
     if (p->bit_moments != 0 && (!(flags & RYDIFF_TANGENT_MOMENTS) || p->dm_atoms != 0))  // (the ket block; a density-matrix register asks with dm_moments)
         return fail(RYDIFF_ENOTIMPL, "tangent sweep: bit moments are not implemented (bit_moments != 0) unless RydTangent.flags has "

@@ -698,6 +698,27 @@ class Hamiltonian:
         i2 = min(i1 + 1, n - 2)
         return coeff[i1] + (coeff[i2] - coeff[i1]) * (t - i1 * self.dt) / self.dt
 
+    def energy_tables(self, tsave: Tensor, frame: bool = False) -> tuple[Tensor, Tensor]:
+        """The coefficient tables AT the evaluation times, ``(1, n_amp_terms, n_t)`` complex and ``(1, n_det_terms, n_t)`` real, for the
+        native energy rows (``RydProblem.energy_amp`` / ``energy_det``): ``_interp`` (hamiltonian.py:532-542) vectorised over the times,
+        entry for entry, so that the Hamiltonian the rows are taken with is ``get_hamiltonian(t_k)``.  Written in torch: gradients
+        w.r.t. the pulse parameters behind the tables and — through the interpolation weight — w.r.t. ``tsave`` itself flow by ordinary
+        autograd (the explicit ``dH/dt`` term of ``d<H(t)>/dt``).  ``frame``: the amplitude tables of the frame that rotates with the
+        constant drive phase (``amp_tables_frame``), for states that are evolved there."""
+        n = self.n_samples
+        amp = self.amp_tables_frame if (frame and self.amp_tables_frame is not None) else self.amp_tables
+        det = self.det_tables
+        t = torch.as_tensor(tsave).to(det.device, RD)
+        i1 = torch.clamp(torch.clamp(torch.floor(t.detach() / self.dt), max=n - 2), min=0).to(torch.long)
+        i2 = torch.clamp(torch.clamp(i1 + 1, max=n - 2), min=0)
+        rel = t - i1.to(RD) * self.dt
+
+        def at(coeff: Tensor) -> Tensor:
+            c1, c2 = coeff.index_select(-1, i1), coeff.index_select(-1, i2)
+            return c1 + (c2 - c1) * rel / self.dt
+
+        return at(amp), at(det)
+
     def build_ham_tensor(self) -> Callable[[Union[float, Tensor]], Tensor]:
         """hamiltonian.py:499-548: returns H_t(t) -> explicit sparse COO matrix (small registers; for inspection)."""
         n = self._size

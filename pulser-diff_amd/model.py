@@ -21,7 +21,7 @@ from .backend import TorchEmulator
 from .simconfig import SimConfig
 from .simresults import SimulationResults
 from .solver import SolverType
-from .observables import OccupationCorrelations, PauliObservable, ReducedDensityMatrix, StateOverlap
+from .observables import Energy, OccupationCorrelations, PauliObservable, ReducedDensityMatrix, StateOverlap
 from .utils import DiagonalObservable, total_magnetization, total_magnetization_diag
 from .waveform_funcs import constant_waveform
 
@@ -211,6 +211,15 @@ class QuantumModel(Module):
         obs = qubits if isinstance(qubits, ReducedDensityMatrix) else ReducedDensityMatrix(qubits)
         evaluation_times, results = self._run(observables=[obs], store_states=False)
         return evaluation_times, results.reduced_density_matrix(obs)
+
+    def energy(self, variance: bool = False) -> tuple:
+        """Evaluation times and the energy ``<psi(t)| H(t) |psi(t)>`` under the sequence's own Hamiltonian, real ``(n_t,)``, evaluated
+        and differentiated natively (the loss of a ground-state preparation: no target state, no stored trajectory); with
+        ``variance=True`` a third entry, ``<H^2> - <H>^2`` at every evaluation time.  Ket runs only."""
+        evaluation_times, results = self._run(observables=[Energy(second_moment=variance)], store_states=False)
+        if variance:
+            return evaluation_times, results.energy(), results.energy_variance()
+        return evaluation_times, results.energy()
 
     def occupation_correlations(self, connected: bool = False) -> tuple[Tensor, Tensor]:
         """Evaluation times and ``<n_i n_j>`` (``connected=True``: ``g_ij = <n_i n_j> - <n_i><n_j>``), real ``(n_t, N, N)`` with

@@ -417,6 +417,25 @@ class OccupationCorrelations:
     ``store_states=False`` serves it from the diagonal of rho (``RydProblem.dm_moments``; ``csrc/dm_kernels.hpp``: ``k_dm_moments``)."""
 
 
+class Energy:
+    """The energy of the state under the sequence's own Hamiltonian, ``E(t_k) = <psi(t_k)| H(t_k) |psi(t_k)>``, and (with
+    ``second_moment=True``, the default) ``<H(t_k)^2> = |H(t_k) psi(t_k)|^2`` at every evaluation time — the score of a
+    state-preparation or annealing sequence that needs no target state, and through the variance the distance from any eigenstate.
+    Handed to ``run(observables=[...])`` of a ket run it is evaluated and differentiated natively (``include/rydiff.h``:
+    ``RydProblem.energy_rows``; ``csrc/energy_kernels.hpp``): no stored trajectory, and ``H(t_k)`` is ``get_hamiltonian(t_k)`` — the
+    tables interpolated at the evaluation times (``Hamiltonian.energy_tables``), so that gradients w.r.t. pulse parameters, the
+    register and (``time_grad``) the evaluation times include the explicit dependence of ``H``.  Read it with ``results.energy()``,
+    ``results.energy_second_moment()`` and ``results.energy_variance()``.  Not an operator: ``results.expect`` does not take it."""
+
+    def __init__(self, second_moment: bool = True):
+        self.second_moment = bool(second_moment)
+
+    @property
+    def rows(self) -> int:
+        """Rows of the energy block: 1 (E) or 2 (E, then the second moment)."""
+        return 2 if self.second_moment else 1
+
+
 def moment_rows(n_qubits: int) -> int:
     """Rows of the moments block: ``1 + N + N(N-1)/2``."""
     return 1 + n_qubits + n_qubits * (n_qubits - 1) // 2

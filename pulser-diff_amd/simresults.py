@@ -12,7 +12,7 @@ from __future__ import annotations
 import collections.abc
 from abc import ABC, abstractmethod
 from collections import Counter
-from typing import Mapping, Optional
+from typing import Callable, Mapping, Optional
 
 import numpy as np
 import torch
@@ -22,7 +22,7 @@ from .result import SampledResult, TorchResult
 from .observables import (PauliObservable, ReducedDensityMatrix, StateOverlap, dm_occupation_moments, fidelity_states,
                           occupation_moments, overlap_states, purity_states, reduced_density_matrix)
 from .shots import ShotRequest, bitstring_counts, indices_to_bitstrings
-from .utils import (DiagonalObservable, connected_correlations, expect, negativity, occupation_correlations_from_moments,
+from .utils import (DiagonalObservable, connected_correlations, energy_variance, expect, negativity, occupation_correlations_from_moments,
                     occupations_from_moments, structure_factor, von_neumann_entropy)
 
 
@@ -62,7 +62,8 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
                  overlap_observables: Optional[list] = None, native_shots: Optional[ShotRequest] = None,
                  native_rdms: Optional[list] = None, rdm_observables: Optional[list] = None,
                  native_fidelities: Optional[list] = None, native_purity: Optional[Tensor] = None,
-                 native_moments: Optional[Tensor] = None) -> None:
+                 native_moments: Optional[Tensor] = None, native_energy: Optional[Tensor] = None,
+                 hamiltonian_at: Optional[Callable] = None) -> None:
         super().__init__(size, basis_name, sim_times)
         if self._basis_name == "all":  # simresults.py:381-383
             if meas_basis not in {"ground-rydberg", "digital"}:
@@ -85,6 +86,8 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
         self._native_fidelities = native_fidelities  # master-equation runs, per StateOverlap: real (n_t, B) = <phi|rho|phi>
         self._native_purity = native_purity  # master-equation runs with a Purity observable: real (n_t, B)
         self._native_moments = native_moments  # run with OccupationCorrelations: real (1 + N + N(N-1)/2, n_t, B): S, B_q, B_qr
+        self._native_energy = native_energy  # run with Energy: real (1 | 2, n_t, B): E, then the second moment
+        self._hamiltonian_at = hamiltonian_at  # t (us) -> explicit H(t): energies of stored states where no native rows were asked for
         self._native_shots = native_shots  # filled by the solver: amplitude indices (n_shot_times, B, n_shots)
         self.solver_stats = dict(stats or {})
 
@@ -223,6 +226,47 @@ class CoherentResults(SimulationResults, collections.abc.Sequence):
         """``sum_ij s_i s_j g_ij / N`` at every evaluation time, real ``(n_t,)``, for a pattern ``signs`` of +-1 over the atoms in
         ``atom_order``; the Neel pattern gives the antiferromagnetic order parameter."""
         return structure_factor(self.occupation_correlations(connected=True), signs)
+
+    def _energy_rows(self, second_moment: bool) -> Tensor:
+        """(2, n_t, B) (or (1, n_t, B) where only E was asked for natively and only E is wanted): the native rows of a run that was
+        handed ``Energy``, else ``<psi_k|H(t_k)|psi_k>`` and ``|H(t_k) psi_k|^2`` of the stored kets with the explicit matrix of
+        ``get_hamiltonian`` (small registers)."""
+        if self._density:
+            raise NotImplementedError("Energy is not available in master-equation runs; apply get_hamiltonian to the stored density matrices.")
+        if self._basis_name == "all":
+            raise NotImplementedError("Energy is not available in the three-level all-basis.")
+        if self._native_energy is not None and (self._native_energy.shape[0] == 2 or not second_moment):
+            return self._native_energy
+        if self._states_tbd.numel() == 0:
+            raise RuntimeError("States were not stored for this run (store_states=False) and it evaluated no native energy rows"
+                               + (" with the second moment" if self._native_energy is not None else "")
+                               + ": hand run(observables=[Energy()]) the observable.")
+        if self._hamiltonian_at is None:
+            raise RuntimeError("These results do not know the sequence's Hamiltonian: hand run(observables=[Energy()]) the observable.")
+        states = self.states  # (n_t, dim, B)
+        e, m2 = [], []
+        for k in range(states.shape[0]):
+            h = self._hamiltonian_at(self._sim_times[k].to("cpu")).to_dense().to(states.device) @ states[k]
+            e.append((states[k].conj() * h).sum(dim=0).real)
+            m2.append((h.conj() * h).sum(dim=0).real)
+        return torch.stack([torch.stack(e), torch.stack(m2)])
+
+    def energy(self) -> Tensor:
+        """``E(t_k) = <psi(t_k)| H(t_k) |psi(t_k)>`` with the sequence's own Hamiltonian (``get_hamiltonian(t_k)``) at every
+        evaluation time, real ``(n_t,)``, summed over the columns of the initial state like ``expect``; not normalised (the state is
+        taken as it is).  The native rows when the run was handed ``Energy()``, else computed from the stored states."""
+        return self._energy_rows(False)[0].sum(dim=-1)
+
+    def energy_second_moment(self) -> Tensor:
+        """``<psi(t_k)| H(t_k)^2 |psi(t_k)> = |H(t_k) psi(t_k)|^2``, real ``(n_t,)``; native with ``Energy(second_moment=True)``."""
+        return self._energy_rows(True)[1].sum(dim=-1)
+
+    def energy_variance(self) -> Tensor:
+        """``<H^2> - <H>^2`` per column of the initial state, summed over the columns, real ``(n_t,)``; clamped at 0 in the value
+        only.  An eigenstate gives rounding noise of about ``1e-12 R^2`` (``R``: the spectral bound of ``H``), not an exact 0:
+        ``utils.energy_variance`` states the floor."""
+        rows = self._energy_rows(True)
+        return energy_variance(rows[0], rows[1]).sum(dim=-1)
 
     def sample_state(self, t: float, n_samples: int = 1000, t_tol: float = 1.0e-3) -> Counter:
         """simresults.py:497-540: ideal samples, then the detection errors of the SPAM model (a measured 0 flips with

@@ -90,6 +90,11 @@ class ProblemSpec:
     # XY exchange as a term of its own (RydProblem.xy_mode): 0 none | 1 Hermitian | 2 one-directional, as the reference writes it; the
     # couplings J_ij are the `xy_pairs` input of ``evolve`` (N(N-1)/2 values in the order of u_pairs; they take part in autograd)
     xy_mode: int = 0
+    # energy observables (RydProblem.energy_rows): 0 off | 1 the row E(t_k) = <psi_k|H(t_k)|psi_k> | 2 E then M2 = |H(t_k) psi_k|^2, the last
+    # rows of a ket's `expect` (split_energy takes them off the end); H(t_k) is built from the `energy_amp` / `energy_det` inputs of
+    # ``evolve``: the coefficient tables AT the save points (Hamiltonian.energy_tables), which take part in autograd
+    energy: int = 0
+    energy_kernel: int = 0  # RydProblem.energy_kernel: 0 automatic | 1 the direct version | 2 the LDS-tile version (13 .. 24 qubits, no exchange)
 
     def moment_rows(self) -> int:
         """Rows of `expect` the occupation correlations take: 1 + N + N(N-1)/2, or 0."""
@@ -167,12 +172,13 @@ class _Call:
     """Keeps the ctypes structures and every buffer they point to alive for the duration of a native call."""
 
     def __init__(self, spec: ProblemSpec, amp: Tensor, det: Tensor, u_pairs: Tensor, tsave_host: np.ndarray,
-                 batch: int, obs: Optional[Tensor], real_amp_grad: bool = False, xy_pairs: Optional[Tensor] = None):
+                 batch: int, obs: Optional[Tensor], real_amp_grad: bool = False, xy_pairs: Optional[Tensor] = None,
+                 energy_amp: Optional[Tensor] = None, energy_det: Optional[Tensor] = None):
         self.spec = spec
         self.amp_masks = np.asarray(spec.amp_masks, dtype=np.uint32)
         self.det_masks = np.asarray(spec.det_masks, dtype=np.uint32)
         self.tsave = np.ascontiguousarray(tsave_host, dtype=np.float64)
-        self.tensors = (amp, det, u_pairs, obs, xy_pairs)
+        self.tensors = (amp, det, u_pairs, obs, xy_pairs, energy_amp, energy_det)
         p = _native.RydProblem()
         p.n_qubits = spec.n_qubits
         p.batch = batch
@@ -237,6 +243,11 @@ class _Call:
         p.bit_moments = int(spec.moments)
         p.xy_mode = int(spec.xy_mode)
         p.xy_pairs = xy_pairs.data_ptr() if (spec.xy_mode and xy_pairs is not None and xy_pairs.numel()) else None
+        p.energy_rows = int(spec.energy)
+        p.energy_kernel = int(spec.energy_kernel) if spec.energy else 0
+        if spec.energy:
+            p.energy_amp = energy_amp.data_ptr() if (ka and energy_amp is not None) else None
+            p.energy_det = energy_det.data_ptr() if (kd and energy_det is not None) else None
         self.dm_buffers = None
         if spec.dm is not None:
             dm = spec.dm
@@ -273,10 +284,10 @@ class _Call:
 
     def expect_rows(self) -> int:
         """Rows of `expect` / `dexpect[d]`, in the order the library writes them (ExpectRows, csrc/plan.hpp): diagonal observables,
-        then the Pauli ones, then Re / Im of every overlap, then Re / Im of every RDM entry, then the moments S, B_q, B_qr of the occupation correlations, then the density-matrix rows."""
+        then the Pauli ones, then Re / Im of every overlap, then Re / Im of every RDM entry, then the moments S, B_q, B_qr of the occupation correlations, then the energy rows E (and M2), then the density-matrix rows."""
         p = self.problem
         dm_rows = self.spec.dm.rows() if self.spec.dm is not None else 0
-        return p.n_obs + p.n_pauli_obs + 2 * p.n_overlaps + self.spec.rdm_rows() + self.spec.moment_rows() + dm_rows
+        return p.n_obs + p.n_pauli_obs + 2 * p.n_overlaps + self.spec.rdm_rows() + self.spec.moment_rows() + int(self.spec.energy) + dm_rows
 
     def set_shots(self, times: np.ndarray, uniforms: Tensor, out: Tensor) -> None:
         """RydProblem.n_shots / shot_*: sampled save points (host int32), uniforms (device float64) and the output (device, 32-bit),
@@ -309,7 +320,8 @@ def _check_overlaps(spec: ProblemSpec, batch: int, device: Optional[torch.device
 
 
 def _check_shapes(spec: ProblemSpec, amp: Tensor, det: Tensor, u_pairs: Tensor, obs: Optional[Tensor], batch: int,
-                  device: Optional[torch.device] = None, xy_pairs: Optional[Tensor] = None) -> None:
+                  device: Optional[torch.device] = None, xy_pairs: Optional[Tensor] = None, energy_amp: Optional[Tensor] = None,
+                  energy_det: Optional[Tensor] = None, n_t: int = 0) -> None:
     """The C ABI sees raw pointers only: every buffer is checked against the spec here, so that a mismatch is a ValueError and
     never an out-of-bounds device read."""
     ka, kd, n, nq = len(spec.amp_masks), len(spec.det_masks), spec.n_samples, spec.n_qubits
@@ -339,6 +351,21 @@ def _check_shapes(spec: ProblemSpec, amp: Tensor, det: Tensor, u_pairs: Tensor, 
         raise ValueError(f"xy_pairs must hold N(N-1)/2 = {n_pairs} values, got {xy_pairs.numel()}")
     if xy_pairs is not None and device is not None and xy_pairs.device != torch.device(device):
         raise ValueError(f"xy_pairs must live on the device of the states ({device}), got {xy_pairs.device}")
+    if spec.energy not in (0, 1, 2):
+        raise ValueError(f"ProblemSpec.energy must be 0 (off), 1 (E) or 2 (E and its second moment), got {spec.energy}")
+    if not spec.energy and (energy_amp is not None or energy_det is not None):
+        raise ValueError("energy_amp / energy_det given without ProblemSpec.energy")
+    if spec.energy:
+        for name, t, k in (("energy_amp", energy_amp, ka), ("energy_det", energy_det, kd)):
+            if k == 0:
+                continue
+            if t is None:
+                raise ValueError(f"ProblemSpec.energy is set: evolve needs {name}, the coefficients at the evaluation times "
+                                 "(Hamiltonian.energy_tables)")
+            if t.ndim != 3 or t.shape[1] != k or t.shape[2] != n_t or t.shape[0] != cb:
+                raise ValueError(f"{name} must have shape ({cb}, {k}, {n_t}) = (coeff_batch, terms, evaluation times), got {tuple(t.shape)}")
+            if device is not None and t.device != torch.device(device):
+                raise ValueError(f"{name} must live on the device of the states ({device}), got {t.device}")
     if obs is not None and obs.numel() and (obs.ndim != 2 or obs.shape[1] != 2 ** nq):
         raise ValueError(f"obs_diag must have shape (n_obs, {2 ** nq}), got {tuple(obs.shape)}")
     spec.packed_pauli()  # raises ValueError on a mask bit at or above N, inconsistent counts, too many strings
@@ -408,10 +435,13 @@ class _Prepared(NamedTuple):
     n_t: int
     call: _Call
     xy: Optional[Tensor] = None
+    energy_amp: Optional[Tensor] = None
+    energy_det: Optional[Tensor] = None
 
 
 def _prepare(amp: Tensor, det: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Tensor, spec: ProblemSpec, obs: Optional[Tensor],
-             real_amp_grad: bool = False, xy_pairs: Optional[Tensor] = None) -> _Prepared:
+             real_amp_grad: bool = False, xy_pairs: Optional[Tensor] = None, energy_amp: Optional[Tensor] = None,
+             energy_det: Optional[Tensor] = None) -> _Prepared:
     """What every entry point does first: the inputs must be on the GPU; detached, contiguous copies in the library's dtypes; their
     shapes against the spec; the ctypes problem."""
     for t, name in ((amp, "amp_tables"), (det, "det_tables"), (u_pairs, "u_pairs"), (psi0, "psi0")):
@@ -422,31 +452,38 @@ def _prepare(amp: Tensor, det: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Ten
     psi_c = psi0.detach().to(torch.complex128).contiguous()
     obs_c = None if obs is None else obs.detach().to(torch.float64).contiguous()
     xy_c = None if xy_pairs is None else xy_pairs.detach().to(torch.float64).contiguous()
+    ea_c = None if energy_amp is None else energy_amp.detach().to(torch.complex128).contiguous()
+    ed_c = None if energy_det is None else energy_det.detach().to(torch.float64).contiguous()
     ts_host = tsave.detach().to("cpu", torch.float64).numpy()
     if psi_c.ndim != 2:
         raise ValueError(f"psi0 must be (batch, 2^N), got shape {tuple(psi_c.shape)}")
     batch, dim = psi_c.shape
     if dim != 2 ** spec.n_qubits:
         raise ValueError(f"Incompatible shape of initial state.Expected {2 ** spec.n_qubits}, got {dim}.")
-    _check_shapes(spec, amp_c, det_c, u_c, obs_c, batch, psi0.device, xy_c)
-    call = _Call(spec, amp_c, det_c, u_c, ts_host, batch, obs_c, real_amp_grad=real_amp_grad, xy_pairs=xy_c)
-    return _Prepared(amp_c, det_c, u_c, psi_c, obs_c, ts_host, batch, dim, len(ts_host), call, xy_c)
+    _check_shapes(spec, amp_c, det_c, u_c, obs_c, batch, psi0.device, xy_c, ea_c, ed_c, len(ts_host))
+    call = _Call(spec, amp_c, det_c, u_c, ts_host, batch, obs_c, real_amp_grad=real_amp_grad, xy_pairs=xy_c, energy_amp=ea_c,
+                 energy_det=ed_c)
+    return _Prepared(amp_c, det_c, u_c, psi_c, obs_c, ts_host, batch, dim, len(ts_host), call, xy_c, ea_c, ed_c)
 
 
 class _RydbergEvolve(torch.autograd.Function):
-    """states, expect = evolve(amp_tables, det_tables, u_pairs, tsave, psi0; obs_diag, spec; xy_pairs)."""
+    """states, expect = evolve(amp_tables, det_tables, u_pairs, tsave, psi0; obs_diag, spec; xy_pairs, energy_amp, energy_det)."""
 
     @staticmethod
     def forward(ctx, amp: Tensor, det: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Tensor,
-                obs: Optional[Tensor], spec: ProblemSpec, xy_pairs: Optional[Tensor] = None):
+                obs: Optional[Tensor], spec: ProblemSpec, xy_pairs: Optional[Tensor] = None, energy_amp: Optional[Tensor] = None,
+                energy_det: Optional[Tensor] = None):
         L = _native.lib()
         dev = psi0.device
         # (real_amp_grad only matters to the adjoint launches; set here as well so that the plan's kernel_bwd names what will run)
         if xy_pairs is not None:
             _require_cuda(xy_pairs, "xy_pairs")
-        amp_c, det_c, u_c, psi_c, obs_c, ts_host, batch, dim, n_t, call, xy_c = _prepare(amp, det, u_pairs, tsave, psi0, spec, obs,
-                                                                                         real_amp_grad=not amp.is_complex(),
-                                                                                         xy_pairs=xy_pairs)
+        for t, name in ((energy_amp, "energy_amp"), (energy_det, "energy_det")):
+            if t is not None:
+                _require_cuda(t, name)
+        amp_c, det_c, u_c, psi_c, obs_c, ts_host, batch, dim, n_t, call, xy_c, ea_c, ed_c = _prepare(
+            amp, det, u_pairs, tsave, psi0, spec, obs, real_amp_grad=not amp.is_complex(), xy_pairs=xy_pairs, energy_amp=energy_amp,
+            energy_det=energy_det)
         # the kernel variant this call resolved to (spec field, else the CALLING thread's default): the backward pass runs on the
         # autograd engine's device thread, where that thread-local default is not visible
         ctx.kernel_variant = int(call.problem.kernel_variant)
@@ -460,7 +497,7 @@ class _RydbergEvolve(torch.autograd.Function):
                 shot_out = torch.empty(shot_u.shape, dtype=torch.int32, device=dev)
             call.set_shots(shot_times, shot_u, shot_out)
             ctx.shot_buffers = call.shot_buffers
-        needs_grad = any(ctx.needs_input_grad[:5]) or ctx.needs_input_grad[7]
+        needs_grad = any(ctx.needs_input_grad[:5]) or any(ctx.needs_input_grad[7:10])
         need_tape = int(bool(needs_grad and not spec.store_states))
         with torch.cuda.device(dev):
             stream = _stream_ptr(dev)
@@ -535,6 +572,8 @@ class _RydbergEvolve(torch.autograd.Function):
         ctx.in_dtypes = (amp.dtype, det.dtype, u_pairs.dtype, psi0.dtype)
         ctx.xy = xy_c  # (a constant of the backward pass, like the masks: not an output, kept on the context)
         ctx.xy_dtype = None if xy_pairs is None else xy_pairs.dtype
+        ctx.energy = (ea_c, ed_c)  # (inputs of the backward pass that are not saved outputs: kept on the context, like xy)
+        ctx.energy_dtypes = (None if energy_amp is None else energy_amp.dtype, None if energy_det is None else energy_det.dtype)
         ctx.need_tape = need_tape
         ctx.tape_steps = int(call.problem.tape_steps)
         ctx.keep_tape = True  # retain_graph=True callers may run backward again
@@ -562,8 +601,9 @@ class _RydbergEvolve(torch.autograd.Function):
         dev = psi_c.device
         batch, dim = psi_c.shape
         obs = obs_c if ctx.has_obs else None
+        ea_c, ed_c = ctx.energy
         call = _Call(spec, amp_c, det_c, u_c, ctx.tsave_host, batch, obs, real_amp_grad=not ctx.in_dtypes[0].is_complex,
-                     xy_pairs=ctx.xy)
+                     xy_pairs=ctx.xy, energy_amp=ea_c, energy_det=ed_c)
         call.problem.kernel_variant = ctx.kernel_variant  # same kernel family as the forward pass (see forward)
         call.problem.tape_steps = ctx.tape_steps
         if ctx.shot_buffers is not None:  # ignored by the adjoint sweep, but the counts are part of the workspace layout
@@ -584,6 +624,10 @@ class _RydbergEvolve(torch.autograd.Function):
             g_psi = torch.empty_like(psi_c) if need[4] else None
             g_xy = torch.empty_like(ctx.xy) if (need[7] and ctx.xy is not None and ctx.xy.numel()) else None
             call.problem.g_xy = None if g_xy is None else g_xy.data_ptr()
+            g_ea = torch.empty_like(ea_c) if (spec.energy and need[8] and ea_c is not None and ea_c.numel()) else None
+            g_ed = torch.empty_like(ed_c) if (spec.energy and need[9] and ed_c is not None and ed_c.numel()) else None
+            call.problem.g_energy_amp = None if g_ea is None else g_ea.data_ptr()
+            call.problem.g_energy_det = None if g_ed is None else g_ed.data_ptr()
             info = ctx.info
             if ctx.need_tape:
                 workspace = ctx.tape_workspace  # sized for forward + backward by the forward call
@@ -611,7 +655,12 @@ class _RydbergEvolve(torch.autograd.Function):
             g_psi = g_psi.to(p_dt)
         if g_xy is not None:
             g_xy = g_xy.to(ctx.xy_dtype)
-        return g_amp, g_det, g_u, g_ts, g_psi, None, None, g_xy
+        if g_ea is not None:
+            ea_dt = ctx.energy_dtypes[0]
+            g_ea = g_ea.to(ea_dt) if ea_dt.is_complex else g_ea.real.to(ea_dt)
+        if g_ed is not None:
+            g_ed = g_ed.to(ctx.energy_dtypes[1])
+        return g_amp, g_det, g_u, g_ts, g_psi, None, None, g_xy, g_ea, g_ed
 
 
 @dataclass
@@ -625,6 +674,7 @@ class SolveResult:
     shots: Optional[ShotRequest] = None  # the request handed to sesolve(shots=...), holding the native shots (.indices)
     rdms: Optional[list] = None  # per ReducedDensityMatrix: complex (n_t, B, 2^m, 2^m), evaluated natively (differentiable), or None
     moments: Optional[Tensor] = None  # (1 + N + N(N-1)/2, n_t, B): S, B_q, B_qr evaluated natively (differentiable), or None
+    energy: Optional[Tensor] = None  # (1 | 2, n_t, B): E(t_k) = <psi_k|H(t_k)|psi_k>, then M2 = |H(t_k) psi_k|^2, evaluated natively (differentiable), or None
 
 
 def split_expect(expect: Tensor, n_overlaps: int) -> tuple[Tensor, Optional[Tensor]]:
@@ -636,11 +686,39 @@ def split_expect(expect: Tensor, n_overlaps: int) -> tuple[Tensor, Optional[Tens
     return expect[:n_real], torch.complex(pairs[:, 0], pairs[:, 1])
 
 
-def split_observables(expect: Tensor, n_overlaps: int, rdms=None) -> tuple[Tensor, Optional[Tensor], Optional[list]]:
+def split_energy(expect: Tensor, energy: int) -> tuple[Tensor, Optional[Tensor]]:
+    """Takes the energy rows (``ProblemSpec.energy`` = 1: E; 2: E, M2), the last block of a ket's rows — behind the moments — off the
+    END of `expect`, before ``split_moments`` and ``split_observables`` take theirs: -> (the other rows, the energy rows
+    (energy, n_t, B) or None).  ``energy = 0``: `expect` as it is."""
+    energy = int(energy)
+    if not energy:
+        return expect, None
+    if energy not in (1, 2) or expect.shape[0] < energy:
+        raise ValueError(f"split_energy: energy must be 0, 1 or 2 and `expect` must hold that many rows, got {energy} and {expect.shape[0]} rows")
+    return expect[:expect.shape[0] - energy], expect[expect.shape[0] - energy:]
+
+
+def split_ket_tail(expect: Tensor, n_qubits: int, moments: bool = False, energy: int = 0) -> tuple[Tensor, Optional[Tensor], Optional[Tensor]]:
+    """The one splitter of the blocks at the END of a ket's `expect`, in the only order that is right (the energy rows sit behind the
+    moments): -> (the rows ``split_observables`` takes, the moments (1 + N + N(N-1)/2, n_t, B) or None, the energy rows
+    (energy, n_t, B) or None)."""
+    expect, en = split_energy(expect, energy)
+    mom = None
+    if moments:
+        expect, mom = split_moments(expect, n_qubits)
+    return expect, mom, en
+
+
+def split_observables(expect: Tensor, n_overlaps: int, rdms=None, energy: int = 0) -> tuple:
     """``split_expect`` that also takes the reduced-density-matrix rows out: `expect` of ``evolve`` -> (diagonal and Pauli rows,
     complex overlaps (n_ov, n_t, B) or None, one complex (n_t, B, 2^m, 2^m) per entry of ``rdms`` or None).  ``rdms``: what
     ``ProblemSpec.rdms`` held — ``ReducedDensityMatrix`` objects (the matrices come back in the order of their ``qubits``) or integer
-    masks (ascending qubit order, the library's)."""
+    masks (ascending qubit order, the library's).  ``energy`` (``ProblemSpec.energy``) > 0: the energy rows, which sit behind every
+    other row of a ket, are taken off the end first and returned as a fourth entry (a run that also asked for the moments takes
+    both tail blocks off with ``split_ket_tail`` first); 0: the three entries as before."""
+    if energy:
+        expect, en = split_energy(expect, energy)
+        return split_observables(expect, n_overlaps, rdms) + (en,)
     rdms = list(rdms or [])
     if not rdms:
         return split_expect(expect, n_overlaps) + (None,)
@@ -687,19 +765,23 @@ def frame_factor(n_sub: int, phi: float) -> Tensor:
 
 
 def evolve(amp_tables: Tensor, det_tables: Tensor, u_pairs: Tensor, tsave: Tensor, psi0: Tensor,
-           spec: ProblemSpec, obs_diag: Optional[Tensor] = None, xy_pairs: Optional[Tensor] = None) -> tuple[Tensor, Tensor]:
+           spec: ProblemSpec, obs_diag: Optional[Tensor] = None, xy_pairs: Optional[Tensor] = None,
+           energy_amp: Optional[Tensor] = None, energy_det: Optional[Tensor] = None) -> tuple[Tensor, Tensor]:
     """Low-level entry: psi0 is (B, dim); returns states (n_t, B, dim) and expect (n_obs + n_pauli + 2 n_overlaps, n_t, B)
     (``split_expect`` takes the overlap rows of ``spec.overlaps`` out as complex numbers).  ``spec.shots`` (a ``ShotRequest``)
     receives its measurement shots as a by-product; the return value does not change.  ``xy_pairs`` (with ``spec.xy_mode``): the
-    N(N-1)/2 exchange couplings J_ij in the order of ``u_pairs``, a device tensor that takes part in autograd (``g_xy``)."""
-    return _RydbergEvolve.apply(amp_tables, det_tables, u_pairs, tsave, psi0, obs_diag, spec, xy_pairs)
+    N(N-1)/2 exchange couplings J_ij in the order of ``u_pairs``, a device tensor that takes part in autograd (``g_xy``).
+    ``energy_amp`` / ``energy_det`` (with ``spec.energy``): the coefficient tables at the evaluation times, (coeff_batch, terms, n_t)
+    in the conventions of ``amp_tables`` / ``det_tables``; the energy rows E (and M2) are the last rows of ``expect``
+    (``split_energy``), and the explicit dependence of H(t_k) on the two tables comes back as their gradients."""
+    return _RydbergEvolve.apply(amp_tables, det_tables, u_pairs, tsave, psi0, obs_diag, spec, xy_pairs, energy_amp, energy_det)
 
 
 def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverType.DP5_SE,
             options: Optional[dict] = None, obs_diag: Optional[Tensor] = None, store_states: bool = True,
             pauli_obs: Optional[Sequence[PauliObservable]] = None,
             overlap_obs: Optional[Sequence[StateOverlap]] = None, shots: Union[None, int, ShotRequest] = None,
-            rdm_obs: Optional[Sequence[ReducedDensityMatrix]] = None, moments: bool = False) -> SolveResult:
+            rdm_obs: Optional[Sequence[ReducedDensityMatrix]] = None, moments: bool = False, energy: int = 0) -> SolveResult:
     """Drop-in for ``pyqtorch.sesolve(H=..., psi0, tsave, solver, options)`` at ``backend.py:488-494``.
 
     ``problem`` is the structured Hamiltonian (``pulser_diff_amd.hamiltonian.Hamiltonian``) instead of the opaque
@@ -710,7 +792,8 @@ def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverTyp
     per atom, see ``shots.indices_to_bitstrings``).  ``rdm_obs``: ``ReducedDensityMatrix`` observables evaluated natively into
     ``SolveResult.rdms`` (lab frame, the order of their ``qubits``).  ``moments``: the occupation correlations — the moments
     ``S, B_q, B_qr`` of ``|psi|^2`` over the index bits — evaluated natively into ``SolveResult.moments`` (diagonal: they do not see
-    the rotating frame).
+    the rotating frame).  ``energy`` (1, or 2 for the second moment too): ``E(t_k) = <psi_k|H(t_k)|psi_k>`` and ``|H(t_k) psi_k|^2`` with
+    the problem's own Hamiltonian at the evaluation times (``Hamiltonian.energy_tables``), evaluated natively into ``SolveResult.energy``.
     """
     options = dict(options or {})
     spec = problem.problem_spec(solver=solver, tol=tolerance_from_options(options), store_states=store_states)
@@ -747,6 +830,18 @@ def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverTyp
             raise NotImplementedError("OccupationCorrelations is not available in the three-level all-basis (an atom is two qubits "
                                       "there); reduce the stored states instead.")
         spec.moments = True
+    energy = int(energy)
+    if energy:
+        if embed is not None:
+            raise NotImplementedError("Energy is not available in the three-level all-basis (conditioned terms are not part of the "
+                                      "native energy rows); apply get_hamiltonian to the stored states instead.")
+        if spec.pair_terms:
+            raise NotImplementedError("Energy is not available with dense pair terms (the XY mode on the dense route, master-equation "
+                                      "runs); the XY mode takes it on the native exchange term: TorchEmulator(..., xy_native=True).")
+        if spec.xy_mode == 2:
+            raise NotImplementedError("Energy needs a Hermitian Hamiltonian: the XY exchange as the reference writes it is one-directional. "
+                                      "Pass xy_hermitian=True to TorchEmulator (Hamiltonian.XY_HERMITIAN = True).")
+        spec.energy = energy
     pauli_obs = list(pauli_obs or [])
     if pauli_obs and embed is not None:
         raise NotImplementedError("Pauli observables are not available in the three-level all-basis; use results.expect on stored states.")
@@ -777,21 +872,25 @@ def sesolve(problem, psi0: Tensor, tsave: Tensor, solver: SolverType = SolverTyp
             targets = targets * rot[None, None, :]
     if targets is not None:
         spec.overlaps = targets.contiguous()
+    e_amp = e_det = None
+    if spec.energy:
+        # the tables at the evaluation times, in the frame the states are evolved in (<V psi|V H V^dagger|V psi> = <psi|H|psi>)
+        e_amp, e_det = problem.energy_tables(tsave, frame=rot is not None)
+        if getattr(problem, "amp_is_real", False):
+            e_amp = e_amp.real
     states, expect = evolve(amp_tables, problem.det_tables, problem.u_pairs, tsave, psi_bd, spec, obs_diag,
-                            xy_pairs=problem.xy_pairs if spec.xy_mode else None)
+                            xy_pairs=problem.xy_pairs if spec.xy_mode else None, energy_amp=e_amp, energy_det=e_det)
     if rot is not None and states.numel():
         states = states * rot.conj()[None, None, :]
     if embed is not None and states.numel():
         states = states.index_select(2, embed)
-    mom = None
-    if spec.moments:
-        expect, mom = split_moments(expect, spec.n_qubits)
+    expect, mom, en = split_ket_tail(expect, spec.n_qubits, spec.moments, spec.energy)
     expect, overlaps, rdms = split_observables(expect, len(overlap_obs), rdm_obs)
     if rdms is not None and rot is not None:
         # the library saw V psi: rho_lab[a][a'] = rho[a][a'] exp(-i phi (ones(a) - ones(a'))), on the small matrix (differentiable)
         rdms = [r * frame_factor(o.n_sub, float(phi)).to(r.device) for o, r in zip(rdm_obs, rdms)]
     return SolveResult(states.permute(0, 2, 1) if states.numel() else states, expect,
-                       dict(spec.options.get("_last_stats", {})), overlaps, spec.shots, rdms, mom)
+                       dict(spec.options.get("_last_stats", {})), overlaps, spec.shots, rdms, mom, en)
 
 
 def _tangent_take(t: Optional[Tensor], sel, shape: tuple, dtype: torch.dtype, name: str, dev) -> Optional[Tensor]:

@@ -245,6 +245,18 @@ def logarithmic_negativity(rho: Tensor, n_first: int, base: float = 2) -> Tensor
 
 
 # ---- occupation correlations from the moments block (observables.occupation_moments / RydProblem.bit_moments) --------------------
+def energy_variance(energy: Tensor, second_moment: Tensor, norm=1.0) -> Tensor:
+    """``<H^2> - <H>^2`` from the two native energy rows (``observables.Energy``), clamped at 0 — in the value only: where the clamp
+    acts the gradient is that of the unclamped difference.  For a state of squared norm ``norm`` (a number, or a tensor of the rows'
+    shape) the rows are taken as ``E / norm`` and ``M2 / norm``.  Cancellation floor: both terms are of the size of the squared
+    spectral bound ``R^2`` of ``H`` and each carries a relative rounding error of about 1e-13 from the float64 sums over ``2^N``
+    amplitudes, so a variance below about ``1e-12 R^2`` — that of an eigenstate — comes back as rounding noise of that size (or 0
+    after the clamp), not as the true value; compare it with ``R^2``, never with 0."""
+    e, m2 = energy / norm, second_moment / norm
+    var = m2 - e * e
+    return var + (var.clamp(min=0.0) - var).detach()
+
+
 def _moment_parts(moments: Tensor, n_qubits: int) -> tuple[Tensor, Tensor, Tensor]:
     """(S (...), B_q (N, ...), B_qr as a symmetric (N, N, ...) with zeros on the diagonal) of rows ``(1 + N + N(N-1)/2, ...)``."""
     n = int(n_qubits)
